@@ -7,10 +7,14 @@ A step = layer forward (segment GEMMs, edge softmax, aggregation, self-loop GEMM
 into its backward time, hrt/python/RGNNUtils/RGNNUtils.py:304-311 -- deviation stated here and in
 DESIGN.md).  Inputs are synthetic (het_amd/synth.py): no dataset can be downloaded.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (ms_per_step = wall
+time of the K timed steps / K); --dump-outputs DIR writes what the last timed step computed (dump_outputs).  Everything else the
+line can carry (CPU baseline, per-kernel and per-op timers, rooflines, other variants and models, the partition rehearsal,
+the exchange timers of a multi-rank run) takes runs of its own and is measured with --full only; without it those keys are null
+or absent.
 """
 import argparse
 import datetime
@@ -213,7 +217,7 @@ def hgt_rooflines(g, kt, E_local, N_local, K, X, H, hbm_view):
 
 def other_model(model, args, coo, dev, world):
     """BASELINE.json configs[1] (RGCN) / configs[3] (HGT, 8 heads) on the same graph, timed like the headline (barrier, K steps,
-    barrier) with fewer steps, with their own rooflines: the driver's default run then carries a number for every single-GPU
+    barrier) with fewer steps, with their own rooflines: a --full run then carries a number for every single-GPU
     config, not only the headline."""
     from het_amd import _lib as HL
     from het_amd.graph import HetGraph
@@ -449,15 +453,44 @@ def parse():
                    help="rgat = the BASELINE.json metric; rgcn / hgt time BASELINE.json configs[1] / configs[3] (single GPU)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-variants", action="store_true", help="skip timing the other reference flag combinations")
-    p.add_argument("--no-models", action="store_true", help="skip the RGCN / HGT legs (BASELINE.json configs[1], configs[3]) of the default run")
+    p.add_argument("--no-models", action="store_true", help="skip the RGCN / HGT legs (BASELINE.json configs[1], configs[3]) of a --full run")
     p.add_argument("--no-dist-rehearsal", action="store_true",
-                   help="skip the 8-way feat-128 partition rehearsal (BASELINE.json configs[4] on one GPU: dist_rehearsal) of the default run")
+                   help="skip the 8-way feat-128 partition rehearsal (BASELINE.json configs[4] on one GPU: dist_rehearsal) of a --full run")
     p.add_argument("--cpu-scale", type=float, default=0.25, help="graph scale of the CPU-baseline sample (1.0 = the full workload: "
                    "one warm-up + one timed iteration, about 3 minutes of host time -- outside the default run)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: the CPU baseline, per-kernel and per-op timers, rooflines, the reference-named ops, the "
+                        "other flag combinations, models and edge order, the partition rehearsal and the multi-rank exchange timers "
+                        "(each still subject to its --no-* option); a plain run times the headline steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most)")
     a = p.parse_args()
     if a.heads is None:
         a.heads = 8 if a.model == "hgt" else 4
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     return a
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, out, embed, layer):
+    """--dump-outputs: what a caller of the timed step receives from its last step, as float32 .npy files under `path`: the layer
+    output (out.npy), the gradient of the layer input (grad_x.npy) and every parameter gradient (grad_<parameter>.npy).  The
+    parameter gradients are written whole.  out and grad_x have one row per node (0.5 GB each at full size), so both keep the
+    same rows only: the first rows of a permutation seeded with 0, in ascending order, as many as the 64 MB limit leaves.  The
+    rows depend on the node count alone, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+    params = {"grad_" + n: q.grad for n, q in layer.named_parameters() if q.grad is not None}
+    room = DUMP_LIMIT_BYTES - sum(4 * t.numel() + 4096 for t in params.values()) - 2 * 4096  # (4096: an .npy header, at most)
+    n = out.shape[0]
+    rows = min(n, room // (4 * (out[0].numel() + embed.grad[0].numel())))
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:rows].sort().values.to(out.device)
+    arrays = {"out": out.detach().index_select(0, idx), "grad_x": embed.grad.index_select(0, idx), **params}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def layer_flags(variant):
@@ -601,11 +634,13 @@ def _main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (world > 1 or os.environ.get("HET_FORCE_DIST") == "1"):
+        raise SystemExit("bench.py --dump-outputs: the outputs of a partitioned run are spread over its ranks; dump a single-process run")
     # The host-cores baseline runs FIRST (it is ~60 s of CPU work and touches no GPU): everything after `gpu_phase_start` is one
     # contiguous window of GPU work, which is what a utilisation sampler outside this process wants to see.
     wall = {"process_start": _stamp()}
     cpu_res = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(args)
         wall["cpu_baseline_end"] = _stamp()
     wall["gpu_phase_start"] = _stamp()
@@ -678,6 +713,7 @@ def _main():
             embed.grad = None
             out = layer(g, embed, *extra)
             out.backward(go)
+            return out
 
     def barrier():
         if world > 1:
@@ -693,27 +729,33 @@ def _main():
     step_events = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        out_last = None  # (the previous step's output is released before the next step, as the warm-up steps release theirs)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        step()
+        out_last = step()
         b.record()
         step_events.append((a, b))
     barrier()
     dt = time.perf_counter() - t0
-    # per-kernel durations: a few more steps AFTER the timed region, with HIP-event pairs on the launch stream around the
-    # library's dominant kernels (include/het_amd.h: het_kernel_timing_enable) -- the headline steps run without that
-    # instrumentation (two event records per launch under a mutex)
-    ksteps = max(1, min(args.steps, 5))
-    HL.kernel_timing(True)
-    for _ in range(ksteps):
-        step()
-    barrier()
-    HL.kernel_timing(False)
+    if args.dump_outputs:  # (before the steps of --full below overwrite the gradients)
+        dump_outputs(args.dump_outputs, out_last, embed, layer)
+    del out_last
+    kt = {}
+    if args.full:
+        # per-kernel durations: a few more steps AFTER the timed region, with HIP-event pairs on the launch stream around the
+        # library's dominant kernels (include/het_amd.h: het_kernel_timing_enable) -- the headline steps run without that
+        # instrumentation (two event records per launch under a mutex)
+        ksteps = max(1, min(args.steps, 5))
+        HL.kernel_timing(True)
+        for _ in range(ksteps):
+            step()
+        barrier()
+        HL.kernel_timing(False)
+        # live per-kernel durations of the timed region: {kernel: (avg ms per launch, launches per step, ms per step)}; the roofline
+        # objects use ms per step = the summed duration of the launches that together implement the op in one step
+        kt = read_kernel_timers(ksteps)
     per_step = sorted(a.elapsed_time(b) for a, b in step_events)  # device time of every step (events, this rank)
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
-    # live per-kernel durations of the timed region: {kernel: (avg ms per launch, launches per step, ms per step)}; the roofline
-    # objects use ms per step = the summed duration of the launches that together implement the op in one step
-    kt = read_kernel_timers(ksteps)
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
@@ -724,7 +766,7 @@ def _main():
 
     # per-entry-point device time, from a few extra steps after the timed region (HIP events around every C-ABI call)
     per_op = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         HK.event_timers["*"] = []
         for _ in range(3):
             step()
@@ -742,7 +784,7 @@ def _main():
     # API-visible tensor once, indices at 8 B) / the kernel's own average duration in the timed region.  Only the
     # bytes of THAT op are counted -- work fused into the launch from other ops is reported beside it, not added.
     roofline = roofline_fwd = None
-    if args.model == "rgat":
+    if args.full and args.model == "rgat":
         S_row = S_col = None
         compact_flow = "HET_rgat_backward_src" in kt or "HET_gat_backward_src" in kt
         if compact_flow:
@@ -809,22 +851,22 @@ def _main():
                         ex["frac_with_per_edge_row_gather"] = round(req / (f_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
             roofline_fwd = hbm_view(f"{fname} (relational_fused_gat_separate_coo, kind {4 if S_row else 0}{'; also leaves the per-run sums grad_er is formed from' if isinstance(pmf, tuple) else ''})",
                                     f_ms, nf_, ex, pmc_name=pmf)
-    if args.model == "rgat" and world == 1 and not use_dist and roofline is not None and roofline_fwd is not None and S_row is not None:
+    if args.full and args.model == "rgat" and world == 1 and not use_dist and roofline is not None and roofline_fwd is not None and S_row is not None:
         ref = gather_rate_reference(g, dev, N_local, X)
         if ref:
             roofline["gather_rate_reference_ms"], roofline_fwd["gather_rate_reference_ms"] = ref["backward_ms"], ref["forward_ms"]
             roofline["gather_rate_reference_what"] = roofline_fwd["gather_rate_reference_what"] = ref["what"]
-    if args.model == "rgcn" and "HET_segment_sum" in kt and not use_dist:
+    if args.full and args.model == "rgcn" and "HET_segment_sum" in kt and not use_dist:
         roofline, roofline_fwd = rgcn_rooflines(g, kt, E_local, N_local, K, X, hbm_view)
-    if args.model == "hgt" and "HET_hgt_aggregate_rows" in kt and not use_dist:
+    if args.full and args.model == "hgt" and "HET_hgt_aggregate_rows" in kt and not use_dist:
         roofline, roofline_fwd = hgt_rooflines(g, kt, E_local, N_local, K, X, H, hbm_view)
-    kernel_ms = {k: {"avg_ms": round(v[0], 4), "launches_per_step": round(v[1], 2), "ms_per_step": round(v[2], 4)} for k, v in kt.items()}
+    kernel_ms = None if not args.full else {k: {"avg_ms": round(v[0], 4), "launches_per_step": round(v[1], 2), "ms_per_step": round(v[2], 4)} for k, v in kt.items()}
 
     # the reference-named ops exactly as the reference's model code calls them (kind 0, [E,H,D] feat), each launched a
     # few times on its own after the timed region: these are the SURVEY 8(d) worked figures (a4 7.28 GB, a5 13.86 GB,
     # a1 172.9 GFLOP at C3).  Entry-point HIP events on the launch stream: the whole op (its fills and every kernel).
     roofline_ops = roofline_gemm = None
-    if args.model == "rgat" and world == 1 and not use_dist:
+    if args.full and args.model == "rgat" and world == 1 and not use_dist:
         sc = g.get_separate_coo_original()
         d_src = {"separate_coo_rel_ptrs": sc["rel_ptrs"], "separate_coo_node_indices": sc["row_indices"],
                  "separate_coo_eids": sc["eids"]}
@@ -877,7 +919,7 @@ def _main():
         del Wp, retp, el, er, sm, ex_, rt, gfe, gel, ger
 
     dist_info = None
-    if use_dist:
+    if args.full and use_dist:
         # what every rank moved and waited for: a few more steps with the halo contexts' wait timers on
         import torch.distributed as dist
         halo = runner.dl.halo
@@ -944,14 +986,14 @@ def _main():
                                       "groupings": round(plan_bytes / 2**30, 2),
                                       "groupings_inside_torch_allocator": bool(HL.allocator_is_external())},
         }
-        if world == 1 and not args.no_variants and args.variant == "default" and args.model == "rgat":
+        if args.full and world == 1 and not args.no_variants and args.variant == "default" and args.model == "rgat":
             out["variants"] = other_variants(args, coo, dev, min(args.steps, 10), ms_per_step, value)
-        if world == 1 and not use_dist and not args.no_models and args.model == "rgat" and args.feat % 8 == 0:
+        if args.full and world == 1 and not use_dist and not args.no_models and args.model == "rgat" and args.feat % 8 == 0:
             # BASELINE.json configs[1] and configs[3] in the same line (about 10 s each)
             out["models"] = {m: other_model(m, args, coo, dev, world) for m in ("rgcn", "hgt")}
-        if world == 1 and not use_dist and not args.no_variants and args.model == "rgat" and args.edge_order != "random":
+        if args.full and world == 1 and not use_dist and not args.no_variants and args.model == "rgat" and args.edge_order != "random":
             out["edge_order_random"] = edge_order_random(args, dev)
-        if world == 1 and not use_dist and not args.no_dist_rehearsal and args.model == "rgat" and args.variant == "default":
+        if args.full and world == 1 and not use_dist and not args.no_dist_rehearsal and args.model == "rgat" and args.variant == "default":
             out["dist_rehearsal"] = dist_rehearsal(args, dev)
         if cpu_res is not None:
             out["cpu_baseline"] = cpu_res

@@ -2,7 +2,7 @@
 # same-box A/B on any model's step with EVERY timed launch printed (round 5, the dense kernels):
 #   exp/ab_dense.sh "<bench args, e.g. --model hgt>" name1 name2@ENV=v ...     (names as in exp/ab_r05.sh)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-A=$1; shift
+A="--full $1"; shift  # (the per-kernel timers are part of the --full line)
 for spec in "$@"; do
   n=${spec%%@*}
   envs=""

@@ -3,7 +3,7 @@
 #   ("cur" = the product library het_amd/libhet_amd.so, other names = exp/libs/lib_<name>.so; every name runs in the given order)
 # prints step time, the two gather ops (entry-to-return) and their launches' own durations
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-A=$1; shift
+A="--full $1"; shift  # (the per-op and per-kernel timers are part of the --full line)
 #   a name may carry environment switches: cur@HET_SIDE_STREAM=0@HET_RGAT_OVERLAP=0
 for spec in "$@"; do
   n=${spec%%@*}

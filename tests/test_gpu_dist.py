@@ -180,6 +180,35 @@ def test_bench_distributed_flow_one_rank(backend):
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["scaling"] == "strong"
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run times its --steps and nothing else, and --dump-outputs writes what the last timed step computed:
+    float32 arrays of 64 MB at most in all, the same from run to run with the same arguments."""
+    import sys
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HET_FORCE_DIST", "HET_DIST_BACKEND"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                           "--dump-outputs", str(d)], env)
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+        assert out["dtype"] == "f32" and out["unit"] == "million edges/s"
+        assert out["roofline"] is None and out["kernel_ms"] is None and out["per_op_ms"] is None
+        assert not {"cpu_baseline", "variants", "models", "edge_order_random", "dist_rehearsal"} & set(out)
+        files = sorted(os.listdir(d))
+        assert {"out.npy", "grad_x.npy", "grad_conv_weights.npy", "grad_loop_weight.npy"} <= set(files)
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10**6
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["out.npy"].shape[1] == 64 and arrays["out.npy"].shape == arrays["grad_x.npy"].shape
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    for f in dumps[0]:
+        torch.testing.assert_close(torch.from_numpy(dumps[1][f]), torch.from_numpy(dumps[0][f]), rtol=2e-4, atol=2e-5)
+
+
 @pytest.mark.parametrize("world,feat", [(2, 64), (4, 128)])
 def test_bench_ranks_through_torchrun(world, feat):
     """The driver's launch line for N = 2 / 4 (python -m torch.distributed.run ... bench.py --gpus N), the ranks sharing the one
@@ -192,7 +221,7 @@ def test_bench_ranks_through_torchrun(world, feat):
         env.pop(k, None)
     out = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(world), "--scale", "0.02", "--feat",
-                       str(feat), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env)
+                       str(feat), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env)
     assert out["n_gpus"] == world and out["value"] > 0
     assert "RCCL all-to-all" in out["config"]["parallelism"]
     d = out["dist"]
@@ -260,7 +289,7 @@ def test_bench_rccl_two_ranks():
         env.pop(k, None)
     out = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                        "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--scale", "0.05", "--steps",
-                       "3", "--warmup", "1", "--no-cpu-baseline"], env)
+                       "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env)
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["dist"]["ranks"] == 2 and "RCCL" in out["dist"]["backend"]
     assert len(out["dist"]["per_rank"]) == 2 and all(r["halo_rows_sent"] > 0 for r in out["dist"]["per_rank"])
 
