@@ -204,7 +204,11 @@ def _gat_case(g, kind, H, D, seed):
 def test_fused_gat_separate_coo(K, plan_mode, kind, H, D, n):
     # n = 24: ~50 edges per (relation, node) row, rows with several hundred -- the wave-per-item compact backward and
     # its split (atomic) rows; n = 300: ~4 per row -- the lane-group-per-item one
-    g = random_graph(seed=21, n=n, r=4, e=5000)
+    fused_gat_case(K, random_graph(seed=21, n=n, r=4, e=5000), kind, H, D)
+
+
+def fused_gat_case(K, g, kind, H, D):
+    """relational_fused_gat_separate_coo and its backward on graph g against the oracle (also tests/test_gpu_thresholds.py)."""
     s, feat, el, er, go, df, db = _gat_case(g, kind, H, D, seed=9)
     N, E, slope = g.get_num_nodes(), g.get_num_edges(), 0.2
     idx = (s["eids"], s["rel_ptrs"], s["row_indices"], s["col_indices"])
@@ -287,8 +291,11 @@ def test_rgat_compact_passes(K, H, D, n, e, fold, bias):
     relational_fused_gat_separate_coo pair with CompactAsOfNodeKind 4.  n = 12 / 40: (relation, source) rows with
     hundreds of edges (pieces of long segments add atomically, hub destinations are split over work items);
     n = 300: a few edges per row (several whole segments per pack); e = 700: packs of a single short segment."""
+    rgat_compact_case(K, random_graph(seed=27, n=n, r=4, e=e), H, D, fold, bias)
+
+
+def rgat_compact_case(K, g, H, D, fold, bias):
     import het_amd.kernels as k
-    g = random_graph(seed=27, n=n, r=4, e=e)
     s, feat, el, er, go, df, db = _gat_case(g, 4, H, D, seed=11)
     N, E, slope = g.get_num_nodes(), g.get_num_edges(), 0.2
     idx = (s["eids"], s["rel_ptrs"], s["row_indices"], s["col_indices"])
@@ -346,8 +353,11 @@ def test_rgat_compact_run_sums(K, H, D, n, e, fold, bias):
     per-edge term) against the oracle's CompactAsOfNodeKind-4 pair.  The er rows are the distinct (relation, destination) pairs
     here -- the precondition of this form (include/het_amd.h).  n = 12 / 20: hubs (more than 256 in-edges: parked work items,
     several runs per hub); n = 40: destinations of 33 .. 256 in-edges (a pack of their own); n = 300: several destinations per pack."""
+    rgat_run_sums_case(K, random_graph(seed=31, n=n, r=4, e=e), H, D, fold, bias)
+
+
+def rgat_run_sums_case(K, g, H, D, fold, bias):
     import het_amd.kernels as k
-    g = random_graph(seed=31, n=n, r=4, e=e)
     s = g.get_separate_coo_original()
     ss = g.get_separate_unique_node_indices_single_sided()
     N, E, R, slope = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels(), 0.2
@@ -507,8 +517,11 @@ def test_hgt_compact_passes(K, H, D, n, e):
     """het_hgt_aggregate_compact / het_hgt_backward_compact (include/het_amd.h) against oracle/ops.py::hgt_attention_rows in
     fp64 (backward: its autograd): a = softmax over the in-edges of <k'[srow], q[dst]> per head, out = SUM a * m[srow].  The layer-level parity with the oracle is tests/test_gpu_layers.py::test_hgt_layer_fused.
     n = 12 / 30 / 40: hub destinations split over work items and long (relation, source) segments whose pieces add atomically."""
+    hgt_compact_case(K, random_graph(seed=29, n=n, r=4, e=e), H, D)
+
+
+def hgt_compact_case(K, g, H, D):
     import het_amd.kernels as k
-    g = random_graph(seed=29, n=n, r=4, e=e)
     s = g.get_separate_coo_original()
     inv = g.get_separate_unique_node_indices_single_sided_inverse_idx()
     ss = g.get_separate_unique_node_indices_single_sided()
@@ -668,7 +681,10 @@ def test_gat_golden_round5_pins(K, plan_mode, golden_mag):
 # ---------------------------------------------------------------- RGCN
 @pytest.mark.parametrize("Kd,D", [(16, 16), (64, 64), (7, 3)])
 def test_rgcn_layer1(K, plan_mode, Kd, D):
-    g = random_graph(seed=31)
+    rgcn_layer1_case(K, random_graph(seed=31), Kd, D)
+
+
+def rgcn_layer1_case(K, g, Kd, D):
     s = g.get_separate_coo_original()
     R, N, E = g.get_num_rels(), g.get_num_nodes(), g.get_num_edges()
     gen = torch.Generator().manual_seed(8)
@@ -692,7 +708,10 @@ def test_rgcn_layer1(K, plan_mode, Kd, D):
 
 @pytest.mark.parametrize("direct", [False, True])
 def test_rgcn_compact_aggregation(K, plan_mode, direct):
-    g = random_graph(seed=32)
+    rgcn_compact_case(K, random_graph(seed=32), direct)
+
+
+def rgcn_compact_case(K, g, direct):
     s = g.get_separate_coo_original()
     ss, ssi = g.get_separate_unique_node_indices_single_sided(), g.get_separate_unique_node_indices_single_sided_inverse_idx()
     U, X, N, E = int(ss["rel_ptrs_row"][-1]), 16, g.get_num_nodes(), g.get_num_edges()
@@ -735,7 +754,10 @@ def _hub_graph(seed, N=500, E=6000, R=3):
 @pytest.mark.parametrize("H,dk,hub", [(8, 8, False), (8, 8, True), (4, 8, True), (16, 4, False), (2, 16, False), (3, 5, False),
                                       (1, 4, False)])
 def test_hgt_edge_softmax_fwd_bwd(K, plan_mode, H, dk, hub):
-    g = _hub_graph(9) if hub else random_graph(seed=61, n=260, r=4, e=4000)
+    hgt_softmax_case(K, _hub_graph(9) if hub else random_graph(seed=61, n=260, r=4, e=4000), H, dk)
+
+
+def hgt_softmax_case(K, g, H, dk):
     s = g.get_separate_coo_original()
     N, E, R = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels()
     gen = torch.Generator().manual_seed(12)
@@ -757,7 +779,10 @@ def test_hgt_edge_softmax_fwd_bwd(K, plan_mode, H, dk, hub):
 
 @pytest.mark.parametrize("H,dk", [(8, 8), (4, 16), (2, 6), (1, 64), (2, 32), (1, 32), (1, 128)])
 def test_hgt_fused_message_fwd_bwd(K, plan_mode, H, dk):
-    g = random_graph(seed=62, n=280, r=4, e=4500)
+    hgt_message_case(K, random_graph(seed=62, n=280, r=4, e=4500), H, dk)
+
+
+def hgt_message_case(K, g, H, dk):
     s = g.get_separate_coo_original()
     N, E, R = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels()
     gen = torch.Generator().manual_seed(13)
@@ -805,7 +830,10 @@ def test_inner_product_right_node(K, plan_mode, kind, H, dk):
 
 @pytest.mark.parametrize("H,dk", [(8, 8), (2, 6)])
 def test_hgt_fused_attention(K, plan_mode, H, dk):
-    g = random_graph(seed=64, n=230, r=3, e=3200)
+    hgt_attention_case(K, random_graph(seed=64, n=230, r=3, e=3200), H, dk)
+
+
+def hgt_attention_case(K, g, H, dk):
     s = g.get_separate_coo_original()
     N, E, R = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels()
     gen = torch.Generator().manual_seed(15)
@@ -847,8 +875,11 @@ def test_gat_and_hgt_on_a_graph_without_edges(K):
 def test_fused_gat_with_folded_attn_l(H, D, nrel):
     """el = <feat, attn_l[r]> + GAT under one autograd node (fold_attn_l of include/het_amd.h) against the unfused
     composition of the two reference-named functions, on a graph whose relations are interleaved (eids != arange)."""
+    folded_attn_l_case(random_graph(seed=77, n=300, r=nrel, e=5000, empty_rel=False), H, D)  # > 8 relations: separate weight-gradient pass
+
+
+def folded_attn_l_case(g, H, D):
     import het_amd.backend as B
-    g = random_graph(seed=77, n=300, r=nrel, e=5000, empty_rel=False)  # > 8 relations: separate weight-gradient pass
     s = g.get_separate_coo_original()
     assert not torch.equal(s["eids"], torch.arange(s["eids"].numel()))
     E, R = g.get_num_edges(), g.get_num_rels()

@@ -47,6 +47,104 @@ def permute_eids(g, seed):
     g._plans.clear()
 
 
+# Counts at which the grouped kernels change code path (HET_PACK_T = 32, the RGAT backward's pack threshold 64, HET_ITEM_MAX = 256, the
+# RGAT hub threshold 256, the edges per unrolled step of the gather loops) and the counts on either side of them.
+LADDER = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 383, 384, 385, 511, 512, 513, 769)
+# destinations whose in-edges are split over several relations: (destination total, runs per relation)
+LADDER_SPLITS = ((256, (128, 128)), (256, (100, 100, 56)), (256, (64, 64, 64, 64)),   # a total of exactly 256, every run shorter
+                 (257, (129, 128)), (257, (86, 86, 85)), (257, (65, 64, 64, 64)),     # 257: a hub made of short runs only
+                 (400, (300, 100)), (523, (513, 10)),                                  # a hub with a run longer than one work item
+                 (32, (16, 16)), (33, (17, 16)), (64, (32, 32)), (65, (33, 32)), (65, (20, 20, 25)))
+# rows per relation of the segment GEMMs (32-row MFMA tiles, 64-row tiles, 2048-row chunks), in an order that puts the relation
+# boundaries mid-tile
+ROW_LADDER = (1, 31, 0, 33, 2047, 32, 65, 2048, 63, 4097, 64, 2049)
+
+
+def ladder_graph(R=5, seed=0, shuffle=True, pool=3000, isolated=7):
+    """A HetGraph whose counts take every value of LADDER exactly, each independently of the others:
+      * in-degree per (relation, destination): one destination per rung, all its in-edges in one relation (so the destination
+        total is the rung too: single runs of 257 / 513 make hubs whose only run spans several work items);
+      * destinations whose in-edges split over several relations (LADDER_SPLITS);
+      * out-degree per (relation, source): one source per rung, in one relation.
+    The destination rungs take their sources from a pool of `pool` nodes, the source rungs their destinations from the same pool,
+    so that the pool's own counts stay small and no rung is disturbed.  Relation 2 is left empty (R >= 4), the last `isolated`
+    nodes have no edges, and with `shuffle` the eids are a random permutation.  With R < 4 the splits fold onto fewer relations
+    (runs of one relation merge); the rungs above stay exact.  About 11 000 edges."""
+    from het_amd.synth import IntegratedCOO
+    gen = torch.Generator().manual_seed(seed)
+    rels = [r for r in range(R) if not (R >= 4 and r == 2)]  # the relations that get edges
+    n_dst = len(LADDER) + len(LADDER_SPLITS)
+    dst0, src0 = 0, n_dst
+    pool0 = src0 + len(LADDER)
+    N = pool0 + pool + isolated
+    rows, cols, rtype = [], [], []
+
+    def add(src, dst, r):
+        rows.append(src)
+        cols.append(dst)
+        rtype.append(torch.full((src.numel(),), r, dtype=torch.int64))
+
+    for i, c in enumerate(LADDER):  # destination rungs (sources from the pool)
+        add(pool0 + torch.randint(0, pool, (c,), generator=gen), torch.full((c,), dst0 + i), rels[i % len(rels)])
+    for i, (total, runs) in enumerate(LADDER_SPLITS):
+        assert sum(runs) == total
+        v = dst0 + len(LADDER) + i
+        for j, c in enumerate(runs):
+            add(pool0 + torch.randint(0, pool, (c,), generator=gen), torch.full((c,), v), rels[(i + j) % len(rels)])
+    for i, c in enumerate(LADDER):  # source rungs (destinations from the pool)
+        add(torch.full((c,), src0 + i), pool0 + torch.randint(0, pool, (c,), generator=gen), rels[(i + 1) % len(rels)])
+    row, col, rel = torch.cat(rows), torch.cat(cols), torch.cat(rtype)
+    o = torch.randperm(row.numel(), generator=gen)  # edges of a relation in no particular order
+    row, col, rel = row[o], col[o], rel[o]
+    o = torch.sort(rel, stable=True).indices
+    coo = IntegratedCOO(N, R, torch.tensor([0, N]), row[o], col[o], rel[o], torch.arange(row.numel(), dtype=torch.int64))
+    g = HetGraph.from_integrated_coo(coo)
+    if shuffle:
+        permute_eids(g, seed + 1000)
+    return g
+
+
+def ladder_counts(g):
+    """The counts ladder_graph prescribes, as measured on a graph: {"in_rel": in-degree per (relation, destination), "in": per
+    destination over all relations, "out_rel": out-degree per (relation, source), "rel": edges per relation} (zeros dropped but
+    for "rel")."""
+    s = g.get_separate_coo_original()
+    N, R = g.get_num_nodes(), g.get_num_rels()
+    rel = torch.repeat_interleave(torch.arange(R), s["rel_ptrs"][1:] - s["rel_ptrs"][:-1])
+    nz = lambda t: t[t > 0]  # noqa: E731
+    return {"in_rel": nz(torch.bincount(rel * N + s["col_indices"], minlength=R * N)),
+            "in": nz(torch.bincount(s["col_indices"], minlength=N)),
+            "out_rel": nz(torch.bincount(rel * N + s["row_indices"], minlength=R * N)),
+            "rel": s["rel_ptrs"][1:] - s["rel_ptrs"][:-1]}
+
+
+def assert_rungs(counts, values, what=""):
+    """Every value of `values` occurs in the histogram `counts`."""
+    have = set(counts.tolist())
+    missing = [v for v in values if v not in have]
+    assert not missing, f"{what}: counts {missing} are not in the graph"
+
+
+def assert_ladder(g):
+    """The rungs of ladder_graph on `g` (R >= 4): every ladder count per (relation, destination), per destination and per
+    (relation, source); the split destinations' totals; an empty relation; nodes without edges."""
+    c = ladder_counts(g)
+    assert_rungs(c["in_rel"], LADDER, "in-degree per (relation, destination)")
+    assert_rungs(c["in"], LADDER + tuple(t for t, _ in LADDER_SPLITS), "in-degree per destination")
+    assert_rungs(c["out_rel"], LADDER, "out-degree per (relation, source)")
+    assert int((c["rel"] == 0).sum()) >= 1, "no empty relation"
+    s = g.get_separate_coo_original()
+    touched = torch.zeros(g.get_num_nodes(), dtype=torch.bool)
+    touched[s["row_indices"]] = True
+    touched[s["col_indices"]] = True
+    assert not bool(touched.all()), "every node has an edge"
+
+
+def row_ladder_ptrs():
+    """Relation pointers [len(ROW_LADDER) + 1] of a row list whose relations have the ROW_LADDER row counts."""
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.tensor(ROW_LADDER, dtype=torch.int64), 0)])
+
+
 def mag_graph(scale=2e-3):
     return HetGraph.from_integrated_coo(make_mag_like(scale=scale))
 
