@@ -30,10 +30,6 @@ from .rgat_fused_layer import OVERLAP, _edge_rows, _has_single_sided_lists, _sid
 from .rgnn_layers_and_funcs import rgnn_relational_matmul_no_scatter_gather_list as B_matmul_no_scatter_gather
 
 FUSED = os.environ.get("HET_HGT_FUSED", "1") != "0"
-# the layer's input gradient in one node-major pass per node type (csrc/node_sum.hip) instead of one read-modify-write launch
-# per relation on the 2X-wide source rows + the destination-side projection's own pass (HET_HGT_NODE_DX=0: the round-3 form)
-REFORK = os.environ.get("HET_HGT_REFORK", "1") != "0"  # diagnostic: 0 = the round-4 hazard of exp/hgt_cold_lag.py back in
-NODE_DX = os.environ.get("HET_HGT_NODE_DX", "1") != "0"
 
 
 def _node_dx_plan(G, ss, offs, K_in, X, dst):
@@ -139,7 +135,7 @@ class _FoldSourceWeights(th.autograd.Function):
 def fold_source_weights(k_lin, v_lin, rel_att, rel_msg, rel_pri, src_type, num_heads, fused_attn):
     """w_kv [R,1,in,2*H*dk] (module docstring).  k_lin / v_lin [T,1,in,H*dk]; rel_att / rel_msg [R,H,dk,dk]; rel_pri [R,H]."""
     if (FOLD_KERNEL and k_lin.is_cuda and k_lin.dtype == th.float32 and k_lin.dim() == 4 and k_lin.shape[1] == 1
-            and src_type.is_cuda and src_type.dtype == th.int64 and _k._lib.has("het_hgt_fold_source_weights")):
+            and src_type.is_cuda and src_type.dtype == th.int64):
         return _FoldSourceWeights.apply(k_lin, v_lin, rel_att, rel_msg, rel_pri, src_type.contiguous(), fused_attn)
     R, H, dk, _ = rel_att.shape
     K_in = k_lin.shape[2]
@@ -229,14 +225,16 @@ class HgtAttentionFunction(th.autograd.Function):
             side.wait_stream(main)
             with th.cuda.stream(side):
                 _k.rows_matmul_backward_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
-        nplan = _node_dx_plan(G, ss, offs, K_in, X, (lists[0], None, lists[1]) if ctx.compact_dst else None) if (NODE_DX and split_kv) else None
+        nplan = _node_dx_plan(G, ss, offs, K_in, X, (lists[0], None, lists[1]) if ctx.compact_dst else None) if split_kv else None
         if nplan is not None:
-            # every consumer of h adds its term in ONE pass over the nodes: the destination-side projection's gradient rows
-            # (g_q . Q_t^T) and, per relation the node is a source of, the two halves of its [k' | m] gradient row
+            # every consumer of h adds its term in ONE pass over the nodes (csrc/node_sum.hip) -- instead of one read-modify-write
+            # launch per relation on the 2X-wide source rows + the destination-side projection's own pass (the round-3 form): the
+            # destination-side projection's gradient rows (g_q . Q_t^T) and, per relation the node is a source of, the two halves
+            # of its [k' | m] gradient row
             grad_h, grad_qw = th.empty_like(h), th.empty_like(q_w)  # (allocated under the main stream)
             g_kv2, g_q2 = g_kv.view(-1, 2 * X), g_q.view(-1, X)
             wt2 = wt.view(-1, 2 * X, K_in)
-            if side is not None and REFORK:
+            if side is not None:
                 # grad_qw (and, on a graph seen for the first time, the plan's temporaries) were allocated AFTER the fork above: the
                 # allocator may have handed out blocks whose previous main-stream use was enqueued after that fork (the kernels
                 # that build the plan), and the side stream would write grad_qw while they still run -- seen once in ~40 cold

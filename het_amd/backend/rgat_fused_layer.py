@@ -37,17 +37,7 @@ from ..kernels import K
 _OFFS = {}
 PER_EDGE = os.environ.get("HET_RGAT_PER_EDGE") == "1"      # default flags on the per-edge (kind 0) dataflow
 LITERAL_ER = os.environ.get("HET_RGAT_LITERAL_ER") == "1"  # er = (x . W) . attn_r unless the layer flag asks otherwise
-RUN_SUMS = os.environ.get("HET_RGAT_RUN_SUMS", "1") != "0"  # A/B switch: grad_er from the forward's run sums
 OVERLAP = os.environ.get("HET_RGAT_OVERLAP", "1") != "0"  # independent launches on a second HIP stream (see _side_stream)
-ATTN_GRAD_IN_PASS = os.environ.get("HET_RGAT_ATTN_GRAD_IN_PASS", "1") != "0"  # grad_attn_l from the source-row kernels
-NODE_ORDER = os.environ.get("HET_RGAT_NODE_ORDER", "1") != "0"  # node-major pass over nodes sorted by relation presence
-NODE_GEMM = os.environ.get("HET_RGAT_NODE_GEMM", "1") != "0"  # backward GEMMs per node (csrc/node_gemm.hip); 0: per relation
-# A/B: the self-loop weight gradient with the other weight gradients beside the node-major pass instead of at the start of the
-# backward, where it stretches the two short per-destination passes (profiles/r04/default_timeline.txt): 3.97 -> 4.02 ms, kept off
-LOOP_DW_LATE = os.environ.get("HET_RGAT_LOOP_DW_LATE", "0") == "1"
-# the bias gradient (column sums of grad_h) from the self-loop's weight-gradient launch, which streams grad_h anyway, instead of
-# a pass of its own inside the gather op (0.088 ms on ogbn-mag).  HET_RGAT_BIAS_IN_DW=0: A/B
-BIAS_IN_DW = os.environ.get("HET_RGAT_BIAS_IN_DW", "1") != "0"
 
 
 def _mulfirst_shape_ok(H, Kd):
@@ -141,9 +131,6 @@ def _side_stream(dev):
     return s
 
 
-PIECEWISE_PUSH = os.environ.get("HET_DIST_PIECEWISE", "1") != "0"  # project the halo rows piece by piece as they arrive
-
-
 def _halo_pieces(g, ss, plan):
     """The unique (relation, source) list of a partition's local graph cut by when the source node's row of x is there: the
     owned nodes together with piece 0 of the halo exchange, then every further piece (local ids n_own + halo_chunk_ptr[c] ..).
@@ -235,7 +222,8 @@ class RgatLayerFunction(th.autograd.Function):
                 else:
                     h = _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c)
             dot_ok = _k.matmul_attn_dot_ok(H, Kd, D)
-            if halo is not None and halo.chunks > 1 and PIECEWISE_PUSH and dot_ok:
+            piecewise = halo is not None and halo.chunks > 1 and dot_ok
+            if piecewise:
                 # the exchange arrives in pieces (het_amd/dist.py: DistPlan.chunks): the rows whose source node is owned are
                 # projected at once, the rows of piece c as soon as piece c is there -- piece c + 1 is on the wire meanwhile
                 for c, (rp_c, nodes_c, rows_c) in enumerate(_halo_pieces(g, ss, halo.plan)):
@@ -244,7 +232,7 @@ class RgatLayerFunction(th.autograd.Function):
                 halo.finish_push()
             elif halo is not None:
                 halo.finish_push()
-            if halo is not None and halo.chunks > 1 and PIECEWISE_PUSH and dot_ok:
+            if piecewise:
                 pass  # (projected above)
             elif dot_ok:
                 _k.matmul_attn_dot(d_row, 1, W, x, featc, attn_l, elc)  # el_c = <feat_c, attn_l[r]> from the GEMM epilogue
@@ -256,7 +244,7 @@ class RgatLayerFunction(th.autograd.Function):
             # edge softmax + aggregation straight from the compact tables: no exp [E,H] tensor (csrc/gat_compact.hip)
             srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
             # (run sums: grad_er from S_col rows the forward leaves instead of a per-edge term -- csrc/gat_compact.hip)
-            run_sums = RUN_SUMS and _k.rgat_runs_shape_ok(H, D)
+            run_sums = _k.rgat_runs_shape_ok(H, D)
             grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp if run_sums else None,
                                             drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
             # (elc IS <featc, attn_l[relation of the row]>: the pass may form it from the rows it gathers -- kernels.py)
@@ -311,7 +299,7 @@ class RgatLayerFunction(th.autograd.Function):
             return RgatLayerFunction._backward_with_halo(ctx, grad_h)
         grad_bias = grad_h.sum(0) if (ctx.has_bias and not ctx.compact) else None
         Wt = th.transpose(W, 2, 3).contiguous()
-        if ctx.compact and ctx.mulfirst and NODE_GEMM and _k.rgat_node_gemm_ok(R, H, Kd, D) and _destinations_below(col, nd):
+        if ctx.compact and ctx.mulfirst and _k.rgat_node_gemm_ok(R, H, Kd, D) and _destinations_below(col, nd):
             return RgatLayerFunction._backward_node_major(ctx, grad_h, Wt)
         grad_W = th.zeros_like(W)
         # one input-gradient buffer: the self-loop writes its rows with plain stores, the projections add to it
@@ -409,17 +397,21 @@ class RgatLayerFunction(th.autograd.Function):
         # (the weight gradient of attn_l from the same pass when the forward left run sums: csrc/gat_compact.hip ga_block_reduce;
         #  grad_el_c then has no reader left -- its other consumer, the gradient through el, is folded into grad_feat_c -- and is
         #  not written at all)
-        attn_in_pass = ATTN_GRAD_IN_PASS and ctx.runs is not None and R <= 8
+        attn_in_pass = ctx.runs is not None and R <= 8
         g_featc, g_erc = th.empty_like(featc), th.empty_like(erc)  # overwritten
-        g_elc = None if (attn_in_pass and _k._lib.has("het_grouping_note_stream")) else th.empty_like(elc)  # (a round-5 library)
+        g_elc = None if attn_in_pass else th.empty_like(elc)
         grad_bias = th.empty(X, dtype=x.dtype, device=x.device) if ctx.has_bias else None
         grad_loop = th.empty_like(loop_w) if ctx.has_loop else None
-        # (the self-loop product names each of the nd output rows once: the column sums of its gradout rows ARE the bias gradient)
+        # (the self-loop product names each of the nd output rows once: the column sums of its gradout rows ARE the bias gradient,
+        #  from the weight-gradient launch that streams grad_h anyway instead of a pass of its own inside the gather op: 0.088 ms on
+        #  ogbn-mag)
         # (offs = [0, nd] by construction in forward())
-        bias_in_dw = BIAS_IN_DW and ctx.has_bias and ctx.has_loop and _k._lib.has("het_rows_matmul_backward_dw_colsum")
+        bias_in_dw = ctx.has_bias and ctx.has_loop
         main, side = th.cuda.current_stream(x.device), _side_stream(x.device) if OVERLAP else None
-        if side is not None and ctx.has_loop and not LOOP_DW_LATE:
+        if side is not None and ctx.has_loop:
             # the self-loop weight gradient needs x and grad_h only: an HBM-bound stream of rows beside the gather passes below
+            # (at the start of the backward: beside the node-major pass instead it stretched the two short per-destination
+            #  passes, profiles/r04/default_timeline.txt: 3.97 -> 4.02 ms)
             side.wait_stream(main)
             with th.cuda.stream(side):
                 _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
@@ -441,7 +433,7 @@ class RgatLayerFunction(th.autograd.Function):
             if not attn_in_pass:
                 _k.matmul_no_scatter_gather_backward(rp_row, attn_l.unsqueeze(2), featc, g_elc, None, grad_attn_l.unsqueeze(-1),
                                                      accumulate=False)
-            if ctx.has_loop and (side is None or LOOP_DW_LATE):
+            if ctx.has_loop and side is None:
                 _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
                                            colsum=grad_bias if bias_in_dw else None)
             _k.rows_matmul_backward_dw(rp_row, ss["node_indices_row"], x, g_featc.view(-1, X), grad_W, accumulate=False)
@@ -449,7 +441,7 @@ class RgatLayerFunction(th.autograd.Function):
                                accumulate=False)
 
         # (on a block only the first nd nodes carry the self-loop term: they stay in front, so that term's tiles are whole too)
-        order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None) if NODE_ORDER else None
+        order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None)
 
         def input_gradient():
             _k.rgat_node_backward_dx(0, N, nd, gh, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc, wa_t, dst_map, grad_x,
@@ -493,11 +485,11 @@ class RgatLayerFunction(th.autograd.Function):
         grad_x = th.empty_like(x)
         grad_W, grad_loop = th.empty_like(W), th.empty_like(loop_w)
         grad_attn_l = th.empty_like(attn_l)
-        node_major = NODE_GEMM and _k.rgat_node_gemm_ok(R, H, Kd, D)
+        node_major = _k.rgat_node_gemm_ok(R, H, Kd, D)
         # as on one GPU (_backward_node_major): the weight gradients are HBM-bound streams of rows -- on the side stream beside the
         # gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once
         main, side = th.cuda.current_stream(x.device), (_side_stream(x.device) if OVERLAP and x.is_cuda else None)
-        bias_in_dw = BIAS_IN_DW and ctx.has_bias and _k._lib.has("het_rows_matmul_backward_dw_colsum")  # (as in _backward_node_major)
+        bias_in_dw = ctx.has_bias  # (as in _backward_node_major)
         if side is not None:
             side.wait_stream(main)
             with th.cuda.stream(side):
@@ -506,7 +498,7 @@ class RgatLayerFunction(th.autograd.Function):
         if not node_major:
             grad_x[nd:].zero_()  # halo rows: only the projection's input gradient adds to them
             _k.rows_matmul_backward_dx(offs, None, loop_w.t().contiguous().view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
-        attn_in_pass = ATTN_GRAD_IN_PASS and ctx.runs is not None and R <= 8 and x.is_cuda
+        attn_in_pass = ctx.runs is not None and R <= 8 and x.is_cuda
         _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:nd], ret[:nd], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
                                  row_rel_ptrs=rp_row, grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=ctx.runs,
                                  drow_nodes=ss["node_indices_col"], grad_attn_l=grad_attn_l if attn_in_pass else None)
@@ -530,7 +522,7 @@ class RgatLayerFunction(th.autograd.Function):
             row_map = _k.node_row_map(rp_row, rows_node, N)
             dst_map = _k.node_row_map(ss["rel_ptrs_col"], ss["node_indices_col"], N)
             loop_wt = loop_w.t().contiguous()
-            order = _k.node_order_by_presence(row_map, dst_map, split=nd) if NODE_ORDER else None
+            order = _k.node_order_by_presence(row_map, dst_map, split=nd)
             args = (grad_h, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc, wa_t.view(R, H, Kd), dst_map, grad_x, order)
             _k.rgat_node_backward_dx(nd, N, nd, *args)
             halo.start_return(grad_x)

@@ -4,8 +4,6 @@
 // step; partial sums are combined with xor-shuffles and every destination row
 // is written once -- no float atomics except for hub destinations whose
 // segment was split over several items (> HET_ITEM_MAX in-edges).
-#include <stdlib.h>
-
 #include "coop.hip.h"
 #include "fused_gat.hip.h"
 #include "seg_reduce.hip.h"
@@ -701,9 +699,8 @@ __global__ __launch_bounds__(kBlock) void HET_gat_backward_src_slot(
     default: { constexpr int LPR = 32, DL = 32; CALL; break; }              \
   }
 static bool gat_coop_shape(int H, int D) {
-  static const bool off = [] { const char* v = getenv("HET_GAT_COOP"); return v && v[0] == '0'; }();  // A/B switch
   const int lpr = H * D / 4, dl = D / 4;
-  return !off && (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr && D % 4 == 0;
+  return (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr && D % 4 == 0;
 }
 
 // Destinations with few in-edges on average: a lane group per item instead of a wave per item (layer path kernels).

@@ -17,7 +17,7 @@
 //             rows in flight per lane group whatever the segment lengths are; rows of a segment are summed in registers
 //             and stored once.  LONG segments (61 % of the edges of the skewed ogbn-mag-like graph): wave per work item
 //             of <= HET_ITEM_MAX edges, lane groups round-robin, one cross-group reduction and store per item.
-//             grad_er: from the forward's run sums (HET_rgat_grad_er_runs), or -- het_rgat_backward_compact -- a per-edge
+//             grad_er: from the forward's run sums (HET_rgat_drow_pass), or -- het_rgat_backward_compact -- a per-edge
 //             term summed per er row.
 #include <stdlib.h>
 
@@ -681,12 +681,10 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
     for (int q = 0; q < U; ++q) {
       if (j0 + q < e) {  // (uniform within the lane group, like everything below)
         const int tagq = head_bcast_i<DL>(tagv, q, lane);
-#ifndef HET_ABL_NO_HIO
         if (hio && (tagq & HET_TAG_FIRST_KEY)) {  // the destination's row of the layer output so far: needed when the destination ends
           const int dstq = head_bcast_i<DL>(dstv, q, lane);
           if (dstq < hio_rows) h0 = ld4_at<O>(hio, ((O)dstq << RS) | xb);
         }
-#endif
         if (ELR) {  // s of the edge from its row: every lane of the head forms it (no broadcast of a gathered term)
           const int rel = tagq >> HET_TAG_REL_SHIFT;
           if (rel != rel_cur) {  // (a run lies in one relation: at most once per run)
@@ -700,31 +698,21 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
         }
         if (tagq & HET_TAG_LAST_RUN) {  // the run ends with this edge: its sums, relative to the maximum of this moment
           const int drowq = head_bcast_i<DL>(drowv, q, lane);
-#ifndef HET_ABL_NO_Q
           st4_at<O>(qrow, ((O)drowq << RS) | xb, accq);
-#endif
-#ifndef HET_ABL_NO_QS
           if (d == 0) {
             st1_at<O>(qsum, ((O)drowq << HS) | hb, sq);
             st1_at<O>(qref, ((O)drowq << HS) | hb, m);
           }
-#endif
           accq = make_float4(0.f, 0.f, 0.f, 0.f);
           sq = 0.f;
           if (tagq & HET_TAG_LAST_KEY) {  // ... and so does the destination
             const int dstq = head_bcast_i<DL>(dstv, q, lane);
             const float inv = __builtin_amdgcn_rcpf(ssum);
             const float4 r4 = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-#ifndef HET_ABL_NO_RET
             st4_at<O>(ret, ((O)dstq << RS) | xb, r4);
-#endif
-#ifndef HET_ABL_NO_HIO
             if (hio && dstq < hio_rows)
               st4_at<O>(hio, ((O)dstq << RS) | xb, make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
-#endif
-#ifndef HET_ABL_NO_LSE
             if (d == 0) st1_at<O>(lse, ((O)dstq << HS) | hb, lse_fast(m, ssum));
-#endif
             acc = make_float4(0.f, 0.f, 0.f, 0.f);
             ssum = 0.f;
             m = -INFINITY;
@@ -962,31 +950,6 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs(
   }
 }
 
-// grad_er[w,h] = exp(ref[w,h] - lse[v,h]) (<gradout[v,h,:], Q[w,h,:]> - <gradout, ret>[v,h] q[w,h]),  v = drow_nodes[w];
-// pack2 [N,H,2] = {lse, <gradout, ret>}.  An er row without edges (q == 0, rows never written) gets 0.
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void HET_rgat_grad_er_runs(const float* __restrict__ qrow, const float* __restrict__ qsum,
-                                                                 const float* __restrict__ qref, const int64_t* __restrict__ drow_nodes,
-                                                                 const float* __restrict__ pack2, const float* __restrict__ gradout,
-                                                                 float* __restrict__ grad_er, int64_t n_rows, int H, int D) {
-  constexpr int EPW = 64 / LPR, X = LPR * 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = x / D, DL = D >> 2;
-  const int64_t step = (int64_t)gridDim.x * (kBlock / 64) * EPW;
-  for (int64_t w0 = ((int64_t)blockIdx.x * (kBlock / 64) + wave) * EPW; w0 < n_rows; w0 += step) {
-    const bool ok = w0 + slot < n_rows;
-    const int64_t w = ok ? w0 + slot : n_rows - 1;
-    const int64_t v = drow_nodes[w];
-    const float sq = qsum[w * H + h];
-    const float4 g = ld4(gradout + v * X + x), q = ld4(qrow + w * X + x);
-    const float2 pkv = *reinterpret_cast<const float2*>(pack2 + (v * H + h) * 2);
-    const float ref = qref[w * H + h];
-    float dot = g.x * q.x + g.y * q.y + g.z * q.z + g.w * q.w;
-    for (int off = DL >> 1; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
-    if (ok && (sub & (DL - 1)) == 0) grad_er[w * H + h] = sq == 0.f ? 0.f : __expf(ref - pkv.x) * (dot - pkv.y * sq);
-  }
-}
-
 // ---- weight gradient of the attention vector from the rows the source-row kernels hold ---------------------------------
 // grad_attn_l[r,h,:] = SUM_u grad_el[u,h] feat_c[u,h,:] over the rows u of relation r: a separate row-dot pass read feat_c again
 // (0.6 GB, 0.15 ms alone and 0.4 ms beside the matrix-core passes).  The source-row kernels have both factors in registers where
@@ -1062,7 +1025,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_attn_grad_finish(const float*
 // Backward, cooperative form of HET_rgat_backward_src_packed.  pack2 [N,H,2] = {lse, <gradout, ret>} interleaved.
 // GA: also the partial rows of grad_attn_l (ga_block_reduce above; needs fold_w for the relation of a row)
 // REC: er / lse / <gradout, ret> of an edge come from ONE 16-byte record per (er row, head) -- rec4 [S_col, H] {er, lse, dot, 0},
-// HET_rgat_drow_rec -- instead of a 4-byte gather from er and an 8-byte one from pack2: a vector-memory instruction and a
+// HET_rgat_drow_pass -- instead of a 4-byte gather from er and an 8-byte one from pack2: a vector-memory instruction and a
 // 128-byte line less per edge (the gathers of these kernels miss L2 once per table and edge: profiles/r04/locality_counters.txt)
 // Round 5 (see HET_rgat_aggregate_runs_packed): where a segment starts / ends and the relation of its row come from the tag of the
 // packed id record (no carried key, no compares against the neighbours, no boundary search), addresses are 32-bit byte offsets off
@@ -1285,24 +1248,9 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
   }
 }
 
-// rec4[w, h] = {er[w, h], lse[v, h], <gradout, ret>[v, h], 0}, v = drow_nodes[w]: everything the source-row kernels need per edge
-// from the destination side, one 16-byte record per (er row, head).  pack2 [N,H,2] interleaved (HET_rgat_dst_pack).
-__global__ __launch_bounds__(kBlock) void HET_rgat_drow_rec(const float* __restrict__ er, const float* __restrict__ pack2,
-                                                             const int64_t* __restrict__ drow_nodes, int64_t n_rows, int H,
-                                                             float* __restrict__ rec4) {
-  const int64_t total = n_rows * H;
-  for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (int64_t)gridDim.x * kBlock) {
-    const int64_t w = t / H;
-    const int h = (int)(t - w * H);
-    const int64_t v = drow_nodes[w];
-    const float2 p = *reinterpret_cast<const float2*>(pack2 + (v * H + h) * 2);
-    st4(rec4 + t * 4, make_float4(er[t], p.x, p.y, 0.f));
-  }
-}
-
 // Round 5: everything the backward needs per er row w = (relation, destination v) in ONE pass, instead of a pass over all N nodes
-// (HET_rgat_dst_pack: {lse, <gradout, ret>} per node), a pass over the er rows that re-packs it (HET_rgat_drow_rec) and, after the
-// source-row kernels, a third one (HET_rgat_grad_er_runs) that reads gradout[v] once more:
+// (HET_rgat_dst_pack: {lse, <gradout, ret>} per node), a pass over the er rows that re-packs it and, after the source-row kernels,
+// a third one that reads gradout[v] once more (round 4):
 //   rec4[w,h]    = {er[w,h], lse[v,h], <gradout[v,h,:], ret[v,h,:]>, 0}                    (read per edge by the source-row kernels)
 //   grad_er[w,h] = exp(ref[w,h] - lse[v,h]) (<gradout[v,h,:], Q[w,h,:]> - <gradout, ret>[v,h] q[w,h]),  0 for a row without edges
 // gradout / ret rows of a destination with several relations are read once per relation (adjacent work: cache hits); nodes
@@ -1428,9 +1376,8 @@ inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
     default: { constexpr int LPR = 32, DL = 32; CALL; break; }              \
   }
 static bool coop_shape_ok(int64_t H, int64_t D) {
-  static const bool off = [] { const char* v = getenv("HET_RGAT_COOP"); return v && v[0] == '0'; }();  // A/B switch
   const int64_t lpr = H * D / 4, dl = D / 4;
-  return !off && (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr;
+  return (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr;
 }
 
 static bool compact_shape_ok(int64_t H, int64_t D) {
@@ -1519,11 +1466,6 @@ static int rgat_bwd_pack_t() {
   return v;
 }
 
-static bool hub_in_row_order() {
-  static const bool on = [] { const char* e = getenv("HET_RGAT_HUB_ORDER"); return !(e && e[0] == '0'); }();  // A/B switch
-  return on;
-}
-
 extern "C" int64_t het_rgat_aggregate_compact_runs_workspace(const het_grouping* by_dst, const het_grouping* by_dst_rel,
                                                              int64_t num_rels, int64_t H, int64_t D, het_stream stream) {
   if (!by_dst || !by_dst_rel || num_rels <= 0) return -1;
@@ -1562,10 +1504,9 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
     if (int rc = grouping_packed_ids(by_dst, false, s)) return rc;
   float* part = static_cast<float*>(workspace);
   // el from the gathered row (ElFold above): heads of 16 floats, up to 8 relations, the caller names the relation boundaries of the
-  // feat rows (host array [R+1]) and attn_l [R, H*D]; otherwise (or HET_RGAT_EL_FROM_ROW=0) el_c is gathered per edge
-  static const bool el_from_row = [] { const char* v = getenv("HET_RGAT_EL_FROM_ROW"); return !(v && v[0] == '0'); }();
+  // feat rows (host array [R+1]) and attn_l [R, H*D]; otherwise el_c is gathered per edge
   ElFold ef{};
-  const bool elr = el_from_row && attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels &&
+  const bool elr = attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels &&
                    (reinterpret_cast<uintptr_t>(attn_l) & 15) == 0;
   if (elr) {
     ef.attn = attn_l; ef.R = (int)num_rels;
@@ -1612,7 +1553,7 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
       const unsigned nbh = (unsigned)ceil_div64(n_hub, kBlock / 64);
 #define HET_HUBS_LAUNCH2(ELRV, WV)                                                                                              \
   hipLaunchKernelGGL((HET_rgat_aggregate_hub_items<LPR, DL, ELRV, WV>), dim3(nbh), dim3(kBlock), 0, s2, it, by_dst_rel->hub_items,  \
-                     hub_in_row_order() ? by_dst_rel->hub_order : nullptr, n_hub, by_dst->p01, feat_c, el_c, er_c,                 \
+                     by_dst_rel->hub_order, n_hub, by_dst->p01, feat_c, el_c, er_c,                 \
                      (float)slope, part, ef)
 #define HET_HUBS_LAUNCH(ELRV) do { if (w64) { HET_HUBS_LAUNCH2(ELRV, true); } else { HET_HUBS_LAUNCH2(ELRV, false); } } while (0)
       if (elr) {
@@ -1690,9 +1631,11 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   const int64_t bias_part_rows = grad_bias ? (int64_t)kBiasBlocks * (kBlock / 64) : 0;
   const int64_t ga_rows = (grad_attn_l && E > 0) ? attn_grad_partial_rows(pv, X) : 0, n_ga = (ga_rows * (X + 1) + 3) / 4 * 4;
   const int64_t n_pack = (num_nodes * 2 * H + 3) / 4 * 4, n_tbuf = runs ? 0 : (E * H + 3) / 4 * 4;  // 16-byte aligned pieces
-  static const bool rec_on = [] { const char* v = getenv("HET_RGAT_DROW_REC"); return !(v && v[0] == '0'); }();  // A/B switch
-  const bool use_rec = runs && coop && rec_on && E > 0 && num_dst_rows > 0;
-  const int64_t n_rec = (runs && coop) ? num_dst_rows * H * 4 : 0;
+  // Run-sum form (runs implies coop): one pass over the er rows (HET_rgat_drow_pass) leaves both the records the source-row kernels
+  // read and grad_er, instead of dst pack + record pack + grad_er pass; the bias gradient's column sums then are a pass of their own
+  // on the side stream
+  const bool use_rec = runs && E > 0 && num_dst_rows > 0;
+  const int64_t n_rec = runs ? num_dst_rows * H * 4 : 0;
   const int64_t need = (int64_t)sizeof(float) * (n_pack + n_tbuf + bias_part_rows * X + n_ga + n_rec);
   HET_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_backward_compact_workspace)", op, (long long)need);
@@ -1707,11 +1650,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     HET_HIP(hipMemsetAsync(grad_feat_c, 0, sizeof(float) * num_src_rows * X, s));
     if (grad_el_c) HET_HIP(hipMemsetAsync(grad_el_c, 0, sizeof(float) * num_src_rows * H, s));
   }
-  // One pass over the er rows (HET_rgat_drow_pass: the records of the source-row kernels AND grad_er) instead of dst pack + record
-  // pack + grad_er pass; the bias gradient's column sums then are a pass of their own on the side stream (HET_RGAT_DROW_PASS=0: A/B)
-  static const bool drow_pass_on = [] { const char* v = getenv("HET_RGAT_DROW_PASS"); return !(v && v[0] == '0'); }();
-  const bool fused_drow = use_rec && drow_pass_on;
-  if (num_nodes > 0 && !fused_drow) {
+  if (num_nodes > 0 && !use_rec) {
     const unsigned nbp = grad_bias ? kBiasBlocks : grid_for(num_nodes * (X / 4));
     {
       HET_KTIME("HET_rgat_backward_dst_pack", s);
@@ -1724,11 +1663,6 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   }
   if (E == 0) {
     if (grad_bias && num_nodes > 0) {
-      if (fused_drow) {
-        HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_colsum_rows<LPR>, dim3(kBiasBlocks), dim3(kBlock), 0, s, gradout,
-                                                          bias_rows < num_nodes ? bias_rows : num_nodes, bias_part));
-        HET_LAUNCH_CHECK("HET_rgat_colsum_rows");
-      }
       hipLaunchKernelGGL(HET_rgat_colsum_finish, dim3((unsigned)X), dim3(kBlock), 0, s, bias_part, bias_part_rows, (int)X, grad_bias);
       HET_LAUNCH_CHECK("HET_rgat_colsum_finish");
     }
@@ -1737,26 +1671,16 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   }
   Packs pk{pv.pack_ptr, by_srow->key_of_rank, pv.num_packs};
   const unsigned nb = (unsigned)ceil_div64(pv.num_packs, (int64_t)(kBlock / 64) * (64 / (X / 4)));
-  if (fused_drow) {  // before the fork: both source-row launches read the records
-    // (the rows in the order of their destination nodes; the order is kept with by_srow, the one grouping this path always has.
-    //  HET_RGAT_DROW_ORDER=0: A/B)
-    static const bool drow_order_on = [] { const char* v = getenv("HET_RGAT_DROW_ORDER"); return !(v && v[0] == '0'); }();
-    const int32_t* drow_order = nullptr;
-    if (drow_order_on && num_dst_rows > 0) {
-      if (int rc = grouping_value_order(by_srow, runs->drow_nodes, num_dst_rows, s)) return rc;
-      drow_order = by_srow->val_order;
-    }
+  if (use_rec) {  // before the fork: both source-row launches read the records
+    // (the rows in the order of their destination nodes; the order is kept with by_srow, the one grouping this path always has)
+    if (int rc = grouping_value_order(by_srow, runs->drow_nodes, num_dst_rows, s)) return rc;
     HET_KTIME("HET_rgat_backward_drow_pass", s);
     const unsigned nbd = (unsigned)ceil_div64(num_dst_rows, (int64_t)(kBlock / 64) * (64 / (X / 4)) * 2);
     HET_DISPATCH_COOP((int)(X / 4), (int)(D / 4),
                       hipLaunchKernelGGL((HET_rgat_drow_pass<LPR, DL>), dim3(nbd), dim3(kBlock), 0, s, er_c, sum, ret, gradout,
-                                         runs->q_rows, runs->q_sum, runs->q_ref, runs->drow_nodes, drow_order, num_dst_rows, rec4,
+                                         runs->q_rows, runs->q_sum, runs->q_ref, runs->drow_nodes, by_srow->val_order, num_dst_rows, rec4,
                                          grad_er_c));
     HET_LAUNCH_CHECK("HET_rgat_drow_pass");
-  } else if (use_rec) {
-    hipLaunchKernelGGL(HET_rgat_drow_rec, dim3(grid_for(num_dst_rows * H)), dim3(kBlock), 0, s, er_c, pack, runs->drow_nodes, num_dst_rows,
-                       (int)H, rec4);
-    HET_LAUNCH_CHECK("HET_rgat_drow_rec");
   }
   const float* er_arg = use_rec ? rec4 : er_c;
   bool w64 = true;
@@ -1778,12 +1702,12 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   }
   // Two chains after the per-destination pack, joined at the end (kernel trace on ogbn-mag: the short-segment launch 1.10 ms beside
   // the long-segment one 1.09 ms; with the small launches in front of the short one the op was 0.1 ms longer):
-  //   caller's stream: short segments, grad_er from the run sums
+  //   caller's stream: short segments
   //   side stream:     bias column sums (needed by nobody here), zeroed rows of the split segments, long segments
   HetFork fk(s);
   hipStream_t s2 = fk.side;
   if (grad_bias && num_nodes > 0) {
-    if (fused_drow) {
+    if (use_rec) {
       HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_colsum_rows<LPR>, dim3(kBiasBlocks), dim3(kBlock), 0, s2, gradout,
                                                         bias_rows < num_nodes ? bias_rows : num_nodes, bias_part));
       HET_LAUNCH_CHECK("HET_rgat_colsum_rows");
@@ -1839,17 +1763,13 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
 #undef HET_SRC_LONG2
     }
   } else {
-    static const int u_rows = [] { const char* v = getenv("HET_RGAT_BWD_U"); return v ? atoi(v) : 4; }();  // A/B switch
     const int skip_long = pv.num_long_items > 0 ? 1 : 0;
     {
       HET_KTIME("HET_rgat_backward_src_short", s);
-#define HET_BWD_PACKED(UU)                                                                                                 \
-  HET_DISPATCH_LPR((int)(X / 4),                                                                                           \
-                   hipLaunchKernelGGL((HET_rgat_backward_src_packed<LPR, UU>), dim3(nb), dim3(kBlock), 0, s, pk, by_srow->p0, \
-                                      by_srow->p1, feat_c, el_c, er_c, pack, gradout, grad_feat_c, grad_el_c, tbuf, (int)H, \
-                                      (int)D, (float)slope, fold_attn_l, row_rel_ptrs, (int)num_rels, skip_long))
-      if (u_rows == 2) { HET_BWD_PACKED(2); } else if (u_rows == 8) { HET_BWD_PACKED(8); } else { HET_BWD_PACKED(4); }
-#undef HET_BWD_PACKED
+      HET_DISPATCH_LPR((int)(X / 4),
+                       hipLaunchKernelGGL((HET_rgat_backward_src_packed<LPR, 4>), dim3(nb), dim3(kBlock), 0, s, pk, by_srow->p0,
+                                          by_srow->p1, feat_c, el_c, er_c, pack, gradout, grad_feat_c, grad_el_c, tbuf, (int)H,
+                                          (int)D, (float)slope, fold_attn_l, row_rel_ptrs, (int)num_rels, skip_long));
     }
     if (skip_long) {
       HET_LAUNCH_CHECK("HET_rgat_backward_src_packed");
@@ -1864,28 +1784,13 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     }
   }
   HET_LAUNCH_CHECK("HET_rgat_backward_src_packed");
-  if (runs) {
-    if (num_dst_rows > 0 && !fused_drow) {
-      HET_KTIME("HET_rgat_backward_er_runs", s);
-      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_grad_er_runs<LPR>, dim3(grid_for(num_dst_rows * (X / 4))), dim3(kBlock),
-                                                        0, s, runs->q_rows, runs->q_sum, runs->q_ref, runs->drow_nodes, pack, gradout,
-                                                        grad_er_c, num_dst_rows, (int)H, (int)D));
-    }
-    HET_LAUNCH_CHECK("HET_rgat_grad_er_runs");
-    HET_HIP(fk.join());
-    if (ga_rows) {
-      hipLaunchKernelGGL(HET_rgat_attn_grad_finish, dim3((unsigned)ceil_div64(ga_rows, kAttnFinishRows)), dim3(kBlock), 0, s, ga_part, ga_rel, ga_rows,
-                         (int)X, grad_attn_l);
-      HET_LAUNCH_CHECK("HET_rgat_attn_grad_finish");
-    }
-    return HET_OK;
-  }
   HET_HIP(fk.join());
   if (ga_rows) {
     hipLaunchKernelGGL(HET_rgat_attn_grad_finish, dim3((unsigned)ceil_div64(ga_rows, kAttnFinishRows)), dim3(kBlock), 0, s, ga_part, ga_rel, ga_rows,
                        (int)X, grad_attn_l);
     HET_LAUNCH_CHECK("HET_rgat_attn_grad_finish");
   }
+  if (runs) return HET_OK;  // (grad_er: HET_rgat_drow_pass)
   // grad_er[w, :] = SUM over the edges of er row w of tbuf[rank, :]   (segments of by_drow are the er rows in order)
   return launch_segment_sum(by_drow, tbuf, grad_er_c, (int)H, nullptr, s);
 }

@@ -11,8 +11,6 @@
 // collects the rows of every source that has one for any of its nodes in one MFMA accumulator tile and stores the output row
 // once; the weights of the launch stay in LDS.  A wide row ([k' | m] of HGT's folded source projection: 2X floats) enters as
 // two sources -- two halves of the same rows, each with its half of the weight.
-#include <stdlib.h>
-
 #include "common.hip.h"
 
 namespace {
@@ -39,7 +37,7 @@ struct SumArgs {
                                  // presence puts the nodes without any row first: in list order every wave stores its empty tiles first
                                  // (matrix cores idle) and multiplies afterwards (stores idle); a stride near 0.618 * tiles, coprime with
                                  // tiles, hands every wave a uniform sample of the classes (RGCN forward pass 0.239 -> 0.225 ms,
-                                 // the backward one unchanged; HET_NODE_SUM_MIX=0: A/B)
+                                 // the backward one unchanged)
 };
 
 // Workgroup = WAVES independent waves sharing the S weights in LDS; a wave walks 32-node tiles (grid-stride), loads the rows of
@@ -317,10 +315,9 @@ int launch_sum_w16(const SumArgs& a, hipStream_t s, bool* done) {
   const size_t limit = het_lds_budget(), wbytes = sizeof(float) * (size_t)a.S * KS * XO, per_wave = sizeof(float) * 32 * 36;
   *done = false;
   if (wbytes + 8 * per_wave > limit) return HET_OK;  // fewer than 8 waves: the tile form above does as well
-  // (HET_NODE_SUM_WAVES: A/B -- 16 waves of 128 VGPRs are a CU's whole register file, nothing runs beside such a workgroup)
-  static const int max_waves = [] { const char* v = getenv("HET_NODE_SUM_WAVES"); const int w = v ? atoi(v) : 16; return w < 4 ? 4 : (w > 16 ? 16 : w); }();
+  // (at most 16 waves: 16 waves of 128 VGPRs are a CU's whole register file, nothing runs beside such a workgroup)
   int waves = (int)((limit - wbytes) / per_wave);
-  if (waves > max_waves) waves = max_waves;
+  if (waves > 16) waves = 16;
   const int64_t tiles = (a.n_end - a.n_begin + 31) / 32;
   int64_t gx = (tiles + waves - 1) / waves;
   const int64_t cus = het_num_cus();
@@ -328,9 +325,8 @@ int launch_sum_w16(const SumArgs& a, hipStream_t s, bool* done) {
   if (gx < 1) gx = 1;
   const size_t lds = wbytes + (size_t)waves * per_wave;
   SumArgs b = a;
-  static const bool no_mix = getenv("HET_NODE_SUM_MIX") && atoi(getenv("HET_NODE_SUM_MIX")) == 0;  // A/B: tiles in list order
   b.mix = 1;
-  if (!no_mix && a.order && tiles > 4 * gx * waves) {
+  if (a.order && tiles > 4 * gx * waves) {
     auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t r = x % y; x = y; y = r; } return x; };
     int64_t m = (int64_t)(0.6180339887 * (double)tiles) | 1;
     while (m > 1 && gcd(m, tiles) != 1) m -= 2;
@@ -352,12 +348,9 @@ size_t lds_for(int S, int waves) {
 
 template <int KS, int NO>
 int launch_sum(const SumArgs& a, hipStream_t s) {
-  static const bool tile_form = getenv("HET_NODE_SUM_LDS_TILE") && atoi(getenv("HET_NODE_SUM_LDS_TILE")) != 0;  // A/B: the round-4a kernel
-  if (!tile_form) {
-    bool done = false;
-    if (int rc = launch_sum_w16<KS, NO>(a, s, &done)) return rc;
-    if (done) return HET_OK;
-  }
+  bool done = false;
+  if (int rc = launch_sum_w16<KS, NO>(a, s, &done)) return rc;
+  if (done) return HET_OK;
   const int64_t tiles = (a.n_end - a.n_begin + 31) / 32;
   const size_t limit = het_lds_budget();
   HET_KTIME("HET_node_rows_sum", s);

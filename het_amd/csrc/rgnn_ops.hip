@@ -778,9 +778,7 @@ extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het
   float* gsum = static_cast<float*>(workspace);
   float* cpart = gsum + (gs->S > 0 ? gs->S : 1) * D;
   // grad_w[r] = SUM over the (r, v) rows of ssum[(r,v)]^T (x) gradout[v] (half as many rows as the (relation, source) form, no second
-  // read of x) and the bias gradient: streams of rows, on the library's side stream beside the node pass (HET_RGCN_BWD_FORK: 0 = on
-  // the caller's stream, 1 = beside the gather pass, 2 = beside the node pass)
-  static const int fork_mode = [] { const char* v = getenv("HET_RGCN_BWD_FORK"); return v ? atoi(v) : 2; }();
+  // read of x) and the bias gradient: streams of rows, on the library's side stream beside the node pass
   auto weight_gradients = [&](hipStream_t st) -> int {
     HET_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * num_rels * K * D, st));
     if (gd->S > 0) {
@@ -793,40 +791,24 @@ extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het
       if (int rc = launch_colsum(gradout, num_dst_nodes, (int)D, cpart, grad_bias, st)) return rc;
     return HET_OK;
   };
+  // grad_x NULL: the layer input needs no gradient -- fixed features --, the gather pass and the node pass are skipped
+  if (!grad_x) return weight_gradients(s);
   // gsum[(r,u), :] = SUM over the out-edges of u in relation r of norm * gradout[dst]
-  // (grad_x NULL: the layer input needs no gradient -- fixed features -- and the gather pass + node pass are skipped)
-  auto gather_pass = [&]() -> int {
-    if (gs->E > 0 && grad_x)
-      return launch_segment_sum(gs, gradout, gsum, (int)D, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0);
-    return HET_OK;
-  };
+  if (gs->E > 0)
+    if (int rc = launch_segment_sum(gs, gradout, gsum, (int)D, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0))
+      return rc;
+  HetFork fk(s);
+  if (int rc = weight_gradients(fk.side)) return rc;
   // grad_x[u] = SUM_r gsum[(r,u)] . Wt[r]
-  auto node_pass = [&]() -> int {
-    if (!(num_src_nodes > 0 && grad_x)) return HET_OK;
+  if (num_src_nodes > 0) {
     const float* rows[16]; int64_t strides[16]; const int32_t* maps[16]; int64_t ident[16]; const float* wts[16];
     for (int r = 0; r < (int)num_rels; ++r) {
       rows[r] = gsum; strides[r] = D; maps[r] = src_map + (int64_t)r * num_src_nodes; ident[r] = 0; wts[r] = weights_t + (int64_t)r * D * K;
     }
-    return het_node_rows_matmul_sum_bias(0, num_src_nodes, num_src_nodes, num_rels, rows, strides, maps, ident, wts, nullptr, grad_x, D, K,
-                                         node_order, stream);
-  };
-  if (fork_mode == 0 || !grad_x) {
-    if (int rc = weight_gradients(s)) return rc;
-    if (int rc = gather_pass()) return rc;
-    return node_pass();
+    if (int rc = het_node_rows_matmul_sum_bias(0, num_src_nodes, num_src_nodes, num_rels, rows, strides, maps, ident, wts, nullptr, grad_x,
+                                               D, K, node_order, stream))
+      return rc;
   }
-  if (fork_mode == 1) {
-    HetFork fk(s);
-    if (int rc = weight_gradients(fk.side)) return rc;
-    if (int rc = gather_pass()) return rc;
-    if (int rc = node_pass()) return rc;
-    HET_HIP(fk.join());
-    return HET_OK;
-  }
-  if (int rc = gather_pass()) return rc;
-  HetFork fk(s);
-  if (int rc = weight_gradients(fk.side)) return rc;
-  if (int rc = node_pass()) return rc;
   HET_HIP(fk.join());
   return HET_OK;
 }

@@ -8,7 +8,6 @@
 // accumulators.  The k index is permuted between the two lane halves
 // (half h owns k in [h*K/2, (h+1)*K/2)) -- A and B use the same permutation, so
 // the sum is unchanged while every lane's fragment is one contiguous half row.
-#include <stdlib.h>
 
 #include "seg_gemm_mfma.hip.h"
 #include "coop.hip.h"
@@ -20,9 +19,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kChunkRows = 2048;  // rows of one relation per workgroup at most (16 tiles per wave)
 // Smaller inputs (a rank's share of a partitioned graph, a sampled block) get smaller chunks so that the launch still
 // has ~2000 workgroups: 128 rows = one 32-row tile per wave is the floor.
+constexpr int64_t kGemmWgs = 2048;
 inline int chunk_rows_for(int64_t num_rows) {
-  static const int64_t wgs = [] { const char* v = getenv("HET_GEMM_WGS"); return v && atoi(v) > 0 ? (int64_t)atoi(v) : 2048; }();  // A/B switch
-  int64_t c = ((num_rows / wgs) + 127) / 128 * 128;
+  int64_t c = ((num_rows / kGemmWgs) + 127) / 128 * 128;
   return (int)(c < 128 ? 128 : (c > kChunkRows ? kChunkRows : c));
 }
 
@@ -124,11 +123,7 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
 #pragma unroll
     for (int it = 0; it < NITA; ++it) {
       const idx_t i = wb + it * RPIA + ra, ic = i < re ? i : re - 1;
-#ifdef HET_ABL_NOLOAD
-      const int64_t r64 = ra;
-#else
       const int64_t r64 = has_g ? (int64_t)ar[it] : (int64_t)ic;
-#endif
       areg[it] = *reinterpret_cast<const float4*>(a.A + r64 * a.a_ld + ca);
     }
   };
@@ -187,21 +182,13 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
     for (int s = 0; s < KH; ++s) {
       if (PAIRED) {
         const float2 b2 = *reinterpret_cast<const float2*>(&Bs[(half * KH + s) * X + 2 * row]);
-#ifdef HET_ABL_NOMFMA
-        acc[0][s & 15] += af[s] * b2.x; acc[NT - 1][s & 15] += af[s] * b2.y;
-#else
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], b2.x, acc[0], 0, 0, 0);
         acc[NT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], b2.y, acc[NT - 1], 0, 0, 0);
-#endif
       } else {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
           const float b = B_REGS ? breg[B_REGS ? s * NT + nt : 0] : Bs[(half * KH + s) * X + nt * 32 + row];
-#ifdef HET_ABL_NOMFMA  // diagnostic builds only (exp/mfma_bench.hip)
-          acc[nt][s & 15] += af[s] * b;
-#else
           acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], b, acc[nt], 0, 0, 0);
-#endif
         }
       }
     }
@@ -239,9 +226,6 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
           const float4 c = cold[RMW ? it : 0];
           v = make_float4(v.x + c.x, v.y + c.y, v.z + c.z, v.w + c.w);
         }
-#ifdef HET_ABL_NOSTORE
-        if (a.num_rows < 0)
-#endif
         if (!RMW || real) *reinterpret_cast<float4*>(a.C + (int64_t)crow[it] * a.c_ld + cc) = v;
         if (DOT) {
           float p = v.x * dotw.x + v.y * dotw.y + v.z * dotw.z + v.w * dotw.w;
@@ -412,9 +396,6 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgs a, int chunk) 
     }
   }
   constexpr int NACC = KT * NT * 16;
-#ifdef HET_ABL_DW_NOEPI  // experiment builds only: the whole flush behind a condition that is never true
-  if (a.num_rows >= 0) return;
-#endif
   // Flush: the four partial products are summed through LDS by ALL four waves -- wave q owns the quarter [q*Q, (q+1)*Q) of the
   // NACC accumulator registers, the three others hand it theirs -- and every wave adds its quarter to the output.  (Until round 5
   // wave 0 summed and added everything while the other twelve wave slots of the workgroup's LDS share sat empty: the flush
@@ -482,8 +463,9 @@ int launch_dw_kx(const MfmaDwArgs& a, hipStream_t s) {
   HET_REQUIRE(a.a_ld % 2 == 0 && a.g_ld % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.G) & 7) == 0,
               "segment dW (MFMA): rows must be 8-byte aligned");
   // 48 KiB of LDS per workgroup -> 3 resident per CU, 768 on the chip: aim for about 4 rounds of them
-  static const int64_t n_chunks = [] { const char* v = getenv("HET_DW_CHUNKS"); return v ? (int64_t)atoi(v) : 1536; }();  // A/B switch (same box: 768 0.325, 1536 0.316, 3072 0.354, 6144 0.380 ms per launch on ogbn-mag: every workgroup ends with K*X atomic adds)
-  int64_t chunk = ceil_div64(a.num_rows, n_chunks);
+  // (same box: 768 0.325, 1536 0.316, 3072 0.354, 6144 0.380 ms per launch on ogbn-mag: every workgroup ends with K*X atomic adds)
+  constexpr int64_t kDwChunks = 1536;
+  int64_t chunk = ceil_div64(a.num_rows, kDwChunks);
   if (chunk < 512) chunk = 512;
   chunk = (chunk + 7) & ~7ll;
   const int64_t gx = ceil_div64(a.num_rows, chunk) + a.num_segs;
@@ -596,9 +578,8 @@ int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s) {
   //  64-deep kernel runs two workgroups per CU against one for the 128-deep one, but reading and writing C once more costs more
   //  than the occupancy gives: RGAT at feat 128 10.7 -> 11.5 ms per step.)
   // K <= 64 into X = 128 (HGT's k' | m rows): two launches of the X = 64 kernel beat the one with four column tiles per
-  // wave (0.60 -> 0.55 ms for 2.4 M rows), although the A rows are read twice.  HET_GEMM_XSLAB64=0: A/B switch
-  static const bool xslab64 = [] { const char* v = getenv("HET_GEMM_XSLAB64"); return !(v && v[0] == '0'); }();
-  if (xslab64 && a.X == 128 && a.K <= 64 && !a.dot_w && !a.bias && !a.atomic) {
+  // wave (0.60 -> 0.55 ms for 2.4 M rows), although the A rows are read twice.
+  if (a.X == 128 && a.K <= 64 && !a.dot_w && !a.bias && !a.atomic) {
     for (int n0 = 0; n0 < 128; n0 += 64) {  // two 64-wide column slabs (the A rows are read twice)
       MfmaGemmArgs w = a;
       // (a may itself be a window of a wider weight -- the 128-wide slabs above: offsets compose, the full size is kept)

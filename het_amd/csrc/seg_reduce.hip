@@ -1,6 +1,4 @@
 // Segmented sum of gathered rows, one lane group per work item (no atomics except for split hub segments).
-#include <stdlib.h>
-
 #include <mutex>
 
 #include "seg_reduce.hip.h"
@@ -393,8 +391,7 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
     HET_LAUNCH_CHECK("HET_segsum_zero_split");
     return HET_OK;
   };
-  static const bool flat_off = [] { const char* v = getenv("HET_SEGSUM_FLAT"); return v && v[0] == '0'; }();  // A/B switch
-  if (X == 4 && !scale && scatter_rows < 0 && !accumulate && !nt_in && !flat_off && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
+  if (X == 4 && !scale && scatter_rows < 0 && !accumulate && !nt_in && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
     if (int rc = grouping_seg_of_rank(g, s)) return rc;
     HET_HIP(hipMemsetAsync(out, 0, sizeof(float) * g->S * X, s));  // (pieces of straddling segments are added atomically)
@@ -414,9 +411,8 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
   HET_KTIME("HET_segment_sum", s);
   // cooperative kernels: rows of >= 16 floats, a scale shared by the 4 lanes of a quad (per row, or heads of >= 16 floats),
   // cached rows (nt_in streams keep the item kernel)
-  static const bool coop_off = [] { const char* v = getenv("HET_SEGSUM_COOP"); return v && v[0] == '0'; }();  // A/B switch
   const int LPRv = X / 4;
-  const bool coop = !coop_off && LPRv >= 4 && LPRv <= 64 && !nt_in && !(scale && scale_heads == X);
+  const bool coop = LPRv >= 4 && LPRv <= 64 && !nt_in && !(scale && scale_heads == X);
   const int scale_quad = !scale || scale_heads == 0 || (X / scale_heads) % 16 == 0;
   if (coop) {
     if (int rc = grouping_packs(g, s)) return rc;

@@ -1,8 +1,6 @@
 // Row-dot kernels (see seg_rowdot.hip.h).  A row of H*K floats is covered by LPR = H*K/4 lanes
 // (one float4 each, fully coalesced); KL = K/4 adjacent lanes share a head and combine their
 // partial dot products with xor-shuffles.  A wave handles 64/LPR rows per step.
-#include <stdlib.h>
-
 #include "seg_rowdot.hip.h"
 
 namespace {
@@ -386,14 +384,15 @@ int launch_rowdot_bwd_dx(const RowDotArgs& a, hipStream_t s) {
   return HET_OK;
 }
 
+// Every workgroup of the dW launches ends with one atomic flush into the SAME H*K floats of its relation, and those serialise
+// (~50 ns per workgroup): on ogbn-mag (2.4 M rows) 8192 / 4096 / 2048 / 1024 / 512 workgroups take 0.48 / 0.27 / 0.17 / 0.136 /
+// 0.131 ms.  (The minimum chunk only matters for short lists: a rank's share of a partition.)
+constexpr int64_t kDwWgs = 512, kDwMinChunk = 512;
+
 int launch_rowdot_bwd_dw(const RowDotArgs& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
-  // Every workgroup ends with one atomic flush into the SAME H*K floats of its relation, and those serialise (~50 ns per
-  // workgroup): on ogbn-mag (2.4 M rows) 8192 / 4096 / 2048 / 1024 / 512 workgroups take 0.48 / 0.27 / 0.17 / 0.136 / 0.131 ms.
-  static const int64_t min_chunk = [] { const char* v = getenv("HET_ROWDOT_DW_MIN"); return v ? (int64_t)atoi(v) : 512; }();  // A/B switches (the minimum only matters for short lists: a rank's share of a partition)
-  static const int64_t n_wg = [] { const char* v = getenv("HET_ROWDOT_DW_WGS"); return v ? (int64_t)atoi(v) : 512; }();
-  int64_t chunk = ceil_div64(a.num_rows, n_wg);
-  if (chunk < min_chunk) chunk = min_chunk;
+  int64_t chunk = ceil_div64(a.num_rows, kDwWgs);
+  if (chunk < kDwMinChunk) chunk = kDwMinChunk;
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
   HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL(HET_rowdot_bwd_dw<LPR>, grid, block, 0, s, a, (int)chunk));
   HET_LAUNCH_CHECK("HET_rowdot_bwd_dw");
@@ -437,10 +436,8 @@ int launch_rowdot1h_bwd_dx(const RowDotArgs& a, hipStream_t s) {
 
 int launch_rowdot1h_bwd_dw(const RowDotArgs& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
-  static const int64_t min_chunk = [] { const char* v = getenv("HET_ROWDOT_DW_MIN"); return v ? (int64_t)atoi(v) : 512; }();  // A/B switches (the minimum only matters for short lists: a rank's share of a partition)
-  static const int64_t n_wg = [] { const char* v = getenv("HET_ROWDOT_DW_WGS"); return v ? (int64_t)atoi(v) : 512; }();
-  int64_t chunk = ceil_div64(a.num_rows, n_wg);  // see launch_rowdot_bwd_dw
-  if (chunk < min_chunk) chunk = min_chunk;
+  int64_t chunk = ceil_div64(a.num_rows, kDwWgs);  // see kDwWgs
+  if (chunk < kDwMinChunk) chunk = kDwMinChunk;
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
   HET_ROWDOT1H_DISPATCH(HET_rowdot1h_bwd_dw, a, (int)chunk)
   HET_LAUNCH_CHECK("HET_rowdot1h_bwd_dw");

@@ -1136,15 +1136,12 @@ def rgcn_layer_plan(rel_ptrs, eids, row, col, num_nodes: int):
     return gd, gs, dst_map, node_order_by_presence(dst_map), src_map, node_order_by_presence(src_map)
 
 
-SCALE_SORTED = _os.environ.get("HET_RGCN_NORM_SORTED", "1") != "0"  # A/B: 0 = the norm is gathered by edge id in every pass
-
-
 def scale_in_rank_order(g, values):
     """``values`` ([E] or [E, H] by edge id) in the order of the grouping ``g`` (whose second payload is the edge id), or None.
     For a scale that is the same tensor step after step (an edge norm): built at its SECOND sighting -- a scale that changes every
     step never pays for it -- and kept with the grouping, one per grouping (a new tensor replaces it); the entry holds the source
     tensor, so its address cannot come back with other contents, and (data_ptr, numel, _version) catches in-place edits."""
-    if not SCALE_SORTED or g is None or values is None:
+    if g is None or values is None:
         return None
     ident = _plan._ident(values)
     with _derived_lock:

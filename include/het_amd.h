@@ -568,7 +568,7 @@ int het_rgat_backward_compact_runs(const het_grouping* by_srow, const float* q_r
  * workspace: het_rgat_backward_compact_runs_workspace(by_srow, N, num_dst_rows, H, D, grad_bias != NULL, grad_attn_l != NULL, stream)
  *   bytes (the first call with the attention gradient builds by_srow's packs on `stream`); -1 on error.  It holds, beside the
  *   per-destination {lse, <gradout, ret>} pairs, one 16-byte record {er, lse, <gradout, ret>, 0} per (er row, head): the source-row
- *   kernels fetch everything they need from the destination side of an edge with one load (round 4; HET_RGAT_DROW_REC=0: two). */
+ *   kernels fetch everything they need from the destination side of an edge with one load instead of two (round 4). */
 int64_t het_rgat_backward_compact_runs_workspace(const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t H,
                                                  int64_t D, int with_bias, int with_attn_grad, het_stream stream);
 

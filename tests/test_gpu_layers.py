@@ -444,11 +444,12 @@ def _run_hgt_fused(fused_attn, compact_dst, H, in_dim, out_dim, monkeypatch, pri
 
 
 @pytest.mark.parametrize("rels_per_type", [1, 3, 4])
-def test_hgt_layer_fused_node_major_input_gradient_shapes(rels_per_type, monkeypatch):
+def test_hgt_layer_fused_node_major_input_gradient_launches(rels_per_type, monkeypatch):
     """The node-major input gradient of the HGT layer (csrc/node_sum.hip) on typed graphs with 1, 3 and 4 relations leaving the
     same node type: 3 relations = 7 sources in one launch (4 waves per workgroup), 4 = 9 sources, more than the weights the
     pass keeps in LDS -- the layer falls back to the per-relation launches; a node type that is only a destination and one that is
-    only a source are in the graph too.  Output and all gradients against the fp64 oracle either way."""
+    only a source are in the graph too.  Output and all gradients against the fp64 oracle either way, and the sources of every
+    node-major launch (none with 9 sources)."""
     import het_amd.kernels as k
     from het_amd.graph import HetGraph
     from het_amd.synth import make_hetero_graph
@@ -459,10 +460,7 @@ def test_hgt_layer_fused_node_major_input_gradient_shapes(rels_per_type, monkeyp
     real = k.node_rows_matmul_sum
     monkeypatch.setattr(k, "node_rows_matmul_sum", lambda *a, **kw: (calls.append(len(a[2])), real(*a, **kw))[1])
     _run_hgt_fused(False, True, 4, 64, 64, monkeypatch, g=g)
-    from het_amd.backend import hgt_fused_layer
-    if not hgt_fused_layer.NODE_DX:  # (HET_HGT_NODE_DX=0: the per-relation launches everywhere; parity was checked above)
-        assert not calls
-    elif rels_per_type <= 3:
+    if rels_per_type <= 3:
         assert calls and max(calls) == 1 + 2 * rels_per_type, calls  # the destination term + two halves per relation (type 1)
     else:
         assert not calls  # 9 sources: outside the pass
