@@ -1,6 +1,6 @@
 """HGT ops behind torch.autograd; mirrors /root/reference/hrt/python/backend/hgt_layers_and_funcs.py
 (HGTFullGraphHeteroAttentionOps :9-121, HGTFullGraphMessageCalcEdgeSoftmaxAndMessageMeanAggregationCOO :124-295,
-wrappers :425-503) and the inner-product classes of rgnn_layers_and_funcs.py:192-418, 499-591."""
+HGTFullGraphEdgeSoftmaxAndMessageMeanAggregationOpsCSR :298-422, wrappers :425-503) and the inner-product classes of rgnn_layers_and_funcs.py:192-418, 499-591."""
 import torch as th
 
 from ..plan import consistent as _consistent_plan
@@ -10,6 +10,7 @@ from ..kernels import K
 
 __all__ = [
     "HGTFullGraphHeteroAttentionOps", "HGTFullGraphMessageCalcEdgeSoftmaxAndMessageMeanAggregationCOO",
+    "HGTFullGraphEdgeSoftmaxAndMessageMeanAggregationOpsCSR",
     "hgt_full_graph_hetero_attention_ops_coo",
     "hgt_full_graph_message_calc_edge_softmax_and_message_mean_aggregation_coo",
     "hgt_full_graph_edge_softmax_and_message_mean_aggregation_csr",
@@ -83,6 +84,42 @@ class HGTFullGraphMessageCalcEdgeSoftmaxAndMessageMeanAggregationCOO(th.autograd
         K.backward_hgt_full_graph_enorm_to_unnormalized_attn_score_separate_coo(row, col, eids, relptrs, score, a,
                                                                                 grad_a, mu, grad_score, grad_mu, tmp)
         return (None,) * 8 + (grad_w, grad_input, grad_score, None, grad_mu, None, None, None)
+
+
+@_consistent_plan
+class HGTFullGraphEdgeSoftmaxAndMessageMeanAggregationOpsCSR(th.autograd.Function):
+    """reference: hgt_layers_and_funcs.py:298-422 -- HGT's unfused aggregation: edge softmax on the in-CSR, then the
+    attention-weighted mean of per-edge messages [E,H,dk]; the backward walks the out-CSR.  Each op gets the arguments its
+    launcher declares (HGTOps.inc.h), not what the reference's class passes: the aggregation takes the mu-applied
+    UNNORMALISED score, which it divides by the sum itself (the reference passes the normalised score and
+    so normalises twice), and the in-CSR's (reltypes, eids) go in the launcher's order (Q12).  The result is the HGT layer
+    as intended, the value of the fused COO path."""
+    @staticmethod
+    def forward(ctx, incsr_row_ptrs, incsr_col_indices, incsr_eids, incsr_reltypes, outcsr_row_ptrs, outcsr_col_indices,
+                outcsr_eids, outcsr_reltypes, unnormalized_attn_score, mu, edgesoftmax_sum_per_node,
+                mu_softmax_applied_unnormalized_attn_score, normalized_attn_score, message_per_edge, new_h):
+        K.hgt_full_graph_edge_softmax_ops_csr(incsr_row_ptrs, incsr_col_indices, incsr_eids, incsr_reltypes,
+                                              unnormalized_attn_score, mu, edgesoftmax_sum_per_node,
+                                              mu_softmax_applied_unnormalized_attn_score, normalized_attn_score)
+        K.hgt_full_graph_message_mean_aggregation_csr(incsr_row_ptrs, incsr_col_indices, incsr_reltypes, incsr_eids,
+                                                      message_per_edge, mu_softmax_applied_unnormalized_attn_score,
+                                                      edgesoftmax_sum_per_node, mu, new_h)
+        ctx.save_for_backward(outcsr_row_ptrs, outcsr_col_indices, outcsr_eids, outcsr_reltypes, unnormalized_attn_score,
+                              mu, edgesoftmax_sum_per_node, normalized_attn_score, message_per_edge, new_h)
+        return new_h
+
+    @staticmethod
+    def backward(ctx, gradout):
+        (row_ptrs, col, eids, rel, score, mu, sum_per_node, a, message, new_h) = ctx.saved_tensors
+        gradout = gradout.contiguous()
+        grad_message = th.empty_like(message, memory_format=th.contiguous_format)  # (every edge row is written)
+        K.backward_hgt_full_graph_message_mean_aggregation_csr(row_ptrs, col, rel, eids, sum_per_node, a, gradout,
+                                                               grad_message)
+        grad_attn_score = th.empty_like(score, memory_format=th.contiguous_format)
+        grad_mu = th.zeros_like(mu, memory_format=th.contiguous_format)  # (the op accumulates into it)
+        K.backward_hgt_full_graph_edge_softmax_ops_csr(row_ptrs, col, eids, rel, message, score, a, new_h, gradout, mu,
+                                                       grad_attn_score, grad_mu)
+        return (None,) * 8 + (grad_attn_score, grad_mu, None, None, None, grad_message, None)
 
 
 def hgt_full_graph_hetero_attention_ops_coo(graph, weight, applied_klinear_node_features, applied_qlinear_node_features):

@@ -651,6 +651,69 @@ void backward_hgt_edge_softmax(Tensor row, Tensor col, Tensor eids, Tensor rel_p
                                                                                   fpw(gscore), fpw(gmu), fpw(tmp), H, g.get(), stream_of(mu)),
         "backward_hgt_full_graph_enorm_to_unnormalized_attn_score_separate_coo");
 }
+// HGT's unfused aggregation on the CSR layouts (include/het_amd.h a10c): positions grouped by destination, payload0 = eids,
+// payload1 = reltypes -- an in-CSR's expanded rows (cached per row_ptrs) or an out-CSR's col_indices
+GroupingRef csr_by_dst(const Tensor& dst, int64_t N, const Tensor& eids, const Tensor& rel) {
+  return eids.numel() > 0 ? grouping(nullptr, dst, N, &eids, &rel) : nullptr;
+}
+GroupingRef incsr_by_dst(const Tensor& row_ptr, const Tensor& eids, const Tensor& rel) {
+  if (eids.numel() == 0 || !groupings_enabled()) return nullptr;
+  Tensor dst = derived("csr_rows", {&row_ptr}, [&] { return std::vector<Tensor>{csr_rows(row_ptr)}; })[0];
+  return csr_by_dst(dst, row_ptr.numel() - 1, eids, rel);
+}
+void hgt_edge_softmax_csr(Tensor row_ptr, Tensor col, Tensor eids, Tensor rel, Tensor score, Tensor mu, Tensor sum, Tensor m, Tensor a) {
+  will_write({sum, m, a});
+  HET_ON_DEVICE_OF(sum);
+  const int64_t H = mu.size(1), N = sum.size(0);
+  GroupingRef g = H % 4 == 0 ? incsr_by_dst(row_ptr, eids, rel) : nullptr;
+  check(het_hgt_full_graph_edge_softmax_ops_csr(ip(row_ptr), row_ptr.numel(), ip(col), ip(eids), ip(rel), N, eids.numel(), fp(score), fp(mu),
+                                                fpw(sum), fpw(m), fpw(a), H, g.get(), stream_of(mu)),
+        "hgt_full_graph_edge_softmax_ops_csr");
+}
+void hgt_message_mean_aggregation_csr(Tensor row_ptr, Tensor col, Tensor rel, Tensor eids, Tensor msg, Tensor attn, Tensor sum, Tensor mu,
+                                      Tensor ret) {
+  will_write({ret});
+  HET_ON_DEVICE_OF(ret);
+  const int64_t H = attn.size(-1), dk = msg.size(-1);
+  GroupingRef g = incsr_by_dst(row_ptr, eids, rel);
+  check(het_hgt_full_graph_message_mean_aggregation_csr(ip(row_ptr), row_ptr.numel(), ip(col), ip(rel), ip(eids), ret.size(0), eids.numel(),
+                                                        fp(msg), fp(attn), fp(sum), fp(mu), fpw(ret), H, dk, g.get(), stream_of(ret)),
+        "hgt_full_graph_message_mean_aggregation_csr");
+}
+void backward_hgt_message_mean_aggregation_csr(Tensor row_ptr, Tensor col, Tensor rel, Tensor eids, Tensor sum, Tensor a, Tensor gradout,
+                                               Tensor grad_msg) {
+  will_write({grad_msg});
+  HET_ON_DEVICE_OF(grad_msg);
+  const int64_t H = a.size(-1), dk = grad_msg.size(-1);
+  check(het_backward_hgt_full_graph_message_mean_aggregation_csr(ip(row_ptr), row_ptr.numel(), ip(col), ip(rel), ip(eids), gradout.size(0),
+                                                                 eids.numel(), fp(sum), fp(a), fp(gradout), fpw(grad_msg), H, dk,
+                                                                 stream_of(grad_msg)),
+        "backward_hgt_full_graph_message_mean_aggregation_csr");
+}
+void backward_hgt_edge_softmax_csr(Tensor row_ptr, Tensor col, Tensor eids, Tensor rel, Tensor msg, Tensor score, Tensor a, Tensor out,
+                                   Tensor gradout, Tensor mu, Tensor gscore, Tensor gmu) {
+  will_write({gscore, gmu});
+  HET_ON_DEVICE_OF(gscore);
+  const int64_t H = gscore.size(-1), dk = msg.size(-1), N = gradout.size(0);
+  GroupingRef g = csr_by_dst(col, N, eids, rel);  // destination-major view of the out-CSR
+  check(het_backward_hgt_full_graph_edge_softmax_ops_csr(ip(row_ptr), row_ptr.numel(), ip(col), ip(eids), ip(rel), N, eids.numel(), mu.size(0),
+                                                         fp(msg), fp(score), fp(a), fp(out), fp(gradout), fp(mu), fpw(gscore), fpw(gmu), H,
+                                                         dk, g.get(), stream_of(gscore)),
+        "backward_hgt_full_graph_edge_softmax_ops_csr");
+}
+void backward_hgt_enorm_csr(Tensor row_ptr, Tensor col, Tensor eids, Tensor rel, Tensor score, Tensor a, Tensor grad_a, Tensor mu,
+                            Tensor gscore, Tensor gmu) {
+  will_write({gscore, gmu});
+  HET_ON_DEVICE_OF(gscore);
+  const int64_t H = mu.size(1), N = row_ptr.numel() - 1;
+  GroupingRef g = H % 4 == 0 ? incsr_by_dst(row_ptr, eids, rel) : nullptr;
+  Tensor ws = g ? workspace(N * H, mu) : Tensor();  // (split hub destinations)
+  check(het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(ip(row_ptr), row_ptr.numel(), ip(col), ip(eids), ip(rel), N,
+                                                                         eids.numel(), mu.size(0), fp(score), fp(a), fp(grad_a), fp(mu),
+                                                                         fpw(gscore), fpw(gmu), H, g.get(), g ? ws.data_ptr() : nullptr,
+                                                                         g ? ws.numel() * 4 : 0, stream_of(mu)),
+        "backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr");
+}
 void hgt_message_mean_aggregation(Tensor rel_ptrs, Tensor eids, Tensor row, Tensor col, Tensor x, Tensor W, Tensor norm, Tensor new_h) {
   will_write({new_h});
   HET_ON_DEVICE_OF(new_h);
@@ -789,6 +852,26 @@ TORCH_LIBRARY_FRAGMENT(torch_hrt, m) {
         "Tensor grad_normalized_attn_score, Tensor mu, Tensor(a!) grad_unnormalized_attn_score, Tensor(b!) grad_mu, "
         "Tensor(c!) sum_incoming_edges_product_softmax_score) -> ()",
         backward_hgt_edge_softmax);
+  m.def("hgt_full_graph_edge_softmax_ops_csr(Tensor row_ptr, Tensor col_indices, Tensor eids, Tensor reltypes, "
+        "Tensor unnormalized_attn_score, Tensor mu, Tensor(a!) edgesoftmax_sum_per_node, "
+        "Tensor(b!) mu_softmax_applied_unnormalized_attn_score, Tensor(c!) normalized_attn_score) -> ()",
+        hgt_edge_softmax_csr);
+  m.def("hgt_full_graph_message_mean_aggregation_csr(Tensor incsr_row_ptrs, Tensor incsr_col_indices, Tensor incsr_reltypes, "
+        "Tensor incsr_eids, Tensor edge_messages, Tensor edge_attn_score, Tensor edgesoftmax_sum_per_node, Tensor mu, "
+        "Tensor(a!) ret) -> ()",
+        hgt_message_mean_aggregation_csr);
+  m.def("backward_hgt_full_graph_message_mean_aggregation_csr(Tensor outcsr_row_ptrs, Tensor outcsr_col_indices, "
+        "Tensor outcsr_reltypes, Tensor outcsr_eids, Tensor edgesoftmax_sum_per_node, Tensor normalized_attn_score, "
+        "Tensor gradout, Tensor(a!) grad_message) -> ()",
+        backward_hgt_message_mean_aggregation_csr);
+  m.def("backward_hgt_full_graph_edge_softmax_ops_csr(Tensor outcsr_row_ptr, Tensor outcsr_col_indices, Tensor outcsr_eids, "
+        "Tensor outcsr_reltypes, Tensor message, Tensor unnormalized_attn_score, Tensor normalized_attn_score, Tensor out, "
+        "Tensor gradout, Tensor mu, Tensor(a!) grad_attn_score, Tensor(b!) grad_mu) -> ()",
+        backward_hgt_edge_softmax_csr);
+  m.def("backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(Tensor incsr_row_ptr, Tensor incsr_col_indices, "
+        "Tensor incsr_eids, Tensor incsr_reltypes, Tensor unnormalized_attn_score, Tensor normalized_attn_score, "
+        "Tensor grad_normalized_attn_score, Tensor mu, Tensor(a!) grad_unnormalized_attn_score, Tensor(b!) grad_mu) -> ()",
+        backward_hgt_enorm_csr);
   m.def("hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo(Tensor separate_coo_relptrs, "
         "Tensor separate_coo_eids, Tensor separate_coo_row_indices, Tensor separate_coo_col_indices, Tensor inputs, "
         "Tensor weights, Tensor edge_norm, Tensor(a!) new_h) -> ()",

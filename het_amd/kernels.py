@@ -1384,6 +1384,105 @@ def backward_hgt_full_graph_enorm_to_unnormalized_attn_score_separate_coo(
           _p(sum_incoming_edges_product_softmax_score), H, None if g is None else g.handle, _stream(mu))
 
 
+# HGT's unfused aggregation on the CSR layouts (HGTOps.inc.h IntegratedCSR; include/het_amd.h a10c).  The fast paths take the
+# positions grouped by destination: an in-CSR's expanded rows, an out-CSR's col_indices (payload0 = eids, payload1 = reltypes).
+def _csr_by_dst(dst, num_nodes, eids, reltypes):
+    return _plan.get_grouping(None, dst, num_nodes, eids, reltypes) if eids.numel() > 0 else None
+
+
+def _incsr_by_dst(row_ptr, eids, reltypes):
+    if eids.numel() == 0 or not _plan.is_enabled():
+        return None
+    dst, _ = _csr_expanded_rows(row_ptr, eids.numel())
+    return _csr_by_dst(dst, row_ptr.numel() - 1, eids, reltypes)
+
+
+@_op("hgt_full_graph_edge_softmax_ops_csr(Tensor row_ptr, Tensor col_indices, Tensor eids, Tensor reltypes, "
+     "Tensor unnormalized_attn_score, Tensor mu, Tensor(a!) edgesoftmax_sum_per_node, "
+     "Tensor(b!) mu_softmax_applied_unnormalized_attn_score, Tensor(c!) normalized_attn_score) -> ()")
+def hgt_full_graph_edge_softmax_ops_csr(row_ptr, col_indices, eids, reltypes, unnormalized_attn_score, mu,
+                                        edgesoftmax_sum_per_node, mu_softmax_applied_unnormalized_attn_score,
+                                        normalized_attn_score):
+    _chk("hgt_full_graph_edge_softmax_ops_csr",
+         (unnormalized_attn_score, mu, edgesoftmax_sum_per_node, mu_softmax_applied_unnormalized_attn_score,
+          normalized_attn_score), (row_ptr, col_indices, eids, reltypes))
+    H, N = mu.shape[1], edgesoftmax_sum_per_node.shape[0]
+    g = _incsr_by_dst(row_ptr, eids, reltypes) if H % 4 == 0 else None
+    _call(mu, "het_hgt_full_graph_edge_softmax_ops_csr", _p(row_ptr), row_ptr.numel(), _p(col_indices), _p(eids),
+          _p(reltypes), N, eids.numel(), _p(unnormalized_attn_score), _p(mu), _p(edgesoftmax_sum_per_node),
+          _p(mu_softmax_applied_unnormalized_attn_score), _p(normalized_attn_score), H, None if g is None else g.handle,
+          _stream(mu))
+
+
+@_op("hgt_full_graph_message_mean_aggregation_csr(Tensor incsr_row_ptrs, Tensor incsr_col_indices, Tensor incsr_reltypes, "
+     "Tensor incsr_eids, Tensor edge_messages, Tensor edge_attn_score, Tensor edgesoftmax_sum_per_node, Tensor mu, "
+     "Tensor(a!) ret) -> ()")
+def hgt_full_graph_message_mean_aggregation_csr(incsr_row_ptrs, incsr_col_indices, incsr_reltypes, incsr_eids, edge_messages,
+                                                edge_attn_score, edgesoftmax_sum_per_node, mu, ret):
+    _chk("hgt_full_graph_message_mean_aggregation_csr", (edge_messages, edge_attn_score, edgesoftmax_sum_per_node, mu, ret),
+         (incsr_row_ptrs, incsr_col_indices, incsr_reltypes, incsr_eids))
+    H, dk = edge_attn_score.shape[-1], edge_messages.shape[-1]
+    g = _incsr_by_dst(incsr_row_ptrs, incsr_eids, incsr_reltypes)
+    _call(ret, "het_hgt_full_graph_message_mean_aggregation_csr", _p(incsr_row_ptrs), incsr_row_ptrs.numel(),
+          _p(incsr_col_indices), _p(incsr_reltypes), _p(incsr_eids), ret.shape[0], incsr_eids.numel(), _p(edge_messages),
+          _p(edge_attn_score), _p(edgesoftmax_sum_per_node), _p(mu), _p(ret), H, dk, None if g is None else g.handle,
+          _stream(ret))
+
+
+@_op("backward_hgt_full_graph_message_mean_aggregation_csr(Tensor outcsr_row_ptrs, Tensor outcsr_col_indices, "
+     "Tensor outcsr_reltypes, Tensor outcsr_eids, Tensor edgesoftmax_sum_per_node, Tensor normalized_attn_score, "
+     "Tensor gradout, Tensor(a!) grad_message) -> ()")
+def backward_hgt_full_graph_message_mean_aggregation_csr(outcsr_row_ptrs, outcsr_col_indices, outcsr_reltypes, outcsr_eids,
+                                                         edgesoftmax_sum_per_node, normalized_attn_score, gradout,
+                                                         grad_message):
+    _chk("backward_hgt_full_graph_message_mean_aggregation_csr",
+         (edgesoftmax_sum_per_node, normalized_attn_score, gradout, grad_message),
+         (outcsr_row_ptrs, outcsr_col_indices, outcsr_reltypes, outcsr_eids))
+    H, dk = normalized_attn_score.shape[-1], grad_message.shape[-1]
+    _call(grad_message, "het_backward_hgt_full_graph_message_mean_aggregation_csr", _p(outcsr_row_ptrs),
+          outcsr_row_ptrs.numel(), _p(outcsr_col_indices), _p(outcsr_reltypes), _p(outcsr_eids), gradout.shape[0],
+          outcsr_eids.numel(), _p(edgesoftmax_sum_per_node), _p(normalized_attn_score), _p(gradout), _p(grad_message), H, dk,
+          _stream(grad_message))
+
+
+@_op("backward_hgt_full_graph_edge_softmax_ops_csr(Tensor outcsr_row_ptr, Tensor outcsr_col_indices, Tensor outcsr_eids, "
+     "Tensor outcsr_reltypes, Tensor message, Tensor unnormalized_attn_score, Tensor normalized_attn_score, Tensor out, "
+     "Tensor gradout, Tensor mu, Tensor(a!) grad_attn_score, Tensor(b!) grad_mu) -> ()")
+def backward_hgt_full_graph_edge_softmax_ops_csr(outcsr_row_ptr, outcsr_col_indices, outcsr_eids, outcsr_reltypes, message,
+                                                 unnormalized_attn_score, normalized_attn_score, out, gradout, mu,
+                                                 grad_attn_score, grad_mu):
+    _chk("backward_hgt_full_graph_edge_softmax_ops_csr",
+         (message, unnormalized_attn_score, normalized_attn_score, out, gradout, mu, grad_attn_score, grad_mu),
+         (outcsr_row_ptr, outcsr_col_indices, outcsr_eids, outcsr_reltypes))
+    H, dk, N = grad_attn_score.shape[-1], message.shape[-1], gradout.shape[0]
+    # destination-major view of the out-CSR: its positions grouped by col_indices (cached per graph)
+    g = _csr_by_dst(outcsr_col_indices, N, outcsr_eids, outcsr_reltypes)
+    _call(grad_attn_score, "het_backward_hgt_full_graph_edge_softmax_ops_csr", _p(outcsr_row_ptr), outcsr_row_ptr.numel(),
+          _p(outcsr_col_indices), _p(outcsr_eids), _p(outcsr_reltypes), N, outcsr_eids.numel(), mu.shape[0], _p(message),
+          _p(unnormalized_attn_score), _p(normalized_attn_score), _p(out), _p(gradout), _p(mu), _p(grad_attn_score),
+          _p(grad_mu), H, dk, None if g is None else g.handle, _stream(grad_attn_score))
+
+
+@_op("backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(Tensor incsr_row_ptr, Tensor incsr_col_indices, "
+     "Tensor incsr_eids, Tensor incsr_reltypes, Tensor unnormalized_attn_score, Tensor normalized_attn_score, "
+     "Tensor grad_normalized_attn_score, Tensor mu, Tensor(a!) grad_unnormalized_attn_score, Tensor(b!) grad_mu) -> ()")
+def backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(incsr_row_ptr, incsr_col_indices, incsr_eids, incsr_reltypes,
+                                                                 unnormalized_attn_score, normalized_attn_score,
+                                                                 grad_normalized_attn_score, mu, grad_unnormalized_attn_score,
+                                                                 grad_mu):
+    _chk("backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr",
+         (unnormalized_attn_score, normalized_attn_score, grad_normalized_attn_score, mu, grad_unnormalized_attn_score,
+          grad_mu), (incsr_row_ptr, incsr_col_indices, incsr_eids, incsr_reltypes))
+    H, N = mu.shape[1], incsr_row_ptr.numel() - 1
+    g = _incsr_by_dst(incsr_row_ptr, incsr_eids, incsr_reltypes) if H % 4 == 0 else None
+    ws = None if g is None else torch.empty(max(1, N * H), dtype=torch.float32, device=mu.device)  # (split hub destinations)
+    _call(mu, "het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr", _p(incsr_row_ptr), incsr_row_ptr.numel(),
+          _p(incsr_col_indices), _p(incsr_eids), _p(incsr_reltypes), N, incsr_eids.numel(), mu.shape[0],
+          _p(unnormalized_attn_score), _p(normalized_attn_score), _p(grad_normalized_attn_score), _p(mu),
+          _p(grad_unnormalized_attn_score), _p(grad_mu), H, None if g is None else g.handle, _p(ws),
+          0 if ws is None else ws.numel() * 4, _stream(mu))
+
+
 @_op("hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo(Tensor separate_coo_relptrs, "
      "Tensor separate_coo_eids, Tensor separate_coo_row_indices, Tensor separate_coo_col_indices, Tensor inputs, "
      "Tensor weights, Tensor edge_norm, Tensor(a!) new_h) -> ()")

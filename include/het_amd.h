@@ -376,6 +376,70 @@ int het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_separate_coo(
     int64_t num_edges, int64_t num_nodes, const float* score, const float* a, const float* grad_a, const float* mu,
     float* grad_score, float* grad_mu, float* tmp, int64_t H, const het_grouping* by_dst, het_stream stream);
 
+/* a10c HGT's unfused aggregation on the CSR layouts (hgt_layers_and_funcs.py:298-422, the path of
+ *      --fused_message_mean_aggregation_flag off).  The same formulas as a10 with the edges given as a CSR:
+ *      row_ptrs [num_nodes + 1] (row_ptrs_len is its length and must equal num_nodes + 1), col_indices / eids /
+ *      reltypes [num_edges] per position.  In-CSR rows are destinations (col = source); out-CSR rows are sources
+ *      (col = destination).  Score tensors are [E,H] rows indexed by eids[i]; message rows are [E,H,dk]; node rows
+ *      ([N,H] sums, [N,H,dk] out / gradout / ret) by node id.  r(i) = reltypes[i], v(i) = the destination of position i.
+ *      by_dst (optional): het_grouping_create(NULL, 0, <destination of every position>, E, N, payload0 = eids,
+ *      payload1 = reltypes) -- the in-CSR's expanded rows, or the out-CSR's col_indices.  With it (and H % 4 == 0 for
+ *      the score-only ops, dk a power of two >= 4 with 8 <= H*dk <= 256 for the message ops, 16-byte aligned rows) a
+ *      wave per work item reduces a destination in registers; destinations with more than HET_ITEM_MAX in-edges are
+ *      split over several items whose partial sums meet in float atomics.  Otherwise a plain thread-per-element kernel
+ *      runs.  Host-side checks (HET_ERR_INVALID_ARG before any launch): sizes, row_ptrs_len, null pointers.
+ *
+ *      hgt_full_graph_edge_softmax_ops_csr                 HGTOps.inc.h:190-204 -> 23-106 (switch 3, in-CSR)
+ *   m[eids[i],h] = exp(mu[r(i),h] * score[eids[i],h]);  sum[v,h] = SUM over the in-edges of v of m;  a = m / sum[v,h]
+ *   (no max subtraction: DESIGN.md Q2).  sum, m, a are overwritten (sum = 0 for a destination without in-edges).
+ */
+int het_hgt_full_graph_edge_softmax_ops_csr(const int64_t* row_ptrs, int64_t row_ptrs_len, const int64_t* col_indices,
+                                            const int64_t* eids, const int64_t* reltypes, int64_t num_nodes,
+                                            int64_t num_edges, const float* score, const float* mu, float* sum, float* m,
+                                            float* a, int64_t H, const het_grouping* by_dst, het_stream stream);
+/*      hgt_full_graph_message_mean_aggregation_csr         HGTOps.inc.h:180-188 -> 109-178 (switch 1, in-CSR)
+ *   ret[v,h,:] = SUM over the in-edges of v of edge_attn_score[eids[i],h] / sum[v,h] * edge_messages[eids[i],h,:]
+ *   edge_attn_score is the mu-applied UNNORMALISED score (m of the softmax); mu is not read.
+ *   ret is overwritten (0 for a destination without in-edges). */
+int het_hgt_full_graph_message_mean_aggregation_csr(const int64_t* row_ptrs, int64_t row_ptrs_len, const int64_t* col_indices,
+                                                    const int64_t* reltypes, const int64_t* eids, int64_t num_nodes,
+                                                    int64_t num_edges, const float* edge_messages,
+                                                    const float* edge_attn_score, const float* sum, const float* mu,
+                                                    float* ret, int64_t H, int64_t dk, const het_grouping* by_dst,
+                                                    het_stream stream);
+/*      backward_hgt_full_graph_message_mean_aggregation_csr   HGTOps.inc.h:477-487 -> 410-475 (switch 2, out-CSR)
+ *   grad_message[eids[i],h,:] = a[eids[i],h] * gradout[col[i],h,:]     (every edge row written once: overwritten)
+ *   sum is not read (the normalised score a is given).  No grouping: a map over the positions. */
+int het_backward_hgt_full_graph_message_mean_aggregation_csr(const int64_t* row_ptrs, int64_t row_ptrs_len,
+                                                             const int64_t* col_indices, const int64_t* reltypes,
+                                                             const int64_t* eids, int64_t num_nodes, int64_t num_edges,
+                                                             const float* sum, const float* normalized_attn_score,
+                                                             const float* gradout, float* grad_message, int64_t H,
+                                                             int64_t dk, het_stream stream);
+/*      backward_hgt_full_graph_edge_softmax_ops_csr        HGTOps.inc.h:553-566 -> 489-551 (switch 2, out-CSR)
+ *   c = a[eids[i],h] * < gradout[v,h,:], message[eids[i],h,:] - out[v,h,:] >       (v = col[i], per head)
+ *   grad_attn_score[eids[i],h] = mu[r(i),h] * c    (overwritten)
+ *   grad_mu[r(i),h] += c * score[eids[i],h]         (accumulated; every edge credits its own relation: DESIGN.md Q13)
+ *   by_dst here groups the out-CSR positions by col_indices: a work item reads gradout[v] / out[v] once; grad_mu is
+ *   reduced per block in LDS (num_rels * H <= 4096) and flushed with one atomic per (relation, head) and block. */
+int het_backward_hgt_full_graph_edge_softmax_ops_csr(const int64_t* row_ptrs, int64_t row_ptrs_len, const int64_t* col_indices,
+                                                     const int64_t* eids, const int64_t* reltypes, int64_t num_nodes,
+                                                     int64_t num_edges, int64_t num_rels, const float* message,
+                                                     const float* score, const float* normalized_attn_score,
+                                                     const float* out, const float* gradout, const float* mu,
+                                                     float* grad_attn_score, float* grad_mu, int64_t H, int64_t dk,
+                                                     const het_grouping* by_dst, het_stream stream);
+/*      backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr   HGTOps.inc.h:282-325 (in-CSR)
+ *   the formulas of a10's backward:  tmp[v,h] = SUM over the in-edges of v of a*grad_a;  c = (grad_a - tmp[v,h]) * a
+ *   grad_score[eids[i],h] = c * mu[r(i),h]   (overwritten);   grad_mu[r(i),h] += c * score[eids[i],h]   (accumulated)
+ *   tmp stays in registers per destination; with by_dst and split hub destinations it is summed in `workspace`
+ *   (num_nodes * H floats, 16-byte aligned); without room there the plain kernel runs. */
+int het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(
+    const int64_t* row_ptrs, int64_t row_ptrs_len, const int64_t* col_indices, const int64_t* eids, const int64_t* reltypes,
+    int64_t num_nodes, int64_t num_edges, int64_t num_rels, const float* score, const float* normalized_attn_score,
+    const float* grad_normalized_attn_score, const float* mu, float* grad_score, float* grad_mu, int64_t H,
+    const het_grouping* by_dst, void* workspace, int64_t workspace_bytes, het_stream stream);
+
 /* a11  hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo (+ backward)
  *      OpExport/HGTOpsEdgeParallel.inc.h:33-88, 295-369
  *   new_h[col[i],h,:] += (v[row[i],h,:] * a[eids[i],h]) . W[r,h]                      W [R,H,dk,dout]
