@@ -50,6 +50,8 @@ _SIGNATURES = {
     "het_node_rows_matmul_sum_bias": [I64, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P],
     "het_rgcn_layer_forward": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
     "het_rgcn_layer_backward": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
+    "het_rgcn_layer_forward_bf16": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
+    "het_rgcn_layer_backward_bf16": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
     "het_rgat_backward_compact": [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, I64, P],
     "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
     "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],

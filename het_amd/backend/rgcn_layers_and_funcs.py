@@ -13,7 +13,7 @@ from ..kernels import K
 FUSED = os.environ.get("HET_RGCN_FUSED", "1") != "0"
 
 __all__ = [
-    "RgcnLayer1SeparateCoo", "RgcnLayerFused", "rgcn_layer1_separate_coo", "RGCNNodeMeanAggregationCompactAsOfNodeSeparateCOO",
+    "RgcnLayer1SeparateCoo", "RgcnLayerFused", "rgcn_layer1_separate_coo", "rgcn_layer_fused_applies", "RGCNNodeMeanAggregationCompactAsOfNodeSeparateCOO",
     "RGCNNodeMeanAggregationCompactAsOfNodeDirectIndexingSeparateCOO",
     "rgcn_node_mean_aggregation_compact_as_of_node_separate_coo_single_sided",
 ]
@@ -73,11 +73,14 @@ class RgcnLayerFused(th.autograd.Function):
     rows per (relation, destination) are kept from the forward -- the weight gradient is formed from them (half as many rows as
     the (relation, source) sums of a8, and x is not read again) -- the output and the input gradient are written once by a pass
     over the nodes (no zero-filled buffers, no read-modify-write per relation, no transposed-weight / bias-sum torch kernels):
-    ogbn-mag, feat 64: 3.0 -> 2.3 ms per step.  Same values as RgcnLayer1SeparateCooBias up to the order of the fp32 sums."""
+    ogbn-mag, feat 64: 3.0 -> 2.3 ms per step.  Same values as RgcnLayer1SeparateCooBias up to the order of the fp32 sums.
+    A bf16 ``x`` takes the bf16 entries: the output and grad_x are bf16 (rounded once, when stored), the weight, norm and bias
+    gradients and every sum fp32."""
 
     @staticmethod
     def forward(ctx, plan, x, weight, norm, bias):
-        ret, ssum = _k.rgcn_layer_forward(plan, x, weight, norm, bias)
+        ctx.bf16 = x.dtype == th.bfloat16
+        ret, ssum = (_k.rgcn_layer_forward_bf16 if ctx.bf16 else _k.rgcn_layer_forward)(plan, x, weight, norm, bias)
         ctx.plan, ctx.has_bias = plan, bias is not None
         ctx.save_for_backward(weight, norm, ssum)
         return ret
@@ -85,25 +88,33 @@ class RgcnLayerFused(th.autograd.Function):
     @staticmethod
     def backward(ctx, gradout):
         weight, norm, ssum = ctx.saved_tensors
-        grad_x, grad_w, grad_bias = _k.rgcn_layer_backward(ctx.plan, ssum, weight.transpose(1, 2).contiguous(), norm,
-                                                           gradout.contiguous(), ctx.has_bias, want_x=ctx.needs_input_grad[1])
+        backward = _k.rgcn_layer_backward_bf16 if ctx.bf16 else _k.rgcn_layer_backward
+        grad_x, grad_w, grad_bias = backward(ctx.plan, ssum, weight.transpose(1, 2).contiguous(), norm,
+                                             gradout.to(th.bfloat16 if ctx.bf16 else th.float32).contiguous(), ctx.has_bias,
+                                             want_x=ctx.needs_input_grad[1])
         # (the reference's a8 takes a grad_norm buffer and leaves it as it was given: zeros)
         grad_norm = th.zeros_like(norm) if ctx.needs_input_grad[3] else None
         return None, grad_x, grad_w, grad_norm, grad_bias
 
 
 def _fused_plan(graph, s, x, weight, norm, bias):
-    """The plan of the two-call layer when it applies: float32 GPU tensors of the graph's size, shapes the node-major pass takes,
-    groupings switched on."""
+    """The plan of the two-call layer when it applies: GPU tensors of the graph's size (x float32 or bfloat16, the weight, norm and
+    bias float32), shapes the node-major pass takes, groupings switched on."""
     if not (FUSED and x.is_cuda and x.dim() == 2 and weight.dim() == 3 and _k._plan.is_enabled()):
         return None
     N, E = graph.get_num_nodes(), s["eids"].numel()
     R, Kin, D = weight.shape
-    if not (E > 0 and x.shape == (N, Kin) and norm.numel() == E and x.dtype == weight.dtype == norm.dtype == th.float32 and
+    if not (E > 0 and x.shape == (N, Kin) and norm.numel() == E and x.dtype in (th.float32, th.bfloat16) and
+            weight.dtype == norm.dtype == th.float32 and
             (bias is None or (bias.dtype == th.float32 and bias.numel() == D)) and R == s["rel_ptrs"].numel() - 1 and
             _k.rgcn_layer_ok(R, Kin, D)):
         return None
     return _k.rgcn_layer_plan(s["rel_ptrs"], s["eids"], s["row_indices"], s["col_indices"], N)
+
+
+def rgcn_layer_fused_applies(graph, x, weight, norm, bias=None) -> bool:
+    """Whether rgcn_layer1_separate_coo runs these arguments as the two-call layer (for a bf16 x: the bf16 kernels)."""
+    return _fused_plan(graph, graph.get_separate_coo_original(), x, weight, norm, bias) is not None
 
 
 def rgcn_layer1_separate_coo(graph, x, weight, norm, bias=None):
@@ -113,6 +124,9 @@ def rgcn_layer1_separate_coo(graph, x, weight, norm, bias=None):
     if plan is not None:
         return RgcnLayerFused.apply(plan, x.contiguous(), weight.contiguous(), norm.contiguous(),
                                     None if bias is None else bias.contiguous())
+    if x.dtype == th.bfloat16 and weight.dtype == th.float32:
+        # (no bf16 kernels on this path: fp32 on an upcast copy, the result rounded back -- correct, not faster)
+        return rgcn_layer1_separate_coo(graph, x.float(), weight, norm, bias).to(th.bfloat16)
     if bias is not None:
         return RgcnLayer1SeparateCooBias.apply(s["rel_ptrs"], s["eids"], s["row_indices"], s["col_indices"], graph.get_num_nodes(),
                                                x.contiguous(), weight.contiguous(), norm.contiguous(), bias)

@@ -212,6 +212,40 @@ template <typename O>
 __device__ __forceinline__ void st1_at(float* base, O byte_off, float v) {
   *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
+// ---- row element types: float, or bf16 (het_bf16, the upper half of a float) -------------------------------------------
+// The bf16 rows of a layer are widened on load (exact) and rounded once, round-to-nearest-even, where a result row is stored:
+// a plain conversion, v_cvt_pk_bf16_f32 (keeps a NaN a NaN, which bit arithmetic on the float does not).  Sums stay fp32.
+typedef __bf16 het_bf16x2v __attribute__((ext_vector_type(2)));
+typedef float het_f2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float bf16_to_f32(het_bf16 v) { return __uint_as_float((uint32_t)v << 16); }
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(het_bf16 v) { return bf16_to_f32(v); }
+__device__ __forceinline__ uint32_t f32x2_to_bf16x2(float a, float b) {
+  const het_f2v v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, het_bf16x2v));
+}
+// 4 consecutive elements as a float4: 16 bytes of float, 8 bytes of bf16
+__device__ __forceinline__ float4 ldrow4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 ldrow4(const het_bf16* p) {
+  const uint2 u = *reinterpret_cast<const uint2*>(p);
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+// 2 consecutive elements as a float2: 8 bytes of float, 4 bytes of bf16
+__device__ __forceinline__ float2 ldrow2(const float* p) { return *reinterpret_cast<const float2*>(p); }
+__device__ __forceinline__ float2 ldrow2(const het_bf16* p) {
+  const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
+  return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u));
+}
+__device__ __forceinline__ void strow4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void strow4(het_bf16* p, float4 v) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(f32x2_to_bf16x2(v.x, v.y), f32x2_to_bf16x2(v.z, v.w));
+}
+__device__ __forceinline__ void strow2(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
+__device__ __forceinline__ void strow2(het_bf16* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = f32x2_to_bf16x2(a, b); }
+__device__ __forceinline__ void strow1(float* p, float v) { *p = v; }
+__device__ __forceinline__ void strow1(het_bf16* p, float v) { *p = __builtin_bit_cast(het_bf16, (__bf16)v); }
+
 constexpr int het_log2_ce(int v) { return v <= 1 ? 0 : 1 + het_log2_ce(v >> 1); }
 // rows * row_bytes fits an unsigned 32-bit byte offset (with room for the lane's piece of the row)
 static inline bool het_fits_u32(int64_t rows, int64_t row_bytes) { return rows >= 0 && rows * row_bytes <= 0xffffffffll - 4096; }

@@ -21,7 +21,9 @@ constexpr int kMaxSrc = 9;
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-struct SumArgs {
+// TO: the element type of the output rows, float or het_bf16 (rounded once, at the store); everything else is fp32
+template <typename TO>
+struct SumArgsT {
   int64_t n_begin, n_end;        // positions of `order` (or node ids) of this launch
   int64_t N;                     // nodes = rows of out = length of every map
   int S;                         // sources
@@ -31,7 +33,7 @@ struct SumArgs {
   int64_t ident_rows[kMaxSrc];
   const float* wt[kMaxSrc];      // [KS][XO] row-major
   const int32_t* order;          // [>= n_end] node at position p, or NULL (node p)
-  float* out;                    // [N, XO]
+  TO* out;                       // [N, XO]
   const float* bias;             // [XO] added to every output row, or NULL
   int64_t mix;                   // tile walked at step L of the grid-stride loop: (L * mix) % tiles (1: in list order).  A list sorted by
                                  // presence puts the nodes without any row first: in list order every wave stores its empty tiles first
@@ -39,12 +41,13 @@ struct SumArgs {
                                  // tiles, hands every wave a uniform sample of the classes (RGCN forward pass 0.239 -> 0.225 ms,
                                  // the backward one unchanged)
 };
+typedef SumArgsT<float> SumArgs;
 
 // Workgroup = WAVES independent waves sharing the S weights in LDS; a wave walks 32-node tiles (grid-stride), loads the rows of
 // every PRESENT source coalesced (KS/4 lanes x float4 per row) into its LDS tile, reads them back as MFMA A fragments and
 // multiplies them into the same XO/32 accumulators; the rows of the next present source are in flight during the MFMAs.
-template <int KS, int NO, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void HET_node_rows_sum(SumArgs a) {
+template <int KS, int NO, int WAVES, typename TO = float>
+__global__ __launch_bounds__(WAVES * 64) void HET_node_rows_sum(SumArgsT<TO> a) {
   constexpr int XO = NO * 32, KH = KS / 2;
   constexpr int LD = (KS > XO ? KS : XO) + 4;
   constexpr int LPRA = KS / 4, RPIA = 64 / LPRA, NITA = 32 / RPIA;
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(WAVES * 64) void HET_node_rows_sum(SumArgs a) {
       const int64_t node = idsN[it * RPIC + rc];
       float4 v = ld4(&Ws[(it * RPIC + rc) * LD + cc]);
       v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-      if (node >= 0) st4(a.out + node * XO + cc, v);
+      if (node >= 0) strow4(a.out + node * XO + cc, v);
     }
   }
 }
@@ -178,8 +181,8 @@ __global__ __launch_bounds__(WAVES * 64) void HET_node_rows_sum(SumArgs a) {
 // of the sorted list instead of by node id (coalesced instead of one random 4-byte gather per node and map) changed nothing
 // measurable -- the [R, N] int32 maps sit in the L2 / Infinity Cache -- and was removed again.
 // k mapping of a 32-column phase p: MFMA step q of lane (i, kk) multiplies A[i][32p + 16kk + q] with B[32p + 16kk + q][col].
-template <int KS, int NO>
-__global__ __launch_bounds__(1024) void HET_node_rows_sum_w16(SumArgs a) {
+template <int KS, int NO, typename TO = float>
+__global__ __launch_bounds__(1024) void HET_node_rows_sum_w16(SumArgsT<TO> a) {
   constexpr int XO = NO * 32;
   constexpr int LDA = 36;                                   // staged row: 32 floats + 4 (conflict-free 16-byte reads down a column of rows)
   constexpr int LPRA = KS / 4, RPIA = 64 / LPRA, NITA = 32 / RPIA;
@@ -299,18 +302,21 @@ __global__ __launch_bounds__(1024) void HET_node_rows_sum_w16(SumArgs a) {
       const int64_t n = __shfl(node, (reg & 3) + 8 * (reg >> 2) + 4 * kk);
       if (n >= 0) {
         if (PAIRED) {
-          *reinterpret_cast<float2*>(a.out + n * XO + 2 * i) = make_float2(acc[0][reg] + bias2.x, acc[NO - 1][reg] + bias2.y);
+          strow2(a.out + n * XO + 2 * i, acc[0][reg] + bias2.x, acc[NO - 1][reg] + bias2.y);
         } else {
 #pragma unroll
-          for (int nt = 0; nt < NO; ++nt) a.out[n * XO + nt * 32 + i] = acc[nt][reg] + (a.bias ? a.bias[nt * 32 + i] : 0.f);
+          for (int nt = 0; nt < NO; ++nt) {
+            const float v = acc[nt][reg] + (a.bias ? a.bias[nt * 32 + i] : 0.f);
+            strow1(a.out + n * XO + nt * 32 + i, v);
+          }
         }
       }
     }
   }
 }
 
-template <int KS, int NO>
-int launch_sum_w16(const SumArgs& a, hipStream_t s, bool* done) {
+template <int KS, int NO, typename TO>
+int launch_sum_w16(const SumArgsT<TO>& a, hipStream_t s, bool* done) {
   constexpr int XO = NO * 32;
   const size_t limit = het_lds_budget(), wbytes = sizeof(float) * (size_t)a.S * KS * XO, per_wave = sizeof(float) * 32 * 36;
   *done = false;
@@ -324,7 +330,7 @@ int launch_sum_w16(const SumArgs& a, hipStream_t s, bool* done) {
   if (gx > cus) gx = cus;  // one workgroup per CU (the weights are staged once), its waves walk the tiles grid-stride
   if (gx < 1) gx = 1;
   const size_t lds = wbytes + (size_t)waves * per_wave;
-  SumArgs b = a;
+  SumArgsT<TO> b = a;
   b.mix = 1;
   if (a.order && tiles > 4 * gx * waves) {
     auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t r = x % y; x = y; y = r; } return x; };
@@ -333,8 +339,8 @@ int launch_sum_w16(const SumArgs& a, hipStream_t s, bool* done) {
     b.mix = m < 1 ? 1 : m;
   }
   HET_KTIME("HET_node_rows_sum", s);
-  HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum_w16<KS, NO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((HET_node_rows_sum_w16<KS, NO>), dim3((unsigned)gx), dim3(waves * 64), lds, s, b);
+  HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum_w16<KS, NO, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((HET_node_rows_sum_w16<KS, NO, TO>), dim3((unsigned)gx), dim3(waves * 64), lds, s, b);
   HET_LAUNCH_CHECK("HET_node_rows_sum_w16");
   *done = true;
   return HET_OK;
@@ -346,8 +352,8 @@ size_t lds_for(int S, int waves) {
   return sizeof(float) * ((size_t)S * KS * XO + (size_t)waves * (32 * LD + (S + 1) * 32));
 }
 
-template <int KS, int NO>
-int launch_sum(const SumArgs& a, hipStream_t s) {
+template <int KS, int NO, typename TO>
+int launch_sum(const SumArgsT<TO>& a, hipStream_t s) {
   bool done = false;
   if (int rc = launch_sum_w16<KS, NO>(a, s, &done)) return rc;
   if (done) return HET_OK;
@@ -358,15 +364,15 @@ int launch_sum(const SumArgs& a, hipStream_t s) {
     const size_t lds = lds_for<KS, NO>(a.S, 8);
     int64_t gx = (tiles + 8 * 4 - 1) / (8 * 4);  // ~4 tiles per wave: the weights are staged once per workgroup
     if (gx < 1) gx = 1;
-    HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum<KS, NO, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((HET_node_rows_sum<KS, NO, 8>), dim3((unsigned)gx), dim3(512), lds, s, a);
+    HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum<KS, NO, 8, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((HET_node_rows_sum<KS, NO, 8, TO>), dim3((unsigned)gx), dim3(512), lds, s, a);
   } else {
     const size_t lds = lds_for<KS, NO>(a.S, 4);
     HET_REQUIRE(lds <= limit, "het_node_rows_matmul_sum: the weights of %d sources do not fit the LDS (het_node_rows_matmul_sum_ok)", a.S);
     int64_t gx = (tiles + 4 * 4 - 1) / (4 * 4);
     if (gx < 1) gx = 1;
-    HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum<KS, NO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((HET_node_rows_sum<KS, NO, 4>), dim3((unsigned)gx), dim3(256), lds, s, a);
+    HET_HIP(hipFuncSetAttribute((const void*)HET_node_rows_sum<KS, NO, 4, TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((HET_node_rows_sum<KS, NO, 4, TO>), dim3((unsigned)gx), dim3(256), lds, s, a);
   }
   HET_LAUNCH_CHECK("HET_node_rows_sum");
   return HET_OK;
@@ -384,10 +390,12 @@ extern "C" int het_node_rows_matmul_sum_ok(int64_t num_sources, int64_t KS, int6
   return lds_any((int)num_sources, KS, XO, 4) <= het_lds_budget() ? 1 : 0;
 }
 
-extern "C" int het_node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources,
-                                             const float* const* rows, const int64_t* row_strides, const int32_t* const* maps,
-                                             const int64_t* ident_rows, const float* const* weights_t, const float* bias,
-                                             float* out, int64_t KS, int64_t XO, const int32_t* node_order, het_stream stream) {
+namespace {
+template <typename TO>
+int node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources, const float* const* rows,
+                              const int64_t* row_strides, const int32_t* const* maps, const int64_t* ident_rows,
+                              const float* const* weights_t, const float* bias, TO* out, int64_t KS, int64_t XO,
+                              const int32_t* node_order, het_stream stream) {
   const char* op = "het_node_rows_matmul_sum";
   HET_REQUIRE(0 <= n_begin && n_begin <= n_end && n_end <= num_nodes && num_nodes < (1ll << 31), "%s: bad node range", op);
   HET_REQUIRE(het_node_rows_matmul_sum_ok(num_sources, KS, XO), "%s: unsupported shape: %lld sources of %lld -> %lld floats", op,
@@ -395,7 +403,7 @@ extern "C" int het_node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int
   if (n_begin == n_end) return HET_OK;
   HET_REQUIRE(rows && row_strides && maps && ident_rows && weights_t && out, "%s: null argument", op);
   HET_REQUIRE(((uintptr_t)bias & 15) == 0 && ((uintptr_t)out & 15) == 0, "%s: bias / out not 16-byte aligned", op);
-  SumArgs a{};
+  SumArgsT<TO> a{};
   a.n_begin = n_begin; a.n_end = n_end; a.N = num_nodes; a.S = (int)num_sources; a.order = node_order; a.out = out; a.bias = bias;
   for (int s = 0; s < a.S; ++s) {
     HET_REQUIRE(rows[s] && weights_t[s] && row_strides[s] >= KS && (row_strides[s] & 3) == 0 &&
@@ -407,6 +415,24 @@ extern "C" int het_node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int
   hipStream_t st = (hipStream_t)stream;
   if (KS == 64) return XO == 64 ? launch_sum<64, 2>(a, st) : launch_sum<64, 1>(a, st);
   return XO == 64 ? launch_sum<32, 2>(a, st) : launch_sum<32, 1>(a, st);
+}
+}  // namespace
+
+extern "C" int het_node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources,
+                                             const float* const* rows, const int64_t* row_strides, const int32_t* const* maps,
+                                             const int64_t* ident_rows, const float* const* weights_t, const float* bias,
+                                             float* out, int64_t KS, int64_t XO, const int32_t* node_order, het_stream stream) {
+  return node_rows_matmul_sum_bias(n_begin, n_end, num_nodes, num_sources, rows, row_strides, maps, ident_rows, weights_t, bias, out,
+                                   KS, XO, node_order, stream);
+}
+
+// the same with bf16 output rows (fp32 rows, weights, bias and sums; every output row rounded once): the RGCN layer's bf16 entries
+int node_rows_matmul_sum_bias_bf16(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources, const float* const* rows,
+                                   const int64_t* row_strides, const int32_t* const* maps, const int64_t* ident_rows,
+                                   const float* const* weights_t, const float* bias, het_bf16* out, int64_t KS, int64_t XO,
+                                   const int32_t* node_order, het_stream stream) {
+  return node_rows_matmul_sum_bias(n_begin, n_end, num_nodes, num_sources, rows, row_strides, maps, ident_rows, weights_t, bias, out,
+                                   KS, XO, node_order, stream);
 }
 
 extern "C" int het_node_rows_matmul_sum(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources,

@@ -661,14 +661,15 @@ extern "C" int het_backward_rgcn_layer1_separate_coo(const int64_t* rel_ptrs, co
 // ---- the RGCN layer as two calls (layer-level fusion of a7 / a8 with the layer's bias; include/het_amd.h) -------------------
 namespace {
 // column sums of a [rows, 4 * LPR] matrix: per-workgroup partial rows (grid-stride, 16 bytes per lane), finished by HET_colsum_finish
-template <int LPR>
-__global__ __launch_bounds__(256) void HET_colsum_partial(const float* __restrict__ in, int64_t rows, float* __restrict__ part) {
+// (T: the element type of `in`, float or het_bf16; the sums are fp32)
+template <int LPR, typename T = float>
+__global__ __launch_bounds__(256) void HET_colsum_partial(const T* __restrict__ in, int64_t rows, float* __restrict__ part) {
   constexpr int RPI = 256 / LPR;
   __shared__ float4 red[256];
   const int c = threadIdx.x % LPR, r = threadIdx.x / LPR;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t i = (int64_t)blockIdx.x * RPI + r; i < rows; i += (int64_t)gridDim.x * RPI) {
-    const float4 v = *reinterpret_cast<const float4*>(in + i * (4 * LPR) + 4 * c);
+    const float4 v = ldrow4(in + i * (4 * LPR) + 4 * c);
     acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
   }
   red[threadIdx.x] = acc;
@@ -696,15 +697,16 @@ __global__ __launch_bounds__(256) void HET_colsum_finish(const float* __restrict
 }
 constexpr int kColsumBlocks = 1024;
 
-int launch_colsum(const float* in, int64_t rows, int X, float* part, float* out, hipStream_t s) {
+template <typename T>
+int launch_colsum(const T* in, int64_t rows, int X, float* part, float* out, hipStream_t s) {
   HET_KTIME("HET_colsum", s);
   const int lpr = X / 4;
   const int64_t rpi = 256 / lpr;
   int blocks = (int)(ceil_div64(rows, rpi) < kColsumBlocks ? ceil_div64(rows, rpi) : kColsumBlocks);
   if (blocks < 1) blocks = 1;
   switch (lpr) {
-    case 8: hipLaunchKernelGGL(HET_colsum_partial<8>, dim3(blocks), dim3(256), 0, s, in, rows, part); break;
-    case 16: hipLaunchKernelGGL(HET_colsum_partial<16>, dim3(blocks), dim3(256), 0, s, in, rows, part); break;
+    case 8: hipLaunchKernelGGL((HET_colsum_partial<8, T>), dim3(blocks), dim3(256), 0, s, in, rows, part); break;
+    case 16: hipLaunchKernelGGL((HET_colsum_partial<16, T>), dim3(blocks), dim3(256), 0, s, in, rows, part); break;
     default: het_set_error("colsum: %d columns unsupported", X); return HET_ERR_UNSUPPORTED;
   }
   HET_LAUNCH_CHECK("HET_colsum_partial");
@@ -731,11 +733,39 @@ extern "C" int64_t het_rgcn_layer_backward_workspace(int64_t n_src_rows, int64_t
   return (int64_t)sizeof(float) * ((n_src_rows > 0 ? n_src_rows : 1) * D + (int64_t)kColsumBlocks * D);
 }
 
-extern "C" int het_rgcn_layer_forward(const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const float* x,
-                                      const float* weights, const float* norm, const float* norm_sorted, const float* bias,
-                                      const int32_t* dst_map, const int32_t* node_order, float* ssum, float* ret, int64_t K,
-                                      int64_t D, het_stream stream) {
-  const char* op = "het_rgcn_layer_forward";
+// node_sum.hip: het_node_rows_matmul_sum_bias with bf16 output rows
+int node_rows_matmul_sum_bias_bf16(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources, const float* const* rows,
+                                   const int64_t* row_strides, const int32_t* const* maps, const int64_t* ident_rows,
+                                   const float* const* weights_t, const float* bias, het_bf16* out, int64_t KS, int64_t XO,
+                                   const int32_t* node_order, het_stream stream);
+
+namespace {
+// The launches of the layer for activation rows of type T (float, or het_bf16: x, ret, gradout and grad_x; every sum, ssum / gsum,
+// the weights, the norm and the bias stay fp32)
+int rgcn_gather_sum(const het_grouping* g, const float* in, float* out, int X, const float* norm, const float* norm_sorted,
+                    hipStream_t s) {
+  return launch_segment_sum(g, in, out, X, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0);
+}
+int rgcn_gather_sum(const het_grouping* g, const het_bf16* in, float* out, int X, const float* norm, const float* norm_sorted,
+                    hipStream_t s) {
+  return launch_segment_sum_bf16(g, in, out, X, norm_sorted ? norm_sorted : norm, s, norm_sorted ? 1 : 0);
+}
+int rgcn_node_pass(int64_t num_nodes, int64_t S, const float* const* rows, const int64_t* strides, const int32_t* const* maps,
+                   const int64_t* ident, const float* const* wts, const float* bias, float* out, int64_t KS, int64_t XO,
+                   const int32_t* node_order, het_stream stream) {
+  return het_node_rows_matmul_sum_bias(0, num_nodes, num_nodes, S, rows, strides, maps, ident, wts, bias, out, KS, XO, node_order, stream);
+}
+int rgcn_node_pass(int64_t num_nodes, int64_t S, const float* const* rows, const int64_t* strides, const int32_t* const* maps,
+                   const int64_t* ident, const float* const* wts, const float* bias, het_bf16* out, int64_t KS, int64_t XO,
+                   const int32_t* node_order, het_stream stream) {
+  return node_rows_matmul_sum_bias_bf16(0, num_nodes, num_nodes, S, rows, strides, maps, ident, wts, bias, out, KS, XO, node_order,
+                                        stream);
+}
+
+template <typename T>
+int rgcn_layer_forward(const char* op, const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const T* x,
+                       const float* weights, const float* norm, const float* norm_sorted, const float* bias, const int32_t* dst_map,
+                       const int32_t* node_order, float* ssum, T* ret, int64_t K, int64_t D, het_stream stream) {
   const het_grouping* g = by_rel_dst;
   HET_REQUIRE(g && g->R == (int)num_rels && g->p0 && g->p1, "%s: needs the grouping by (relation, destination) with payloads (source row, edge id)", op);
   HET_REQUIRE(rgcn_layer_shape_ok(num_rels, K, D), "%s: unsupported shape (het_rgcn_layer_ok)", op);
@@ -749,22 +779,21 @@ extern "C" int het_rgcn_layer_forward(const het_grouping* by_rel_dst, int64_t nu
   // (norm_sorted: the norm in the grouping's order, het_grouping_gather_payload1 -- a coalesced stream instead of a random 4-byte
   //  gather per edge: the forward visits the edges by destination, their ids are scattered)
   if (g->E > 0)
-    if (int rc = launch_segment_sum(g, x, ssum, (int)K, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0)) return rc;
+    if (int rc = rgcn_gather_sum(g, x, ssum, (int)K, norm, norm_sorted, s)) return rc;
   // ret[v, :] = bias + SUM_r ssum[(r,v), :] . W[r]: one pass over the nodes, every output row stored once
   const float* rows[16]; int64_t strides[16]; const int32_t* maps[16]; int64_t ident[16]; const float* wts[16];
   for (int r = 0; r < (int)num_rels; ++r) {
     rows[r] = ssum; strides[r] = K; maps[r] = dst_map + (int64_t)r * num_nodes; ident[r] = 0; wts[r] = weights + (int64_t)r * K * D;
   }
-  return het_node_rows_matmul_sum_bias(0, num_nodes, num_nodes, num_rels, rows, strides, maps, ident, wts, bias, ret, K, D, node_order, stream);
+  return rgcn_node_pass(num_nodes, num_rels, rows, strides, maps, ident, wts, bias, ret, K, D, node_order, stream);
 }
 
-extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
-                                       int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t,
-                                       const float* norm, const float* norm_sorted, const float* gradout,
-                                       const int32_t* src_map, const int32_t* node_order, float* grad_x, float* grad_w,
-                                       float* grad_bias, int64_t K, int64_t D, void* workspace, int64_t workspace_bytes,
-                                       het_stream stream) {
-  const char* op = "het_rgcn_layer_backward";
+template <typename T>
+int rgcn_layer_backward(const char* op, const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
+                        int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t, const float* norm,
+                        const float* norm_sorted, const T* gradout, const int32_t* src_map, const int32_t* node_order, T* grad_x,
+                        float* grad_w, float* grad_bias, int64_t K, int64_t D, void* workspace, int64_t workspace_bytes,
+                        het_stream stream) {
   const het_grouping *gs = by_rel_src, *gd = by_rel_dst;
   HET_REQUIRE(gs && gd && gs->R == (int)num_rels && gd->R == (int)num_rels && gs->E == gd->E && gs->p0 && gs->p1,
               "%s: needs the groupings by (relation, source) [payloads: destination row, edge id] and by (relation, destination)", op);
@@ -782,7 +811,7 @@ extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het
   auto weight_gradients = [&](hipStream_t st) -> int {
     HET_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * num_rels * K * D, st));
     if (gd->S > 0) {
-      MfmaDwArgs w;
+      MfmaDwArgsT<T> w;
       w.A = ssum; w.a_ld = K; w.G = gradout; w.g_ld = D; w.g_gather = gd->seg_key64; w.dW = grad_w; w.dw_rel_stride = K * D;
       w.seg_ptrs = gd->seg_rel_ptr64; w.num_segs = (int)num_rels; w.num_rows = gd->S; w.K = (int)K; w.X = (int)D;
       if (int rc = launch_seg_dw_mfma(w, st)) return rc;
@@ -795,8 +824,7 @@ extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het
   if (!grad_x) return weight_gradients(s);
   // gsum[(r,u), :] = SUM over the out-edges of u in relation r of norm * gradout[dst]
   if (gs->E > 0)
-    if (int rc = launch_segment_sum(gs, gradout, gsum, (int)D, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0))
-      return rc;
+    if (int rc = rgcn_gather_sum(gs, gradout, gsum, (int)D, norm, norm_sorted, s)) return rc;
   HetFork fk(s);
   if (int rc = weight_gradients(fk.side)) return rc;
   // grad_x[u] = SUM_r gsum[(r,u)] . Wt[r]
@@ -805,12 +833,50 @@ extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het
     for (int r = 0; r < (int)num_rels; ++r) {
       rows[r] = gsum; strides[r] = D; maps[r] = src_map + (int64_t)r * num_src_nodes; ident[r] = 0; wts[r] = weights_t + (int64_t)r * D * K;
     }
-    if (int rc = het_node_rows_matmul_sum_bias(0, num_src_nodes, num_src_nodes, num_rels, rows, strides, maps, ident, wts, nullptr, grad_x,
-                                               D, K, node_order, stream))
+    if (int rc = rgcn_node_pass(num_src_nodes, num_rels, rows, strides, maps, ident, wts, nullptr, grad_x, D, K, node_order, stream))
       return rc;
   }
   HET_HIP(fk.join());
   return HET_OK;
+}
+}  // namespace
+
+extern "C" int het_rgcn_layer_forward(const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const float* x,
+                                      const float* weights, const float* norm, const float* norm_sorted, const float* bias,
+                                      const int32_t* dst_map, const int32_t* node_order, float* ssum, float* ret, int64_t K,
+                                      int64_t D, het_stream stream) {
+  return rgcn_layer_forward("het_rgcn_layer_forward", by_rel_dst, num_rels, num_nodes, x, weights, norm, norm_sorted, bias, dst_map,
+                            node_order, ssum, ret, K, D, stream);
+}
+
+extern "C" int het_rgcn_layer_forward_bf16(const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const het_bf16* x,
+                                           const float* weights, const float* norm, const float* norm_sorted, const float* bias,
+                                           const int32_t* dst_map, const int32_t* node_order, float* ssum, het_bf16* ret, int64_t K,
+                                           int64_t D, het_stream stream) {
+  return rgcn_layer_forward("het_rgcn_layer_forward_bf16", by_rel_dst, num_rels, num_nodes, x, weights, norm, norm_sorted, bias,
+                            dst_map, node_order, ssum, ret, K, D, stream);
+}
+
+extern "C" int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
+                                       int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t,
+                                       const float* norm, const float* norm_sorted, const float* gradout,
+                                       const int32_t* src_map, const int32_t* node_order, float* grad_x, float* grad_w,
+                                       float* grad_bias, int64_t K, int64_t D, void* workspace, int64_t workspace_bytes,
+                                       het_stream stream) {
+  return rgcn_layer_backward("het_rgcn_layer_backward", by_rel_src, by_rel_dst, num_rels, num_src_nodes, num_dst_nodes, ssum,
+                             weights_t, norm, norm_sorted, gradout, src_map, node_order, grad_x, grad_w, grad_bias, K, D, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int het_rgcn_layer_backward_bf16(const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
+                                            int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t,
+                                            const float* norm, const float* norm_sorted, const het_bf16* gradout,
+                                            const int32_t* src_map, const int32_t* node_order, het_bf16* grad_x, float* grad_w,
+                                            float* grad_bias, int64_t K, int64_t D, void* workspace, int64_t workspace_bytes,
+                                            het_stream stream) {
+  return rgcn_layer_backward("het_rgcn_layer_backward_bf16", by_rel_src, by_rel_dst, num_rels, num_src_nodes, num_dst_nodes, ssum,
+                             weights_t, norm, norm_sorted, gradout, src_map, node_order, grad_x, grad_w, grad_bias, K, D, workspace,
+                             workspace_bytes, stream);
 }
 
 // ---- layer epilogue: out[i, :] = a[i, :] (+ b[i, :]) (+ bias[:]) -- the "h + loop_message + h_bias" of the layers

@@ -9,6 +9,8 @@
 // (half h owns k in [h*K/2, (h+1)*K/2)) -- A and B use the same permutation, so
 // the sum is unchanged while every lane's fragment is one contiguous half row.
 
+#include <type_traits>
+
 #include "seg_gemm_mfma.hip.h"
 #include "coop.hip.h"
 
@@ -274,8 +276,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // add per element and workgroup.
 // CS: additionally colsum[n] += SUM_rows G[row, n] (the bias gradient of a layer whose output gradient this launch streams
 // anyway: one VALU add per loaded G value instead of another pass over the rows); the workgroups of the first K block add it.
-template <int KT, int NT, bool CS = false>
-__global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgs a, int chunk) {
+template <int KT, int NT, bool CS = false, typename TG = float>
+__global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG> a, int chunk) {
   // blockIdx.y selects a (KT*32) x (NT*32) block of the K x X product when K or X exceed 64 (each block re-reads its
   // column slices of the A and G rows)
   const int Kf = a.K, Xf = a.X, nbn = Xf / (NT * 32);
@@ -341,11 +343,11 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgs a, int chunk) 
           for (int kt = 0; kt < KT; ++kt) AV[st][kt] = a.A[(int64_t)A[st] * a.a_ld + kbase + kt * 32 + col];
         }
         if (NT == 2) {
-          const float2 t = *reinterpret_cast<const float2*>(a.G + (int64_t)G[st] * a.g_ld + nbase + 2 * col);
+          const float2 t = ldrow2(a.G + (int64_t)G[st] * a.g_ld + nbase + 2 * col);
           GV[st][0] = t.x; GV[st][NT - 1] = t.y;
         } else {
 #pragma unroll
-          for (int nt = 0; nt < NT; ++nt) GV[st][nt] = a.G[(int64_t)G[st] * a.g_ld + nbase + nt * 32 + col];
+          for (int nt = 0; nt < NT; ++nt) GV[st][nt] = to_f32(a.G[(int64_t)G[st] * a.g_ld + nbase + nt * 32 + col]);
         }
       }
     };
@@ -456,8 +458,8 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgs a, int chunk) 
   }
 }
 
-template <int KT, int NT>
-int launch_dw_kx(const MfmaDwArgs& a, hipStream_t s) {
+template <int KT, int NT, typename TG>
+int launch_dw_kx(const MfmaDwArgsT<TG>& a, hipStream_t s) {
   const size_t lds = sizeof(float) * (3 * KT * NT * 16 * 64 + (a.colsum ? 3 * NT * 32 : 0));
   HET_REQUIRE(!a.row_scale, "segment dW (MFMA): row scales are applied by the segment-sum pre-pass, not here");
   HET_REQUIRE(a.a_ld % 2 == 0 && a.g_ld % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.G) & 7) == 0,
@@ -471,13 +473,17 @@ int launch_dw_kx(const MfmaDwArgs& a, hipStream_t s) {
   const int64_t gx = ceil_div64(a.num_rows, chunk) + a.num_segs;
   const unsigned gy = (unsigned)((a.K / (KT * 32)) * (a.X / (NT * 32)));
   if (a.colsum) {
-    HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HET_KTIME("HET_seg_dw_mfma", s);
-    hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, true>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
+    if constexpr (std::is_same<TG, float>::value) {
+      HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HET_KTIME("HET_seg_dw_mfma", s);
+      hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, true>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
+    } else {
+      HET_REQUIRE(false, "segment dW (MFMA, bf16 G rows): no column sums");
+    }
   } else {
-    HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, false, TG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HET_KTIME("HET_seg_dw_mfma", s);
-    hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
+    hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, false, TG>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
   }
   HET_LAUNCH_CHECK("HET_seg_dw_mfma");
   return HET_OK;
@@ -613,6 +619,14 @@ int launch_seg_dw_mfma(const MfmaDwArgs& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
   HET_REQUIRE(mfma_dw_supported(a.K, a.X), "segment dW (MFMA): unsupported shape K=%d X=%d", a.K, a.X);
   // 64-wide blocks of the product per workgroup; K or X = 128 are covered by 2 (or 4) blocks along blockIdx.y
+  if (a.K == 32) return a.X == 32 ? launch_dw_kx<1, 1>(a, s) : launch_dw_kx<1, 2>(a, s);
+  return a.X == 32 ? launch_dw_kx<2, 1>(a, s) : launch_dw_kx<2, 2>(a, s);
+}
+
+int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16>& a, hipStream_t s) {
+  if (a.num_rows == 0) return HET_OK;
+  HET_REQUIRE((a.K == 32 || a.K == 64) && (a.X == 32 || a.X == 64) && a.headcat == 0,
+              "segment dW (MFMA, bf16 G rows): unsupported shape K=%d X=%d", a.K, a.X);
   if (a.K == 32) return a.X == 32 ? launch_dw_kx<1, 1>(a, s) : launch_dw_kx<1, 2>(a, s);
   return a.X == 32 ? launch_dw_kx<2, 1>(a, s) : launch_dw_kx<2, 2>(a, s);
 }

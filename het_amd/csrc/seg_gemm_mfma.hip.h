@@ -55,14 +55,15 @@ inline int launch_seg_gemm_mfma_fwd(const float* x, int64_t x_ld, const idx_t* g
 
 // dW_r(k, n) += sum_{i in segment r} scale(i) * A[ga(i), k] * G[gg(i), n]   on the matrix cores
 // (the MFMA k dimension runs over rows).  Output layout: plain [K][X] per segment, or
-// head-concatenated [Hc][K][Dh] with n = (h, d).
-struct MfmaDwArgs {
+// head-concatenated [Hc][K][Dh] with n = (h, d).  TG: the element type of the G rows, float or het_bf16 (widened on load).
+template <typename TG = float>
+struct MfmaDwArgsT {
   const float* A = nullptr;
   int64_t a_ld = 0;
   const idx_t* gather = nullptr;
   const float* row_scale = nullptr;
   const idx_t* scale_idx = nullptr;
-  const float* G = nullptr;
+  const TG* G = nullptr;
   int64_t g_ld = 0;
   const idx_t* g_gather = nullptr;
   float* dW = nullptr;
@@ -75,5 +76,8 @@ struct MfmaDwArgs {
   int64_t num_rows = 0;
   int K = 0, X = 0;
 };
+typedef MfmaDwArgsT<float> MfmaDwArgs;
 bool mfma_dw_supported(int K, int X);
 int launch_seg_dw_mfma(const MfmaDwArgs& a, hipStream_t s);
+// bf16 G rows: K, X in {32, 64}, plain layout, no column sums (the RGCN layer's bf16 weight gradient)
+int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16>& a, hipStream_t s);

@@ -115,14 +115,14 @@ __device__ __forceinline__ int ss_bcast_i(int v, int q) {
 __device__ __forceinline__ float ss_bcast(float v, int q) { return __int_as_float(ss_bcast_i(__float_as_int(v), q)); }
 
 // SHORT segments: a lane group per pack of whole segments (grouping_packs), rows of a segment summed in registers and
-// stored once; ids a step ahead.
-template <int LPR>
+// stored once; ids a step ahead.  T: the element type of the gathered rows, float or het_bf16 (the sums are fp32 either way).
+template <int LPR, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_segment_sum_packed(const int32_t* __restrict__ pack_ptr, int64_t num_packs,
                                                                   const int32_t* __restrict__ seg_of_rank,
                                                                   const int32_t* __restrict__ p_row,
                                                                   const int32_t* __restrict__ p_scale,
                                                                   const float* __restrict__ scale, int scale_heads,
-                                                                  const float* __restrict__ in, float* __restrict__ out,
+                                                                  const T* __restrict__ in, float* __restrict__ out,
                                                                   const int32_t* __restrict__ out_row, int accumulate,
                                                                   int contig, int scale_quad) {
   constexpr int EPW = 64 / LPR, X = LPR * 4, U = 4;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_packed(const int32_t* 
     }
     float4 f[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) f[u] = ld4(in + (int64_t)ss_bcast_i(rowv, u) * X + x);
+    for (int u = 0; u < U; ++u) f[u] = ldrow4(in + (int64_t)ss_bcast_i(rowv, u) * X + x);
     jn = j0 + U + q4 < e ? j0 + U + q4 : e - 1;
     rown = contig ? jn : p_row[jn];
     segn = seg_of_rank[jn];
@@ -183,8 +183,8 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_packed(const int32_t* 
 }
 
 // LONG segments: a wave per work item (<= HET_ITEM_MAX rows of one segment), lane groups round-robin, one cross-group
-// reduction; an item that is not its whole segment adds atomically (the launcher cleared those rows).
-template <int LPR>
+// reduction; an item that is not its whole segment adds atomically (the launcher cleared those rows).  T as above.
+template <int LPR, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_segment_sum_long(const int32_t* __restrict__ long_items, int64_t num_long,
                                                                 const int32_t* __restrict__ item_seg,
                                                                 const int32_t* __restrict__ item_begin,
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_long(const int32_t* __
                                                                 const int32_t* __restrict__ p_row,
                                                                 const int32_t* __restrict__ p_scale,
                                                                 const float* __restrict__ scale, int scale_heads,
-                                                                const float* __restrict__ in, float* __restrict__ out,
+                                                                const T* __restrict__ in, float* __restrict__ out,
                                                                 const int32_t* __restrict__ out_row, int accumulate,
                                                                 int contig, int scale_quad) {
   constexpr int EPW = 64 / LPR, X = LPR * 4, U = 4;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_long(const int32_t* __
     }
     float4 f[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) f[u] = ld4(in + (int64_t)ss_bcast_i(rowv, u) * X + x);
+    for (int u = 0; u < U; ++u) f[u] = ldrow4(in + (int64_t)ss_bcast_i(rowv, u) * X + x);
     jn = j0 + (U + q4) * EPW < e ? j0 + (U + q4) * EPW : e - 1;
     rown = contig ? jn : p_row[jn];
     if (scale) sin = p_scale ? p_scale[jn] : jn;
@@ -462,6 +462,42 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
   }
 #undef HET_SS
   HET_LAUNCH_CHECK("HET_segment_sum");
+  return HET_OK;
+}
+
+int launch_segment_sum_bf16(const het_grouping* g, const het_bf16* in, float* out, int X, const float* scale, hipStream_t s,
+                            int scale_sorted) {
+  HET_REQUIRE(g->p0 && (X == 32 || X == 64) && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+              "segment sum (bf16 rows): unsupported shape or grouping, or out not 16-byte aligned");
+  if (g->S == 0) return HET_OK;
+  // the cooperative kernels of launch_segment_sum with its defaults (dense output, overwritten; one scale per row)
+  if (g->num_split > 0) {
+    const int64_t n4 = g->num_split * (X / 4);
+    hipLaunchKernelGGL(HET_segsum_zero_split, dim3((unsigned)ceil_div64(n4, kBlock)), dim3(kBlock), 0, s, g->split_seg, n4, X / 4, out);
+    HET_LAUNCH_CHECK("HET_segsum_zero_split");
+  }
+  if (int rc = grouping_packs(g, s)) return rc;
+  const int32_t* p_scale = scale_sorted ? nullptr : (g->p1 ? g->p1 : g->p0);
+  const int contig = g->p0_contiguous, LPRv = X / 4;
+  HET_KTIME("HET_segment_sum", s);
+  const unsigned nbp = (unsigned)ceil_div64(g->num_packs, (int64_t)(kBlock / 64) * (64 / LPRv));
+#define HET_SSP(L)                                                                                                              \
+  hipLaunchKernelGGL((HET_segment_sum_packed<L, het_bf16>), dim3(nbp), dim3(kBlock), 0, s, g->pack_ptr, g->num_packs, g->seg_of_rank, \
+                     g->p0, p_scale, scale, 0, in, out, nullptr, 0, contig, 1)
+  if (LPRv == 8) HET_SSP(8);
+  else HET_SSP(16);
+#undef HET_SSP
+  HET_LAUNCH_CHECK("HET_segment_sum_packed");
+  if (g->num_long_items > 0) {
+    const unsigned nbl = (unsigned)ceil_div64(g->num_long_items, kBlock / 64);
+#define HET_SSL(L)                                                                                                              \
+  hipLaunchKernelGGL((HET_segment_sum_long<L, het_bf16>), dim3(nbl), dim3(kBlock), 0, s, g->long_items, g->num_long_items,          \
+                     g->item_seg, g->item_begin, g->item_end, g->seg_ptr, g->p0, p_scale, scale, 0, in, out, nullptr, 0, contig, 1)
+    if (LPRv == 8) HET_SSL(8);
+    else HET_SSL(16);
+#undef HET_SSL
+    HET_LAUNCH_CHECK("HET_segment_sum_long");
+  }
   return HET_OK;
 }
 

@@ -16,6 +16,10 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
                        int scale_heads = 0, int64_t scatter_rows = -1, int accumulate = 0, int scale_by_p0 = 0,
                        int nt_in = 0,          // nt_in: `in` is read once (an [E, X] stream): non-temporal loads
                        int scale_sorted = 0);  // `scale` is in the grouping's order: scale[j (* H + h)] belongs to sorted rank j
+// The same sum over bf16 rows (widened on load, summed and stored in fp32) for the RGCN layer's bf16 entries: X = 32 or 64, dense
+// output (16-byte aligned) that is overwritten, one scale per row (index: payload1, or with scale_sorted the rank)
+int launch_segment_sum_bf16(const het_grouping* g, const het_bf16* in, float* out, int X, const float* scale, hipStream_t s,
+                            int scale_sorted);
 // out[j, :] = values[payload1 of rank j, :] (H floats per entry): a per-edge-id scale brought into the grouping's order once, for
 // callers that pass the same scale every step (an edge norm)
 int launch_gather_by_p1(const het_grouping* g, const float* values, int H, float* out, hipStream_t s);

@@ -1191,6 +1191,49 @@ def rgcn_layer_backward(plan, ssum, weights_t, norm, gradout, want_bias: bool, w
     return grad_x, grad_w, grad_bias
 
 
+def _chk_bf16(name: str, rows=(), floats=()):
+    """The bf16 layer entries: activation rows (``rows``) contiguous bfloat16 GPU tensors, everything else as _chk."""
+    for t in rows:
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
+            raise _lib.HetError(f"{name}: expected contiguous bfloat16 GPU activation rows, got {t.dtype} on {t.device}"
+                                f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+    _chk(name, floats)
+
+
+def rgcn_layer_forward_bf16(plan, x, weights, norm, bias):
+    """rgcn_layer_forward with bf16 activations (het_rgcn_layer_forward_bf16): x and the returned ret [N,D] bf16; weights, norm,
+    bias and the kept sums ssum [S_col,K] fp32."""
+    gd, _, dst_map, dst_order, _, _ = plan
+    _chk_bf16("rgcn_layer_forward_bf16", (x,), tuple(t for t in (weights, norm, bias) if t is not None))
+    R, K, D = weights.shape
+    N = dst_map.shape[1]
+    ssum = torch.empty((max(1, gd.num_segments), K), dtype=torch.float32, device=x.device)
+    ret = torch.empty((N, D), dtype=torch.bfloat16, device=x.device)
+    _call(ret, "het_rgcn_layer_forward_bf16", gd.handle, R, N, _p(x), _p(weights), _p(norm), _p(scale_in_rank_order(gd, norm)),
+          _p(bias), _p(dst_map), _p(dst_order), _p(ssum), _p(ret), K, D, _stream(ret))
+    return ret, ssum
+
+
+def rgcn_layer_backward_bf16(plan, ssum, weights_t, norm, gradout, want_bias: bool, want_x: bool = True):
+    """rgcn_layer_backward with bf16 activations (het_rgcn_layer_backward_bf16): gradout and grad_x [N,K] bf16; grad_w [R,K,D]
+    and grad_bias [D] fp32."""
+    gd, gs, _, _, src_map, src_order = plan
+    _chk_bf16("rgcn_layer_backward_bf16", (gradout,), (ssum, weights_t, norm))
+    R, D, K = weights_t.shape
+    N = src_map.shape[1]
+    dev = gradout.device
+    grad_x = torch.empty((N, K), dtype=torch.bfloat16, device=dev) if want_x else None
+    grad_w = torch.empty((R, K, D), dtype=torch.float32, device=dev)
+    grad_bias = torch.empty((D,), dtype=torch.float32, device=dev) if want_bias else None
+    nbytes = int(_lib.lib().het_rgcn_layer_backward_workspace(gs.num_segments, D))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    _call(gradout, "het_rgcn_layer_backward_bf16", gs.handle, gd.handle, R, N, gradout.shape[0], _p(ssum), _p(weights_t), _p(norm),
+          _p(scale_in_rank_order(gs, norm) if want_x else None),
+          _p(gradout), _p(src_map), _p(src_order), _p(grad_x), _p(grad_w), _p(grad_bias), K, D, _p(ws),
+          ws.numel() * 4, _stream(gradout))
+    return grad_x, grad_w, grad_bias
+
+
 def _rgcn_maps(d: Dict[str, Tensor], direct: bool):
     if direct:
         return d["inverse_indices_row"], None

@@ -266,7 +266,15 @@ class HET_RGATLayer(nn.Module):
 
 
 class HET_EglRelGraphConv_EdgeParallel(nn.Module):
-    """RGCN layer on the fused separate-COO op (RGCN/RGCN.py:194-350)."""
+    """RGCN layer on the fused separate-COO op (RGCN/RGCN.py:194-350).
+
+    bf16 activations: a ``torch.bfloat16`` input gives a bf16 output (and a bf16 input gradient); the parameters, their
+    gradients, the edge norm and every sum stay fp32.  Where the two-call layer applies (groupings on, a shape of
+    kernels.rgcn_layer_ok, output width 32 or 64 after padding, HET_RGCN_FUSED on, not compact_as_of_node_flag) the library's
+    bf16 entries run and the bias, zero-padded to a padded width, is added inside them, so the output is rounded once.  Every
+    other path -- compact_as_of_node_flag, groupings off (plan.forced(False): one-shot block graphs), shapes outside
+    rgcn_layer_ok such as 8 relations at 64 x 64, HET_RGCN_FUSED=0, widths padded to 128 -- runs the fp32 layer on an upcast copy
+    of the input and rounds its output to bf16: correct, not faster, and it needs the fp32 copy."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_bases=-1, *, bias=True, activation=None,
                  compact_as_of_node_flag=False, compact_direct_indexing_flag=False, dropout=0.0):
@@ -287,21 +295,9 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, g, x, norm, num_dst=None):
-        if self.num_bases < self.num_rels:  # basis decomposition, RGCN.py:286-301
-            weight = th.matmul(self.w_comp, self.weight.view(self.num_bases, -1)).view(
-                self.num_rels, self.in_feat, self.out_feat)
-        else:
-            weight = self.weight
-        Xp = next((w for w in (32, 64, 128) if w >= self.out_feat), self.out_feat)
-        if PAD_WIDTHS and x.is_cuda and Xp != self.out_feat:
-            # Output widths below / between the matrix-core kernels' (the reference's RGCN experiments are 128 | 32 -> 16 | 8
-            # classes, hrt/experiments/run_het_rgcn.sh): zero columns appended to the weights change no value -- the extra
-            # output columns are zero and dropped, their gradients too -- and the whole layer runs on the 32 / 64 / 128-wide
-            # kernels (ogbn-mag, 128 -> 8: 5.15 -> 3.9 ms per step).  HET_PAD_WIDTHS=0: the any-shape kernels as before.
-            weight = nn.functional.pad(weight, (0, Xp - self.out_feat))
-        Kp = _padded_in_width(self.in_feat) if x.is_cuda else self.in_feat
-        if Kp != self.in_feat:  # (input widths outside 32 / 64 / 128: _padded_in_width)
-            x, weight = nn.functional.pad(x, (0, Kp - self.in_feat)), nn.functional.pad(weight, (0, 0, 0, Kp - self.in_feat))
+        if x.dtype == th.bfloat16:
+            return self._forward_bf16(g, x, norm, num_dst)
+        weight, x = self._weight_and_input(x)
         if self.compact_as_of_node_flag:  # RGCN.py:310-336
             ss = g.get_separate_unique_node_indices_single_sided()
             d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"],
@@ -326,6 +322,41 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
         if self.activation:
             node_repr = self.activation(node_repr)
         return self.dropout(node_repr)
+
+    def _weight_and_input(self, x):
+        """The layer's [R, K, D] weight (basis-composed, zero-padded to the kernels' widths) and the input, padded to match."""
+        if self.num_bases < self.num_rels:  # basis decomposition, RGCN.py:286-301
+            weight = th.matmul(self.w_comp, self.weight.view(self.num_bases, -1)).view(
+                self.num_rels, self.in_feat, self.out_feat)
+        else:
+            weight = self.weight
+        Xp = next((w for w in (32, 64, 128) if w >= self.out_feat), self.out_feat)
+        if PAD_WIDTHS and x.is_cuda and Xp != self.out_feat:
+            # Output widths below / between the matrix-core kernels' (the reference's RGCN experiments are 128 | 32 -> 16 | 8
+            # classes, hrt/experiments/run_het_rgcn.sh): zero columns appended to the weights change no value -- the extra
+            # output columns are zero and dropped, their gradients too -- and the whole layer runs on the 32 / 64 / 128-wide
+            # kernels (ogbn-mag, 128 -> 8: 5.15 -> 3.9 ms per step).  HET_PAD_WIDTHS=0: the any-shape kernels as before.
+            weight = nn.functional.pad(weight, (0, Xp - self.out_feat))
+        Kp = _padded_in_width(self.in_feat) if x.is_cuda else self.in_feat
+        if Kp != self.in_feat:  # (input widths outside 32 / 64 / 128: _padded_in_width)
+            x, weight = nn.functional.pad(x, (0, Kp - self.in_feat)), nn.functional.pad(weight, (0, 0, 0, Kp - self.in_feat))
+        return weight, x
+
+    def _forward_bf16(self, g, x, norm, num_dst):
+        weight, xp = self._weight_and_input(x)
+        if not self.compact_as_of_node_flag:
+            bias = nn.functional.pad(self.h_bias, (0, weight.shape[2] - self.out_feat)) if self.bias else None
+            if B.rgcn_layer_fused_applies(g, xp, weight, norm, bias):
+                # the bf16 kernels, the bias inside them: the output is rounded once; slicing rounds nothing
+                node_repr = B.rgcn_layer1_separate_coo(g, xp, weight, norm, bias)
+                if num_dst is not None and num_dst < node_repr.shape[0]:
+                    node_repr = node_repr[:num_dst]
+                if node_repr.shape[1] != self.out_feat:
+                    node_repr = node_repr[:, :self.out_feat]
+                if self.activation:
+                    node_repr = self.activation(node_repr)
+                return self.dropout(node_repr)
+        return self.forward(g, x.float(), norm, num_dst).to(th.bfloat16)
 
 
 def _heads_first(w, H):

@@ -41,6 +41,8 @@ extern "C" {
 #define HET_ERR_UNSUPPORTED 3
 
 typedef void* het_stream; /* hipStream_t */
+/* a bfloat16 value: the upper 16 bits of an IEEE float (the layer entries named *_bf16 take activation rows of it) */
+typedef uint16_t het_bf16;
 
 /* CompactAsOfNodeKind, include/kernel_enums.h:6-14 (the int the ops take) */
 #define HET_KIND_DISABLED 0
@@ -735,6 +737,18 @@ int het_rgcn_layer_backward(const het_grouping* by_rel_src, const het_grouping* 
                             const float* norm, const float* norm_sorted, const float* gradout, const int32_t* src_map,
                             const int32_t* node_order, float* grad_x, float* grad_w, float* grad_bias, int64_t K, int64_t D, void* workspace,
                             int64_t workspace_bytes, het_stream stream);
+/* The same layer with bf16 activations: x, ret, gradout and grad_x are het_bf16 rows; the weights, norm, bias, ssum, the workspace,
+ * grad_w and grad_bias stay fp32, as do all sums.  bf16 values are widened on load (exact) and ret / grad_x are rounded once, to
+ * nearest even, when stored (after the fp32 bias is added).  Arguments, shapes, workspace and validation as the fp32 pair. */
+int het_rgcn_layer_forward_bf16(const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const het_bf16* x,
+                                const float* weights, const float* norm, const float* norm_sorted, const float* bias,
+                                const int32_t* dst_map, const int32_t* node_order, float* ssum, het_bf16* ret, int64_t K, int64_t D,
+                                het_stream stream);
+int het_rgcn_layer_backward_bf16(const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
+                                 int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t,
+                                 const float* norm, const float* norm_sorted, const het_bf16* gradout, const int32_t* src_map,
+                                 const int32_t* node_order, het_bf16* grad_x, float* grad_w, float* grad_bias, int64_t K, int64_t D,
+                                 void* workspace, int64_t workspace_bytes, het_stream stream);
 
 /* self-loop + bias of a layer as one pass (RGAT/models.py:378-381: h + th.matmul(inputs_dst, loop_weight) + h_bias):
  * out[i,:] = x[i,:] . w + bias for rows [offsets[0], offsets[1]) (offsets: device array), w [K,X], bias [X] or NULL.
