@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Device code of two source trees, kernel by kernel: the proof a refactor of het_amd/csrc owes.
+
+    git worktree add /tmp/parent HEAD~1
+    python3 exp/tools/isa_diff.py /tmp/parent/het_amd/csrc het_amd/csrc [--rename 8CsrItems=5Items] [--keep DIR] [-j N]
+
+Compiles every file of the Makefile's SRCS in both trees with the Makefile's flags plus --cuda-device-only -S and compares
+the set of kernel symbols and the text of every kernel, label to .end_amdhsa_kernel (descriptor included).  --rename
+rewrites a substring of the OLD tree's assembly first (a renamed parameter type changes the mangled names).  The
+per-translation-unit __hip_cuid_<hash> symbol lies outside the kernels and is not compared.  One summary line per file;
+exit status 1 when anything differs."""
+import argparse
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import isa_stats  # noqa: E402
+
+
+def kernels(path):  # isa_stats' parser also returns device functions and data labels: keep what ends in a kernel descriptor
+    return {k: b for k, b in isa_stats.kernels(path).items() if b and b[-1].strip().startswith(".end_amdhsa_kernel")}
+
+
+def make_var(csrc, name):
+    m = re.search(rf"^{name}\s*\??:?=\s*(.*)$", (Path(csrc) / "Makefile").read_text(), re.M)
+    return m.group(1).strip()
+
+
+def assemble(csrc, src, out):
+    flags = make_var(csrc, "CXXFLAGS").replace("$(ARCH)", make_var(csrc, "ARCH")).replace("$(GIT_SHA)", "isa_diff").replace('\\"', '"')
+    out.parent.mkdir(parents=True, exist_ok=True)
+    subprocess.run([make_var(csrc, "HIPCC"), *flags.split(), "--cuda-device-only", "-S", src, "-o", str(out)], cwd=csrc, check=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("--keep", help="directory for the .s files (default: a temporary one)")
+    ap.add_argument("-j", type=int, default=8)
+    a = ap.parse_args()
+    tmp = Path(a.keep or tempfile.mkdtemp(prefix="isa_diff_"))
+    srcs = make_var(a.new, "SRCS").split()
+    if srcs != make_var(a.old, "SRCS").split():
+        print("SRCS differ between the trees")
+        return 1
+    with ThreadPoolExecutor(a.j) as ex:
+        jobs = [(s, ex.submit(assemble, a.old, s, tmp / "old" / (s + ".s")), ex.submit(assemble, a.new, s, tmp / "new" / (s + ".s"))) for s in srcs]
+        files = [(s, o.result(), n.result()) for s, o, n in jobs]
+    bad = 0
+    for s, o, n in files:
+        text = o.read_text()
+        renamed = 0
+        for r in a.rename:
+            frm, to = r.split("=")
+            renamed += len({k for k in kernels(o) if frm in k})
+            text = text.replace(frm, to)
+        o.write_text(text)
+        ko, kn = kernels(o), kernels(n)
+        only_old, only_new = sorted(set(ko) - set(kn)), sorted(set(kn) - set(ko))
+        differ = sorted(k for k in set(ko) & set(kn) if ko[k] != kn[k])
+        same = len(set(ko) & set(kn)) - len(differ)
+        print(f"{s}: {len(ko)} kernels compared, {same} identical, {renamed} renamed, {len(differ)} differ, {len(only_old)} only old, {len(only_new)} only new")
+        for tag, names in (("differs", differ), ("only old", only_old), ("only new", only_new)):
+            for k in names:
+                print(f"    {tag}: {k}")
+        bad += len(differ) + len(only_old) + len(only_new)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

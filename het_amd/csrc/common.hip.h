@@ -106,6 +106,31 @@ struct HetFork {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- launch shapes every kernel file shares -----------------------------------------------------------------------------
+constexpr int kBlock = 256;
+// workgroups of a grid-stride launch over `total` threads: at most 64 per CU of a 256-CU part unless the caller says otherwise
+static inline unsigned grid_for(int64_t total, int64_t cap = 256 * 64) {
+  int64_t b = ceil_div64(total, kBlock);
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+static inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
+// every pointer on a 16-byte boundary (float4 accesses); NULL counts as aligned
+template <typename... P>
+static inline bool aligned16(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
+
+// Lanes per row (a row of X floats is covered by LPR = X/4 lanes holding a float4 each) as a template argument: CALL sees
+// `constexpr int LPR`.  The shape predicates admit powers of two up to 64 only, so the default is 64.
+#define HET_DISPATCH_LPR(LPRV, CALL)                    \
+  switch (LPRV) {                                       \
+    case 1: { constexpr int LPR = 1; CALL; break; }     \
+    case 2: { constexpr int LPR = 2; CALL; break; }     \
+    case 4: { constexpr int LPR = 4; CALL; break; }     \
+    case 8: { constexpr int LPR = 8; CALL; break; }     \
+    case 16: { constexpr int LPR = 16; CALL; break; }   \
+    case 32: { constexpr int LPR = 32; CALL; break; }   \
+    default: { constexpr int LPR = 64; CALL; break; }   \
+  }
+
 // LDS a workgroup of the current device may ask for (160 KB on gfx950, 64 KB on the other gfx9 parts, the runtime's
 // hipDeviceAttributeMaxSharedMemoryPerBlock elsewhere; 64 KB when nothing can be queried) -- the `_ok` predicates and the launchers of the weight-resident kernels both use it,
 // so a build for another target (the Makefile's ARCH override) falls back instead of failing at the launch.  node_sum.hip.
@@ -168,6 +193,13 @@ __device__ __forceinline__ bool tile_to_relation(const idx_t* __restrict__ rel_p
     acc += nt;
   }
   return false;
+}
+
+// 16-byte accesses through a float pointer, and a float4 added to 4 consecutive floats with 4 float atomics
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void atomic_add4(float* p, float4 v) {
+  atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
 // Non-temporal 16-byte accesses.  Same-box A/B (exp/README.md): they pay where a kernel SCATTERS whole rows of a

@@ -54,4 +54,24 @@ __device__ __forceinline__ float head_sum(float p) {
   return p;
 }
 __device__ __forceinline__ float fast_leaky_exp(float z, float slope) { return __expf(z > 0.f ? z : slope * z); }
+
+// (lanes per row, lanes per head) pairs the cooperative GAT kernels are built for: rows of 32 / 64 / 128 floats, heads of >= 16
+inline bool coop_shape_ok(int64_t H, int64_t D) {
+  const int64_t lpr = H * D / 4, dl = D / 4;
+  return (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr;
+}
 }  // namespace
+
+// CALL sees `constexpr int LPR, DL`; for shapes coop_shape_ok admits (D a power of two: the callers' own shape checks)
+#define HET_DISPATCH_COOP(LPRV, DLV, CALL)                                  \
+  switch ((LPRV) * 64 + (DLV)) {                                            \
+    case 8 * 64 + 4: { constexpr int LPR = 8, DL = 4; CALL; break; }        \
+    case 8 * 64 + 8: { constexpr int LPR = 8, DL = 8; CALL; break; }        \
+    case 16 * 64 + 4: { constexpr int LPR = 16, DL = 4; CALL; break; }      \
+    case 16 * 64 + 8: { constexpr int LPR = 16, DL = 8; CALL; break; }      \
+    case 16 * 64 + 16: { constexpr int LPR = 16, DL = 16; CALL; break; }    \
+    case 32 * 64 + 4: { constexpr int LPR = 32, DL = 4; CALL; break; }      \
+    case 32 * 64 + 8: { constexpr int LPR = 32, DL = 8; CALL; break; }      \
+    case 32 * 64 + 16: { constexpr int LPR = 32, DL = 16; CALL; break; }    \
+    default: { constexpr int LPR = 32, DL = 32; CALL; break; }              \
+  }

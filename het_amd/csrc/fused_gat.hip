@@ -10,14 +10,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;  // 64 workgroups per CU, grid-stride beyond
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // exp[eid,h] = leaky_exp(el[srow,h] + er[drow,h]);  sum[dst,h] += exp
 __global__ __launch_bounds__(kBlock) void HET_gat_exp_sum_edge(EdgeView v, RowMaps m, const float* __restrict__ el,
                                                                 const float* __restrict__ er, float* __restrict__ sum,
@@ -102,8 +94,6 @@ __global__ __launch_bounds__(kBlock) void HET_gat_backward_edge(
     }
   }
 }
-
-inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 
 // CompactAsOfNodeKind 2 (EnabledWithDirectIndexing) in the reference's fused GAT maps BOTH edge ends through the one
 // inverse index of the two-sided unique list (RGATKernelsSeparateCOO.cu.h:163-170: the non-dual branch hands the same

@@ -10,12 +10,8 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kFoldRelMax = 8;  // relations the fused weight gradient of the folded GAT backward keeps in registers
 constexpr int kFoldReplicas = 64;  // copies of that [R,X] gradient the workgroups spread their final atomics over
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // exp[eid,h] = leaky_exp(el[srow,h] + er[drow,h]) -- pure streaming, no sum.
 __global__ __launch_bounds__(kBlock) void HET_gat_exp_edge(EdgeView v, RowMaps m, const float* __restrict__ el,
@@ -34,11 +30,6 @@ __global__ __launch_bounds__(kBlock) void HET_gat_exp_edge(EdgeView v, RowMaps m
     exp[eid * H + h] = leaky_exp(el[srow * H + h] + er[drow * H + h], slope);
   }
 }
-
-struct Items {
-  const int32_t *seg, *begin, *end, *seg_ptr, *seg_key;
-  int64_t n;
-};
 
 // Wave per work item: the 64/LPR lane groups take the item's edges round-robin, U edges per group and step; the
 // ids of the next step are fetched while the current rows are in flight (one dependent round trip per step).
@@ -147,10 +138,7 @@ __global__ __launch_bounds__(kBlock) void HET_gat_aggregate_grouped(Items it, co
     st4(rp, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
     if (x % D == 0) sum[v * H + h] = ssum;
   } else {  // hub destination: unnormalised partials, normalised by HET_gat_normalize_split
-    atomicAdd(rp + 0, acc.x);
-    atomicAdd(rp + 1, acc.y);
-    atomicAdd(rp + 2, acc.z);
-    atomicAdd(rp + 3, acc.w);
+    atomic_add4(rp, acc);
     if (x % D == 0) atomicAdd(&sum[v * H + h], ssum);
   }
 }
@@ -217,10 +205,7 @@ __global__ __launch_bounds__(kBlock) void HET_gat_aggregate_grouped_coop(Items i
     st4(rp, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
     if (d == 0) sum[v * H + h] = ssum;
   } else {  // hub destination: unnormalised partials, normalised by HET_gat_normalize_split
-    atomicAdd(rp + 0, acc.x);
-    atomicAdd(rp + 1, acc.y);
-    atomicAdd(rp + 2, acc.z);
-    atomicAdd(rp + 3, acc.w);
+    atomic_add4(rp, acc);
     if (d == 0) atomicAdd(&sum[v * H + h], ssum);
   }
 }
@@ -407,7 +392,7 @@ __global__ __launch_bounds__(kBlock) void HET_gat_backward_grouped(
         }
         // replicas > 1: the workgroups spread their flushes over that many copies (summed by HET_gat_fold_w_reduce)
         float* p = grad_fold_w + ((int64_t)(blockIdx.x % (unsigned)replicas) * R + q) * X + x;
-        atomicAdd(p + 0, t.x); atomicAdd(p + 1, t.y); atomicAdd(p + 2, t.z); atomicAdd(p + 3, t.w);
+        atomic_add4(p, t);
       }
     }
   }
@@ -578,17 +563,10 @@ __global__ __launch_bounds__(kBlock) void HET_gat_backward_src_grouped(
     st4(gp, acc);
     if ((sub & (DL - 1)) == 0) grad_el[u * H + h] = acc_el;
   } else {
-    atomicAdd(gp + 0, acc.x); atomicAdd(gp + 1, acc.y); atomicAdd(gp + 2, acc.z); atomicAdd(gp + 3, acc.w);
+    atomic_add4(gp, acc);
     if ((sub & (DL - 1)) == 0) atomicAdd(&grad_el[u * H + h], acc_el);
   }
 }
-
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 
 // shapes the grouped kernels cover: D a power of two >= 4, X/4 a power of two <= 64
 inline bool grouped_shape_ok(int H, int D) {
@@ -667,41 +645,12 @@ __global__ __launch_bounds__(kBlock) void HET_gat_backward_src_slot(
     st4(gp, acc);
     if ((sub & (DL - 1)) == 0) grad_el[u * H + h] = acc_el;
   } else {
-    atomicAdd(gp + 0, acc.x); atomicAdd(gp + 1, acc.y); atomicAdd(gp + 2, acc.z); atomicAdd(gp + 3, acc.w);
+    atomic_add4(gp, acc);
     if ((sub & (DL - 1)) == 0) atomicAdd(&grad_el[u * H + h], acc_el);
   }
 }
 
 }  // namespace
-
-#define HET_DISPATCH_LPR(LPRV, CALL)           \
-  switch (LPRV) {                              \
-    case 1: { constexpr int LPR = 1; CALL; break; }   \
-    case 2: { constexpr int LPR = 2; CALL; break; }   \
-    case 4: { constexpr int LPR = 4; CALL; break; }   \
-    case 8: { constexpr int LPR = 8; CALL; break; }   \
-    case 16: { constexpr int LPR = 16; CALL; break; } \
-    case 32: { constexpr int LPR = 32; CALL; break; } \
-    default: { constexpr int LPR = 64; CALL; break; } \
-  }
-
-// (lanes per row, lanes per head) pairs the cooperative kernels are built for: rows of 32 / 64 / 128 floats, heads of >= 16
-#define HET_DISPATCH_COOP_G(LPRV, DLV, CALL)                                \
-  switch ((LPRV) * 64 + (DLV)) {                                            \
-    case 8 * 64 + 4: { constexpr int LPR = 8, DL = 4; CALL; break; }        \
-    case 8 * 64 + 8: { constexpr int LPR = 8, DL = 8; CALL; break; }        \
-    case 16 * 64 + 4: { constexpr int LPR = 16, DL = 4; CALL; break; }      \
-    case 16 * 64 + 8: { constexpr int LPR = 16, DL = 8; CALL; break; }      \
-    case 16 * 64 + 16: { constexpr int LPR = 16, DL = 16; CALL; break; }    \
-    case 32 * 64 + 4: { constexpr int LPR = 32, DL = 4; CALL; break; }      \
-    case 32 * 64 + 8: { constexpr int LPR = 32, DL = 8; CALL; break; }      \
-    case 32 * 64 + 16: { constexpr int LPR = 32, DL = 16; CALL; break; }    \
-    default: { constexpr int LPR = 32, DL = 32; CALL; break; }              \
-  }
-static bool gat_coop_shape(int H, int D) {
-  const int lpr = H * D / 4, dl = D / 4;
-  return (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr && D % 4 == 0;
-}
 
 // Destinations with few in-edges on average: a lane group per item instead of a wave per item (layer path kernels).
 // Same-box A/B on one rank's share of an 8-way ogbn-mag partition (9 in-edges per destination): backward 0.528 -> 0.506 ms,
@@ -721,7 +670,7 @@ int gat_forward_grouped(const het_grouping* g, const EdgeView& v, const RowMaps&
   HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * v.N * H, s));
   HET_HIP(hipMemsetAsync(ret, 0, sizeof(float) * v.N * X, s));
   if (v.E == 0) return HET_OK;
-  Items it{g->item_seg, g->item_begin, g->item_end, g->seg_ptr, g->seg_key, g->num_items};
+  const Items it = items_of(g);
   const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
   const int32_t* srow = m.kind == HET_KIND_DISABLED ? nullptr : g->p1;
   // (a persistent variant -- a fixed grid of waves striding over the items, the next item's record and first ids
@@ -729,8 +678,7 @@ int gat_forward_grouped(const het_grouping* g, const EdgeView& v, const RowMaps&
   // own workgroup turnover already overlaps the per-item prologues; the pass runs at the rate random 256-byte rows
   // come out of HBM)
   if (!el_sorted) {
-    if (m.kind == HET_KIND_DISABLED && H == 4 && ((reinterpret_cast<uintptr_t>(el) | reinterpret_cast<uintptr_t>(er) |
-                                                  reinterpret_cast<uintptr_t>(exp)) & 15) == 0) {
+    if (m.kind == HET_KIND_DISABLED && H == 4 && aligned16(el, er, exp)) {
       hipLaunchKernelGGL(HET_gat_exp_edge_h4, dim3(grid_for(v.E)), dim3(kBlock), 0, s, v.eids, v.E, el, er, exp, slope);
     } else {
       hipLaunchKernelGGL(HET_gat_exp_edge, dim3(grid_for(v.E * H)), dim3(kBlock), 0, s, v, m, el, er, exp, H, slope);
@@ -748,8 +696,8 @@ int gat_forward_grouped(const het_grouping* g, const EdgeView& v, const RowMaps&
     HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_gat_aggregate_grouped<LPR, true>), dim3(nb), dim3(kBlock), 0, s,
                                                       it, g->p0, srow, feat, (const float*)nullptr, sum, ret, exp_sorted,
                                                       H, D, el_sorted, er_sorted, exp, slope));
-  } else if (gat_coop_shape(H, D)) {
-    HET_DISPATCH_COOP_G((int)(X / 4), D / 4,
+  } else if (coop_shape_ok(H, D)) {
+    HET_DISPATCH_COOP((int)(X / 4), D / 4,
                         hipLaunchKernelGGL((HET_gat_aggregate_grouped_coop<LPR, DL>), dim3(nb), dim3(kBlock), 0, s, it, g->p0,
                                            srow, feat, exp, sum, ret, exp_sorted, H));
   } else {
@@ -782,7 +730,7 @@ int gat_backward_grouped(const het_grouping* g, const EdgeView& v, const RowMaps
   }
   if (v.E == 0) return HET_OK;
   const int64_t X = (int64_t)H * D;
-  Items it{g->item_seg, g->item_begin, g->item_end, g->seg_ptr, g->seg_key, g->num_items};
+  const Items it = items_of(g);
   HET_REQUIRE(!fold_w || g->p1, "backward_relational_fused_gat_separate_coo: fold_attn_l needs payload1 = relation");
   const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
   const bool sorted = exp_sorted && slope >= 0.f;
@@ -833,9 +781,9 @@ int gat_backward_grouped(const het_grouping* g, const EdgeView& v, const RowMaps
   } else if (fold_w) {
     HET_KTIME("HET_gat_backward_grouped", s);
     if (sorted) { HET_GAT_BWD(true, true); } else { HET_GAT_BWD(false, true); }
-  } else if (!sorted && !grad_el_sorted && grad_el && grad_er && gat_coop_shape(H, D)) {
+  } else if (!sorted && !grad_el_sorted && grad_el && grad_er && coop_shape_ok(H, D)) {
     HET_KTIME("HET_gat_backward_grouped", s);
-    HET_DISPATCH_COOP_G((int)(X / 4), D / 4,
+    HET_DISPATCH_COOP((int)(X / 4), D / 4,
                         hipLaunchKernelGGL((HET_gat_backward_grouped_coop<LPR, DL>), dim3(nb), dim3(kBlock), 0, s, it, g->p0,
                                            feat, el, er, sum, ex, ret, gradout, grad_feat, grad_el, grad_er, H, slope));
   } else {
@@ -864,8 +812,7 @@ int gat_backward_compact_grouped(const het_grouping* by_srow, const het_grouping
   HET_HIP(hipMemsetAsync(grad_el, 0, sizeof(float) * n_src_rows * H, s));
   if (by_srow->num_split > 0 || by_srow->S != n_src_rows)
     HET_HIP(hipMemsetAsync(grad_feat, 0, sizeof(float) * n_src_rows * X, s));
-  Items it{by_srow->item_seg, by_srow->item_begin, by_srow->item_end, by_srow->seg_ptr, by_srow->seg_key,
-           by_srow->num_items};
+  const Items it = items_of(by_srow);
   if (by_srow->E < 16 * by_srow->num_items) {
     // short segments (5.7 edges per (relation, source) row on ogbn-mag): a lane group per item, two edges in flight
     // (same box: wave per item 3.4-3.5 ms for the whole op, lane group per item with U = 1 / 2 / 4: 3.7 / 3.1 / 3.65 ms)

@@ -27,16 +27,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-struct Items {
-  const int32_t *seg, *begin, *end, *seg_ptr, *seg_key;
-  int64_t n;
-};
-
 // Softmax WITHOUT overflow inside the one-node layer.  The reference's kernels exponentiate the raw pre-activation
 // (gatLeakyReluExp, GAT/FusedGAT.cu.h:23-26: exp(leaky_relu(el + er)), no maximum subtracted -- SURVEY.md Q2), which the
 // reference-named ops keep because exp / sum are API tensors there.  Here neither is visible to the caller, so every pass
@@ -268,11 +258,6 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_colsum_finish(const float* __
   if (t == 0) out[x] = red[0];
 }
 
-struct Packs {
-  const int32_t *ptr, *key;
-  int64_t n;
-};
-
 // Lane group per pack of the grouping by feat row u (payload0 = destination, payload1 = er row):
 //   a_e = exp(leaky(el[u,h] + er[drow_e,h]) - lse[dst_e,h]);  dl_e = (el + er > 0) ? 1 : slope
 //   grad_feat[u,h,:] = SUM_e a_e * gradout[dst_e,h,:]  (+ grad_el[u,h] * fold_w[r(u),h,:])
@@ -371,7 +356,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_packed(
           st4(gp, o);
           if (head_lane) grad_el[u * H + h] = acc_el;
         } else {
-          atomicAdd(gp + 0, o.x); atomicAdd(gp + 1, o.y); atomicAdd(gp + 2, o.z); atomicAdd(gp + 3, o.w);
+          atomic_add4(gp, o);
           if (head_lane) atomicAdd(&grad_el[u * H + h], acc_el);
         }
         acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -457,7 +442,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long_any(
     st4(gp, acc);
     if (head_lane) grad_el[u * H + h] = acc_el;
   } else {  // (rows cleared by HET_rgat_zero_long_rows)
-    atomicAdd(gp + 0, acc.x); atomicAdd(gp + 1, acc.y); atomicAdd(gp + 2, acc.z); atomicAdd(gp + 3, acc.w);
+    atomic_add4(gp, acc);
     if (head_lane) atomicAdd(&grad_el[u * H + h], acc_el);
   }
 }
@@ -960,7 +945,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs(
 template <int LPR>
 __device__ __forceinline__ void ga_flush_atomic(float* __restrict__ out, int rel, int x, const float4& v) {
   float* p = out + (int64_t)rel * (LPR * 4) + x;
-  atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
+  atomic_add4(p, v);
 }
 // every thread of the workgroup calls this once; (ga, rel) per lane group, rel < 0: none
 template <int LPR>
@@ -1243,7 +1228,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
     st4(gp, acc);
     if (grad_el && d == 0) grad_el[u * H + h] = acc_el;
   } else {
-    atomicAdd(gp + 0, acc.x); atomicAdd(gp + 1, acc.y); atomicAdd(gp + 2, acc.z); atomicAdd(gp + 3, acc.w);
+    atomic_add4(gp, acc);
     if (grad_el && d == 0) atomicAdd(&grad_el[u * H + h], acc_el);
   }
 }
@@ -1342,43 +1327,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_zero_long_rows(const int32_t*
   }
 }
 
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
-
 }  // namespace
-
-#define HET_DISPATCH_LPR(LPRV, CALL)           \
-  switch (LPRV) {                              \
-    case 1: { constexpr int LPR = 1; CALL; break; }   \
-    case 2: { constexpr int LPR = 2; CALL; break; }   \
-    case 4: { constexpr int LPR = 4; CALL; break; }   \
-    case 8: { constexpr int LPR = 8; CALL; break; }   \
-    case 16: { constexpr int LPR = 16; CALL; break; } \
-    case 32: { constexpr int LPR = 32; CALL; break; } \
-    default: { constexpr int LPR = 64; CALL; break; } \
-  }
-
-// (lanes per row, lanes per head) pairs the cooperative kernels are built for: rows of 32 / 64 / 128 floats, heads of >= 16
-#define HET_DISPATCH_COOP(LPRV, DLV, CALL)                                  \
-  switch ((LPRV) * 64 + (DLV)) {                                            \
-    case 8 * 64 + 4: { constexpr int LPR = 8, DL = 4; CALL; break; }        \
-    case 8 * 64 + 8: { constexpr int LPR = 8, DL = 8; CALL; break; }        \
-    case 16 * 64 + 4: { constexpr int LPR = 16, DL = 4; CALL; break; }      \
-    case 16 * 64 + 8: { constexpr int LPR = 16, DL = 8; CALL; break; }      \
-    case 16 * 64 + 16: { constexpr int LPR = 16, DL = 16; CALL; break; }    \
-    case 32 * 64 + 4: { constexpr int LPR = 32, DL = 4; CALL; break; }      \
-    case 32 * 64 + 8: { constexpr int LPR = 32, DL = 8; CALL; break; }      \
-    case 32 * 64 + 16: { constexpr int LPR = 32, DL = 16; CALL; break; }    \
-    default: { constexpr int LPR = 32, DL = 32; CALL; break; }              \
-  }
-static bool coop_shape_ok(int64_t H, int64_t D) {
-  const int64_t lpr = H * D / 4, dl = D / 4;
-  return (lpr == 8 || lpr == 16 || lpr == 32) && dl >= 4 && dl <= lpr;
-}
 
 static bool compact_shape_ok(int64_t H, int64_t D) {
   const int64_t X = H * D;
@@ -1403,7 +1352,7 @@ extern "C" int het_rgat_aggregate_compact(const het_grouping* by_dst, const floa
   HET_REQUIRE(by_dst->R == 0 && by_dst->key_bound <= num_nodes && (by_dst->E == 0 || (by_dst->p0 && by_dst->p1 && feat_c && el_c && er_c)),
               "%s: by_dst must group the positions by destination with payload0 = feat row and payload1 = er row", op);
   const int64_t need = het_rgat_aggregate_compact_workspace(by_dst, H, D);
-  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_aggregate_compact_workspace)", op, (long long)need);
   const int64_t X = H * D;
   HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * num_nodes * H, s));  // destinations without in-edges (never read by an edge)
@@ -1411,7 +1360,7 @@ extern "C" int het_rgat_aggregate_compact(const het_grouping* by_dst, const floa
   // reads ret only where edges point (the backward): then nothing is filled (0.5 GB less)
   if (!h_inout) HET_HIP(hipMemsetAsync(ret, 0, sizeof(float) * num_nodes * X, s));
   if (by_dst->E == 0) return HET_OK;
-  Items it{by_dst->item_seg, by_dst->item_begin, by_dst->item_end, by_dst->seg_ptr, by_dst->seg_key, by_dst->num_items};
+  const Items it = items_of(by_dst);
   const unsigned nb = (unsigned)ceil_div64(by_dst->num_items, kBlock / 64);
   float* part = static_cast<float*>(workspace);
   if (coop_shape_ok(H, D))
@@ -1492,7 +1441,7 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
               "%s: by_dst_rel must group the same positions by destination * num_rels + relation", op);
   const int64_t need = het_rgat_aggregate_compact_runs_workspace(by_dst, by_dst_rel, num_rels, H, D, stream);
   if (need < 0) return HET_ERR_INVALID_ARG;
-  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_aggregate_compact_runs_workspace)", op, (long long)need);
   const int64_t X = H * D;
   HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * num_nodes * H, s));
@@ -1507,7 +1456,7 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
   // feat rows (host array [R+1]) and attn_l [R, H*D]; otherwise el_c is gathered per edge
   ElFold ef{};
   const bool elr = attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels &&
-                   (reinterpret_cast<uintptr_t>(attn_l) & 15) == 0;
+                   aligned16(attn_l);
   if (elr) {
     ef.attn = attn_l; ef.R = (int)num_rels;
     for (int k = 0; k < kElMaxRels - 1; ++k)
@@ -1545,8 +1494,7 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
   HET_LAUNCH_CHECK("HET_rgat_aggregate_runs_packed");
   if (by_dst_rel->num_hub_items > 0) {
     hipStream_t s2 = fk.side;
-    Items it{by_dst_rel->item_seg, by_dst_rel->item_begin, by_dst_rel->item_end, by_dst_rel->seg_ptr, by_dst_rel->seg_key,
-             by_dst_rel->num_items};
+    const Items it = items_of(by_dst_rel);
     const int64_t n_hub = by_dst_rel->num_hub_items;
     {
       HET_KTIME("HET_rgat_aggregate_hubs", s2);
@@ -1637,7 +1585,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   const bool use_rec = runs && E > 0 && num_dst_rows > 0;
   const int64_t n_rec = runs ? num_dst_rows * H * 4 : 0;
   const int64_t need = (int64_t)sizeof(float) * (n_pack + n_tbuf + bias_part_rows * X + n_ga + n_rec);
-  HET_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+  HET_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_backward_compact_workspace)", op, (long long)need);
   float* pack = (float*)workspace;  // [N, 2H]
   float* tbuf = runs ? nullptr : pack + n_pack;  // [E, H], rank order of by_srow
@@ -1741,7 +1689,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     }
     HET_LAUNCH_CHECK("HET_rgat_backward_src_coop");
     if (pv.num_long_items > 0) {
-      Items it{by_srow->item_seg, by_srow->item_begin, by_srow->item_end, by_srow->seg_ptr, by_srow->seg_key, by_srow->num_items};
+      const Items it = items_of(by_srow);
       const unsigned nbl = (unsigned)ceil_div64(pv.num_long_items, kBlock / 64);
       int* ga_rel_long = ga_rel ? ga_rel + nb : nullptr;  // (the long launch's workgroups follow the short launch's in the partial rows)
       HET_KTIME("HET_rgat_backward_src_long", s2);
@@ -1773,7 +1721,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     }
     if (skip_long) {
       HET_LAUNCH_CHECK("HET_rgat_backward_src_packed");
-      Items it{by_srow->item_seg, by_srow->item_begin, by_srow->item_end, by_srow->seg_ptr, by_srow->seg_key, by_srow->num_items};
+      const Items it = items_of(by_srow);
       const unsigned nbl = (unsigned)ceil_div64(pv.num_long_items, kBlock / 64);
       HET_KTIME("HET_rgat_backward_src_long", s2);
       HET_DISPATCH_LPR((int)(X / 4),

@@ -86,6 +86,22 @@ struct het_grouping {
   mutable int64_t val_order_n = 0;
 };
 
+// What a kernel takes of a grouping, by value: its work items, and its packs.  Kernel parameter types, so they live in an
+// anonymous namespace like the kernels of the files that use them (a type at global scope would change their mangled names).
+namespace {
+struct Items {
+  const int32_t *seg, *begin, *end, *seg_ptr, *seg_key;
+  int64_t n;
+};
+struct Packs {
+  const int32_t *ptr, *key;
+  int64_t n;
+};
+inline Items items_of(const het_grouping* g) {
+  return Items{g->item_seg, g->item_begin, g->item_end, g->seg_ptr, g->seg_key, g->num_items};
+}
+}  // namespace
+
 constexpr int HET_PACK_T = 32;
 // Builds g->pack_ptr / key_of_rank / long_items (threshold HET_PACK_T) once (thread-safe; synchronises `s` before publishing them).
 int grouping_packs(const het_grouping* g, hipStream_t s);

@@ -11,14 +11,7 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxLdsHeads = 64 * 64;  // (relation-local) head slots reduced in LDS
-
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
 
 // m[eid,h] = exp(score[eid,h] * mu[r,h]);  sum[dst,h] += m
 __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_exp_sum(const idx_t* __restrict__ col,
@@ -58,9 +51,6 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_normalize(const idx_t*
 //   HET_hgt_softmax_sum_grouped   sum[dst, :] = SUM over the in-edges of exp(score[eid, :] * mu[r, :])
 //                                 (wave per work item, H/4 lanes x float4 per edge; atomics only for split hub segments)
 //   HET_hgt_softmax_finish        edge order, streaming: m = exp(score * mu[r]), a = m / sum[dst]
-__device__ __forceinline__ float4 hgt_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void hgt_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_sum_grouped(
     const int32_t* __restrict__ item_seg, const int32_t* __restrict__ item_begin, const int32_t* __restrict__ item_end,
@@ -85,9 +75,9 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_sum_grouped(
     }
     float4 sc[U], mv[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) sc[u] = hgt_ld4(score + eid[u] * H + x);
+    for (int u = 0; u < U; ++u) sc[u] = ld4(score + eid[u] * H + x);
 #pragma unroll
-    for (int u = 0; u < U; ++u) mv[u] = hgt_ld4(mu + (int64_t)rl[u] * H + x);
+    for (int u = 0; u < U; ++u) mv[u] = ld4(mu + (int64_t)rl[u] * H + x);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const float ok = j0 + u * EPW < e ? 1.f : 0.f;
@@ -103,9 +93,9 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_sum_grouped(
   if (slot != 0) return;
   float* p = sum + (int64_t)seg_key[seg] * H + x;
   if (b == seg_ptr[seg] && e == seg_ptr[seg + 1]) {
-    hgt_st4(p, acc);
+    st4(p, acc);
   } else {  // hub destination split over several items (sum is zero-filled by the caller)
-    atomicAdd(p + 0, acc.x); atomicAdd(p + 1, acc.y); atomicAdd(p + 2, acc.z); atomicAdd(p + 3, acc.w);
+    atomic_add4(p, acc);
   }
 }
 
@@ -122,13 +112,13 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_softmax_finish(const idx_t* __
   idx_t rb, re;
   if (!tile_to_relation(rel_ptrs, R, chunk, blockIdx.x, r, rb, re)) return;
   const int slot = threadIdx.x / LPR, x = (threadIdx.x % LPR) * 4;
-  const float4 mv = hgt_ld4(mu + (int64_t)r * H + x);
+  const float4 mv = ld4(mu + (int64_t)r * H + x);
   for (idx_t i = rb + slot; i < re; i += EPB) {
     const idx_t eid = eids[i], dst = col[i];
-    const float4 sc = hgt_ld4(score + eid * H + x), sv = hgt_ld4(sum + dst * H + x);
+    const float4 sc = ld4(score + eid * H + x), sv = ld4(sum + dst * H + x);
     const float4 v = make_float4(expf(sc.x * mv.x), expf(sc.y * mv.y), expf(sc.z * mv.z), expf(sc.w * mv.w));
-    hgt_st4(m + eid * H + x, v);
-    hgt_st4(a + eid * H + x, make_float4(v.x / sv.x, v.y / sv.y, v.z / sv.z, v.w / sv.w));
+    st4(m + eid * H + x, v);
+    st4(a + eid * H + x, make_float4(v.x / sv.x, v.y / sv.y, v.z / sv.z, v.w / sv.w));
   }
 }
 
@@ -276,8 +266,6 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_grad_attn(const idx_t* __restr
 
 // ---- row kernels: a feature row of X = H*D floats is covered by LPR = X/4 lanes (float4 each); the DL = D/4
 // lanes of a head combine with xor-shuffles; U rows per lane group are in flight per step -----------------
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 constexpr int UR = 4;
 __device__ __forceinline__ int quad_bcast_sw(int v, int q) {  // value of lane q of the caller's quad (DPP quad_perm)
   switch (q) {
@@ -529,22 +517,10 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_untranspose_w(const float* __r
   }
 }
 
-inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 inline bool rows_shape_ok(int64_t H, int64_t D) {  // X/4 a power of two <= 64, a head = whole float4 pieces
   const int64_t X = H * D;
   return D >= 4 && is_pow2(D) && is_pow2(X) && X / 4 <= 64;
 }
-
-#define HET_HGT_LPR(LPRV, CALL)                         \
-  switch (LPRV) {                                       \
-    case 1: { constexpr int LPR = 1; CALL; break; }     \
-    case 2: { constexpr int LPR = 2; CALL; break; }     \
-    case 4: { constexpr int LPR = 4; CALL; break; }     \
-    case 8: { constexpr int LPR = 8; CALL; break; }     \
-    case 16: { constexpr int LPR = 16; CALL; break; }   \
-    case 32: { constexpr int LPR = 32; CALL; break; }   \
-    default: { constexpr int LPR = 64; CALL; break; }   \
-  }
 
 int check_edges(const char* op, const idx_t* row, const idx_t* col, const idx_t* eids, const idx_t* rel_ptrs,
                 int64_t R, int64_t E, int64_t N) {
@@ -565,18 +541,16 @@ extern "C" int het_hgt_full_graph_edge_softmax_ops_separate_coo(
   hipStream_t s = (hipStream_t)stream;
   HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * num_nodes * H, s));
   if (num_edges == 0) return HET_OK;
-  if (softmax_grouped_ok(by_dst, num_edges, H) && ((reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(mu) |
-                                                     reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(m) |
-                                                     reinterpret_cast<uintptr_t>(a)) & 15) == 0) {
+  if (softmax_grouped_ok(by_dst, num_edges, H) && aligned16(score, mu, sum, m, a)) {
     const het_grouping* g = by_dst;
     const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
-    HET_HGT_LPR((int)(H / 4), hipLaunchKernelGGL(HET_hgt_softmax_sum_grouped<LPR>, dim3(nb), dim3(kBlock), 0, s, g->item_seg,
+    HET_DISPATCH_LPR((int)(H / 4), hipLaunchKernelGGL(HET_hgt_softmax_sum_grouped<LPR>, dim3(nb), dim3(kBlock), 0, s, g->item_seg,
                                                  g->item_begin, g->item_end, g->seg_ptr, g->seg_key, g->num_items, g->p0,
                                                  g->p1, score, mu, sum));
     HET_LAUNCH_CHECK("HET_hgt_softmax_sum_grouped");
     const int64_t chunk = 2048;
     const unsigned nf = (unsigned)(ceil_div64(num_edges, chunk) + num_rels);
-    HET_HGT_LPR((int)(H / 4), hipLaunchKernelGGL(HET_hgt_softmax_finish<LPR>, dim3(nf), dim3(kBlock), 0, s, col, eids, rel_ptrs,
+    HET_DISPATCH_LPR((int)(H / 4), hipLaunchKernelGGL(HET_hgt_softmax_finish<LPR>, dim3(nf), dim3(kBlock), 0, s, col, eids, rel_ptrs,
                                                  (int)num_rels, (int)chunk, score, mu, sum, m, a));
     HET_LAUNCH_CHECK("HET_hgt_softmax_finish");
     return HET_OK;
@@ -600,7 +574,7 @@ extern "C" int het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_sepa
               "%s: null data pointer or too many heads", op);
   hipStream_t s = (hipStream_t)stream;
   if (num_edges > 0 && softmax_grouped_ok(by_dst, num_edges, H) && segment_sum_supported((int)H) &&
-      ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(grad_a) | reinterpret_cast<uintptr_t>(tmp)) & 15) == 0) {
+      aligned16(a, grad_a, tmp)) {
     // tmp[dst, :] = SUM over the in-edges of a[eid, :] * grad_a[eid, :]: a segmented sum instead of E*H float atomics
     if (int rc = launch_segment_sum(by_dst, grad_a, tmp, (int)H, a, s, (int)H, num_nodes, 0, 1)) return rc;
   } else {
@@ -631,8 +605,7 @@ extern "C" int het_hgt_full_graph_fused_message_calc_and_mean_aggregation_separa
   const het_grouping* gr = by_rel_dst;
   if (gr && gr->R == (int)num_rels && gr->E == num_edges && gr->p0 && gr->p1 && rows_shape_ok(H, dk) &&
       segment_sum_supported((int)(H * dk)) && workspace &&
-      workspace_bytes >= (int64_t)sizeof(float) * gr->S * H * dk && (reinterpret_cast<uintptr_t>(v) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(new_h) & 15) == 0) {
+      workspace_bytes >= (int64_t)sizeof(float) * gr->S * H * dk && aligned16(v, workspace, new_h)) {
     // new_h[dst] += SUM_r ( SUM_{e in (r,dst)} a[e,h] * v[src_e,h,:] ) . W[r,h]: attention-weighted segment sum of
     // the source rows per (relation, destination), then one block-diagonal row GEMM per distinct pair
     hipStream_t s = (hipStream_t)stream;
@@ -677,9 +650,8 @@ extern "C" int het_backward_hgt_full_graph_fused_message_calc_and_mean_aggregati
   if (!msg_rows && !reg_w) gr = nullptr;  // neither fits: the generic kernels below
   if (gr && gr->R == (int)num_rels && gr->E == num_edges && gr->p0 && gr->p1 && dk == dout &&
       rows_shape_ok(H, dk) && segment_sum_supported((int)(H * dout)) &&
-      workspace && workspace_bytes >= (int64_t)sizeof(float) * gr->S * H * dout + ws_msg && (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(grad_v) & 15) == 0) {
+      workspace && workspace_bytes >= (int64_t)sizeof(float) * gr->S * H * dout + ws_msg &&
+      aligned16(gradout, v, workspace, grad_v)) {
     // gsum[(r,u)] = SUM over the out-edges of u in relation r of a[e,h] * gradout[dst_e,h,:]; then
     //   grad_v[u] += gsum . Wt[r] (block diagonal),  grad_w[r,h] += v[u,h,:]^T (x) gsum[(r,u),h,:]
     float* gsum = static_cast<float*>(workspace);
@@ -710,7 +682,7 @@ extern "C" int het_backward_hgt_full_graph_fused_message_calc_and_mean_aggregati
       const int epw = 64 / (int)(H * dout / 4);
       int64_t nbm = ceil_div64(num_edges, (int64_t)4 * epw * 4);
       if (nbm > 256 * 64) nbm = 256 * 64;
-      HET_HGT_LPR((int)(H * dout / 4), hipLaunchKernelGGL(HET_hgt_grad_attn_msg<LPR>, dim3((unsigned)nbm), dim3(kBlock), 0, s,
+      HET_DISPATCH_LPR((int)(H * dout / 4), hipLaunchKernelGGL(HET_hgt_grad_attn_msg<LPR>, dim3((unsigned)nbm), dim3(kBlock), 0, s,
                                                           gr->seg_of_rank, gr->p0, gr->p1, num_edges, msg, gradout, grad_a,
                                                           (int)H, (int)dout));
       HET_LAUNCH_CHECK("HET_hgt_grad_attn_msg");
@@ -718,7 +690,7 @@ extern "C" int het_backward_hgt_full_graph_fused_message_calc_and_mean_aggregati
     }
     int64_t chunk = 4096;
     dim3 grid((unsigned)(ceil_div64(num_edges, chunk) + num_rels)), block(kBlock);
-#define HET_GA(DKV) HET_HGT_LPR((int)(H * dk / 4), hipLaunchKernelGGL((HET_hgt_grad_attn_rows<LPR, DKV>), grid, block, 0, s, \
+#define HET_GA(DKV) HET_DISPATCH_LPR((int)(H * dk / 4), hipLaunchKernelGGL((HET_hgt_grad_attn_rows<LPR, DKV>), grid, block, 0, s, \
                                 row, col, eids, rel_ptrs, (int)num_rels, (int)chunk, v, weights_t, gradout, grad_a, (int)H))
     if (dk == 4) { HET_GA(4); } else if (dk == 8) { HET_GA(8); } else { HET_GA(16); }
 #undef HET_GA
@@ -757,8 +729,7 @@ extern "C" int het_rgnn_inner_product_right_node_separatecoo(
   HET_REQUIRE((kind == 0) || (map_a && (kind == 2 || map_b)), "%s: compact kinds need their index lists", op);
   HET_REQUIRE(H > 0 && D > 0 && (num_edges == 0 || (left && right && out)), "%s: null data pointer", op);
   if (num_edges == 0) return HET_OK;
-  if (kind != HET_KIND_ENABLED && rows_shape_ok(H, D) && (reinterpret_cast<uintptr_t>(left) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(right) & 15) == 0) {
+  if (kind != HET_KIND_ENABLED && rows_shape_ok(H, D) && aligned16(left, right)) {
     const unsigned nb = grid_for(num_edges * (H * D / 4));
     if (H * D / 4 >= 4 && num_edges < (1ll << 31)) {
       switch ((int)(H * D / 4)) {
@@ -772,7 +743,7 @@ extern "C" int het_rgnn_inner_product_right_node_separatecoo(
       HET_LAUNCH_CHECK("HET_rows_inner_product_coop");
       return HET_OK;
     }
-    HET_HGT_LPR((int)(H * D / 4), hipLaunchKernelGGL(HET_rows_inner_product<LPR>, dim3(nb), dim3(kBlock), 0,
+    HET_DISPATCH_LPR((int)(H * D / 4), hipLaunchKernelGGL(HET_rows_inner_product<LPR>, dim3(nb), dim3(kBlock), 0,
                                                       (hipStream_t)stream, eids, kind == 2 ? map_a : nullptr, row,
                                                       num_edges, left, right, out, (int)H, (int)D));
     HET_LAUNCH_CHECK("HET_rows_inner_product");
@@ -803,8 +774,7 @@ extern "C" int het_backward_inner_product_right_node_separatecoo(
   const het_grouping* gr = by_right;
   const bool fast = kind != HET_KIND_ENABLED && rows_shape_ok(H, D) && gr && gr->R == 0 && gr->E == num_edges && gr->p0 &&
                     gr->p1 && segment_sum_supported((int)X) && n_right_rows >= 0 && n_left_rows >= 0 &&
-                    (reinterpret_cast<uintptr_t>(left) & 15) == 0 && (reinterpret_cast<uintptr_t>(right) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(grad_left) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_right) & 15) == 0;
+                    aligned16(left, right, grad_left, grad_right);
   if (fast) {
     // grad_left: one writer per row for kind 0 (left rows are edge rows) -> store / read-modify-write;
     // shared compact rows (kind 2) -> atomics on zeroed rows
@@ -820,7 +790,7 @@ extern "C" int het_backward_inner_product_right_node_separatecoo(
     }
     if (num_edges > 0 && !left_grouped) {
       const unsigned nb = grid_for(num_edges * (X / 4));
-#define HET_IPL(MODEV) HET_HGT_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rows_inner_product_bwd_left<LPR, MODEV>), dim3(nb), \
+#define HET_IPL(MODEV) HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rows_inner_product_bwd_left<LPR, MODEV>), dim3(nb), \
                                    dim3(kBlock), 0, s, eids, lmap, row, num_edges, right, gradout, grad_left, (int)H, (int)D))
       if (mode == 2) { HET_IPL(2); } else if (mode == 1) { HET_IPL(1); } else { HET_IPL(0); }
 #undef HET_IPL
@@ -855,15 +825,14 @@ extern "C" int het_hgt_full_graph_hetero_attention_ops_coo(
   if (num_edges == 0) return HET_OK;
   hipStream_t s = (hipStream_t)stream;
   if (mfma_shape_supported((int)(H * dk), (int)(H * dout)) && rows_shape_ok(H, dout) &&
-      (reinterpret_cast<uintptr_t>(k) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(inner) & 15) == 0) {
+      aligned16(k, q, inner)) {
     MfmaGemmArgs m;  // inner[eid, :] = k[row, :] . blockdiag(W[r])
     m.A = k; m.a_ld = H * dk; m.gather = row; m.B = weights; m.b_rel_stride = H * dk * dout; m.b_headcat = 2;
     m.headcat_d = (int)dout; m.blockdiag_k = (int)dk; m.C = inner; m.c_ld = H * dout; m.scatter = eids;
     m.seg_ptrs = rel_ptrs; m.num_segs = (int)num_rels; m.num_rows = num_edges; m.K = (int)(H * dk); m.X = (int)(H * dout);
     if (int rc = launch_seg_gemm_mfma(m, s)) return rc;
     const unsigned nb = grid_for(num_edges * (H * dout / 4));
-    HET_HGT_LPR((int)(H * dout / 4), hipLaunchKernelGGL(HET_rows_inner_product<LPR>, dim3(nb), dim3(kBlock), 0, s, eids,
+    HET_DISPATCH_LPR((int)(H * dout / 4), hipLaunchKernelGGL(HET_rows_inner_product<LPR>, dim3(nb), dim3(kBlock), 0, s, eids,
                                                          (const idx_t*)nullptr, col, num_edges, inner, q, score, (int)H,
                                                          (int)dout));
     HET_LAUNCH_CHECK("HET_rows_inner_product");
@@ -902,9 +871,7 @@ extern "C" int het_backward_hgt_full_graph_hetero_attention_ops_coo(
       gs->p1 && rows_shape_ok(H, dout) && segment_sum_supported((int)(H * dout)) &&
       mfma_shape_supported((int)(H * dout), (int)(H * dk)) && mfma_dw_supported((int)(H * dk), (int)(H * dout)) &&
       workspace && workspace_bytes >= (int64_t)sizeof(float) * gs->S * H * dout && n_q_rows >= 0 &&
-      (reinterpret_cast<uintptr_t>(q) & 15) == 0 && (reinterpret_cast<uintptr_t>(inner) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_q) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(grad_k) & 15) == 0 && (reinterpret_cast<uintptr_t>(k) & 15) == 0) {
+      aligned16(q, inner, workspace, grad_q, grad_k, k)) {
     // grad_q[dst] += SUM_{e into dst} gs[e,h] * inner[e,h,:]     (by_dst: payload0 = eids)
     if (int rc = launch_segment_sum(gd, inner, grad_q, (int)(H * dout), grad_score, s, (int)H, n_q_rows, 1, 0, /*nt_in=*/0)) return rc;
     // qs[(r,u)] = SUM over the out-edges of u in relation r of gs[e,h] * q[dst_e,h,:]   (payload0 = col, payload1 = eids)

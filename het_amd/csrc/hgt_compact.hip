@@ -29,16 +29,9 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ void fma4(float4& acc, float w, float4 v) {
   acc.x = fmaf(w, v.x, acc.x); acc.y = fmaf(w, v.y, acc.y); acc.z = fmaf(w, v.z, acc.z); acc.w = fmaf(w, v.w, acc.w);
-}
-__device__ __forceinline__ void atomic_add4(float* p, float4 v) {
-  atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
 __device__ __forceinline__ int quad_bcast(int v, int q) {  // value of lane q of the caller's quad; q is a constant after unrolling
@@ -49,15 +42,6 @@ __device__ __forceinline__ int quad_bcast(int v, int q) {  // value of lane q of
     default: return quad_bcast_i<3>(v);
   }
 }
-
-struct Items {
-  const int32_t *seg, *begin, *end, *seg_ptr, *seg_key;
-  int64_t n;
-};
-struct Packs {
-  const int32_t *ptr, *key;
-  int64_t n;
-};
 
 // Forward: wave per destination work item, the 64/LPR lane groups take its edges round-robin, U = 4 rows per group in
 // flight, the ids of the next step prefetched.
@@ -443,12 +427,6 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_long(Items it, co
   }
 }
 
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 // (lanes per row, lanes per head): rows of 16 .. 128 floats, heads of 8 .. 128
@@ -496,13 +474,13 @@ extern "C" int het_hgt_aggregate_compact(const het_grouping* by_dst, const float
   HET_REQUIRE(by_dst->R == 0 && by_dst->key_bound <= num_nodes && num_src_rows >= 0 && (by_dst->E == 0 || (by_dst->p0 && kv_c && q)),
               "%s: by_dst must group the positions by destination with payload0 = the (relation, source) row", op);
   const int64_t need = het_hgt_aggregate_compact_workspace(by_dst, H, D);
-  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0),
+  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_hgt_aggregate_compact_workspace)", op, (long long)need);
   const int64_t X = H * D;
   HET_HIP(hipMemsetAsync(lsum, 0, sizeof(float) * num_nodes * H, s));
   if (by_dst->S != num_nodes) HET_HIP(hipMemsetAsync(out, 0, sizeof(float) * num_nodes * X, s));  // destinations without in-edges: zero rows
   if (by_dst->E == 0) return HET_OK;
-  Items it{by_dst->item_seg, by_dst->item_begin, by_dst->item_end, by_dst->seg_ptr, by_dst->seg_key, by_dst->num_items};
+  const Items it = items_of(by_dst);
   const unsigned nb = (unsigned)ceil_div64(by_dst->num_items, kBlock / 64);
   float* part = static_cast<float*>(workspace);
   {
@@ -544,7 +522,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
               "%s: by_dst groups the positions by destination (payload0 = (relation, source) row), by_srow by that row "
               "(payload0 = destination)", op);
   const int64_t need = het_hgt_backward_compact_workspace(num_nodes, H);
-  HET_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+  HET_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_hgt_backward_compact_workspace)", op, (long long)need);
   float* pack2 = (float*)workspace;  // [N, H, 2]
   if (by_dst->S != num_nodes) {
@@ -563,7 +541,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
   }
   if (E == 0) return HET_OK;
   {
-    Items it{by_dst->item_seg, by_dst->item_begin, by_dst->item_end, by_dst->seg_ptr, by_dst->seg_key, by_dst->num_items};
+    const Items it = items_of(by_dst);
     const unsigned nb = (unsigned)ceil_div64(by_dst->num_items, kBlock / 64);
     HET_KTIME("HET_hgt_backward_dst_rows", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),
@@ -582,7 +560,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
   }
   HET_LAUNCH_CHECK("HET_hgt_backward_src_short");
   if (by_srow->num_long_items > 0) {
-    Items it{by_srow->item_seg, by_srow->item_begin, by_srow->item_end, by_srow->seg_ptr, by_srow->seg_key, by_srow->num_items};
+    const Items it = items_of(by_srow);
     const unsigned nbl = (unsigned)ceil_div64(by_srow->num_long_items, kBlock / 64);
     HET_KTIME("HET_hgt_backward_src_long", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),

@@ -13,31 +13,10 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxLdsSlots = 64 * 64;  // (relation, head) partial sums of grad_mu reduced in LDS
 
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ void atomic_add4(float* p, float4 v) {
-  atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
-}
 
-struct CsrItems {  // the work items of a destination grouping (grouping.hip.h)
-  const int32_t *seg, *begin, *end, *seg_ptr, *seg_key;
-  int64_t n;
-};
-inline CsrItems items_of(const het_grouping* g) {
-  return CsrItems{g->item_seg, g->item_begin, g->item_end, g->seg_ptr, g->seg_key, g->num_items};
-}
 // a grouping of exactly these E positions by destination alone, carrying the edge id (and the relation when `need_rel`)
 inline bool dst_grouping_ok(const het_grouping* g, int64_t E, bool need_rel) {
   return g && g->R == 0 && g->E == E && g->p0 && (!need_rel || g->p1);
@@ -50,16 +29,6 @@ inline bool rows_shape_ok(int64_t H, int64_t dk) {
   return dk >= 4 && dk <= 128 && is_pow2(dk) && is_pow2(X) && X >= 8 && X <= 256;
 }
 
-#define HET_CSR_LPR(LPRV, CALL)                         \
-  switch (LPRV) {                                       \
-    case 1: { constexpr int LPR = 1; CALL; break; }     \
-    case 2: { constexpr int LPR = 2; CALL; break; }     \
-    case 4: { constexpr int LPR = 4; CALL; break; }     \
-    case 8: { constexpr int LPR = 8; CALL; break; }     \
-    case 16: { constexpr int LPR = 16; CALL; break; }   \
-    case 32: { constexpr int LPR = 32; CALL; break; }   \
-    default: { constexpr int LPR = 64; CALL; break; }   \
-  }
 #define HET_CSR_DL(DLV, CALL)                           \
   switch (DLV) {                                        \
     case 1: { constexpr int DL = 1; CALL; break; }      \
@@ -97,7 +66,7 @@ __device__ __forceinline__ float4 softmax_val(const SoftmaxArgs& p, int64_t eid,
 // true (launched after): split items finish their edges with the completed p.total[v].  MODE 1 reduces grad_mu over the block in
 // LDS ([R, H]) and flushes one atomic per (relation, head) and block.
 template <int LPR, int MODE, bool SPLIT_PASS>
-__global__ __launch_bounds__(kBlock) void HET_hgt_csr_softmax_items(CsrItems it, const int32_t* __restrict__ p_eid,
+__global__ __launch_bounds__(kBlock) void HET_hgt_csr_softmax_items(Items it, const int32_t* __restrict__ p_eid,
                                                                      const int32_t* __restrict__ p_rel, SoftmaxArgs p) {
   constexpr int EPW = 64 / LPR, H = LPR * 4, U = 4;
   extern __shared__ float part[];  // [R * H] (MODE 1)
@@ -232,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_csr_softmax_plain(const idx_t*
 // once to the destination's total.  With DL = dk/4 >= 4 lanes per head, lane (head h, d < 4) fetches the edge id and the
 // score of edge d of a step and the head's lanes share them (coop.hip.h); narrower heads load them per lane.
 template <int LPR, int DL>
-__global__ __launch_bounds__(kBlock) void HET_hgt_csr_aggregate_items(CsrItems it, const int32_t* __restrict__ p_eid,
+__global__ __launch_bounds__(kBlock) void HET_hgt_csr_aggregate_items(Items it, const int32_t* __restrict__ p_eid,
                                                                        const float* __restrict__ msg,
                                                                        const float* __restrict__ attn,
                                                                        const float* __restrict__ sum, float* __restrict__ ret,
@@ -355,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_csr_message_bwd_plain(const id
 // rows in registers and takes <gradout[v], out[v]> once, then streams the message rows of the destination's edges.  grad_mu is
 // reduced in LDS ([R, H]) and flushed with one atomic per (relation, head) and block.
 template <int LPR, int DL>
-__global__ __launch_bounds__(kBlock) void HET_hgt_csr_softmax_bwd_items(CsrItems it, const int32_t* __restrict__ p_eid,
+__global__ __launch_bounds__(kBlock) void HET_hgt_csr_softmax_bwd_items(Items it, const int32_t* __restrict__ p_eid,
                                                                          const int32_t* __restrict__ p_rel,
                                                                          const float* __restrict__ msg,
                                                                          const float* __restrict__ score,
@@ -448,8 +417,8 @@ int check_csr(const char* op, const idx_t* row_ptrs, int64_t row_ptrs_len, const
 int launch_softmax_items(int mode, const het_grouping* g, int64_t H, const SoftmaxArgs& p, hipStream_t s) {
   const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
   const size_t lds = mode == 1 ? sizeof(float) * p.R * H : 0;
-  const CsrItems it = items_of(g);
-#define HET_SM(MODEV, SPLIT) HET_CSR_LPR((int)(H / 4), hipLaunchKernelGGL((HET_hgt_csr_softmax_items<LPR, MODEV, SPLIT>), dim3(nb), \
+  const Items it = items_of(g);
+#define HET_SM(MODEV, SPLIT) HET_DISPATCH_LPR((int)(H / 4), hipLaunchKernelGGL((HET_hgt_csr_softmax_items<LPR, MODEV, SPLIT>), dim3(nb), \
                                                                            dim3(kBlock), lds, s, it, g->p0, g->p1, p))
   if (mode == 0) { HET_SM(0, false); } else { HET_SM(1, false); }
   HET_LAUNCH_CHECK("HET_hgt_csr_softmax_items");
@@ -473,8 +442,7 @@ extern "C" int het_hgt_full_graph_edge_softmax_ops_csr(const int64_t* row_ptrs, 
   HET_REQUIRE(H > 0 && (num_nodes == 0 || sum) && (num_edges == 0 || (score && mu && m && a)), "%s: null data pointer", op);
   hipStream_t s = (hipStream_t)stream;
   SoftmaxArgs p{score, mu, nullptr, nullptr, sum, m, a, nullptr, nullptr, 0};
-  if (num_edges > 0 && dst_grouping_ok(by_dst, num_edges, true) && heads_shape_ok(H) && aligned16(score) && aligned16(mu) &&
-      aligned16(sum) && aligned16(m) && aligned16(a)) {
+  if (num_edges > 0 && dst_grouping_ok(by_dst, num_edges, true) && heads_shape_ok(H) && aligned16(score, mu, sum, m, a)) {
     HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * num_nodes * H, s));  // (destinations without in-edges; hub partial sums)
     return launch_softmax_items(0, by_dst, H, p, s);
   }
@@ -497,13 +465,12 @@ extern "C" int het_hgt_full_graph_message_mean_aggregation_csr(const int64_t* ro
               "%s: null data pointer", op);
   (void)mu;  // switch 1: the score is mu-applied already
   hipStream_t s = (hipStream_t)stream;
-  if (num_edges > 0 && dst_grouping_ok(by_dst, num_edges, false) && rows_shape_ok(H, dk) && aligned16(edge_messages) &&
-      aligned16(ret)) {
+  if (num_edges > 0 && dst_grouping_ok(by_dst, num_edges, false) && rows_shape_ok(H, dk) && aligned16(edge_messages, ret)) {
     HET_HIP(hipMemsetAsync(ret, 0, sizeof(float) * num_nodes * H * dk, s));
     const het_grouping* g = by_dst;
     const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
-    const CsrItems it = items_of(g);
-    HET_CSR_LPR((int)(H * dk / 4), HET_CSR_DL((int)(dk / 4), hipLaunchKernelGGL((HET_hgt_csr_aggregate_items<LPR, DL>), dim3(nb),
+    const Items it = items_of(g);
+    HET_DISPATCH_LPR((int)(H * dk / 4), HET_CSR_DL((int)(dk / 4), hipLaunchKernelGGL((HET_hgt_csr_aggregate_items<LPR, DL>), dim3(nb),
                                                                                  dim3(kBlock), 0, s, it, g->p0, edge_messages,
                                                                                  edge_attn_score, sum, ret, (int)H)));
     HET_LAUNCH_CHECK("HET_hgt_csr_aggregate_items");
@@ -526,10 +493,10 @@ extern "C" int het_backward_hgt_full_graph_message_mean_aggregation_csr(
   (void)sum;  // switch 2: the normalised score is given
   if (num_edges == 0) return HET_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (rows_shape_ok(H, dk) && aligned16(gradout) && aligned16(grad_message)) {
+  if (rows_shape_ok(H, dk) && aligned16(gradout, grad_message)) {
     const int lpr = (int)(H * dk / 4);
     const unsigned nb = grid_for(ceil_div64(num_edges * lpr, 4));
-    HET_CSR_LPR(lpr, hipLaunchKernelGGL(HET_hgt_csr_message_bwd_rows<LPR>, dim3(nb), dim3(kBlock), 0, s, col_indices, eids, num_edges,
+    HET_DISPATCH_LPR(lpr, hipLaunchKernelGGL(HET_hgt_csr_message_bwd_rows<LPR>, dim3(nb), dim3(kBlock), 0, s, col_indices, eids, num_edges,
                                         normalized_attn_score, gradout, grad_message, (int)H, (int)dk));
     HET_LAUNCH_CHECK("HET_hgt_csr_message_bwd_rows");
     return HET_OK;
@@ -552,12 +519,12 @@ extern "C" int het_backward_hgt_full_graph_edge_softmax_ops_csr(
               "%s: null data pointer", op);
   if (num_edges == 0) return HET_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dst_grouping_ok(by_dst, num_edges, true) && rows_shape_ok(H, dk) && num_rels * H <= kMaxLdsSlots && aligned16(message) &&
-      aligned16(out) && aligned16(gradout)) {
+  if (dst_grouping_ok(by_dst, num_edges, true) && rows_shape_ok(H, dk) && num_rels * H <= kMaxLdsSlots &&
+      aligned16(message, out, gradout)) {
     const het_grouping* g = by_dst;
     const unsigned nb = (unsigned)ceil_div64(g->num_items, kBlock / 64);
-    const CsrItems it = items_of(g);
-    HET_CSR_LPR((int)(H * dk / 4), HET_CSR_DL((int)(dk / 4), hipLaunchKernelGGL((HET_hgt_csr_softmax_bwd_items<LPR, DL>), dim3(nb),
+    const Items it = items_of(g);
+    HET_DISPATCH_LPR((int)(H * dk / 4), HET_CSR_DL((int)(dk / 4), hipLaunchKernelGGL((HET_hgt_csr_softmax_bwd_items<LPR, DL>), dim3(nb),
                                                                                  dim3(kBlock), sizeof(float) * num_rels * H, s, it,
                                                                                  g->p0, g->p1, message, score,
                                                                                  normalized_attn_score, out, gradout, mu,
@@ -588,8 +555,8 @@ extern "C" int het_backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(
   const het_grouping* g = by_dst;
   const bool ws_ok = g && (g->num_split == 0 || (workspace && workspace_bytes >= (int64_t)sizeof(float) * num_nodes * H &&
                                                  aligned16(workspace)));
-  if (dst_grouping_ok(g, num_edges, true) && ws_ok && heads_shape_ok(H) && num_rels * H <= kMaxLdsSlots && aligned16(score) &&
-      aligned16(mu) && aligned16(normalized_attn_score) && aligned16(grad_normalized_attn_score) && aligned16(grad_score)) {
+  if (dst_grouping_ok(g, num_edges, true) && ws_ok && heads_shape_ok(H) && num_rels * H <= kMaxLdsSlots &&
+      aligned16(score, mu, normalized_attn_score, grad_normalized_attn_score, grad_score)) {
     if (g->num_split > 0) HET_HIP(hipMemsetAsync(workspace, 0, sizeof(float) * num_nodes * H, s));
     return launch_softmax_items(1, g, H, p, s);
   }

@@ -9,7 +9,7 @@
 #include "common.hip.h"
 
 namespace {
-constexpr int kBlock = 256;
+constexpr int64_t kGridCap = 65536;  // this file's grid-stride launches (grid_for's default is 256 * 64)
 
 // A[r,h,d,e]: rel_att as stored (fused score: s = <k . att, q>) or transposed (s = <q . att, k> = <k . att^T, q>)
 __device__ __forceinline__ float att_at(const float* __restrict__ att, int64_t rh, int dk, int d, int e, int transpose) {
@@ -109,10 +109,6 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_fold_backward_rel(const float*
   if (threadIdx.x == 0) grad_pri[rh] = red[0] * inv_sqrt;
 }
 
-inline unsigned grid_for(int64_t total) {
-  const int64_t b = ceil_div64(total, kBlock);
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
 }  // namespace
 
 extern "C" int het_hgt_fold_source_weights(const float* k_lin, const float* v_lin, const float* rel_att, const float* rel_msg,
@@ -121,7 +117,7 @@ extern "C" int het_hgt_fold_source_weights(const float* k_lin, const float* v_li
   const char* op = "het_hgt_fold_source_weights";
   HET_REQUIRE(k_lin && v_lin && rel_att && rel_msg && rel_pri && src_type && w_kv, "%s: null argument", op);
   HET_REQUIRE(num_types > 0 && num_rels > 0 && H > 0 && dk > 0 && K_in > 0 && num_rels * K_in * 2 * H * dk < (1ll << 40), "%s: bad sizes", op);
-  hipLaunchKernelGGL(HET_hgt_fold_weights, dim3(grid_for(num_rels * K_in * 2 * H * dk)), dim3(kBlock), 0, (hipStream_t)stream, k_lin, v_lin,
+  hipLaunchKernelGGL(HET_hgt_fold_weights, dim3(grid_for(num_rels * K_in * 2 * H * dk, kGridCap)), dim3(kBlock), 0, (hipStream_t)stream, k_lin, v_lin,
                      rel_att, rel_msg, rel_pri, src_type, (int)num_rels, (int)H, (int)dk, (int)K_in, transpose_att, w_kv);
   HET_LAUNCH_CHECK("HET_hgt_fold_weights");
   return HET_OK;
@@ -137,7 +133,7 @@ extern "C" int het_hgt_fold_source_weights_backward(const float* grad_w_kv, cons
                   grad_pri, "%s: null argument", op);
   HET_REQUIRE(num_types > 0 && num_rels > 0 && H > 0 && dk > 0 && K_in > 0, "%s: bad sizes", op);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(HET_hgt_fold_backward_lin, dim3(grid_for(2 * num_types * K_in * H * dk)), dim3(kBlock), 0, s, grad_w_kv, rel_att, rel_msg,
+  hipLaunchKernelGGL(HET_hgt_fold_backward_lin, dim3(grid_for(2 * num_types * K_in * H * dk, kGridCap)), dim3(kBlock), 0, s, grad_w_kv, rel_att, rel_msg,
                      rel_pri, src_type, (int)num_types, (int)num_rels, (int)H, (int)dk, (int)K_in, transpose_att, grad_k_lin, grad_v_lin);
   HET_LAUNCH_CHECK("HET_hgt_fold_backward_lin");
   hipLaunchKernelGGL(HET_hgt_fold_backward_rel, dim3((unsigned)(num_rels * H)), dim3(kBlock), 0, s, grad_w_kv, k_lin, v_lin, rel_att, rel_pri,

@@ -11,8 +11,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-
 inline unsigned blocks_for(int64_t n) {
   int64_t b = ceil_div64(n, kBlock);
   return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));

@@ -23,9 +23,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMaxRels = 8;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 __global__ __launch_bounds__(256) void HET_node_row_map(const idx_t* __restrict__ rel_ptrs, int R,
                                                          const idx_t* __restrict__ nodes, int64_t N,
                                                          int32_t* __restrict__ map) {

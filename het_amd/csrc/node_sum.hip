@@ -18,9 +18,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMaxSrc = 9;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // TO: the element type of the output rows, float or het_bf16 (rounded once, at the store); everything else is fp32
 template <typename TO>
 struct SumArgsT {

@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-
 // BACKWARD = false: out = ret (row = dst), in = feat (row = crow)
 // BACKWARD = true : out = grad_feat (row = crow), in = gradout (row = dst)
 template <bool BACKWARD>
@@ -30,12 +28,6 @@ __global__ __launch_bounds__(kBlock) void HET_rgcn_compact_aggregate(EdgeView v,
   }
 }
 
-inline unsigned grid_for(int64_t total) {
-  int64_t b = ceil_div64(total, kBlock);
-  const int64_t cap = 256 * 64;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 extern "C" int het_rgcn_node_mean_aggregation_compact_as_of_node_separate_coo(
@@ -48,7 +40,7 @@ extern "C" int het_rgcn_node_mean_aggregation_compact_as_of_node_separate_coo(
               "%s: null pointer", op);
   hipStream_t s = (hipStream_t)stream;
   if (by_dst && by_dst->R == 0 && by_dst->E == num_edges && by_dst->p0 && by_dst->p1 && segment_sum_supported((int)X) &&
-      num_edges > 0 && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(ret)) & 15) == 0)
+      num_edges > 0 && aligned16(feat, ret))
     // ret[dst, :] = SUM over the in-edges of enorm[eid] * feat[srow, :]: a segmented sum over the destination grouping
     // (payload0 = compact row of the edge's source, payload1 = edge id) instead of E*X float atomics
     return launch_segment_sum(by_dst, feat, ret, (int)X, enorm, s, 0, num_nodes, 0);
@@ -76,7 +68,7 @@ extern "C" int het_backward_rgcn_node_mean_aggregation_compact_as_of_node_separa
   hipStream_t s = (hipStream_t)stream;
   if (by_src_row && by_src_row->R == 0 && by_src_row->E == num_edges && by_src_row->p0 && by_src_row->p1 &&
       segment_sum_supported((int)X) && n_src_rows >= 0 &&
-      ((reinterpret_cast<uintptr_t>(gradout) | reinterpret_cast<uintptr_t>(grad_feat)) & 15) == 0)
+      aligned16(gradout, grad_feat))
     // grad_feat[srow, :] += SUM over the edges of that compact row of enorm[eid] * gradout[dst, :]
     // (grouping by compact row, payload0 = destination, payload1 = edge id)
     return launch_segment_sum(by_src_row, gradout, grad_feat, (int)X, enorm, s, 0, n_src_rows, 1);

@@ -37,7 +37,7 @@ extern "C" int het_rgnn_relational_matmul(int64_t kind, const int64_t* rel_ptrs,
   if (in1head && by_rel_gather && kind == HET_KIND_DISABLED && by_rel_gather->R == (int)num_rels &&
       by_rel_gather->E == num_rows && by_rel_gather->p0 && by_rel_gather->S > 0 && D > 1 && segment_rows_supported((int)(H * D)) &&
       workspace && workspace_bytes >= (int64_t)sizeof(float) * by_rel_gather->S * H * D &&
-      ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(ret)) & 15) == 0) {
+      aligned16(workspace, ret)) {
     // the caller passed the (relation, x row) grouping (het_amd.kernels does for shapes outside the 32..128 MFMA tiles: an
     // 8- or 16-wide output layer, 256-wide features): project only the S distinct rows and duplicate them, instead of
     // one GEMM row per position
@@ -50,23 +50,23 @@ extern "C" int het_rgnn_relational_matmul(int64_t kind, const int64_t* rel_ptrs,
     if (int rc = launch_rows_gemm(m, s)) return rc;
     return launch_segment_broadcast(g, comp, ret, (int)(H * D), nullptr, nullptr, 0, s);
   }
-  if (in1head && mfma_fwd_supported((int)K, (int)(H * D)) && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+  if (in1head && mfma_fwd_supported((int)K, (int)(H * D)) && aligned16(x))
     return launch_seg_gemm_mfma_fwd(x, K, gather_idx, weights, H * K * D, (int)H, (int)D, ret, H * D, scatter, rel_ptrs,
                                     (int)num_rels, num_rows, (int)K, s);
-  if (!in1head && D == 1 && rowdot_supported((int)H, (int)K) && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+  if (!in1head && D == 1 && rowdot_supported((int)H, (int)K) && aligned16(x)) {
     RowDotArgs q;
     q.A = x; q.gather = gather_idx; q.W = weights; q.out = ret; q.scatter = scatter; q.seg_ptrs = rel_ptrs;
     q.num_segs = (int)num_rels; q.num_rows = num_rows; q.H = (int)H; q.K = (int)K;
     return launch_rowdot_fwd(q, s);
   }
-  if (in1head && D == 1 && rowdot1h_supported((int)H, (int)K) && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+  if (in1head && D == 1 && rowdot1h_supported((int)H, (int)K) && aligned16(x)) {
     RowDotArgs q;  // one x row against the H folded attention vectors of its relation
     q.A = x; q.gather = gather_idx; q.W = weights; q.out = ret; q.scatter = scatter; q.seg_ptrs = rel_ptrs;
     q.num_segs = (int)num_rels; q.num_rows = num_rows; q.H = (int)H; q.K = (int)K;
     const het_grouping* g = by_rel_gather;
     if (g && kind == HET_KIND_DISABLED && g->R == (int)num_rels && g->E == num_rows && g->p0 && g->S > 0 &&
         segment_rows_supported((int)H) && workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * H &&
-        (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(ret) & 15) == 0) {
+        aligned16(workspace, ret)) {
       // positions sharing (relation, x row) hold the same [H] product: form the S distinct ones, then duplicate
       float* dots = static_cast<float*>(workspace);
       q.gather = g->seg_key64; q.scatter = nullptr; q.out = dots; q.seg_ptrs = g->seg_rel_ptr64; q.num_rows = g->S;
@@ -75,8 +75,7 @@ extern "C" int het_rgnn_relational_matmul(int64_t kind, const int64_t* rel_ptrs,
     }
     return launch_rowdot1h_fwd(q, s);
   }
-  if (!in1head && H > 1 && mfma_shape_supported((int)(H * K), (int)(H * D)) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(ret) & 15) == 0) {
+  if (!in1head && H > 1 && mfma_shape_supported((int)(H * K), (int)(H * D)) && aligned16(x, ret)) {
     // per-head K x D products (HGT: 8 heads of 8 x 8) as ONE row GEMM with a block-diagonal weight: the
     // kernel is bound by moving the [rows, H*K] / [rows, H*D] tensors, not by the (mostly zero) MFMA work
     MfmaGemmArgs m;
@@ -108,8 +107,7 @@ extern "C" int het_rgnn_relational_matmul_attn_dot(int64_t kind, const int64_t* 
   if (int rc = check_matmul(op, kind, rel_ptrs, num_rels, gather_idx, scatter_idx, num_rows, H, K, D)) return rc;
   HET_REQUIRE(num_rows == 0 || (weights && x && dot_w && dot_out), "%s: null data pointer", op);
   if (num_rows == 0) return HET_OK;
-  if (!(mfma_fwd_supported((int)K, (int)(H * D)) && D >= 4 && (D & (D - 1)) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(dot_w) & 15) == 0)) {
+  if (!(mfma_fwd_supported((int)K, (int)(H * D)) && D >= 4 && (D & (D - 1)) == 0 && aligned16(x, dot_w))) {
     het_set_error("%s: only the MFMA shapes (K, H*D in {32, 64, 128}, D a power of two >= 4, 16-byte aligned rows)", op);
     return HET_ERR_UNSUPPORTED;
   }
@@ -120,8 +118,7 @@ extern "C" int het_rgnn_relational_matmul_attn_dot(int64_t kind, const int64_t* 
   const int64_t X = H * D;
   const int64_t ws_need = g ? (int64_t)sizeof(float) * g->S * ((comp_rows ? 0 : X) + H) : 0;
   if (g && kind == HET_KIND_DISABLED && g->R == (int)num_rels && g->E == num_rows && g->p0 && segment_sum_supported((int)X) &&
-      H <= X / 4 && workspace && workspace_bytes >= ws_need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(ret) & 15) == 0 && (reinterpret_cast<uintptr_t>(comp_rows) & 15) == 0 && num_rows > 0 &&
+      H <= X / 4 && workspace && workspace_bytes >= ws_need && aligned16(workspace, ret, comp_rows) && num_rows > 0 &&
       segment_rows_supported((int)H)) {
     // Rows that share (relation, gather_idx) are identical: project the S distinct rows once (dense, into comp_rows
     // or the workspace), then duplicate every row to the positions of its segment -- same values as the per-position
@@ -181,9 +178,7 @@ extern "C" int het_backward_rgnn_relational_matmul_attn_dot_only(
   const int64_t X = H * D;
   if (!(g && g->R == (int)num_rels && g->E == num_rows && g->p0 && segment_rows_supported((int)H) && (D % 4) == 0 &&
         mfma_shape_supported((int)X, (int)K) && mfma_dw_supported((int)K, (int)X) && workspace &&
-        workspace_bytes >= (int64_t)sizeof(float) * g->S * (H + X) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(grad_dot) & 15) == 0 && (reinterpret_cast<uintptr_t>(dot_w) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0)) {
+        workspace_bytes >= (int64_t)sizeof(float) * g->S * (H + X) && aligned16(workspace, grad_dot, dot_w, x, grad_x))) {
     het_set_error("%s: needs the (relation, gather_idx) grouping, a workspace of S*(H + H*D) floats and MFMA shapes", op);
     return HET_ERR_UNSUPPORTED;
   }
@@ -199,7 +194,7 @@ extern "C" int het_backward_rgnn_relational_matmul_attn_dot_only(
   if (comp_rows && grad_dot_w) {
     // grad_dot_w[r, h, :] (+)= SUM over the segments of r of gs[s, h] * comp_rows[s, h, :]  -- the weight gradient of
     // the attention product from the S distinct projected rows of the forward instead of the E duplicated ones
-    HET_REQUIRE(rowdot_supported((int)H, (int)D) && (reinterpret_cast<uintptr_t>(comp_rows) & 15) == 0,
+    HET_REQUIRE(rowdot_supported((int)H, (int)D) && aligned16(comp_rows),
                 "%s: comp_rows path needs the row-dot shapes", op);
     if (!accumulate) HET_HIP(hipMemsetAsync(grad_dot_w, 0, sizeof(float) * num_rels * X, s));
     RowDotArgs q;
@@ -249,10 +244,9 @@ extern "C" int het_backward_rgnn_relational_matmul(int64_t kind, const int64_t* 
   // gather list IS the edge-id list, so every input row belongs to exactly one position
   const bool unique = kind == HET_KIND_DISABLED && gather_idx == scatter_idx;
   const bool rowdot = !in1head && D == 1 && rowdot_supported((int)H, (int)K) &&
-                      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0;
+                      aligned16(x, grad_x);
   // grad_x == NULL: weight gradient only (a caller that folded the input gradient elsewhere); row-dot shape only
-  const bool rowdot1h = in1head && D == 1 && rowdot1h_supported((int)H, (int)K) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0;
+  const bool rowdot1h = in1head && D == 1 && rowdot1h_supported((int)H, (int)K) && aligned16(x, grad_x);
   HET_REQUIRE(num_rows == 0 || grad_x || rowdot || rowdot1h, "%s: grad_x may be NULL only for the D == 1 shapes", op);
   if (!accumulate) {  // "=" semantics: zero what the kernels below accumulate into
     HET_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * num_rels * H * K * D, s));
@@ -280,7 +274,7 @@ extern "C" int het_backward_rgnn_relational_matmul(int64_t kind, const int64_t* 
     q.num_segs = (int)num_rels; q.num_rows = num_rows; q.H = (int)H; q.K = (int)K;
     if (g && kind == HET_KIND_DISABLED && g->R == (int)num_rels && g->E == num_rows && g->p0 &&
         segment_rows_supported((int)H) && workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * H &&
-        (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
+        aligned16(gradout, workspace)) {
       // positions sharing (relation, x row) share both factors: sum their [H] gradients first
       float* gsum = static_cast<float*>(workspace);
       if (int rc = launch_segment_sum(g, gradout, gsum, (int)H, nullptr, s)) return rc;
@@ -303,13 +297,12 @@ extern "C" int het_backward_rgnn_relational_matmul(int64_t kind, const int64_t* 
     return launch_rowdot1h_bwd_dw(q, s);
   }
   if (!in1head && H > 1 && mfma_shape_supported((int)(H * D), (int)(H * K)) && mfma_dw_supported((int)(H * K), (int)(H * D)) &&
-      (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+      aligned16(gradout, grad_x, x)) {
     // per-head products as block-diagonal row GEMMs (see the forward)
     const bool grouped = g && kind == HET_KIND_DISABLED && g->R == (int)num_rels && g->E == num_rows && g->p0 &&
                          segment_sum_supported((int)(H * D)) && workspace &&
                          workspace_bytes >= (int64_t)sizeof(float) * g->S * H * D &&
-                         (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
+                         aligned16(workspace);
     const float* G = gradout;
     const idx_t *g_rows = scatter, *x_rows = gather_idx, *segs = rel_ptrs;
     int64_t rows = num_rows;
@@ -331,7 +324,7 @@ extern "C" int het_backward_rgnn_relational_matmul(int64_t kind, const int64_t* 
   }
   if (in1head && g && kind == HET_KIND_DISABLED && g->R == (int)num_rels && g->E == num_rows && g->p0 &&
       segment_sum_supported((int)(H * D)) && workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * H * D &&
-      (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
+      aligned16(gradout, workspace)) {
     // Rows that share (relation, gather_idx) share x row and weight: by linearity sum their gradout rows
     // first (one pass over gradout), then run both GEMMs on the S distinct (relation, node) rows only.
     float* gsum = static_cast<float*>(workspace);
@@ -348,7 +341,7 @@ extern "C" int het_backward_rgnn_relational_matmul(int64_t kind, const int64_t* 
     return launch_rows_dw(w, s);
   }
   if (in1head && mfma_shape_supported((int)(H * D), (int)K) && mfma_dw_supported((int)K, (int)(H * D)) &&
-      (reinterpret_cast<uintptr_t>(gradout) & 15) == 0) {
+      aligned16(gradout)) {
     // grad_x[gather] += gradout[scatter] . Wt[r]: Wt[r] read as one [H*D, K] matrix (heads summed by the GEMM)
     MfmaGemmArgs m;
     m.A = gradout; m.a_ld = H * D; m.gather = scatter; m.B = weights_t; m.b_rel_stride = H * D * K;
@@ -407,8 +400,7 @@ extern "C" int het_rows_matmul_backward_dx(const int64_t* rel_ptrs, int64_t num_
   HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rows >= 0 && H > 0 && K > 0 && D > 0, "%s: bad arguments", op);
   if (num_rows == 0) return HET_OK;
   HET_REQUIRE(weights_t && gradout && grad_x, "%s: null data pointer", op);
-  if (!(mfma_shape_supported((int)(H * D), (int)K) && (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0)) {
+  if (!(mfma_shape_supported((int)(H * D), (int)K) && aligned16(gradout, grad_x))) {
     het_set_error("%s: only the matrix-core shapes", op);
     return HET_ERR_UNSUPPORTED;
   }
@@ -428,8 +420,7 @@ extern "C" int het_rows_matmul_backward_dw_colsum(const int64_t* rel_ptrs, int64
   const char* op = "het_rows_matmul_backward_dw_colsum";
   HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rows >= 0 && H > 0 && K > 0 && D > 0 && grad_w, "%s: bad arguments", op);
   hipStream_t s = (hipStream_t)stream;
-  if (!(mfma_dw_supported((int)K, (int)(H * D)) && (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(x) & 15) == 0)) {
+  if (!(mfma_dw_supported((int)K, (int)(H * D)) && aligned16(gradout, x))) {
     het_set_error("%s: only the matrix-core shapes", op);
     return HET_ERR_UNSUPPORTED;
   }
@@ -460,10 +451,10 @@ extern "C" int het_rgnn_relational_matmul_no_scatter_gather_list(const int64_t* 
   HET_REQUIRE(num_types > 0 && num_rows >= 0 && H > 0 && K > 0 && D > 0 && offsets, "%s: bad arguments", op);
   HET_REQUIRE(num_rows == 0 || (weights && x && ret), "%s: null data pointer", op);
   hipStream_t s = (hipStream_t)stream;
-  if (!x_per_head && mfma_fwd_supported((int)K, (int)(H * D)) && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+  if (!x_per_head && mfma_fwd_supported((int)K, (int)(H * D)) && aligned16(x))
     return launch_seg_gemm_mfma_fwd(x, K, nullptr, weights, H * K * D, (int)H, (int)D, ret, H * D, nullptr, offsets,
                                     (int)num_types, num_rows, (int)K, s);
-  if ((x_per_head || H == 1) && D == 1 && rowdot_supported((int)H, (int)K) && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+  if ((x_per_head || H == 1) && D == 1 && rowdot_supported((int)H, (int)K) && aligned16(x)) {
     RowDotArgs q;
     q.A = x; q.W = weights; q.out = ret; q.seg_ptrs = offsets; q.num_segs = (int)num_types; q.num_rows = num_rows;
     q.H = (int)H; q.K = (int)K;
@@ -504,8 +495,7 @@ extern "C" int het_rows_linear_bias(const int64_t* offsets, const float* x, cons
   HET_REQUIRE(offsets && num_rows >= 0 && K > 0 && X > 0, "%s: bad arguments", op);
   if (num_rows == 0) return HET_OK;
   HET_REQUIRE(x && w && out, "%s: null data pointer", op);
-  if (!(mfma_shape_supported((int)K, (int)X) && K <= 128 && X <= 128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0)) {
+  if (!(mfma_shape_supported((int)K, (int)X) && K <= 128 && X <= 128 && aligned16(x, out, bias))) {
     het_set_error("%s: only the matrix-core shapes (K, X in {32, 64, 128}, 16-byte aligned rows)", op);
     return HET_ERR_UNSUPPORTED;
   }
@@ -526,9 +516,9 @@ extern "C" int het_backward_rgnn_relational_matmul_no_scatter_gather_list(
   // rows are their own gather list here: every grad_x row has exactly one writer (rows outside
   // [offsets[0], offsets[T]) have none: they are zeroed when overwriting)
   const bool rowdot = (x_per_head || H == 1) && D == 1 && rowdot_supported((int)H, (int)K) &&
-                      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0;
+                      aligned16(x, grad_x);
   const bool mfma = grad_x && !x_per_head && mfma_shape_supported((int)(H * D), (int)K) && mfma_dw_supported((int)K, (int)(H * D)) &&
-                    (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0;
+                    aligned16(gradout, grad_x);
   // grad_x == NULL: weight gradient only (per-head D == 1 shape, as in het_backward_rgnn_relational_matmul)
   HET_REQUIRE(num_rows == 0 || grad_x || rowdot, "%s: grad_x may be NULL only for the per-head D == 1 shape", op);
   if (!accumulate) {
@@ -597,8 +587,7 @@ extern "C" int het_rgcn_layer1_separate_coo(const int64_t* rel_ptrs, const int64
   const het_grouping* g = by_rel_dst;
   if (g && g->R == (int)num_rels && g->E == num_edges && g->p0 && g->p1 && segment_sum_supported((int)K) &&
       workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * K &&
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(ret) & 15) == 0) {
+      aligned16(x, workspace, ret)) {
     // Edges that share (relation, destination) share weight and output row: sum their scaled source rows first
     // (one gather pass over x), then one GEMM row per distinct (relation, destination) pair, added into ret.
     hipStream_t s = (hipStream_t)stream;
@@ -631,8 +620,7 @@ extern "C" int het_backward_rgcn_layer1_separate_coo(const int64_t* rel_ptrs, co
   hipStream_t s = (hipStream_t)stream;
   const het_grouping* g = by_rel_src;
   if (g && g->R == (int)num_rels && g->E == num_edges && g->p0 && g->p1 && segment_sum_supported((int)D) &&
-      workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * D && (reinterpret_cast<uintptr_t>(gradout) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15) == 0) {
+      workspace && workspace_bytes >= (int64_t)sizeof(float) * g->S * D && aligned16(gradout, workspace, grad_x)) {
     // gsum[(r,u)] = SUM over the out-edges of u in relation r of norm * gradout[dst]; then
     //   grad_x[u] += gsum[(r,u)] . Wt[r]      and      grad_w[r] += x[u]^T (x) gsum[(r,u)]
     float* gsum = static_cast<float*>(workspace);
@@ -772,8 +760,7 @@ int rgcn_layer_forward(const char* op, const het_grouping* by_rel_dst, int64_t n
   HET_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "%s: bad node count", op);
   if (num_nodes == 0) return HET_OK;
   HET_REQUIRE(x && weights && (norm || norm_sorted) && dst_map && ssum && ret, "%s: null pointer", op);
-  HET_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ssum) | reinterpret_cast<uintptr_t>(ret) |
-                reinterpret_cast<uintptr_t>(bias)) & 15) == 0, "%s: 16-byte aligned pointers expected", op);
+  HET_REQUIRE(aligned16(x, ssum, ret, bias), "%s: 16-byte aligned pointers expected", op);
   hipStream_t s = (hipStream_t)stream;
   // ssum[(r,v), :] = SUM over the in-edges of v in relation r of norm * x[src]   (one gather pass over x)
   // (norm_sorted: the norm in the grouping's order, het_grouping_gather_payload1 -- a coalesced stream instead of a random 4-byte
@@ -801,8 +788,7 @@ int rgcn_layer_backward(const char* op, const het_grouping* by_rel_src, const he
   HET_REQUIRE(num_src_nodes >= 0 && num_src_nodes < (1ll << 31) && num_dst_nodes >= gd->key_bound, "%s: bad node count", op);
   HET_REQUIRE(grad_w && (num_src_nodes == 0 || (ssum && gradout && (!grad_x || (weights_t && (norm || norm_sorted) && src_map)))), "%s: null pointer", op);
   HET_REQUIRE(workspace && workspace_bytes >= het_rgcn_layer_backward_workspace(gs->S, D) &&
-              ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(gradout) | reinterpret_cast<uintptr_t>(grad_x) |
-                reinterpret_cast<uintptr_t>(ssum)) & 15) == 0, "%s: workspace too small (het_rgcn_layer_backward_workspace) or pointers not 16-byte aligned", op);
+              aligned16(workspace, gradout, grad_x, ssum), "%s: workspace too small (het_rgcn_layer_backward_workspace) or pointers not 16-byte aligned", op);
   hipStream_t s = (hipStream_t)stream;
   float* gsum = static_cast<float*>(workspace);
   float* cpart = gsum + (gs->S > 0 ? gs->S : 1) * D;
@@ -903,8 +889,7 @@ __global__ __launch_bounds__(256) void HET_rows_add_bias(const float* __restrict
 extern "C" int het_rows_add_bias(const float* a, const float* b, const float* bias, float* out, int64_t num_rows, int64_t X,
                                  het_stream stream) {
   HET_REQUIRE(num_rows >= 0 && X > 0 && X % 4 == 0 && (num_rows == 0 || (a && out)), "rows_add_bias: bad arguments");
-  HET_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(bias) |
-                reinterpret_cast<uintptr_t>(out)) & 15) == 0, "rows_add_bias: 16-byte aligned pointers expected");
+  HET_REQUIRE(aligned16(a, b, bias, out), "rows_add_bias: 16-byte aligned pointers expected");
   if (num_rows == 0) return HET_OK;
   const int64_t total4 = num_rows * (X / 4);
   int64_t nb = ceil_div64(total4, 256);
@@ -937,7 +922,7 @@ __global__ __launch_bounds__(256) void HET_rows_scatter_add(const float* __restr
 
 extern "C" int het_rows_gather(const float* x, const int64_t* idx, int64_t num_rows, int64_t X, float* out, het_stream stream) {
   HET_REQUIRE(num_rows >= 0 && X > 0 && X % 4 == 0 && (num_rows == 0 || (x && idx && out)), "rows_gather: bad arguments");
-  HET_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0, "rows_gather: 16-byte aligned pointers expected");
+  HET_REQUIRE(aligned16(x, out), "rows_gather: 16-byte aligned pointers expected");
   if (num_rows == 0) return HET_OK;
   const int64_t total4 = num_rows * (X / 4);
   int64_t nb = ceil_div64(total4, 256);

@@ -8,7 +8,7 @@
 #include "seg_gemm_mfma.hip.h"
 
 inline int launch_rows_gemm(const MfmaGemmArgs& m, hipStream_t s) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(m.A) | reinterpret_cast<uintptr_t>(m.C)) & 15) == 0;
+  const bool aligned = aligned16(m.A, m.C);
   if (mfma_shape_supported(m.K, m.X) && aligned) return launch_seg_gemm_mfma(m, s);
   HET_REQUIRE(!m.dot_out, "row GEMM: the dot epilogue needs an MFMA shape");
   SegGemmArgs a;
@@ -31,7 +31,7 @@ inline int launch_rows_gemm(const MfmaGemmArgs& m, hipStream_t s) {
 // grouping, a unique (relation, node) list): segment by segment with plain read-modify-write instead of float atomics
 // when the segments are few (launches are ordered on the stream); else atomics.
 inline int launch_rows_gemm_add_unique(const MfmaGemmArgs& m, hipStream_t s) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(m.A) | reinterpret_cast<uintptr_t>(m.C)) & 15) == 0;
+  const bool aligned = aligned16(m.A, m.C);
   if (mfma_shape_supported(m.K, m.X) && aligned && m.num_segs <= kRmwMaxSegments && m.K <= 128 && m.X <= 128 && !m.dot_w && !m.bias)
     return launch_seg_gemm_mfma_rmw_per_segment(m, s);
   MfmaGemmArgs a = m;
@@ -41,7 +41,7 @@ inline int launch_rows_gemm_add_unique(const MfmaGemmArgs& m, hipStream_t s) {
 }
 
 inline int launch_rows_dw(const MfmaDwArgs& m, hipStream_t s) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(m.A) | reinterpret_cast<uintptr_t>(m.G)) & 15) == 0;
+  const bool aligned = aligned16(m.A, m.G);
   if (mfma_dw_supported(m.K, m.X) && aligned) return launch_seg_dw_mfma(m, s);
   SegDwArgs w;
   w.A = m.A; w.a_ld = m.a_ld; w.gather = m.gather; w.row_scale = m.row_scale; w.scale_idx = m.scale_idx;

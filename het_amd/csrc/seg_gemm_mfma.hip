@@ -595,13 +595,13 @@ int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s) {
     }
     return HET_OK;
   }
-  HET_REQUIRE(a.a_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0, "segment GEMM (MFMA): A rows must be 16-byte aligned");
-  HET_REQUIRE(a.c_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0, "segment GEMM (MFMA): C rows must be 16-byte aligned");
+  HET_REQUIRE(a.a_ld % 4 == 0 && aligned16(a.A), "segment GEMM (MFMA): A rows must be 16-byte aligned");
+  HET_REQUIRE(a.c_ld % 4 == 0 && aligned16(a.C), "segment GEMM (MFMA): C rows must be 16-byte aligned");
   HET_REQUIRE(!a.row_scale, "segment GEMM (MFMA): row scales are applied by the segment-sum pre-pass, not here");
   if (a.dot_w) {
     const int Dh = a.headcat_d;
     HET_REQUIRE(a.dot_out && !a.atomic && a.b_headcat == 1 && Dh >= 4 && (Dh & (Dh - 1)) == 0 && a.X % Dh == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.dot_w) & 15) == 0,
+                    aligned16(a.dot_w),
                 "segment GEMM (MFMA): the dot epilogue needs plain stores, head-concatenated weights and a power-of-two D >= 4");
   }
   switch (a.K) {

@@ -5,10 +5,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // Slot-per-item: the LPR lanes of a slot own one work item each, so a wave runs 64/LPR items side by side.
 // Short segments (a few rows) then keep every lane group busy, the per-item prologue (item record -> ids -> rows) is
 // shared by 64/LPR items, and the row ids of the next step are fetched while the current rows are in flight, which
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum(const int32_t* __restr
     }
     st4(p, acc);
   } else {
-    atomicAdd(p + 0, acc.x); atomicAdd(p + 1, acc.y); atomicAdd(p + 2, acc.z); atomicAdd(p + 3, acc.w);
+    atomic_add4(p, acc);
   }
 }
 
@@ -244,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_long(const int32_t* __
     }
     st4_nt(p, acc);
   } else {
-    atomicAdd(p + 0, acc.x); atomicAdd(p + 1, acc.y); atomicAdd(p + 2, acc.z); atomicAdd(p + 3, acc.w);
+    atomic_add4(p, acc);
   }
 }
 
@@ -311,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void HET_segment_sum_flat4(const int32_t* _
       if (seg_ptr[k] >= first && seg_ptr[k + 1] <= first + 64) {
         *reinterpret_cast<float4*>(p) = a;
       } else {
-        atomicAdd(p + 0, a.x); atomicAdd(p + 1, a.y); atomicAdd(p + 2, a.z); atomicAdd(p + 3, a.w);
+        atomic_add4(p, a);
       }
     }
   }
@@ -382,7 +378,7 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
   auto zero_split_rows = [&]() -> int {
     if (split_rows_zeroed) return HET_OK;
     split_rows_zeroed = true;
-    if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) {
+    if (!aligned16(out)) {
       HET_HIP(hipMemsetAsync(out, 0, sizeof(float) * g->S * X, s));
       return HET_OK;
     }
@@ -391,8 +387,7 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
     HET_LAUNCH_CHECK("HET_segsum_zero_split");
     return HET_OK;
   };
-  if (X == 4 && !scale && scatter_rows < 0 && !accumulate && !nt_in && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+  if (X == 4 && !scale && scatter_rows < 0 && !accumulate && !nt_in && aligned16(in, out)) {
     if (int rc = grouping_seg_of_rank(g, s)) return rc;
     HET_HIP(hipMemsetAsync(out, 0, sizeof(float) * g->S * X, s));  // (pieces of straddling segments are added atomically)
     constexpr int U = 4;
@@ -447,27 +442,16 @@ int launch_segment_sum(const het_grouping* g, const float* in, float* out, int X
     }
     return HET_OK;
   }
-#define HET_SS(L)                                                                                                   \
-  hipLaunchKernelGGL(HET_segment_sum<L>, dim3(nb), dim3(kBlock), 0, s, g->item_seg, g->item_begin, g->item_end,     \
-                     g->seg_ptr, g->num_items, g->p0, p_scale, scale, scale_heads, in, out, out_row, accumulate, nt_in,  \
-                     contig)
-  switch (X / 4) {
-    case 1: HET_SS(1); break;
-    case 2: HET_SS(2); break;
-    case 4: HET_SS(4); break;
-    case 8: HET_SS(8); break;
-    case 16: HET_SS(16); break;
-    case 32: HET_SS(32); break;
-    default: HET_SS(64); break;
-  }
-#undef HET_SS
+  HET_DISPATCH_LPR(X / 4, hipLaunchKernelGGL(HET_segment_sum<LPR>, dim3(nb), dim3(kBlock), 0, s, g->item_seg, g->item_begin,
+                                            g->item_end, g->seg_ptr, g->num_items, g->p0, p_scale, scale, scale_heads, in, out,
+                                            out_row, accumulate, nt_in, contig));
   HET_LAUNCH_CHECK("HET_segment_sum");
   return HET_OK;
 }
 
 int launch_segment_sum_bf16(const het_grouping* g, const het_bf16* in, float* out, int X, const float* scale, hipStream_t s,
                             int scale_sorted) {
-  HET_REQUIRE(g->p0 && (X == 32 || X == 64) && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+  HET_REQUIRE(g->p0 && (X == 32 || X == 64) && aligned16(out),
               "segment sum (bf16 rows): unsupported shape or grouping, or out not 16-byte aligned");
   if (g->S == 0) return HET_OK;
   // the cooperative kernels of launch_segment_sum with its defaults (dense output, overwritten; one scale per row)
@@ -607,18 +591,8 @@ int launch_segment_broadcast(const het_grouping* g, const float* in, float* out,
   const int epw = 64 / (X / 4);
   int64_t nb = ceil_div64(g->E, (int64_t)(kBlock / 64) * epw * 4);
   if (nb > 256 * 64) nb = 256 * 64;
-#define HET_SB(L) hipLaunchKernelGGL(HET_segment_broadcast<L>, dim3((unsigned)nb), dim3(kBlock), 0, s, g->seg_of_rank, g->p0, \
-                                     g->E, in, out, in2, out2, X2)
-  switch (X / 4) {
-    case 1: HET_SB(1); break;
-    case 2: HET_SB(2); break;
-    case 4: HET_SB(4); break;
-    case 8: HET_SB(8); break;
-    case 16: HET_SB(16); break;
-    case 32: HET_SB(32); break;
-    default: HET_SB(64); break;
-  }
-#undef HET_SB
+  HET_DISPATCH_LPR(X / 4, hipLaunchKernelGGL(HET_segment_broadcast<LPR>, dim3((unsigned)nb), dim3(kBlock), 0, s, g->seg_of_rank,
+                                            g->p0, g->E, in, out, in2, out2, X2));
   HET_LAUNCH_CHECK("HET_segment_broadcast");
   return HET_OK;
 }

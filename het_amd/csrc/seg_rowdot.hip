@@ -5,7 +5,6 @@
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kChunk = 2048;  // rows of one relation per workgroup (upper bound)
 // rows per workgroup so that a short list (the S = 1-4 M distinct (relation, node) rows, not E = 21 M edges) still
 // gives every CU many waves: 1.5 M rows at 2048 per workgroup were 730 workgroups, 3 per CU
@@ -14,9 +13,6 @@ int chunk_for(int64_t num_rows) {
   while (c > 128 && num_rows / c < 8192) c >>= 1;
   return c;
 }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 constexpr int U = 4;  // rows per lane group and step; loads are issued in independent phases
 
@@ -149,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void HET_rowdot_bwd_dw(RowDotArgs a, int ch
       t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w;
     }
     float* p = a.out + (int64_t)r * HK + x;
-    atomicAdd(p + 0, t.x); atomicAdd(p + 1, t.y); atomicAdd(p + 2, t.z); atomicAdd(p + 3, t.w);
+    atomic_add4(p, t);
   }
 }
 
@@ -336,23 +332,10 @@ __global__ __launch_bounds__(kBlock) void HET_rowdot1h_bwd_dw(RowDotArgs a, int 
         o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
       }
       float* p = a.out + ((int64_t)r * H + h) * K + x;
-      atomicAdd(p + 0, o.x); atomicAdd(p + 1, o.y); atomicAdd(p + 2, o.z); atomicAdd(p + 3, o.w);
+      atomic_add4(p, o);
     }
   }
 }
-
-inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
-#define HET_ROWDOT_DISPATCH(LPRV, CALL)                 \
-  switch (LPRV) {                                       \
-    case 1: { constexpr int LPR = 1; CALL; break; }     \
-    case 2: { constexpr int LPR = 2; CALL; break; }     \
-    case 4: { constexpr int LPR = 4; CALL; break; }     \
-    case 8: { constexpr int LPR = 8; CALL; break; }     \
-    case 16: { constexpr int LPR = 16; CALL; break; }   \
-    case 32: { constexpr int LPR = 32; CALL; break; }   \
-    default: { constexpr int LPR = 64; CALL; break; }   \
-  }
 
 }  // namespace
 
@@ -364,7 +347,7 @@ int launch_rowdot_fwd(const RowDotArgs& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
   const int chunk = chunk_for(a.num_rows);
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
-  HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL(HET_rowdot_fwd<LPR>, grid, block, 0, s, a, chunk));
+  HET_DISPATCH_LPR(a.H * a.K / 4, hipLaunchKernelGGL(HET_rowdot_fwd<LPR>, grid, block, 0, s, a, chunk));
   HET_LAUNCH_CHECK("HET_rowdot_fwd");
   return HET_OK;
 }
@@ -374,11 +357,11 @@ int launch_rowdot_bwd_dx(const RowDotArgs& a, hipStream_t s) {
   const int chunk = chunk_for(a.num_rows);
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
   if (a.unique_rows && a.overwrite) {
-    HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 2>), grid, block, 0, s, a, chunk));
+    HET_DISPATCH_LPR(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 2>), grid, block, 0, s, a, chunk));
   } else if (a.unique_rows) {
-    HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 1>), grid, block, 0, s, a, chunk));
+    HET_DISPATCH_LPR(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 1>), grid, block, 0, s, a, chunk));
   } else {
-    HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 0>), grid, block, 0, s, a, chunk));
+    HET_DISPATCH_LPR(a.H * a.K / 4, hipLaunchKernelGGL((HET_rowdot_bwd_dx<LPR, 0>), grid, block, 0, s, a, chunk));
   }
   HET_LAUNCH_CHECK("HET_rowdot_bwd_dx");
   return HET_OK;
@@ -394,7 +377,7 @@ int launch_rowdot_bwd_dw(const RowDotArgs& a, hipStream_t s) {
   int64_t chunk = ceil_div64(a.num_rows, kDwWgs);
   if (chunk < kDwMinChunk) chunk = kDwMinChunk;
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
-  HET_ROWDOT_DISPATCH(a.H * a.K / 4, hipLaunchKernelGGL(HET_rowdot_bwd_dw<LPR>, grid, block, 0, s, a, (int)chunk));
+  HET_DISPATCH_LPR(a.H * a.K / 4, hipLaunchKernelGGL(HET_rowdot_bwd_dw<LPR>, grid, block, 0, s, a, (int)chunk));
   HET_LAUNCH_CHECK("HET_rowdot_bwd_dw");
   return HET_OK;
 }
@@ -405,10 +388,10 @@ bool rowdot1h_supported(int H, int K) {
 
 #define HET_ROWDOT1H_DISPATCH(KERNEL, ...)                                                           \
   switch (a.H) {                                                                                     \
-    case 1: HET_ROWDOT_DISPATCH(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 1>), grid, block, 0, s, __VA_ARGS__)); break; \
-    case 2: HET_ROWDOT_DISPATCH(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 2>), grid, block, 0, s, __VA_ARGS__)); break; \
-    case 4: HET_ROWDOT_DISPATCH(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 4>), grid, block, 0, s, __VA_ARGS__)); break; \
-    default: HET_ROWDOT_DISPATCH(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 8>), grid, block, 0, s, __VA_ARGS__)); break; \
+    case 1: HET_DISPATCH_LPR(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 1>), grid, block, 0, s, __VA_ARGS__)); break; \
+    case 2: HET_DISPATCH_LPR(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 2>), grid, block, 0, s, __VA_ARGS__)); break; \
+    case 4: HET_DISPATCH_LPR(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 4>), grid, block, 0, s, __VA_ARGS__)); break; \
+    default: HET_DISPATCH_LPR(a.K / 4, hipLaunchKernelGGL((KERNEL<LPR, 8>), grid, block, 0, s, __VA_ARGS__)); break; \
   }
 
 int launch_rowdot1h_fwd(const RowDotArgs& a, hipStream_t s) {
@@ -424,7 +407,7 @@ int launch_rowdot1h_bwd_dx(const RowDotArgs& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
   const int chunk = chunk_for(a.num_rows);
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
-  const bool vec = ((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.go) | reinterpret_cast<uintptr_t>(a.W)) & 15) == 0;
+  const bool vec = aligned16(a.out, a.go, a.W);
   if (a.rmw && vec) {
     HET_ROWDOT1H_DISPATCH(HET_rowdot1h_bwd_dx_rmw, a, chunk)
   } else {

@@ -28,7 +28,7 @@ def ladder():
 
 
 # ---------------------------------------------------------------- RGAT compact passes
-# every (lanes per row, lanes per head) pair of HET_DISPATCH_COOP / HET_DISPATCH_COOP_G (coop_shape_ok, gat_coop_shape): rows of
+# every (lanes per row, lanes per head) pair of HET_DISPATCH_COOP (coop_shape_ok, coop.hip.h; both GAT files launch through it): rows of
 # 32 / 64 / 128 floats, heads of 16 .. 128; D = 16 also runs the forward with el formed from the row (kElMaxRels) and the attention
 # gradient in the backward pass
 RUN_SHAPES = [(2, 16), (1, 32), (4, 16), (2, 32), (1, 64), (8, 16), (4, 32), (2, 64), (1, 128)]
@@ -53,7 +53,7 @@ def test_rgat_ladder_compact_passes(K, ladder, H, D):
 
 
 # ---------------------------------------------------------------- fused GAT, reference-named op
-# the grouped kernels: HET_DISPATCH_LPR 1 .. 64 and every pair of HET_DISPATCH_COOP_G; (3, 5): the edge kernels
+# the grouped kernels: HET_DISPATCH_LPR 1 .. 64 and every pair of HET_DISPATCH_COOP; (3, 5): the edge kernels
 GAT_ALL_LPR = LPR_SHAPES + RUN_SHAPES + [(3, 5)]
 
 
