@@ -57,6 +57,12 @@ _SIGNATURES = {
     "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_hgt_aggregate_compact": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
     "het_hgt_backward_compact": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_aggregate_compact_bf16": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_backward_compact_bf16": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_rows_matmul_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
+    "het_rows_matmul_backward_dw_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
+    "het_rows_matmul_backward_dw_bf16_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
+    "het_node_rows_matmul_sum_bf16": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
     "het_rgcn_layer1_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, I64, I64, P, P, I64, P],
     "het_backward_rgcn_layer1_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P, I64, P],
     "het_rgcn_node_mean_aggregation_compact_as_of_node_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P, I64, INT, P, P],

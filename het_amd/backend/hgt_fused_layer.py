@@ -170,6 +170,10 @@ class HgtAttentionFunction(th.autograd.Function):
         ss = G.get_separate_unique_node_indices_single_sided()
         rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
         S_row = rows_node.numel()
+        bf16 = h.dtype == th.bfloat16  # activation rows (h, kv_c, q, out) bf16; lsum and every parameter fp32 (hgt_layer_fused)
+        if bf16 and not (_k.rows_matmul_bf16_ok(K_in, 2 * X) and _k.rows_matmul_backward_split_ok(1, K_in, 2 * X)
+                         and _k.rows_matmul_backward_split_ok(1, K_in, X)):  # (hgt_layer_fused sends such shapes through fp32)
+            raise _k._lib.HetError(f"HgtAttentionFunction: no bf16 kernels for input width {K_in} and row width {X} (hgt_bf16_native_ok)")
         new = lambda *shape: th.empty(shape, dtype=h.dtype, device=h.device)
         # the destination-side projection beside the source-row one (rgat_fused_layer._side_stream: independent launches, the
         # tensors are allocated and freed under the main stream)
@@ -185,20 +189,25 @@ class HgtAttentionFunction(th.autograd.Function):
         if side is not None:
             side.wait_stream(main)
         with th.cuda.stream(side if side is not None else main):
-            if dst is None:
+            if bf16:
+                _k.rows_matmul_bf16(offs if dst is None else run_ptrs, None if dst is None else dst_nodes, None, q_w, h, q.view(ND, X))
+            elif dst is None:
                 K.rgnn_relational_matmul_no_scatter_gather_list(offs, q_w, h, q)
             else:
                 K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": run_ptrs, "unique_srcs_and_dests_node_indices": dst_nodes},
                                          1, q_w, h, q, True)
         q = q.view(ND, X)
-        K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": rp_row, "unique_srcs_and_dests_node_indices": rows_node},
-                                 1, w_kv, h, kv_c, True)
+        if bf16:
+            _k.rows_matmul_bf16(rp_row, rows_node, None, w_kv, h, kv_c.view(S_row, 2 * X))
+        else:
+            K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": rp_row, "unique_srcs_and_dests_node_indices": rows_node},
+                                     1, w_kv, h, kv_c, True)
         if side is not None:
             main.wait_stream(side)
         srow, _ = _edge_rows(G, ss, True, s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"])
         grp = _k.hgt_compact_groupings(keys, srow, ND, S_row)
-        lsum, out = new(ND, H), new(ND, X)
-        _k.hgt_aggregate_compact(grp, kv_c, q, lsum, out)
+        lsum, out = th.empty((ND, H), dtype=th.float32, device=h.device), new(ND, X)
+        (_k.hgt_aggregate_compact_bf16 if bf16 else _k.hgt_aggregate_compact)(grp, kv_c, q, lsum, out)
         ctx.G, ctx.H, ctx.grp, ctx.compact_dst = G, H, grp, dst is not None
         ctx.save_for_backward(h, w_kv, q_w, offs, q, kv_c, lsum, out, *(() if dst is None else (dst[0], dst[2])))
         return out
@@ -212,8 +221,12 @@ class HgtAttentionFunction(th.autograd.Function):
         ss = G.get_separate_unique_node_indices_single_sided()
         rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
         grad_out = grad_out.contiguous()
-        g_kv, g_q = th.empty_like(kv_c), th.empty_like(q)
-        _k.hgt_backward_compact(ctx.grp, kv_c, q, lsum, out, grad_out, g_kv, g_q)
+        bf16 = h.dtype == th.bfloat16
+        # sums over edges, hub rows met by float atomics, streamed once into the fp32 parameter gradients: fp32 for either row type
+        g_kv, g_q = th.empty_like(kv_c, dtype=th.float32), th.empty_like(q, dtype=th.float32)
+        (_k.hgt_backward_compact_bf16 if bf16 else _k.hgt_backward_compact)(ctx.grp, kv_c, q, lsum, out, grad_out, g_kv, g_q)
+        rows_dw = _k.rows_matmul_backward_dw_bf16 if bf16 else _k.rows_matmul_backward_dw
+        node_sum = _k.node_rows_matmul_sum_bf16 if bf16 else _k.node_rows_matmul_sum
         # one input-gradient buffer for both consumers of h
         qwt = q_w.transpose(2, 3).contiguous()
         wt = w_kv.transpose(2, 3).contiguous()
@@ -224,7 +237,7 @@ class HgtAttentionFunction(th.autograd.Function):
         if side is not None and split_kv:
             side.wait_stream(main)
             with th.cuda.stream(side):
-                _k.rows_matmul_backward_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
+                rows_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
         nplan = _node_dx_plan(G, ss, offs, K_in, X, (lists[0], None, lists[1]) if ctx.compact_dst else None) if split_kv else None
         if nplan is not None:
             # every consumer of h adds its term in ONE pass over the nodes (csrc/node_sum.hip) -- instead of one read-modify-write
@@ -242,11 +255,11 @@ class HgtAttentionFunction(th.autograd.Function):
                 side.wait_stream(main)
             with th.cuda.stream(side if side is not None else main):  # the other two weight gradients beside the node pass
                 if side is None:
-                    _k.rows_matmul_backward_dw(rp_row, rows_node, h, g_kv2, grad_wkv, accumulate=False)
+                    rows_dw(rp_row, rows_node, h, g_kv2, grad_wkv, accumulate=False)
                 if ctx.compact_dst:
-                    _k.rows_matmul_backward_dw(lists[1], lists[0], h, g_q2, grad_qw, accumulate=False)
+                    rows_dw(lists[1], lists[0], h, g_q2, grad_qw, accumulate=False)
                 else:
-                    _k.rows_matmul_backward_dw(offs, None, h, g_q2, grad_qw, accumulate=False)
+                    rows_dw(offs, None, h, g_q2, grad_qw, accumulate=False)
             for t, rels in enumerate(nplan["rels_of"]):
                 a, b = nplan["offs"][t], nplan["offs"][t + 1]
                 srcs = []
@@ -258,10 +271,27 @@ class HgtAttentionFunction(th.autograd.Function):
                 if not srcs:
                     grad_h[a:b].zero_()  # (a node type that neither sends nor receives: its rows of the gradient are zero)
                 elif b > a:
-                    _k.node_rows_matmul_sum(a, b, srcs, grad_h, nplan["order"])
+                    node_sum(a, b, srcs, grad_h, nplan["order"])
             if side is not None:
                 main.wait_stream(side)
             return None, None, None, grad_h, grad_wkv, grad_qw, None
+        if bf16:
+            # more relations per node type than the node-major pass keeps in LDS: the per-relation launches add a node's terms in an
+            # fp32 buffer, which is rounded once (the only fp32 [N, in] tensor of the bf16 step; h itself is never widened)
+            rp_q, rows_q = (lists[1], lists[0]) if ctx.compact_dst else (offs, None)
+            grad_h32 = (th.zeros if ctx.compact_dst else th.empty)(h.shape, dtype=th.float32, device=h.device)
+            grad_qw = th.empty_like(q_w)
+            if side is not None:
+                side.wait_stream(main)  # (grad_qw was allocated after the first fork: see the node-major branch)
+            with th.cuda.stream(side if side is not None else main):
+                if side is None:
+                    rows_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
+                rows_dw(rp_q, rows_q, h, g_q.view(-1, X), grad_qw, accumulate=False)
+            _k.rows_matmul_backward_dx(rp_q, rows_q, qwt, g_q.view(-1, X), grad_h32, atomic=False)
+            _k.rows_matmul_backward_dx(rp_row, rows_node, wt, g_kv.view(-1, 2 * X), grad_h32, atomic=2)
+            if side is not None:
+                main.wait_stream(side)
+            return None, None, None, grad_h32.to(th.bfloat16), grad_wkv, grad_qw, None
         if not ctx.compact_dst:  # the typed projection writes every row with plain stores, the source-row GEMM adds to it
             grad_h, grad_qw = th.empty_like(h), th.empty_like(q_w)
             _k.matmul_no_scatter_gather_backward(offs, qwt, h, g_q, grad_h, grad_qw, accumulate=False)
@@ -322,10 +352,60 @@ class RowsLinearScatter(th.autograd.Function):
         return None, None, None, g_x.view_as(x_c), g_wt.transpose(2, 3)
 
 
+class RowsLinearBf16(th.autograd.Function):
+    """The typed output projection with bf16 rows: out[rows[i], :] = x[i, :] . w[t(i)] (``rows`` None: row i), zero elsewhere.  x, out
+    and their gradients bf16 (each rounded once at its kernel's store), ``w`` [T,1,K,X] and its gradient fp32; ``run_ptrs`` [T+1]
+    splits the rows into the runs of ``w``."""
+
+    @staticmethod
+    def forward(ctx, run_ptrs, rows, num_out_rows, x, w):
+        x, w = x.contiguous(), w.contiguous()
+        alloc = th.empty if rows is None else th.zeros
+        out = alloc((num_out_rows, w.shape[3]), dtype=th.bfloat16, device=x.device)
+        _k.rows_matmul_bf16(run_ptrs, None, rows, w, x, out)
+        ctx.save_for_backward(run_ptrs, x, w, *(() if rows is None else (rows,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        run_ptrs, x, w, *rows = ctx.saved_tensors
+        rows = rows[0] if rows else None
+        grad_out = grad_out.contiguous()
+        g_x, g_w = th.empty_like(x), th.empty_like(w)
+        main, side = th.cuda.current_stream(x.device), (_side_stream(x.device) if OVERLAP else None)
+        if side is not None:  # (forked after the allocations above: HgtAttentionFunction.backward says why)
+            side.wait_stream(main)
+        with th.cuda.stream(side if side is not None else main):
+            _k.rows_matmul_backward_dw_bf16(run_ptrs, None, x, grad_out, g_w, accumulate=False, g_rows=rows)
+        _k.rows_matmul_bf16(run_ptrs, rows, None, w.transpose(2, 3).contiguous(), grad_out, g_x)  # g_x[i] = grad_out[rows[i]] . w[t]^T
+        if side is not None:
+            main.wait_stream(side)
+        return None, None, None, g_x, g_w
+
+
+def hgt_bf16_native_ok(G, K_in, num_heads, d_k, proj_in, out_dim):
+    """Whether a bf16 layer input runs on the bf16 kernels: a full graph (one run per node type), input width and row width
+    X = H * d_pad (heads zero-padded to a power of two >= 8) both 32 or 64, one head group, and an output projection of
+    ``proj_in`` = H * d_k -> ``out_dim`` columns with both in {32, 64}.  Everything else runs fp32 on an upcast copy."""
+    d_pad = _padded_head(d_k)
+    X = num_heads * d_pad
+    if G.graph_data["original"].get("node_segment_types") is not None:
+        return False
+    if not (X in (32, 64) and K_in in (32, 64) and _head_groups(num_heads, d_pad) == 1):
+        return False
+    if not (_k.rows_matmul_bf16_ok(K_in, 2 * X) and _k.rows_matmul_bf16_ok(proj_in, out_dim) and _k.rows_matmul_bf16_ok(out_dim, proj_in)):
+        return False
+    return _k.rows_matmul_backward_split_ok(1, K_in, 2 * X) and _k.rows_matmul_backward_split_ok(1, K_in, X)
+
+
 def hgt_layer_fused(G, h, offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pri, num_heads, fused_attn):
     """The HGT layer [N, out]: attention + aggregation as one node, then the typed output projection ``a_w`` [T,1,X,out] (one
     weight per run of offs; the caller folds sigmoid(skip) in) -- on the destinations with in-edges only when those are a
     minority of the nodes (the other rows of the output are zero by construction)."""
+    bf16 = h.dtype == th.bfloat16
+    if bf16 and not hgt_bf16_native_ok(G, h.shape[1], num_heads, q_w.shape[3] // num_heads, a_w.shape[2], a_w.shape[3]):
+        # graphs and shapes without bf16 kernels: the fp32 path on an upcast copy, one final rounding; autograd casts the gradient back
+        return hgt_layer_fused(G, h.float(), offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pri, num_heads, fused_attn).to(th.bfloat16)
     if not _has_single_sided_lists(G):
         G.generate_separate_unique_node_indices_single_sided_for_each_etype()
     st, _ = G.get_rel_node_types()
@@ -338,6 +418,15 @@ def hgt_layer_fused(G, h, offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pr
     col = G.get_separate_coo_original()["col_indices"]
     dst = _k.destination_lists(col, offs)
     groups = _head_groups(num_heads, d_pad)
+    compact = dst[0].numel() < COMPACT_DST_BELOW * N
+    if bf16:
+        # bf16 activations: h, kv_c, q, new_h, the output and their gradients are bf16 rows, each rounded once where its kernel stores it;
+        # the parameters, the folded w_kv, lsum, grad_kv_c / grad_q and every parameter gradient stay fp32 (padded head columns are
+        # dropped with torch ops: dtype-agnostic)
+        new_h = unpad(HgtAttentionFunction.apply(G, num_heads, offs, h, w_kv, q_w, dst if compact else None))
+        if compact:
+            return RowsLinearBf16.apply(dst[2], dst[0], N, new_h, a_w)
+        return RowsLinearBf16.apply(offs, None, N, new_h, a_w)
 
     def attention(dst_lists):
         if groups == 1:
@@ -350,7 +439,7 @@ def hgt_layer_fused(G, h, offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pr
             parts.append(HgtAttentionFunction.apply(G, Hg, offs, h, w_g, q_w[..., i * Xg:(i + 1) * Xg].contiguous(), dst_lists))
         return th.cat(parts, dim=1)
 
-    if dst[0].numel() >= COMPACT_DST_BELOW * N:
+    if not compact:
         new_h = unpad(attention(None))
         return B_matmul_no_scatter_gather(offs, a_w, new_h)
     new_h_c = unpad(attention(dst))

@@ -45,10 +45,10 @@ __device__ __forceinline__ int quad_bcast(int v, int q) {  // value of lane q of
 
 // Forward: wave per destination work item, the 64/LPR lane groups take its edges round-robin, U = 4 rows per group in
 // flight, the ids of the next step prefetched.
-template <int LPR, int DL>
+template <int LPR, int DL, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_hgt_aggregate_rows(Items it, const int32_t* __restrict__ p_srow,
-                                                                  const float* __restrict__ kv, const float* __restrict__ q,
-                                                                  float* __restrict__ lsum, float* __restrict__ out, int H,
+                                                                  const T* __restrict__ kv, const T* __restrict__ q,
+                                                                  float* __restrict__ lsum, T* __restrict__ out, int H,
                                                                   float* __restrict__ part) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4;
   static_assert(DL <= LPR, "heads inside the lane group");  // (LPR >= 4: ids shared by quads; LPR == 2: every lane loads its ids)
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_aggregate_rows(Items it, const
   }
   const int64_t v = it.seg_key[seg];
   const bool whole = b == it.seg_ptr[seg] && e == it.seg_ptr[seg + 1];
-  const float4 q4 = ld4(q + v * X + x);
+  const float4 q4 = ldrow4(q + v * X + x);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   // softmax relative to a running maximum of the scores (the reference exponentiates the raw score, HGT/models.py via
   // hgt_full_graph_edge_softmax_ops: exp(score * mu) -- finite only while |score| < 88): rescale when it grows, keep
@@ -79,9 +79,9 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_aggregate_rows(Items it, const
     for (int u = 0; u < U; ++u) {
       int sid;
       if constexpr (LPR >= 4) sid = quad_bcast(sidn[0], u); else sid = sidn[u];
-      const float* rowp = kv + (int64_t)sid * (2 * X) + x;
-      kk[u] = ld4(rowp);
-      mm[u] = ld4(rowp + X);
+      const T* rowp = kv + (int64_t)sid * (2 * X) + x;
+      kk[u] = ldrow4(rowp);
+      mm[u] = ldrow4(rowp + X);
     }
     if constexpr (LPR >= 4) {
       const int jn = j0 + (U + qd) * EPW < e ? j0 + (U + qd) * EPW : e - 1;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_aggregate_rows(Items it, const
   if (slot != 0) return;
   if (whole) {
     const float inv = 1.f / ssum;
-    st4(out + v * X + x, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
+    strow4(out + v * X + x, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
     if (d == 0) lsum[v * H + h] = m + __logf(ssum);
   } else {  // a piece of a hub destination: parked {acc[X], max[H], sum[H]} for HET_hgt_finish_split
     float* pp = part + item * (X + 2 * H);
@@ -133,10 +133,10 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_aggregate_rows(Items it, const
 }
 
 // One wave per split (hub) destination: its work items' parked partial sums brought to the common maximum, divided, stored.
-template <int LPR>
+template <int LPR, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_hgt_finish_split(const int32_t* __restrict__ split_seg, int64_t num_split, Items it,
                                                                 const float* __restrict__ part, float* __restrict__ lse,
-                                                                float* __restrict__ out, int H, int D) {
+                                                                T* __restrict__ out, int H, int D) {
   constexpr int EPW = 64 / LPR;
   const int lane = threadIdx.x & 63, slot = lane / LPR, x = (lane % LPR) * 4, h = x / D;
   const int64_t k = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_finish_split(const int32_t* __
   }
   if (slot != 0) return;
   const float inv = 1.f / ssum;
-  st4(out + v * X + x, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
+  strow4(out + v * X + x, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
   if (x % D == 0) lse[v * H + h] = M + __logf(ssum);
 }
 
@@ -204,11 +204,11 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_normalize_rows(const int32_t* 
 }
 
 // Backward, destination side: same schedule as the forward.
-template <int LPR, int DL>
+template <int LPR, int DL, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_hgt_backward_dst_rows(Items it, const int32_t* __restrict__ p_srow,
-                                                                     const float* __restrict__ kv, const float* __restrict__ q,
-                                                                     const float* __restrict__ lsum, const float* __restrict__ out,
-                                                                     const float* __restrict__ gradout, float* __restrict__ grad_q,
+                                                                     const T* __restrict__ kv, const T* __restrict__ q,
+                                                                     const float* __restrict__ lsum, const T* __restrict__ out,
+                                                                     const T* __restrict__ gradout, float* __restrict__ grad_q,
                                                                      float* __restrict__ pack2, int H) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4;
   static_assert(DL <= LPR, "heads inside the lane group");  // (LPR >= 4: ids shared by quads; LPR == 2: every lane loads its ids)
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_dst_rows(Items it, co
   }
   const int64_t v = it.seg_key[seg];
   const bool whole = b == it.seg_ptr[seg] && e == it.seg_ptr[seg + 1];
-  const float4 q4 = ld4(q + v * X + x), go = ld4(gradout + v * X + x), o4 = ld4(out + v * X + x);
+  const float4 q4 = ldrow4(q + v * X + x), go = ldrow4(gradout + v * X + x), o4 = ldrow4(out + v * X + x);
   const float lse_v = lsum[v * H + h];  // log-sum-exp of the destination (forward)
   const float dotn = head_sum<DL>(dot4(go, o4));
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -237,9 +237,9 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_dst_rows(Items it, co
     for (int u = 0; u < U; ++u) {
       int sid;
       if constexpr (LPR >= 4) sid = quad_bcast(sidn[0], u); else sid = sidn[u];
-      const float* rowp = kv + (int64_t)sid * (2 * X) + x;
-      kk[u] = ld4(rowp);
-      mm[u] = ld4(rowp + X);
+      const T* rowp = kv + (int64_t)sid * (2 * X) + x;
+      kk[u] = ldrow4(rowp);
+      mm[u] = ldrow4(rowp + X);
     }
     if constexpr (LPR >= 4) {
       const int jn = j0 + (U + qd) * EPW < e ? j0 + (U + qd) * EPW : e - 1;
@@ -271,11 +271,11 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_dst_rows(Items it, co
 }
 
 // Backward, source side, SHORT segments: lane group per pack of whole (relation, source) segments.
-template <int LPR, int DL>
+template <int LPR, int DL, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_short(Packs pk, const int4* __restrict__ kp01,
-                                                                      const float* __restrict__ kv, const float* __restrict__ q,
+                                                                      const T* __restrict__ kv, const T* __restrict__ q,
                                                                       const float* __restrict__ pack2,
-                                                                      const float* __restrict__ gradout,
+                                                                      const T* __restrict__ gradout,
                                                                       float* __restrict__ grad_kv, int H) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4;
   static_assert(DL <= LPR, "heads inside the lane group");  // (LPR >= 4: ids shared by quads; LPR == 2: every lane loads its ids)
@@ -308,8 +308,8 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_short(Packs pk, c
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t dv = dsti[u];
-      qr[u] = ld4(q + dv * X + x);
-      gr[u] = ld4(gradout + dv * X + x);
+      qr[u] = ldrow4(q + dv * X + x);
+      gr[u] = ldrow4(gradout + dv * X + x);
       p2[u] = *reinterpret_cast<const float2*>(pack2 + (dv * H + h) * 2);
     }
 #pragma unroll
@@ -317,9 +317,9 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_short(Packs pk, c
       kq[u] = zero;
       mq[u] = zero;
       if (j0 + u < e && key[u] != (u == 0 ? prev_key : key[u - 1])) {
-        const float* rowp = kv + (int64_t)key[u] * (2 * X) + x;
-        kq[u] = ld4(rowp);
-        mq[u] = ld4(rowp + X);
+        const T* rowp = kv + (int64_t)key[u] * (2 * X) + x;
+        kq[u] = ldrow4(rowp);
+        mq[u] = ldrow4(rowp + X);
       }
     }
     int key_after;
@@ -357,12 +357,12 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_short(Packs pk, c
 }
 
 // Backward, source side, LONG segments: wave per work item (<= HET_ITEM_MAX edges of one source row).
-template <int LPR, int DL>
+template <int LPR, int DL, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_long(Items it, const int32_t* __restrict__ long_items,
                                                                      int64_t num_long_items, const int32_t* __restrict__ p_dst,
-                                                                     const float* __restrict__ kv, const float* __restrict__ q,
+                                                                     const T* __restrict__ kv, const T* __restrict__ q,
                                                                      const float* __restrict__ pack2,
-                                                                     const float* __restrict__ gradout,
+                                                                     const T* __restrict__ gradout,
                                                                      float* __restrict__ grad_kv, int H) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4;
   static_assert(DL <= LPR, "heads inside the lane group");  // (LPR >= 4: ids shared by quads; LPR == 2: every lane loads its ids)
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_long(Items it, co
   }
   const int64_t u = it.seg_key[seg];
   const bool whole = b == it.seg_ptr[seg] && e == it.seg_ptr[seg + 1];
-  const float4 kcur = ld4(kv + u * (2 * X) + x), mcur = ld4(kv + u * (2 * X) + X + x);
+  const float4 kcur = ldrow4(kv + u * (2 * X) + x), mcur = ldrow4(kv + u * (2 * X) + X + x);
   float4 acck = make_float4(0.f, 0.f, 0.f, 0.f), accm = acck;
   for (int j0 = b + slot; j0 < e; j0 += EPW * U) {
     float4 qr[U], gr[U];
@@ -390,8 +390,8 @@ __global__ __launch_bounds__(kBlock) void HET_hgt_backward_src_long(Items it, co
     for (int t = 0; t < U; ++t) {
       int64_t dv;
       if constexpr (LPR >= 4) dv = quad_bcast(dstn[0], t); else dv = dstn[t];
-      qr[t] = ld4(q + dv * X + x);
-      gr[t] = ld4(gradout + dv * X + x);
+      qr[t] = ldrow4(q + dv * X + x);
+      gr[t] = ldrow4(gradout + dv * X + x);
       p2[t] = *reinterpret_cast<const float2*>(pack2 + (dv * H + h) * 2);
     }
     if constexpr (LPR >= 4) {
@@ -464,10 +464,13 @@ extern "C" int64_t het_hgt_aggregate_compact_workspace(const het_grouping* by_ds
   return (int64_t)sizeof(float) * by_dst->num_items * (H * D + 2 * H);
 }
 
-extern "C" int het_hgt_aggregate_compact(const het_grouping* by_dst, const float* kv_c, const float* q, float* lsum, float* out,
-                                         int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
-                                         int64_t workspace_bytes, het_stream stream) {
-  const char* op = "het_hgt_aggregate_compact";
+namespace {
+// T: the element type of the gathered rows (kv_c, q) and of out -- float, or het_bf16 (widened on load, out rounded once at its
+// store); lsum, the hub records of the workspace and every sum are fp32
+template <typename T>
+int hgt_aggregate_compact(const char* op, const het_grouping* by_dst, const T* kv_c, const T* q, float* lsum, T* out,
+                          int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace, int64_t workspace_bytes,
+                          het_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   HET_REQUIRE(by_dst && lsum && out && num_nodes >= 0, "%s: null argument", op);
   if (!hgt_rows_shape_ok(H, D)) { het_set_error("%s: unsupported shape H=%lld D=%lld", op, (long long)H, (long long)D); return HET_ERR_UNSUPPORTED; }
@@ -476,9 +479,10 @@ extern "C" int het_hgt_aggregate_compact(const het_grouping* by_dst, const float
   const int64_t need = het_hgt_aggregate_compact_workspace(by_dst, H, D);
   HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_hgt_aggregate_compact_workspace)", op, (long long)need);
+  HET_REQUIRE(aligned16(kv_c, q, out), "%s: kv_c, q and out must be 16-byte aligned", op);
   const int64_t X = H * D;
   HET_HIP(hipMemsetAsync(lsum, 0, sizeof(float) * num_nodes * H, s));
-  if (by_dst->S != num_nodes) HET_HIP(hipMemsetAsync(out, 0, sizeof(float) * num_nodes * X, s));  // destinations without in-edges: zero rows
+  if (by_dst->S != num_nodes) HET_HIP(hipMemsetAsync(out, 0, sizeof(T) * num_nodes * X, s));  // destinations without in-edges: zero rows
   if (by_dst->E == 0) return HET_OK;
   const Items it = items_of(by_dst);
   const unsigned nb = (unsigned)ceil_div64(by_dst->num_items, kBlock / 64);
@@ -486,33 +490,49 @@ extern "C" int het_hgt_aggregate_compact(const het_grouping* by_dst, const float
   {
     HET_KTIME("HET_hgt_aggregate_rows", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),
-                          hipLaunchKernelGGL((HET_hgt_aggregate_rows<LPR, DL>), dim3(nb), dim3(kBlock), 0, s, it, by_dst->p0, kv_c,
+                          hipLaunchKernelGGL((HET_hgt_aggregate_rows<LPR, DL, T>), dim3(nb), dim3(kBlock), 0, s, it, by_dst->p0, kv_c,
                                              q, lsum, out, (int)H, part));
   }
   HET_LAUNCH_CHECK("HET_hgt_aggregate_rows");
   if (by_dst->num_split > 0) {
     const unsigned nbs = (unsigned)ceil_div64(by_dst->num_split, kBlock / 64);
     switch ((int)(X / 4)) {
-      case 2: hipLaunchKernelGGL(HET_hgt_finish_split<2>, dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
-      case 4: hipLaunchKernelGGL(HET_hgt_finish_split<4>, dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
-      case 8: hipLaunchKernelGGL(HET_hgt_finish_split<8>, dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
-      case 16: hipLaunchKernelGGL(HET_hgt_finish_split<16>, dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
-      default: hipLaunchKernelGGL(HET_hgt_finish_split<32>, dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
+      case 2: hipLaunchKernelGGL((HET_hgt_finish_split<2, T>), dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
+      case 4: hipLaunchKernelGGL((HET_hgt_finish_split<4, T>), dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
+      case 8: hipLaunchKernelGGL((HET_hgt_finish_split<8, T>), dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
+      case 16: hipLaunchKernelGGL((HET_hgt_finish_split<16, T>), dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
+      default: hipLaunchKernelGGL((HET_hgt_finish_split<32, T>), dim3(nbs), dim3(kBlock), 0, s, by_dst->split_seg, by_dst->num_split, it, part, lsum, out, (int)H, (int)D); break;
     }
     HET_LAUNCH_CHECK("HET_hgt_finish_split");
   }
   return HET_OK;
+}
+}  // namespace
+
+extern "C" int het_hgt_aggregate_compact(const het_grouping* by_dst, const float* kv_c, const float* q, float* lsum, float* out,
+                                         int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
+                                         int64_t workspace_bytes, het_stream stream) {
+  return hgt_aggregate_compact("het_hgt_aggregate_compact", by_dst, kv_c, q, lsum, out, num_nodes, num_src_rows, H, D, workspace,
+                               workspace_bytes, stream);
+}
+
+extern "C" int het_hgt_aggregate_compact_bf16(const het_grouping* by_dst, const het_bf16* kv_c, const het_bf16* q, float* lsum,
+                                              het_bf16* out, int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D,
+                                              void* workspace, int64_t workspace_bytes, het_stream stream) {
+  return hgt_aggregate_compact("het_hgt_aggregate_compact_bf16", by_dst, kv_c, q, lsum, out, num_nodes, num_src_rows, H, D, workspace,
+                               workspace_bytes, stream);
 }
 
 extern "C" int64_t het_hgt_backward_compact_workspace(int64_t num_nodes, int64_t H) {
   return (int64_t)sizeof(float) * ((num_nodes * 2 * H + 3) / 4 * 4);
 }
 
-extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_grouping* by_srow, const float* kv_c, const float* q,
-                                        const float* lsum, const float* out, const float* gradout, float* grad_kv_c, float* grad_q,
-                                        int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
-                                        int64_t workspace_bytes, het_stream stream) {
-  const char* op = "het_hgt_backward_compact";
+namespace {
+// T: the element type of kv_c, q, out and gradout (the rows gathered per edge); grad_kv_c, grad_q, lsum and the workspace are fp32
+template <typename T>
+int hgt_backward_compact(const char* op, const het_grouping* by_dst, const het_grouping* by_srow, const T* kv_c, const T* q,
+                         const float* lsum, const T* out, const T* gradout, float* grad_kv_c, float* grad_q, int64_t num_nodes,
+                         int64_t num_src_rows, int64_t H, int64_t D, void* workspace, int64_t workspace_bytes, het_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   HET_REQUIRE(by_dst && by_srow && lsum && out && gradout && grad_kv_c && grad_q, "%s: null argument", op);
   if (!hgt_rows_shape_ok(H, D)) { het_set_error("%s: unsupported shape H=%lld D=%lld", op, (long long)H, (long long)D); return HET_ERR_UNSUPPORTED; }
@@ -524,6 +544,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
   const int64_t need = het_hgt_backward_compact_workspace(num_nodes, H);
   HET_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_hgt_backward_compact_workspace)", op, (long long)need);
+  HET_REQUIRE(aligned16(kv_c, q, out, gradout, grad_kv_c, grad_q), "%s: row tensors must be 16-byte aligned", op);
   float* pack2 = (float*)workspace;  // [N, H, 2]
   if (by_dst->S != num_nodes) {
     HET_HIP(hipMemsetAsync(grad_q, 0, sizeof(float) * num_nodes * X, s));
@@ -545,7 +566,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
     const unsigned nb = (unsigned)ceil_div64(by_dst->num_items, kBlock / 64);
     HET_KTIME("HET_hgt_backward_dst_rows", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),
-                          hipLaunchKernelGGL((HET_hgt_backward_dst_rows<LPR, DL>), dim3(nb), dim3(kBlock), 0, s, it, by_dst->p0,
+                          hipLaunchKernelGGL((HET_hgt_backward_dst_rows<LPR, DL, T>), dim3(nb), dim3(kBlock), 0, s, it, by_dst->p0,
                                              kv_c, q, lsum, out, gradout, grad_q, pack2, (int)H));
   }
   HET_LAUNCH_CHECK("HET_hgt_backward_dst_rows");
@@ -555,7 +576,7 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
     const unsigned nb = (unsigned)ceil_div64(by_srow->num_packs, (int64_t)(kBlock / 64) * (64 / (X / 4)));
     HET_KTIME("HET_hgt_backward_src_short", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),
-                          hipLaunchKernelGGL((HET_hgt_backward_src_short<LPR, DL>), dim3(nb), dim3(kBlock), 0, s, pk, by_srow->kp01,
+                          hipLaunchKernelGGL((HET_hgt_backward_src_short<LPR, DL, T>), dim3(nb), dim3(kBlock), 0, s, pk, by_srow->kp01,
                                              kv_c, q, pack2, gradout, grad_kv_c, (int)H));
   }
   HET_LAUNCH_CHECK("HET_hgt_backward_src_short");
@@ -564,10 +585,27 @@ extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_gr
     const unsigned nbl = (unsigned)ceil_div64(by_srow->num_long_items, kBlock / 64);
     HET_KTIME("HET_hgt_backward_src_long", s);
     HET_DISPATCH_HGT_ROWS((int)(X / 4), (int)(D / 4),
-                          hipLaunchKernelGGL((HET_hgt_backward_src_long<LPR, DL>), dim3(nbl), dim3(kBlock), 0, s, it,
+                          hipLaunchKernelGGL((HET_hgt_backward_src_long<LPR, DL, T>), dim3(nbl), dim3(kBlock), 0, s, it,
                                              by_srow->long_items, by_srow->num_long_items, by_srow->p0, kv_c, q, pack2, gradout,
                                              grad_kv_c, (int)H));
     HET_LAUNCH_CHECK("HET_hgt_backward_src_long");
   }
   return HET_OK;
+}
+}  // namespace
+
+extern "C" int het_hgt_backward_compact(const het_grouping* by_dst, const het_grouping* by_srow, const float* kv_c, const float* q,
+                                        const float* lsum, const float* out, const float* gradout, float* grad_kv_c, float* grad_q,
+                                        int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
+                                        int64_t workspace_bytes, het_stream stream) {
+  return hgt_backward_compact("het_hgt_backward_compact", by_dst, by_srow, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q, num_nodes,
+                              num_src_rows, H, D, workspace, workspace_bytes, stream);
+}
+
+extern "C" int het_hgt_backward_compact_bf16(const het_grouping* by_dst, const het_grouping* by_srow, const het_bf16* kv_c,
+                                             const het_bf16* q, const float* lsum, const het_bf16* out, const het_bf16* gradout,
+                                             float* grad_kv_c, float* grad_q, int64_t num_nodes, int64_t num_src_rows, int64_t H,
+                                             int64_t D, void* workspace, int64_t workspace_bytes, het_stream stream) {
+  return hgt_backward_compact("het_hgt_backward_compact_bf16", by_dst, by_srow, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q,
+                              num_nodes, num_src_rows, H, D, workspace, workspace_bytes, stream);
 }

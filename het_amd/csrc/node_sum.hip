@@ -439,3 +439,13 @@ extern "C" int het_node_rows_matmul_sum(int64_t n_begin, int64_t n_end, int64_t 
   return het_node_rows_matmul_sum_bias(n_begin, n_end, num_nodes, num_sources, rows, row_strides, maps, ident_rows, weights_t, nullptr,
                                        out, KS, XO, node_order, stream);
 }
+
+// bf16 output rows without a bias (the input gradient of the HGT layer with bf16 activations: fp32 gradient rows and weights, every
+// output row rounded once after all of a node's terms are summed)
+extern "C" int het_node_rows_matmul_sum_bf16(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources,
+                                             const float* const* rows, const int64_t* row_strides, const int32_t* const* maps,
+                                             const int64_t* ident_rows, const float* const* weights_t, het_bf16* out, int64_t KS,
+                                             int64_t XO, const int32_t* node_order, het_stream stream) {
+  return node_rows_matmul_sum_bias(n_begin, n_end, num_nodes, num_sources, rows, row_strides, maps, ident_rows, weights_t, nullptr, out,
+                                   KS, XO, node_order, stream);
+}

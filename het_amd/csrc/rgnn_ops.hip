@@ -443,6 +443,62 @@ extern "C" int het_rows_matmul_backward_dw(const int64_t* rel_ptrs, int64_t num_
                                             accumulate, stream);
 }
 
+// bf16 activation rows (the HGT layer, het_amd/backend/hgt_fused_layer.py): the row product and the weight gradient of the matrix-core
+// shapes with bf16 rows widened on load, fp32 weights and fp32 accumulation.
+extern "C" int het_rows_matmul_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
+                                    int64_t num_rows, const float* weights, const het_bf16* x, het_bf16* out, int64_t K, int64_t X,
+                                    het_stream stream) {
+  const char* op = "het_rows_matmul_bf16";
+  HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rows >= 0 && K > 0 && X > 0, "%s: bad arguments", op);
+  if (num_rows == 0) return HET_OK;
+  HET_REQUIRE(weights && x && out, "%s: null data pointer", op);
+  if (!((K == 32 || K == 64) && (X == 32 || X == 64 || X == 128) && aligned16(x, out, weights))) {
+    het_set_error("%s: K in {32, 64} and X in {32, 64, 128} with 16-byte aligned tensors only (K=%lld X=%lld)", op, (long long)K, (long long)X);
+    return HET_ERR_UNSUPPORTED;
+  }
+  MfmaGemmArgsT<het_bf16, het_bf16> m;
+  m.A = x; m.a_ld = K; m.gather = gather_idx; m.B = weights; m.b_rel_stride = K * X;
+  m.C = out; m.c_ld = X; m.scatter = scatter_idx;
+  m.seg_ptrs = rel_ptrs; m.num_segs = (int)num_rels; m.num_rows = num_rows; m.K = (int)K; m.X = (int)X;
+  return launch_seg_gemm_mfma(m, (hipStream_t)stream);
+}
+
+namespace {
+template <typename TG>
+int rows_matmul_backward_dw_bf16(const char* op, const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx,
+                                 const int64_t* g_rows, int64_t num_rows, const het_bf16* x, const TG* gradout, float* grad_w,
+                                 int64_t K, int64_t X, int accumulate, het_stream stream) {
+  HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rows >= 0 && K > 0 && X > 0 && grad_w, "%s: bad arguments", op);
+  hipStream_t s = (hipStream_t)stream;
+  if (!((K == 32 || K == 64) && (X == 32 || X == 64 || X == 128) && aligned16(x) && aligned16(gradout))) {
+    het_set_error("%s: K in {32, 64} and X in {32, 64, 128} with 16-byte aligned tensors only (K=%lld X=%lld)", op, (long long)K, (long long)X);
+    return HET_ERR_UNSUPPORTED;
+  }
+  if (!accumulate) HET_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * num_rels * K * X, s));
+  if (num_rows == 0) return HET_OK;
+  HET_REQUIRE(x && gradout, "%s: null data pointer", op);
+  MfmaDwArgsT<TG, het_bf16> w;
+  w.A = x; w.a_ld = K; w.gather = gather_idx; w.G = gradout; w.g_ld = X; w.g_gather = g_rows; w.dW = grad_w; w.dw_rel_stride = K * X;
+  w.seg_ptrs = rel_ptrs; w.num_segs = (int)num_rels; w.num_rows = num_rows; w.K = (int)K; w.X = (int)X;
+  return launch_seg_dw_mfma(w, s);
+}
+}  // namespace
+
+extern "C" int het_rows_matmul_backward_dw_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx,
+                                                const int64_t* g_rows, int64_t num_rows, const het_bf16* x, const float* gradout,
+                                                float* grad_w, int64_t K, int64_t X, int accumulate, het_stream stream) {
+  return rows_matmul_backward_dw_bf16("het_rows_matmul_backward_dw_bf16", rel_ptrs, num_rels, gather_idx, g_rows, num_rows, x, gradout,
+                                      grad_w, K, X, accumulate, stream);
+}
+
+extern "C" int het_rows_matmul_backward_dw_bf16_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx,
+                                                     const int64_t* g_rows, int64_t num_rows, const het_bf16* x,
+                                                     const het_bf16* gradout, float* grad_w, int64_t K, int64_t X, int accumulate,
+                                                     het_stream stream) {
+  return rows_matmul_backward_dw_bf16("het_rows_matmul_backward_dw_bf16_bf16", rel_ptrs, num_rels, gather_idx, g_rows, num_rows, x,
+                                      gradout, grad_w, K, X, accumulate, stream);
+}
+
 extern "C" int het_rgnn_relational_matmul_no_scatter_gather_list(const int64_t* offsets, int64_t num_types,
                                                                  int64_t num_rows, const float* weights,
                                                                  const float* x, float* ret, int64_t H, int64_t K,

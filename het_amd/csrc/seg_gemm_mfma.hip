@@ -34,8 +34,19 @@ inline int chunk_rows_for(int64_t num_rows) {
 // instead of the float-atomic rate (1.3 TB/s chip-wide).  The old C rows are requested before the MFMAs of the tile.
 // DOTL: 0 = no dot; 4 = heads of 16 floats (4 lanes of the store mapping: the sum over a head is two DPP adds and the head index a
 // shift -- the RGAT shape); -1 = any power-of-two head width (shuffles, runtime lane counts).
-template <int K, int NT, bool ATOMIC, int DOTL = 0, bool RMW = false>
-__device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int chunk_rows) {
+// the 4 elements of an A row a lane loads, as they arrive: a float4, or 4 bf16 in a uint2 (widened where the tile goes to LDS, so
+// that no ALU instruction waits for the load at its issue)
+template <typename T> struct RawRow4 { typedef float4 type; };
+template <> struct RawRow4<het_bf16> { typedef uint2 type; };
+__device__ __forceinline__ uint2 ldraw4(const het_bf16* p) { return *reinterpret_cast<const uint2*>(p); }
+__device__ __forceinline__ float4 widen4(uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+
+template <int K, int NT, bool ATOMIC, int DOTL = 0, bool RMW = false, typename TA = float, typename TC = float>
+__device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgsT<TA, TC>& a, int chunk_rows) {
+  static_assert(std::is_same<TC, float>::value || (!ATOMIC && !RMW), "bf16 C rows: plain stores only");
   constexpr bool DOT = DOTL != 0;
   constexpr int X = NT * 32, KH = K / 2;
   constexpr int LDA = K + 4, LPRA = K / 4, RPIA = 64 / LPRA, NITA = 32 / RPIA;  // A tile: rows per load instr
@@ -98,7 +109,7 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
   // vmcnt counts loads and stores in issue order, so a wait for a load also waits for every older store:
   // with this order everything consumed in iteration t+1 was requested BEFORE the stores of tile t, and
   // no wait in the loop ever covers a store that was just issued.
-  float4 areg[NITA];
+  typename RawRow4<TA>::type areg[NITA];
   int ar_next[NITA];    // A row ids of the next tile (32-bit: row counts < 2^31 are checked by the callers)
   int crow_next[NITC];  // C row ids of the next tile, -1 = no row
   // No branch inside the loop (the waitcnt pass is conservative at block boundaries): a missing gather /
@@ -126,7 +137,8 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
     for (int it = 0; it < NITA; ++it) {
       const idx_t i = wb + it * RPIA + ra, ic = i < re ? i : re - 1;
       const int64_t r64 = has_g ? (int64_t)ar[it] : (int64_t)ic;
-      areg[it] = *reinterpret_cast<const float4*>(a.A + r64 * a.a_ld + ca);
+      if constexpr (std::is_same<TA, float>::value) areg[it] = *reinterpret_cast<const float4*>(a.A + r64 * a.a_ld + ca);
+      else areg[it] = ldraw4(a.A + r64 * a.a_ld + ca);
     }
   };
 
@@ -141,7 +153,10 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
 #pragma unroll
     for (int it = 0; it < NITA; ++it) {
       const bool in = !ATOMIC || wb + it * RPIA + ra < re;
-      *reinterpret_cast<float4*>(&Ws[(it * RPIA + ra) * LDA + ca]) = in ? areg[it] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (std::is_same<TA, float>::value)
+        *reinterpret_cast<float4*>(&Ws[(it * RPIA + ra) * LDA + ca]) = in ? areg[it] : make_float4(0.f, 0.f, 0.f, 0.f);
+      else
+        *reinterpret_cast<float4*>(&Ws[(it * RPIA + ra) * LDA + ca]) = in ? widen4(areg[it]) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     int crow[NITC];
 #pragma unroll
@@ -204,9 +219,11 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int cr = reinterpret_cast<const int*>(Ws)[(reg & 3) + 8 * (reg >> 2) + 4 * half];
-        float* p = a.C + (int64_t)cr * a.c_ld + row;
+        if constexpr (std::is_same<TC, float>::value) {
+          float* p = a.C + (int64_t)cr * a.c_ld + row;
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) atomicAdd(p + nt * 32, acc[nt][reg]);
+          for (int nt = 0; nt < NT; ++nt) atomicAdd(p + nt * 32, acc[nt][reg]);
+        }
       }
     } else {
       // transpose through the wave's LDS region so that every output row leaves as whole 16-byte pieces
@@ -228,7 +245,11 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
           const float4 c = cold[RMW ? it : 0];
           v = make_float4(v.x + c.x, v.y + c.y, v.z + c.z, v.w + c.w);
         }
-        if (!RMW || real) *reinterpret_cast<float4*>(a.C + (int64_t)crow[it] * a.c_ld + cc) = v;
+        if constexpr (std::is_same<TC, float>::value) {
+          if (!RMW || real) *reinterpret_cast<float4*>(a.C + (int64_t)crow[it] * a.c_ld + cc) = v;
+        } else {
+          strow4(a.C + (int64_t)crow[it] * a.c_ld + cc, v);
+        }
         if (DOT) {
           float p = v.x * dotw.x + v.y * dotw.y + v.z * dotw.z + v.w * dotw.w;
           if (DOTL == 4) p = quad_sum(p);  // (coop.hip.h: the four lanes of a head are a DPP quad)
@@ -256,9 +277,9 @@ __device__ __forceinline__ void seg_gemm_mfma_body(const MfmaGemmArgs& a, int ch
   for (wb += 128; wb < re; wb += 128) tile(wb);
 }
 
-template <int K, int NT, bool ATOMIC, int DOTL = 0, bool RMW = false>
-__global__ __launch_bounds__(256) void HET_seg_gemm_mfma(MfmaGemmArgs a, int chunk_rows) {
-  seg_gemm_mfma_body<K, NT, ATOMIC, DOTL, RMW>(a, chunk_rows);
+template <int K, int NT, bool ATOMIC, int DOTL = 0, bool RMW = false, typename TA = float, typename TC = float>
+__global__ __launch_bounds__(256) void HET_seg_gemm_mfma(MfmaGemmArgsT<TA, TC> a, int chunk_rows) {
+  seg_gemm_mfma_body<K, NT, ATOMIC, DOTL, RMW, TA, TC>(a, chunk_rows);
 }
 // The RGAT projection (K <= 64 into 64 columns, heads of 16, dot epilogue) held to the register budget of three waves per SIMD --
 // what the plain-store instance needs anyway (168); without the bound the dot's few extra values cost a whole wave per SIMD (180).
@@ -276,8 +297,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // add per element and workgroup.
 // CS: additionally colsum[n] += SUM_rows G[row, n] (the bias gradient of a layer whose output gradient this launch streams
 // anyway: one VALU add per loaded G value instead of another pass over the rows); the workgroups of the first K block add it.
-template <int KT, int NT, bool CS = false, typename TG = float>
-__global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG> a, int chunk) {
+template <int KT, int NT, bool CS = false, typename TG = float, typename TA = float>
+__global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG, TA> a, int chunk) {
   // blockIdx.y selects a (KT*32) x (NT*32) block of the K x X product when K or X exceed 64 (each block re-reads its
   // column slices of the A and G rows)
   const int Kf = a.K, Xf = a.X, nbn = Xf / (NT * 32);
@@ -336,11 +357,11 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG> a, int ch
 #pragma unroll
       for (int st = 0; st < SB; ++st) {
         if (KT == 2) {
-          const float2 t = *reinterpret_cast<const float2*>(a.A + (int64_t)A[st] * a.a_ld + kbase + 2 * col);
+          const float2 t = ldrow2(a.A + (int64_t)A[st] * a.a_ld + kbase + 2 * col);
           AV[st][0] = t.x; AV[st][KT - 1] = t.y;
         } else {
 #pragma unroll
-          for (int kt = 0; kt < KT; ++kt) AV[st][kt] = a.A[(int64_t)A[st] * a.a_ld + kbase + kt * 32 + col];
+          for (int kt = 0; kt < KT; ++kt) AV[st][kt] = to_f32(a.A[(int64_t)A[st] * a.a_ld + kbase + kt * 32 + col]);
         }
         if (NT == 2) {
           const float2 t = ldrow2(a.G + (int64_t)G[st] * a.g_ld + nbase + 2 * col);
@@ -458,12 +479,13 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG> a, int ch
   }
 }
 
-template <int KT, int NT, typename TG>
-int launch_dw_kx(const MfmaDwArgsT<TG>& a, hipStream_t s) {
+template <int KT, int NT, typename TG, typename TA>
+int launch_dw_kx(const MfmaDwArgsT<TG, TA>& a, hipStream_t s) {
   const size_t lds = sizeof(float) * (3 * KT * NT * 16 * 64 + (a.colsum ? 3 * NT * 32 : 0));
   HET_REQUIRE(!a.row_scale, "segment dW (MFMA): row scales are applied by the segment-sum pre-pass, not here");
   HET_REQUIRE(a.a_ld % 2 == 0 && a.g_ld % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.G) & 7) == 0,
               "segment dW (MFMA): rows must be 8-byte aligned");
+  constexpr bool kAllF32 = std::is_same<TG, float>::value && std::is_same<TA, float>::value;
   // 48 KiB of LDS per workgroup -> 3 resident per CU, 768 on the chip: aim for about 4 rounds of them
   // (same box: 768 0.325, 1536 0.316, 3072 0.354, 6144 0.380 ms per launch on ogbn-mag: every workgroup ends with K*X atomic adds)
   constexpr int64_t kDwChunks = 1536;
@@ -473,17 +495,17 @@ int launch_dw_kx(const MfmaDwArgsT<TG>& a, hipStream_t s) {
   const int64_t gx = ceil_div64(a.num_rows, chunk) + a.num_segs;
   const unsigned gy = (unsigned)((a.K / (KT * 32)) * (a.X / (NT * 32)));
   if (a.colsum) {
-    if constexpr (std::is_same<TG, float>::value) {
+    if constexpr (kAllF32) {
       HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       HET_KTIME("HET_seg_dw_mfma", s);
       hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, true>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
     } else {
-      HET_REQUIRE(false, "segment dW (MFMA, bf16 G rows): no column sums");
+      HET_REQUIRE(false, "segment dW (MFMA, bf16 rows): no column sums");
     }
   } else {
-    HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, false, TG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, false, TG, TA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HET_KTIME("HET_seg_dw_mfma", s);
-    hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, false, TG>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
+    hipLaunchKernelGGL((HET_seg_dw_mfma<KT, NT, false, TG, TA>), dim3((unsigned)gx, gy), dim3(256), lds, s, a, (int)chunk);
   }
   HET_LAUNCH_CHECK("HET_seg_dw_mfma");
   return HET_OK;
@@ -521,6 +543,22 @@ int launch_kx(const MfmaGemmArgs& a, hipStream_t s) {
     HET_HIP(hipFuncSetAttribute((const void*)HET_seg_gemm_mfma<K, NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((HET_seg_gemm_mfma<K, NT, false>), grid, block, lds, s, a, chunk);
   }
+  HET_LAUNCH_CHECK("HET_seg_gemm_mfma");
+  return HET_OK;
+}
+
+// bf16 A and C rows: the plain-store instance only
+template <int K, int NT>
+int launch_kx(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t s) {
+  constexpr int X = NT * 32, LDA = K + 4, LDC = X + 4;
+  const size_t lds = sizeof(float) * (K * X + 4 * 32 * (LDA > LDC ? LDA : LDC));
+  const int chunk = chunk_rows_for(a.num_rows);
+  const int64_t gx = ceil_div64(a.num_rows, chunk) + a.num_segs;
+  HET_REQUIRE(gx < (1ll << 31), "segment GEMM: too many row chunks");
+  HET_KTIME("HET_seg_gemm_mfma<store>", s);
+  HET_HIP(hipFuncSetAttribute((const void*)HET_seg_gemm_mfma<K, NT, false, 0, false, het_bf16, het_bf16>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((HET_seg_gemm_mfma<K, NT, false, 0, false, het_bf16, het_bf16>), dim3((unsigned)gx), dim3(256), lds, s, a, chunk);
   HET_LAUNCH_CHECK("HET_seg_gemm_mfma");
   return HET_OK;
 }
@@ -611,6 +649,27 @@ int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s) {
   }
 }
 
+int launch_seg_gemm_mfma(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t s) {
+  if (a.num_rows == 0) return HET_OK;
+  HET_REQUIRE((a.K == 32 || a.K == 64) && (a.X == 32 || a.X == 64 || a.X == 128) && !a.atomic && !a.dot_w && !a.b_headcat && !a.row_scale,
+              "segment GEMM (MFMA, bf16 rows): unsupported shape K=%d X=%d or epilogue", a.K, a.X);
+  if (a.X == 128) {  // two 64-wide column slabs, as the fp32 launcher runs K <= 64 into 128 columns
+    for (int n0 = 0; n0 < 128; n0 += 64) {
+      MfmaGemmArgsT<het_bf16, het_bf16> w = a;
+      w.X = 64; w.C = a.C + n0; w.b_n0 = a.b_n0 + n0;
+      w.b_kfull = a.b_kfull ? a.b_kfull : a.K; w.b_xfull = a.b_xfull ? a.b_xfull : a.X;
+      if (int rc = launch_seg_gemm_mfma(w, s)) return rc;
+    }
+    return HET_OK;
+  }
+  // (4 bf16 = 8 bytes per lane)
+  HET_REQUIRE(a.a_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 7) == 0, "segment GEMM (MFMA, bf16 rows): A rows must be 8-byte aligned");
+  HET_REQUIRE(a.c_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0, "segment GEMM (MFMA, bf16 rows): C rows must be 8-byte aligned");
+  HET_REQUIRE(!a.bias || aligned16(a.bias), "segment GEMM (MFMA, bf16 rows): bias must be 16-byte aligned");
+  if (a.K == 32) return a.X == 32 ? launch_kx<32, 1>(a, s) : launch_kx<32, 2>(a, s);
+  return a.X == 32 ? launch_kx<64, 1>(a, s) : launch_kx<64, 2>(a, s);
+}
+
 bool mfma_dw_supported(int K, int X) {
   return (K == 32 || K == 64 || K == 128 || K == 256) && (X == 32 || X == 64 || X == 128 || X == 256);
 }
@@ -630,3 +689,17 @@ int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16>& a, hipStream_t s) {
   if (a.K == 32) return a.X == 32 ? launch_dw_kx<1, 1>(a, s) : launch_dw_kx<1, 2>(a, s);
   return a.X == 32 ? launch_dw_kx<2, 1>(a, s) : launch_dw_kx<2, 2>(a, s);
 }
+
+namespace {
+template <typename TG>
+int launch_dw_bf16_a(const MfmaDwArgsT<TG, het_bf16>& a, hipStream_t s) {
+  if (a.num_rows == 0) return HET_OK;
+  HET_REQUIRE((a.K == 32 || a.K == 64) && (a.X == 32 || a.X == 64 || a.X == 128) && a.headcat == 0,
+              "segment dW (MFMA, bf16 A rows): unsupported shape K=%d X=%d", a.K, a.X);
+  // (X = 128: two 64-wide blocks of the product along blockIdx.y)
+  if (a.K == 32) return a.X == 32 ? launch_dw_kx<1, 1>(a, s) : launch_dw_kx<1, 2>(a, s);
+  return a.X == 32 ? launch_dw_kx<2, 1>(a, s) : launch_dw_kx<2, 2>(a, s);
+}
+}  // namespace
+int launch_seg_dw_mfma(const MfmaDwArgsT<float, het_bf16>& a, hipStream_t s) { return launch_dw_bf16_a(a, s); }
+int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16, het_bf16>& a, hipStream_t s) { return launch_dw_bf16_a(a, s); }

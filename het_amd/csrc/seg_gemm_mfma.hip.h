@@ -3,8 +3,11 @@
 #pragma once
 #include "common.hip.h"
 
-struct MfmaGemmArgs {
-  const float* A = nullptr;       // [*, K] rows, gathered
+// TA / TC: the element types of the A and the C rows, float or het_bf16 (A widened on load, C rounded once at its store -- plain
+// stores only); the weight, the bias and the accumulation are fp32
+template <typename TA = float, typename TC = float>
+struct MfmaGemmArgsT {
+  const TA* A = nullptr;          // [*, K] rows, gathered
   int64_t a_ld = 0;
   const idx_t* gather = nullptr;  // NULL: identity
   const float* row_scale = nullptr;
@@ -16,7 +19,7 @@ struct MfmaGemmArgs {
   // a launch may cover a K x X window of a larger weight (K or X = 256 are run as 128-wide slabs by the launcher):
   // window origin and the full sizes the layouts above are indexed with (0 = the launch's own K / X)
   int b_k0 = 0, b_n0 = 0, b_kfull = 0, b_xfull = 0;
-  float* C = nullptr;             // [*, X]
+  TC* C = nullptr;                // [*, X]
   int64_t c_ld = 0;
   const idx_t* scatter = nullptr; // NULL: identity
   int atomic = 0;                 // 0: C rows are stored; 1: float atomic adds; 2: non-atomic read-modify-write (the rows of
@@ -31,9 +34,13 @@ struct MfmaGemmArgs {
   // optional epilogue (plain stores, K, X <= 128): C row += bias[:]   (one [X] vector for all segments)
   const float* bias = nullptr;
 };
+typedef MfmaGemmArgsT<float, float> MfmaGemmArgs;
 
 bool mfma_shape_supported(int K, int X);
 int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s);
+// bf16 A and C rows: K in {32, 64}, X in {32, 64, 128}, plain stores, plain [K][X] weights, no dot epilogue (the HGT layer's bf16
+// projections)
+int launch_seg_gemm_mfma(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t s);
 // C[scatter(i)] += A . B_r with the scatter rows distinct INSIDE every segment (a unique (relation, node) list) but
 // shared between segments: one launch per segment (stream order serialises them), each adding with plain
 // read-modify-write.  Few segments only (every launch is sized for all rows): callers fall back to atomics above 8.
@@ -55,10 +62,11 @@ inline int launch_seg_gemm_mfma_fwd(const float* x, int64_t x_ld, const idx_t* g
 
 // dW_r(k, n) += sum_{i in segment r} scale(i) * A[ga(i), k] * G[gg(i), n]   on the matrix cores
 // (the MFMA k dimension runs over rows).  Output layout: plain [K][X] per segment, or
-// head-concatenated [Hc][K][Dh] with n = (h, d).  TG: the element type of the G rows, float or het_bf16 (widened on load).
-template <typename TG = float>
+// head-concatenated [Hc][K][Dh] with n = (h, d).  TG / TA: the element types of the G and the A rows, float or het_bf16 (widened
+// on load).
+template <typename TG = float, typename TA = float>
 struct MfmaDwArgsT {
-  const float* A = nullptr;
+  const TA* A = nullptr;
   int64_t a_ld = 0;
   const idx_t* gather = nullptr;
   const float* row_scale = nullptr;
@@ -81,3 +89,7 @@ bool mfma_dw_supported(int K, int X);
 int launch_seg_dw_mfma(const MfmaDwArgs& a, hipStream_t s);
 // bf16 G rows: K, X in {32, 64}, plain layout, no column sums (the RGCN layer's bf16 weight gradient)
 int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16>& a, hipStream_t s);
+// bf16 A rows with fp32 or bf16 G rows: K in {32, 64}, X in {32, 64, 128}, plain layout, no column sums (the HGT layer's bf16 weight
+// gradients)
+int launch_seg_dw_mfma(const MfmaDwArgsT<float, het_bf16>& a, hipStream_t s);
+int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16, het_bf16>& a, hipStream_t s);

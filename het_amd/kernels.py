@@ -853,14 +853,11 @@ def node_rows_matmul_sum_ok(num_sources: int, KS: int, XO: int) -> bool:
     return bool(_lib.lib().het_node_rows_matmul_sum_ok(int(num_sources), int(KS), int(XO)))
 
 
-def node_rows_matmul_sum(n_begin, n_end, sources, out, node_order=None):
-    """out[n] = SUM_s rows_s[map_s[n]] . wt_s for the nodes at positions [n_begin, n_end) of node_order (include/het_amd.h:
-    het_node_rows_matmul_sum).  sources: (rows [n_rows, W] float tensor, first column, map [N] int32 or None (row = node id),
-    wt [KS, XO]) each; a source reads the KS columns of its rows that start at ``first column``."""
+def _node_rows_matmul_sum(entry, n_begin, n_end, sources, out, node_order, bias_slot):
+    """The ctypes marshalling of het_node_rows_matmul_sum_bias / het_node_rows_matmul_sum_bf16 (``bias_slot``: the entry has one)."""
     N, XO = out.shape
     S = len(sources)
     KS = sources[0][3].shape[0]
-    _chk("node_rows_matmul_sum", tuple(t for src in sources for t in (src[0], src[3])) + (out,))
     ptrs = (C.c_void_p * S)(*[src[0].data_ptr() + 4 * int(src[1]) for src in sources])
     strides = (C.c_int64 * S)(*[src[0].shape[1] if src[0].dim() == 2 else src[0].numel() // src[0].shape[0] for src in sources])
     maps = (C.c_void_p * S)(*[None if src[2] is None else src[2].data_ptr() for src in sources])
@@ -868,8 +865,16 @@ def node_rows_matmul_sum(n_begin, n_end, sources, out, node_order=None):
     wts = (C.c_void_p * S)(*[src[3].data_ptr() for src in sources])
     for src in sources:
         assert src[3].shape == (KS, XO) and src[3].is_contiguous() and (src[2] is None or (src[2].dtype == torch.int32 and src[2].numel() == N))
-    _call(out, "het_node_rows_matmul_sum_bias", int(n_begin), int(n_end), N, S, ptrs, strides, maps, ident, wts, None, _p(out), KS, XO,
+    _call(out, entry, int(n_begin), int(n_end), N, S, ptrs, strides, maps, ident, wts, *((None,) if bias_slot else ()), _p(out), KS, XO,
           _p(node_order), _stream(out))
+
+
+def node_rows_matmul_sum(n_begin, n_end, sources, out, node_order=None):
+    """out[n] = SUM_s rows_s[map_s[n]] . wt_s for the nodes at positions [n_begin, n_end) of node_order (include/het_amd.h:
+    het_node_rows_matmul_sum).  sources: (rows [n_rows, W] float tensor, first column, map [N] int32 or None (row = node id),
+    wt [KS, XO]) each; a source reads the KS columns of its rows that start at ``first column``."""
+    _chk("node_rows_matmul_sum", tuple(t for src in sources for t in (src[0], src[3])) + (out,))
+    _node_rows_matmul_sum("het_node_rows_matmul_sum_bias", n_begin, n_end, sources, out, node_order, True)
 
 
 def rows_linear_bias_ok(K: int, X: int) -> bool:
@@ -1232,6 +1237,84 @@ def rgcn_layer_backward_bf16(plan, ssum, weights_t, norm, gradout, want_bias: bo
           _p(gradout), _p(src_map), _p(src_order), _p(grad_x), _p(grad_w), _p(grad_bias), K, D, _p(ws),
           ws.numel() * 4, _stream(gradout))
     return grad_x, grad_w, grad_bias
+
+
+# ---- the HGT layer with bf16 activations (backend/hgt_fused_layer.py): activation rows bf16, everything else fp32 ----
+def rows_matmul_bf16_ok(K: int, X: int) -> bool:
+    """Shapes het_rows_matmul_bf16 / het_rows_matmul_backward_dw_bf16 cover."""
+    return K in (32, 64) and X in (32, 64, 128)
+
+
+def rows_matmul_bf16(rel_ptrs, gather_idx, scatter_idx, weights, x, out):
+    """out[scatter_idx[i]] = x[gather_idx[i]] . weights[r(i)] (include/het_amd.h: het_rows_matmul_bf16): x [*,K] and out [*,X] bf16,
+    weights [R,1,K,X] fp32; a missing list means row i.  Plain stores: the output rows of the call are distinct."""
+    lists = tuple(t for t in (gather_idx, scatter_idx) if t is not None)
+    _chk_bf16("rows_matmul_bf16", (x, out), (weights,))
+    _chk("rows_matmul_bf16", (), (rel_ptrs,) + lists)
+    R, _, K, X = weights.shape
+    n = lists[0].numel() if lists else x.shape[0]
+    if x.shape[-1] != K or out.shape[-1] != X or (gather_idx is None and x.shape[0] < n) or (scatter_idx is None and out.shape[0] < n):
+        raise _lib.HetError(f"rows_matmul_bf16: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit weights {tuple(weights.shape)} and {n} rows")
+    _call(out, "het_rows_matmul_bf16", _p(rel_ptrs), R, _p(gather_idx), _p(scatter_idx), n, _p(weights), _p(x), _p(out), K, X,
+          _stream(out))
+
+
+def rows_matmul_backward_dw_bf16(rel_ptrs, gather_idx, x, gradout, grad_w, accumulate: bool, g_rows=None):
+    """grad_w[r(i)] (+)= x[gather_idx[i]]^T (x) gradout[g_rows[i]] (het_rows_matmul_backward_dw_bf16 / _bf16_bf16): x bf16, gradout fp32 or bf16,
+    grad_w [R,1,K,X] fp32."""
+    lists = tuple(t for t in (gather_idx, g_rows) if t is not None)
+    g_bf16 = gradout.dtype == torch.bfloat16
+    _chk_bf16("rows_matmul_backward_dw_bf16", (x, gradout) if g_bf16 else (x,), (grad_w,) if g_bf16 else (gradout, grad_w))
+    _chk("rows_matmul_backward_dw_bf16", (), (rel_ptrs,) + lists)
+    R, _, K, X = grad_w.shape
+    n = lists[0].numel() if lists else gradout.shape[0]
+    if x.shape[-1] != K or gradout.shape[-1] != X or (gather_idx is None and x.shape[0] < n) or (g_rows is None and gradout.shape[0] < n):
+        raise _lib.HetError(f"rows_matmul_backward_dw_bf16: x {tuple(x.shape)} / gradout {tuple(gradout.shape)} do not fit grad_w "
+                            f"{tuple(grad_w.shape)} and {n} rows")
+    _call(gradout, "het_rows_matmul_backward_dw_bf16_bf16" if g_bf16 else "het_rows_matmul_backward_dw_bf16", _p(rel_ptrs), R,
+          _p(gather_idx), _p(g_rows), n, _p(x), _p(gradout), _p(grad_w), K, X, int(accumulate), _stream(gradout))
+
+
+def node_rows_matmul_sum_bf16(n_begin, n_end, sources, out, node_order=None):
+    """node_rows_matmul_sum with bf16 output rows (het_node_rows_matmul_sum_bf16): the source rows and weights are fp32."""
+    _chk_bf16("node_rows_matmul_sum_bf16", (out,), tuple(t for src in sources for t in (src[0], src[3])))
+    _node_rows_matmul_sum("het_node_rows_matmul_sum_bf16", n_begin, n_end, sources, out, node_order, False)
+
+
+def _hgt_bf16_shapes(name, kv_c, q, lsum, out):
+    N, H = lsum.shape
+    D = out.numel() // max(1, N * H)
+    if q.numel() != N * H * D or out.numel() != N * H * D or kv_c.numel() != kv_c.shape[0] * 2 * H * D:
+        raise _lib.HetError(f"{name}: kv_c {tuple(kv_c.shape)}, q {tuple(q.shape)}, out {tuple(out.shape)} do not fit lsum {tuple(lsum.shape)}")
+    return N, H, D
+
+
+def hgt_aggregate_compact_bf16(groupings, kv_c, q, lsum, out, workspace=None):
+    """hgt_aggregate_compact with bf16 rows (het_hgt_aggregate_compact_bf16): kv_c, q and out bf16, lsum fp32.  ``workspace``: a
+    float32 tensor of the caller instead of the one allocated here (the C entry checks its size and alignment)."""
+    _chk_bf16("hgt_aggregate_compact_bf16", (kv_c, q, out), (lsum,))
+    N, H, D = _hgt_bf16_shapes("hgt_aggregate_compact_bf16", kv_c, q, lsum, out)
+    nbytes = int(_lib.lib().het_hgt_aggregate_compact_workspace(groupings[0].handle, H, D))  # (hub destinations only)
+    ws = workspace
+    if ws is None and nbytes:
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
+    _call(out, "het_hgt_aggregate_compact_bf16", groupings[0].handle, _p(kv_c), _p(q), _p(lsum), _p(out), N, kv_c.shape[0], H, D,
+          _p(ws), 0 if ws is None else ws.numel() * 4, _stream(out))
+
+
+def hgt_backward_compact_bf16(groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q, workspace=None):
+    """hgt_backward_compact with bf16 rows (het_hgt_backward_compact_bf16): kv_c, q, out and gradout bf16; lsum, grad_kv_c and
+    grad_q fp32."""
+    _chk_bf16("hgt_backward_compact_bf16", (kv_c, q, out, gradout), (lsum, grad_kv_c, grad_q))
+    N, H, D = _hgt_bf16_shapes("hgt_backward_compact_bf16", kv_c, q, lsum, out)
+    if gradout.numel() != out.numel() or grad_q.numel() != q.numel() or grad_kv_c.numel() != kv_c.numel():
+        raise _lib.HetError("hgt_backward_compact_bf16: gradient shapes do not match their tensors")
+    ws = workspace
+    if ws is None:
+        nbytes = int(_lib.lib().het_hgt_backward_compact_workspace(N, H))
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
+    _call(out, "het_hgt_backward_compact_bf16", groupings[0].handle, groupings[1].handle, _p(kv_c), _p(q), _p(lsum), _p(out),
+          _p(gradout), _p(grad_kv_c), _p(grad_q), N, kv_c.shape[0], H, D, _p(ws), ws.numel() * 4, _stream(out))
 
 
 def _rgcn_maps(d: Dict[str, Tensor], direct: bool):

@@ -377,7 +377,28 @@ class HET_HGTLayerHetero(nn.Module):
     reference's code for it reshapes with ``view`` where a transpose is meant, multiplies relation_msg and V in the
     opposite order and indexes V by the destination type (its own "fixme"s): taken literally it is a different model and
     only type-checks for one head with in_dim == d_k.  Built here with the INTENDED meaning -- the same function as the
-    layer without the flag (associativity), any number of heads -- which is what oracle/layers.py::hgt_layer checks."""
+    layer without the flag (associativity), any number of heads -- which is what oracle/layers.py::hgt_layer checks.
+
+    bf16 activations: a ``torch.bfloat16`` input ``h`` gives a bf16 output, and a bf16 output gradient a bf16 ``h.grad``.  All
+    parameters (k / q / v / a_linears, relation_att / msg / pri, skip), the folded per-relation weights and every parameter
+    gradient stay fp32.  On the fused path the rows gathered once per edge are bf16: ``kv_c`` ([k' | m] of every (relation,
+    source) row) and ``q`` are rounded once at their GEMM's store (bf16 ``h`` widened on load, fp32 weight and accumulation);
+    ``new_h`` is rounded once from the fp32 ``acc / sum`` (whole destinations and hubs alike); the layer output and the gradient
+    of ``new_h`` once by the typed output projection; ``h.grad`` once, after all of a node's terms are summed in the node-major
+    pass.  The log-sum-exp, the gradients of ``kv_c`` and ``q`` (sums over edges that feed the fp32 parameter gradients) and
+    every sum, exponential, maximum and dot product are fp32 on widened values; rounding is to nearest even.
+    The bf16 kernels serve a full graph with canonical relations whose padded input width and row width H * d_k are both 32 or 64,
+    heads narrower than 8 or of odd width zero-padded as in fp32 (row width H * d_pad) -- with and without compact destinations.  Everything else is correct,
+    not faster: it runs fp32 on an upcast copy of ``h`` and the result is cast back to bf16 (the gradient likewise, through
+    autograd) --
+      * the fused path is off or not applicable (HET_HGT_FUSED=0, groupings off, relations that mix node types, CPU tensors): the
+        op-by-op composition, ``multiply_among_weights_first_flag`` included;
+      * sampled blocks whose nodes are runs of equal type (``node_segment_types``);
+      * rows wider than 64 (H * d_pad = 128, or two head groups), padded input widths other than 32 / 64, output widths other
+        than 32 / 64.
+    One branch inside the bf16 path keeps an fp32 buffer: a graph with more relations per node type than the node-major input
+    gradient keeps in LDS (4 and more) adds a node's gradient terms relation by relation in an fp32 [N, in] buffer and rounds
+    it once; ``h``, ``kv_c``, ``q`` and ``new_h`` are bf16 there too."""
 
     def __init__(self, num_ntypes, num_rels, in_dim, out_dim, num_heads=1, dropout=0.2, use_norm=False,
                  hgt_fused_attn_score_flag=False, compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
@@ -411,6 +432,9 @@ class HET_HGTLayerHetero(nn.Module):
     def forward(self, G, h, num_dst=None):
         """``num_dst``: ``G`` is a sampled block whose first ``num_dst`` nodes are its destinations (only their rows are
         returned); its nodes are runs of equal type (``node_segment_types``, het_amd/sampling.py) instead of one run per type."""
+        if h.dtype == th.bfloat16 and not _hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k):
+            # no bf16 kernels behind the op-by-op composition: fp32 on an upcast copy, one final rounding (class docstring)
+            return self.forward(G, h.float(), num_dst).to(th.bfloat16)
         offs = G.get_original_node_type_offsets()
         seg_types = G.graph_data["original"].get("node_segment_types") if hasattr(G, "graph_data") else None
         per_run = (lambda w: w) if seg_types is None else (lambda w: w.index_select(0, seg_types))

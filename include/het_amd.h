@@ -525,7 +525,9 @@ int het_backward_hgt_full_graph_hetero_attention_ops_coo(const int64_t* row, con
  * forward overwrites lsum and out (zero rows for destinations without in-edges); backward overwrites grad_kv_c [S_row,2,H,D]
  * and grad_q [N,H,D].  workspace (backward): het_hgt_backward_compact_workspace(N, H) bytes, 16-byte aligned; (forward):
  * het_hgt_aggregate_compact_workspace(by_dst, H, D) bytes (0 unless a destination has more than 256 in-edges).
- * Shapes: H*D in {8, 16, 32, 64, 128}, D a power of two >= 8 (het_hgt_compact_shape_ok); else HET_ERR_UNSUPPORTED. */
+ * Shapes: H*D in {8, 16, 32, 64, 128}, D a power of two >= 8 (het_hgt_compact_shape_ok); else HET_ERR_UNSUPPORTED.
+ * The row tensors (kv_c, q, out, gradout, grad_kv_c, grad_q) must be 16-byte aligned: the kernels move them in 16-byte (fp32) or
+ * 8-byte (bf16) pieces; a misaligned pointer is refused with HET_ERR_INVALID_ARG before anything is enqueued. */
 int het_hgt_compact_shape_ok(int64_t H, int64_t D);
 int het_hgt_aggregate_compact(const het_grouping* by_dst, const float* kv_c, const float* q, float* lsum, float* out,
                               int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
@@ -536,6 +538,18 @@ int het_hgt_backward_compact(const het_grouping* by_dst, const het_grouping* by_
                              const float* lsum, const float* out, const float* gradout, float* grad_kv_c, float* grad_q,
                              int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
                              int64_t workspace_bytes, het_stream stream);
+
+/* The same pair with bf16 activation rows: kv_c, q, out and gradout are het_bf16 (the rows gathered once per edge: half the bytes);
+ * lsum, grad_kv_c, grad_q, the workspaces and every sum, exponential and dot product are fp32 on widened values.  out is rounded
+ * once (to nearest even) from acc / sum, for whole destinations and for hubs alike; the backward takes <gradout, out> from that
+ * rounded out.  Arguments, validation, workspace queries and shapes are those of the fp32 pair. */
+int het_hgt_aggregate_compact_bf16(const het_grouping* by_dst, const het_bf16* kv_c, const het_bf16* q, float* lsum, het_bf16* out,
+                                   int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
+                                   int64_t workspace_bytes, het_stream stream);
+int het_hgt_backward_compact_bf16(const het_grouping* by_dst, const het_grouping* by_srow, const het_bf16* kv_c, const het_bf16* q,
+                                  const float* lsum, const het_bf16* out, const het_bf16* gradout, float* grad_kv_c, float* grad_q,
+                                  int64_t num_nodes, int64_t num_src_rows, int64_t H, int64_t D, void* workspace,
+                                  int64_t workspace_bytes, het_stream stream);
 
 /* The per-step folding of the HGT layer's parameters into one source-side weight per relation (round 5; extension, reached from
  * het_amd/backend/hgt_fused_layer.py only), forward and backward as one / two launches instead of ~14 + ~24 torch kernels:
@@ -659,6 +673,22 @@ int het_rows_matmul_backward_dw_colsum(const int64_t* rel_ptrs, int64_t num_rels
                                        float* grad_w, float* colsum, int64_t H, int64_t K, int64_t D, int accumulate,
                                        het_stream stream);
 
+/* Row products with bf16 activation rows (the HGT layer with bf16 activations; fp32 weights, fp32 accumulation on the matrix cores):
+ *   het_rows_matmul_bf16:             out[scatter_idx[i], :] = x[gather_idx[i], :] . weights[r(i)]     x [*,K], out [*,X] het_bf16 (x
+ *       widened on load -- exact --, out rounded once at the store), weights [R,K,X] fp32; plain stores (the listed output rows
+ *       are distinct); gather_idx / scatter_idx NULL = row i.  K in {32, 64}, X in {32, 64, 128}; else HET_ERR_UNSUPPORTED.
+ *   het_rows_matmul_backward_dw_bf16: grad_w[r(i)] (+)= x[gather_idx[i], :]^T (x) gradout[g_rows[i], :]   x [*,K] het_bf16; gradout
+ *       [*,X] fp32, or het_bf16 for het_rows_matmul_backward_dw_bf16_bf16; grad_w [R,K,X] fp32.  Same shapes. */
+int het_rows_matmul_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
+                         int64_t num_rows, const float* weights, const het_bf16* x, het_bf16* out, int64_t K, int64_t X,
+                         het_stream stream);
+int het_rows_matmul_backward_dw_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* g_rows,
+                                     int64_t num_rows, const het_bf16* x, const float* gradout, float* grad_w, int64_t K, int64_t X,
+                                     int accumulate, het_stream stream);
+int het_rows_matmul_backward_dw_bf16_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* g_rows,
+                                          int64_t num_rows, const het_bf16* x, const het_bf16* gradout, float* grad_w, int64_t K,
+                                          int64_t X, int accumulate, het_stream stream);
+
 /* ------------------------------------------------------------------------
  * Node-major input gradient of the one-node RGAT layer (layer-level fusion; no reference op of its own).  It replaces,
  * inside het_amd/backend/rgat_fused_layer.py, the per-relation input-gradient passes of a2 (backward_rgnn_relational_matmul
@@ -705,6 +735,13 @@ int het_node_rows_matmul_sum_bias(int64_t n_begin, int64_t n_end, int64_t num_no
                                   const float* const* rows, const int64_t* row_strides, const int32_t* const* maps,
                                   const int64_t* ident_rows, const float* const* weights_t, const float* bias, float* out,
                                   int64_t KS, int64_t XO, const int32_t* node_order, het_stream stream);
+
+/* het_node_rows_matmul_sum with het_bf16 output rows: the source rows, the weights and the sums are fp32, every output row is
+ * rounded once after all of a node's terms are added (the input gradient of the HGT layer with bf16 activations). */
+int het_node_rows_matmul_sum_bf16(int64_t n_begin, int64_t n_end, int64_t num_nodes, int64_t num_sources,
+                                  const float* const* rows, const int64_t* row_strides, const int32_t* const* maps,
+                                  const int64_t* ident_rows, const float* const* weights_t, het_bf16* out, int64_t KS, int64_t XO,
+                                  const int32_t* node_order, het_stream stream);
 
 /* ------------------------------------------------------------------------
  * The RGCN layer as two calls (layer-level fusion; no reference op of its own).  Inside het_amd/backend/rgcn_layers_and_funcs.py
