@@ -8,7 +8,12 @@ Compiles every file of the Makefile's SRCS in both trees with the Makefile's fla
 the set of kernel symbols and the text of every kernel, label to .end_amdhsa_kernel (descriptor included).  --rename
 rewrites a substring of the OLD tree's assembly first (a renamed parameter type changes the mangled names).  The
 per-translation-unit __hip_cuid_<hash> symbol lies outside the kernels and is not compared.  One summary line per file;
-exit status 1 when anything differs."""
+exit status 1 when anything differs.
+
+--local-labels: block labels are .LBB<n>_<block> with n the function's ordinal in its module, so a kernel ADDED to a file renumbers
+the labels of every kernel emitted after it (and, where the number gains a digit, the padding in front of the label's comment).
+With this flag the ordinal and that padding are dropped before the comparison; instructions, operands, block numbers and the
+kernel descriptors are compared as they are."""
 import argparse
 import re
 import subprocess
@@ -21,8 +26,14 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import isa_stats  # noqa: E402
 
 
+LOCAL_LABELS = False
+
+
 def kernels(path):  # isa_stats' parser also returns device functions and data labels: keep what ends in a kernel descriptor
-    return {k: b for k, b in isa_stats.kernels(path).items() if b and b[-1].strip().startswith(".end_amdhsa_kernel")}
+    ks = {k: b for k, b in isa_stats.kernels(path).items() if b and b[-1].strip().startswith(".end_amdhsa_kernel")}
+    if LOCAL_LABELS:
+        ks = {k: [re.sub(r"\s+;", " ;", re.sub(r"BB\d+_", "BB_", line)) for line in b] for k, b in ks.items()}
+    return ks
 
 
 def make_var(csrc, name):
@@ -44,7 +55,10 @@ def main():
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     ap.add_argument("--keep", help="directory for the .s files (default: a temporary one)")
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--local-labels", action="store_true", help="ignore the function ordinal in block labels (see above)")
     a = ap.parse_args()
+    global LOCAL_LABELS
+    LOCAL_LABELS = a.local_labels
     tmp = Path(a.keep or tempfile.mkdtemp(prefix="isa_diff_"))
     srcs = make_var(a.new, "SRCS").split()
     if srcs != make_var(a.old, "SRCS").split():

@@ -54,6 +54,8 @@ _SIGNATURES = {
     "het_rgcn_layer_backward_bf16": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
     "het_rgat_backward_compact": [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, I64, P],
     "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
+    "het_rgat_aggregate_compact_forward_workspace": [P, P, I64, I64, I64, P],  # (returns bytes: restype set in lib())
+    "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_hgt_aggregate_compact": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
     "het_hgt_backward_compact": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
@@ -151,6 +153,7 @@ def lib() -> C.CDLL:
                 raise HetError(f"{LIB_PATH} does not export {name}: rebuild it (make -C het_amd/csrc)")
             f.argtypes = args
             f.restype = INT
+        L.het_rgat_aggregate_compact_forward_workspace.restype = I64
         _lib = L
     return _lib
 

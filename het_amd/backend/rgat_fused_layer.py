@@ -23,6 +23,10 @@ and, for either, ``mulfirst`` (--multiply_among_weights_first_flag, RGAT/models.
 as a row-dot product on the distinct (relation, destination) rows instead of a projection followed by a dot.  The two
 forms of er are the same real number (associativity); the reference offers the flag because it is cheaper, and so the
 node takes it whenever the one-head row-dot kernels cover the shape (HET_RGAT_LITERAL_ER=1 keeps (x . W) . attn_r).
+
+Evaluation (torch.no_grad(), or no input that requires a gradient) on the distinct-row dataflow does not go through the node at
+all: _forward_only runs the same forward with an aggregation that keeps nothing for a backward (HET_RGAT_FORWARD_ONLY=0: the
+node's forward, as before).
 """
 import os
 
@@ -38,6 +42,7 @@ _OFFS = {}
 PER_EDGE = os.environ.get("HET_RGAT_PER_EDGE") == "1"      # default flags on the per-edge (kind 0) dataflow
 LITERAL_ER = os.environ.get("HET_RGAT_LITERAL_ER") == "1"  # er = (x . W) . attn_r unless the layer flag asks otherwise
 OVERLAP = os.environ.get("HET_RGAT_OVERLAP", "1") != "0"  # independent launches on a second HIP stream (see _side_stream)
+FORWARD_ONLY = os.environ.get("HET_RGAT_FORWARD_ONLY", "1") != "0"  # no backward in sight: the forward that keeps nothing for one
 
 
 def _mulfirst_shape_ok(H, Kd):
@@ -156,6 +161,93 @@ def _halo_pieces(g, ss, plan):
     return hit
 
 
+def _loop_offsets(nd, device):
+    """[0, nd] int64 on the device: the one-relation pointer list of the self-loop product (built once per (rows, device): no
+    per-step host-to-device copy)."""
+    offs = _OFFS.get((nd, device))
+    if offs is None:
+        if len(_OFFS) > 64:
+            _OFFS.clear()
+        offs = _OFFS[(nd, device)] = th.tensor([0, nd], dtype=th.int64, device=device)
+    return offs
+
+
+def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias):
+    """The distinct-row forward in front of its aggregation, common to RgatLayerFunction.forward and _forward_only: the
+    projections feat_c / el_c / er_c on the unique (relation, node) rows, the self-loop + bias rows ``h`` the aggregation adds into
+    (None when there is no self-loop or its fused launch does not take the widths) and the groupings of the edges.  Returns
+    (ss, h, saved, grp, run_sums); saved = (feat_c, el_c, er_c[, feat_d])."""
+    s, _, _ = _lists(g)
+    rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
+    N = x.shape[0]
+    R, H, Kd, D = W.shape
+    X = H * D
+    new = lambda *shape: th.empty(shape, dtype=x.dtype, device=x.device)
+    h = None
+    ss = g.get_separate_unique_node_indices_single_sided()
+    d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_node_indices": ss["node_indices_row"]}
+    d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
+    featc = new(ss["node_indices_row"].numel(), H, D)
+    elc = new(featc.shape[0], H)
+    erc = new(ss["node_indices_col"].numel(), H)
+    # (the destination side and the self-loop read rows of destination nodes only -- owned rows on a partition)
+    side = None
+    fused_loop = loop_w is not None and _k.rows_linear_bias_ok(Kd, X)
+    # (the three products below read the same rows of x; one node-major pass that reads them once was built and measured in
+    #  round 5 -- 1 GB less traffic, the same step time: exp/node_fwd.hip.txt)
+    if OVERLAP and halo is None and fused_loop and mulfirst:
+        # er_c (a row-dot) and the self-loop GEMM are HBM-bound streams of rows: on the side stream beside the projection
+        main, side = th.cuda.current_stream(x.device), _side_stream(x.device)
+        # everything the side stream WRITES is allocated before the fork: a block handed out later may have been freed by
+        # a tensor whose last main-stream kernel was enqueued after the fork -- the side stream would not wait for it
+        h = x.new_empty((nd, X))
+        side.wait_stream(main)
+    if mulfirst:
+        with th.cuda.stream(side if side is not None else th.cuda.current_stream(x.device)):
+            K.rgnn_relational_matmul(d_col, 1, wa, x, erc.view(-1, H, 1), True)
+        saved = (featc, elc, erc)
+    else:
+        featd = new(erc.shape[0], H, D)
+        _k.matmul_attn_dot(d_col, 1, W, x, featd, attn_r, erc)
+        saved = (featc, elc, erc, featd)
+    if fused_loop:
+        # self-loop + bias first (bias in the GEMM epilogue); the aggregation adds its rows into h in place: no
+        # separate h = ret + loop + bias pass and no zero fill of ret (read by the backward only where edges point)
+        bias_c = None if bias is None else bias.contiguous()
+        if side is not None:  # (h: allocated, and later freed, under the main stream; the side stream only fills it)
+            with th.cuda.stream(side):
+                _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c, out=h)
+        else:
+            h = _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c)
+    dot_ok = _k.matmul_attn_dot_ok(H, Kd, D)
+    piecewise = halo is not None and halo.chunks > 1 and dot_ok
+    if piecewise:
+        # the exchange arrives in pieces (het_amd/dist.py: DistPlan.chunks): the rows whose source node is owned are
+        # projected at once, the rows of piece c as soon as piece c is there -- piece c + 1 is on the wire meanwhile
+        for c, (rp_c, nodes_c, rows_c) in enumerate(_halo_pieces(g, ss, halo.plan)):
+            halo.wait_push_piece(c)
+            _k.matmul_attn_dot_rows(rp_c, nodes_c, rows_c, W, x, featc, attn_l, elc)
+        halo.finish_push()
+    elif halo is not None:
+        halo.finish_push()
+    if piecewise:
+        pass  # (projected above)
+    elif dot_ok:
+        _k.matmul_attn_dot(d_row, 1, W, x, featc, attn_l, elc)  # el_c = <feat_c, attn_l[r]> from the GEMM epilogue
+    else:  # other widths: any-shape projection, then el_c as a row-dot over the relation-bucketed rows
+        K.rgnn_relational_matmul(d_row, 1, W, x, featc, True)
+        K.rgnn_relational_matmul_no_scatter_gather_list(ss["rel_ptrs_row"], attn_l.unsqueeze(-1), featc, elc.view(-1, H, 1))
+    if side is not None:
+        th.cuda.current_stream(x.device).wait_stream(side)
+    # edge softmax + aggregation straight from the compact tables: no exp [E,H] tensor (csrc/gat_compact.hip)
+    srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
+    # (run sums: grad_er from S_col rows the forward leaves instead of a per-edge term -- csrc/gat_compact.hip)
+    run_sums = _k.rgat_runs_shape_ok(H, D)
+    grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp if run_sums else None,
+                                    drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
+    return ss, h, saved, grp, run_sums
+
+
 @_consistent_plan
 class RgatLayerFunction(th.autograd.Function):
     @staticmethod
@@ -177,76 +269,13 @@ class RgatLayerFunction(th.autograd.Function):
         offs = h = None
         if loop_w is not None:
             loop_w = loop_w.contiguous()
-            offs = _OFFS.get((nd, x.device))  # built once per (rows, device): no per-step host-to-device copy
-            if offs is None:
-                if len(_OFFS) > 64:
-                    _OFFS.clear()
-                offs = _OFFS[(nd, x.device)] = th.tensor([0, nd], dtype=th.int64, device=x.device)
+            offs = _loop_offsets(nd, x.device)
         wa = None
         if mulfirst:  # RGAT/models.py:300-326: the attention vector folded into the weight, [R,H,K,1]
             wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1)
         if compact:
-            ss = g.get_separate_unique_node_indices_single_sided()
-            d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_node_indices": ss["node_indices_row"]}
-            d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
-            featc = new(ss["node_indices_row"].numel(), H, D)
-            elc = new(featc.shape[0], H)
-            erc = new(ss["node_indices_col"].numel(), H)
-            # (the destination side and the self-loop read rows of destination nodes only -- owned rows on a partition)
-            side = None
-            fused_loop = loop_w is not None and _k.rows_linear_bias_ok(Kd, X)
-            # (the three products below read the same rows of x; one node-major pass that reads them once was built and measured in
-            #  round 5 -- 1 GB less traffic, the same step time: exp/node_fwd.hip.txt)
-            if OVERLAP and halo is None and fused_loop and mulfirst:
-                # er_c (a row-dot) and the self-loop GEMM are HBM-bound streams of rows: on the side stream beside the projection
-                main, side = th.cuda.current_stream(x.device), _side_stream(x.device)
-                # everything the side stream WRITES is allocated before the fork: a block handed out later may have been freed by
-                # a tensor whose last main-stream kernel was enqueued after the fork -- the side stream would not wait for it
-                h = x.new_empty((nd, X))
-                side.wait_stream(main)
-            if mulfirst:
-                with th.cuda.stream(side if side is not None else th.cuda.current_stream(x.device)):
-                    K.rgnn_relational_matmul(d_col, 1, wa, x, erc.view(-1, H, 1), True)
-                saved = (featc, elc, erc)
-            else:
-                featd = new(erc.shape[0], H, D)
-                _k.matmul_attn_dot(d_col, 1, W, x, featd, attn_r, erc)
-                saved = (featc, elc, erc, featd)
-            if fused_loop:
-                # self-loop + bias first (bias in the GEMM epilogue); the aggregation adds its rows into h in place: no
-                # separate h = ret + loop + bias pass and no zero fill of ret (read by the backward only where edges point)
-                bias_c = None if bias is None else bias.contiguous()
-                if side is not None:  # (h: allocated, and later freed, under the main stream; the side stream only fills it)
-                    with th.cuda.stream(side):
-                        _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c, out=h)
-                else:
-                    h = _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c)
-            dot_ok = _k.matmul_attn_dot_ok(H, Kd, D)
-            piecewise = halo is not None and halo.chunks > 1 and dot_ok
-            if piecewise:
-                # the exchange arrives in pieces (het_amd/dist.py: DistPlan.chunks): the rows whose source node is owned are
-                # projected at once, the rows of piece c as soon as piece c is there -- piece c + 1 is on the wire meanwhile
-                for c, (rp_c, nodes_c, rows_c) in enumerate(_halo_pieces(g, ss, halo.plan)):
-                    halo.wait_push_piece(c)
-                    _k.matmul_attn_dot_rows(rp_c, nodes_c, rows_c, W, x, featc, attn_l, elc)
-                halo.finish_push()
-            elif halo is not None:
-                halo.finish_push()
-            if piecewise:
-                pass  # (projected above)
-            elif dot_ok:
-                _k.matmul_attn_dot(d_row, 1, W, x, featc, attn_l, elc)  # el_c = <feat_c, attn_l[r]> from the GEMM epilogue
-            else:  # other widths: any-shape projection, then el_c as a row-dot over the relation-bucketed rows
-                K.rgnn_relational_matmul(d_row, 1, W, x, featc, True)
-                K.rgnn_relational_matmul_no_scatter_gather_list(ss["rel_ptrs_row"], attn_l.unsqueeze(-1), featc, elc.view(-1, H, 1))
-            if side is not None:
-                th.cuda.current_stream(x.device).wait_stream(side)
-            # edge softmax + aggregation straight from the compact tables: no exp [E,H] tensor (csrc/gat_compact.hip)
-            srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
-            # (run sums: grad_er from S_col rows the forward leaves instead of a per-edge term -- csrc/gat_compact.hip)
-            run_sums = _k.rgat_runs_shape_ok(H, D)
-            grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp if run_sums else None,
-                                            drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
+            ss, h, saved, grp, run_sums = _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
+            featc, elc, erc = saved[:3]
             # (elc IS <featc, attn_l[relation of the row]>: the pass may form it from the rows it gathers -- kernels.py)
             ctx.runs = _k.rgat_aggregate_compact(grp, featc, elc, erc, sm, ret, slope, h_inout=h, num_rels=R,
                                                  attn_l=attn_l.contiguous() if run_sums else None, feat_rel_ptrs=ss["rel_ptrs_row"] if run_sums else None)
@@ -557,8 +586,53 @@ def rgat_layer_halo_ok(g, x_own, W, slope, compact, mulfirst=False):
     return c and m and _k.rows_linear_bias_ok(Kd, H * D) and _k.rows_matmul_backward_split_ok(H, Kd, D)
 
 
+def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+    """RgatLayerFunction.forward on the distinct-row dataflow when no backward can follow: a plain function (no autograd node,
+    nothing saved), the same projections and the same self-loop rows, and an aggregation that writes the layer output alone
+    (csrc/gat_compact.hip: the _fwd kernels) -- no lse [N,H], no ret [N,H,D], no run sums [S_col,H,D].  Every output row is bit
+    for bit the training forward's."""
+    x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
+    N = x.shape[0]
+    R, H, Kd, D = W.shape
+    X = H * D
+    nd = N if num_dst is None else min(int(num_dst), N)
+    offs = None
+    if loop_w is not None:
+        loop_w = loop_w.contiguous()
+        offs = _loop_offsets(nd, x.device)
+    wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1) if mulfirst else None
+    ss, h, saved, grp, _ = _compact_tables(g, direct, mulfirst, None, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
+    featc, elc, erc = saved[:3]
+    fused = h is not None
+    if not fused:  # no self-loop rows to add into (no self-loop, or widths its fused launch does not take): zeros, the tail below
+        h = x.new_zeros((nd, X))
+    _k.rgat_aggregate_compact_forward(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
+    if fused:
+        return h
+    loop = None
+    if loop_w is not None:
+        loop = x.new_empty((nd, X))
+        K.rgnn_relational_matmul_no_scatter_gather_list(offs, loop_w.view(1, 1, Kd, X), x[:nd], loop)
+    # (the training forward clones its view of ret here when there is nothing to add; h is already a buffer of its own)
+    return _k.rows_add_bias(h, loop, None if bias is None else bias.contiguous()) if (loop is not None or bias is not None) else h
+
+
+def _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
+    """No backward can follow (autograd is off, or nothing that reaches the layer asks for a gradient) and the call is one the
+    forward-only kernels cover: one GPU, the distinct-row dataflow, the shapes and the int32 key range of the run-sum form."""
+    if not FORWARD_ONLY or halo is not None or not compact:
+        return False
+    if th.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, W, attn_l, attn_r, loop_w, bias)):
+        return False
+    R, H, _, D = W.shape
+    return _k.rgat_runs_shape_ok(H, D) and x.shape[0] * R < 2 ** 31
+
+
 def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, direct, num_dst=None, mulfirst=False, halo=None):
     compact, direct, mulfirst = effective_flags(g, W, compact, direct, mulfirst)
     if compact and not _has_single_sided_lists(g):
         g.generate_separate_unique_node_indices_single_sided_for_each_etype()
+    if _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
+        with th.no_grad():
+            return _forward_only(g, direct, mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
     return RgatLayerFunction.apply(g, compact, direct, mulfirst, float(slope), num_dst, halo, x, W, attn_l, attn_r, loop_w, bias)

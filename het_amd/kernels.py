@@ -775,6 +775,30 @@ def rgat_aggregate_compact(groupings, feat_c, el_c, er_c, sum, ret, slope, h_ino
     return None
 
 
+def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l=None, feat_rel_ptrs=None):
+    """The forward of rgat_aggregate_compact's run-sum form when no backward follows (include/het_amd.h:
+    het_rgat_aggregate_compact_forward): h_inout [rows, H*D] += the aggregated rows, in place, and nothing else is written -- no
+    lse, no ret, no run sums.  ``groupings``: rgat_compact_groupings with rel_ptrs (the training forward's, shared with it)."""
+    _chk("rgat_aggregate_compact_forward", (feat_c, el_c, er_c, h_inout))
+    if groupings[3] is None:
+        raise _lib.HetError("rgat_aggregate_compact_forward: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
+    H, D = feat_c.shape[1], feat_c.shape[2]
+    with torch.cuda.device(h_inout.device):
+        nbytes = int(_lib.lib().het_rgat_aggregate_compact_forward_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
+                                                                             _stream(h_inout)))
+    if nbytes < 0:
+        raise _lib.HetError("het_rgat_aggregate_compact_forward_workspace: " + _lib.lib().het_last_error().decode())
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h_inout.device) if nbytes else None
+    host_ptrs = None
+    if attn_l is not None and feat_rel_ptrs is not None:
+        _chk("rgat_aggregate_compact_forward", (attn_l,), (feat_rel_ptrs,))
+        lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
+        host_ptrs = (C.c_int64 * len(lst))(*lst)
+    _call(h_inout, "het_rgat_aggregate_compact_forward", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c),
+          _p(er_c), H, D, float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None, host_ptrs,
+          _p(ws), nbytes, _stream(h_inout))
+
+
 def rows_matmul_backward_split_ok(H: int, K: int, D: int) -> bool:
     """Shapes het_rows_matmul_backward_dx / _dw cover (one input head on the matrix cores)."""
     return K in (32, 64, 128) and H * D in (32, 64, 128)

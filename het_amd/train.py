@@ -121,6 +121,9 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
     p.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic graph")
     p.add_argument("--edges_npy", type=str, default=None, help="[3, E] int array (src, dst, etype) instead of -d")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--inference", action="store_true",
+                   help="time evaluation instead of training: every epoch is one forward under torch.no_grad() with the model in "
+                        "eval(); backward is logged as 0")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -150,7 +153,37 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
     from .sampling import one_shot_graphs, run_blocks
     prep_ms = []
 
+    inference = getattr(args, "inference", False)
+
+    def one_eval(timed):
+        # the evaluation pass of the reference's scripts (model.eval() + torch.no_grad()): same inputs, same event pair around
+        # the model as the training step's forward; loss from the same expression, nothing after it
+        with th.no_grad():
+            node_embed = node_embed_layer()
+            cur_labels = labels
+            if batches is not None:
+                th.cuda.synchronize()
+                t0 = time.perf_counter()
+                blocks, seeds = batches()
+                th.cuda.synchronize()
+                prep_ms.append((time.perf_counter() - t0) * 1e3)
+                node_embed, cur_labels = node_embed[blocks[0].nodes], labels[seeds]
+            th.cuda.synchronize()
+            ev = [th.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            with (one_shot_graphs(blocks) if batches is not None else contextlib.nullcontext()):
+                if batches is None:
+                    logits = model(g, node_embed, *extra)
+                else:
+                    logits = run_blocks(model.layers, blocks, node_embed, extra[0] if extra else None)
+                ev[1].record()
+                loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
+            th.cuda.synchronize()
+        return (ev[0].elapsed_time(ev[1]), 0.0, float(loss)) if timed else None
+
     def one_step(timed):
+        if inference:
+            return one_eval(timed)
         optimizer.zero_grad()
         node_embed = node_embed_layer()
         cur_labels = labels
@@ -181,8 +214,8 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
         th.cuda.synchronize()
         return (ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3]), float(loss.detach())) if timed else None
 
-    model.train()
-    node_embed_layer.train()
+    model.train(not inference)
+    node_embed_layer.train(not inference)
     if not args.no_warm_up:
         for _ in range(5):
             one_step(False)
@@ -257,6 +290,10 @@ def main(argv=None):
            "minibatch_sample_and_layout_ms": (round(aggregate_times(HET_RGNN_train.last_prep_ms), 3)
                                               if HET_RGNN_train.last_prep_ms else None),
            "peak_memory_GB": round(th.cuda.max_memory_allocated() / 2**30, 3), "args": vars(args)}
+    if args.inference:
+        res["mode"] = "inference"
+    else:
+        del res["args"]["inference"]  # (a training run's log line is what it was before the flag existed)
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

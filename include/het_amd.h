@@ -652,6 +652,26 @@ int het_rgat_backward_compact_runs(const het_grouping* by_srow, const float* q_r
 int64_t het_rgat_backward_compact_runs_workspace(const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t H,
                                                  int64_t D, int with_bias, int with_attn_grad, het_stream stream);
 
+/* The forward of that pair when no backward will follow (evaluation, torch.no_grad()): the same groupings -- by_dst and by_dst_rel
+ * as for het_rgat_aggregate_compact_runs, so a training step and an evaluation pass over one graph share them --, the same feat_c /
+ * el_c / er_c / slope / attn_l / feat_rel_ptrs_host, and ONE output:
+ *   h_inout [h_rows, H*D] (required, 16-byte aligned): h_inout[v] += SUM_e softmax_v(leaky(el + er))_e feat_c[srow_e] in place for
+ *     every destination v < h_rows that has in-edges; the other rows are not touched (a caller without a self-loop term passes
+ *     zeros).  Neither lse, ret nor the run sums are formed or stored -- on an ogbn-mag-sized graph that is 0.8 GB the training
+ *     forward writes for its backward.  The value of every row is bit for bit what het_rgat_aggregate_compact_runs leaves in its
+ *     h_inout for the same arguments (same operations, same order, same roundings).
+ *   Shapes as there (else HET_ERR_UNSUPPORTED); null groupings, a null or misaligned h_inout and groupings of the wrong shape are
+ *   HET_ERR_INVALID_ARG; nothing is enqueued before these checks pass.  No edges: HET_OK, h_inout untouched.
+ *   workspace: het_rgat_aggregate_compact_forward_workspace(by_dst, by_dst_rel, num_rels, H, D, stream) bytes, 16-byte aligned -- one
+ *     record {O[H*D], max[H], sum[H]} per work item of a hub destination (num_hub_items * (H*D + 2*H) floats); lists those items on
+ *     `stream` on first use, as its twin does; -1 on error. */
+int64_t het_rgat_aggregate_compact_forward_workspace(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                                     int64_t H, int64_t D, het_stream stream);
+int het_rgat_aggregate_compact_forward(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                       const float* feat_c, const float* el_c, const float* er_c, int64_t H, int64_t D, double slope,
+                                       float* h_inout, int64_t h_rows, const float* attn_l, const int64_t* feat_rel_ptrs_host,
+                                       void* workspace, int64_t workspace_bytes, het_stream stream);
+
 /* The two halves of a2 (backward_rgnn_relational_matmul, one input head, matrix-core shapes) as separate calls, so that a
  * caller can order them around a collective (het_amd/dist.py).  Rows i in [0, num_rows) of relation-bucketed lists:
  *   dx: grad_x[gather_idx[i], :] (+)= gradout[g_rows[i], :] . Wt[r(i)]      atomic 0: "=";  1: "+=" with float atomics (rows
