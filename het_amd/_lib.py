@@ -56,6 +56,11 @@ _SIGNATURES = {
     "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
     "het_rgat_aggregate_compact_forward_workspace": [P, P, I64, I64, I64, P],  # (returns bytes: restype set in lib())
     "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
+    "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
+    "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
+    "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
+    "het_rows_matmul_heads_bf16": [P, I64, P, I64, P, P, P, I64, I64, I64, P],
+    "het_rows_dot1h_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
     "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_hgt_aggregate_compact": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
     "het_hgt_backward_compact": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],

@@ -27,6 +27,14 @@ node takes it whenever the one-head row-dot kernels cover the shape (HET_RGAT_LI
 Evaluation (torch.no_grad(), or no input that requires a gradient) on the distinct-row dataflow does not go through the node at
 all: _forward_only runs the same forward with an aggregation that keeps nothing for a backward (HET_RGAT_FORWARD_ONLY=0: the
 node's forward, as before).
+
+bf16 activations (a torch.bfloat16 input) exist on that evaluation path only: _forward_only_bf16 keeps x, feat_c and the layer output
+h as bf16 rows, each rounded once (to nearest even) where its kernel stores it; W, attn_l, attn_r, the self-loop weight, the bias,
+el_c, er_c, the hub records and every sum, maximum and exponential are fp32 on widened values.  er always comes from the folded
+weight there (HET_RGAT_LITERAL_ER does not apply: the literal form needs a second projection table), and el_c is the dot of the
+ROUNDED feat_c row, so the walks that form el from the row they gather and those that gather el_c compute one function.  Every
+other bf16 call (gradients required, halo, per-edge dataflow, other shapes) is served by the fp32 layer on an upcast copy
+(het_amd/layers.py): correct, not faster.
 """
 import os
 
@@ -617,6 +625,70 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     return _k.rows_add_bias(h, loop, None if bias is None else bias.contiguous()) if (loop is not None or bias is not None) else h
 
 
+def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+    """_forward_only for a bf16 input (the module docstring has the precision contract): feat_c [S_row,H,D] and h [nd,X] are bf16
+    rows, no fp32 copy of x, feat_c or h is made, and the aggregation rounds h once more where it adds a destination's row in place.
+    The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
+    instead of the projection's epilogue."""
+    x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
+    s, _, _ = _lists(g)
+    rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
+    N = x.shape[0]
+    R, H, Kd, D = W.shape
+    X = H * D
+    nd = N if num_dst is None else min(int(num_dst), N)
+    dev = x.device
+    ss = g.get_separate_unique_node_indices_single_sided()
+    wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd)  # the folded weight, fp32
+    # (everything the side stream writes is allocated before the fork: see _compact_tables)
+    featc = th.empty((ss["node_indices_row"].numel(), H, D), dtype=th.bfloat16, device=dev)
+    erc = th.empty((ss["node_indices_col"].numel(), H), dtype=th.float32, device=dev)
+    elc = None if _k.rgat_el_from_row(H, D, R) else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
+    bias_c = None if bias is None else bias.contiguous()
+    offs = None
+    if loop_w is not None:  # (the cached [0, nd] list and a copy of the weight too: made under the main stream)
+        loop_w = loop_w.contiguous()
+        offs = _loop_offsets(nd, dev)
+        h = th.empty((nd, X), dtype=th.bfloat16, device=dev)
+    elif bias_c is not None:  # no self-loop: the rows the aggregation adds into hold the (rounded) bias alone
+        h = bias_c.to(th.bfloat16).expand(nd, X).contiguous()
+    else:
+        h = th.zeros((nd, X), dtype=th.bfloat16, device=dev)
+    main = th.cuda.current_stream(dev)
+    side = _side_stream(dev) if OVERLAP else None
+    if side is not None:
+        side.wait_stream(main)
+    with th.cuda.stream(side if side is not None else main):  # er_c and the self-loop: HBM-bound streams of rows beside the projection
+        _k.rows_dot1h_bf16(ss["rel_ptrs_col"], ss["node_indices_col"], wa, x, erc)
+        if loop_w is not None:
+            _k.rows_linear_bias_bf16(offs, x[:nd], loop_w, bias_c, out=h)
+    _k.rows_matmul_heads_bf16(ss["rel_ptrs_row"], ss["node_indices_row"], W, x, featc)
+    if elc is not None:
+        _k.rgat_el_rows_bf16(ss["rel_ptrs_row"], featc, attn_l, elc)
+    if side is not None:
+        main.wait_stream(side)
+    srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
+    grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp,
+                                    drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
+    _k.rgat_aggregate_compact_forward_bf16(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
+    return h
+
+
+def rgat_layer_bf16_ok(g, x, W, slope, compact, mulfirst, tensors):
+    """Whether a bf16 input runs natively (_forward_only_bf16): no backward can follow, the one-node layer covers the call on the
+    distinct-row dataflow, and the shapes are those of the bf16 entries (kernels.rgat_bf16_shape_ok).  ``W``: a tensor of the
+    (padded) weight's shape; ``tensors``: everything whose gradient could be asked for."""
+    if not (FORWARD_ONLY and x.is_cuda and x.dtype == th.bfloat16):
+        return False
+    if th.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        return False
+    if not rgat_layer_fused_ok(g, x, W, slope, compact, mulfirst):
+        return False
+    R, H, Kd, D = W.shape
+    compact, _, _ = effective_flags(g, W, compact, True, mulfirst)
+    return compact and _k.rgat_bf16_shape_ok(H, Kd, D) and x.shape[0] * R < 2 ** 31
+
+
 def _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
     """No backward can follow (autograd is off, or nothing that reaches the layer asks for a gradient) and the call is one the
     forward-only kernels cover: one GPU, the distinct-row dataflow, the shapes and the int32 key range of the run-sum form."""
@@ -632,6 +704,10 @@ def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, dire
     compact, direct, mulfirst = effective_flags(g, W, compact, direct, mulfirst)
     if compact and not _has_single_sided_lists(g):
         g.generate_separate_unique_node_indices_single_sided_for_each_etype()
+    if x.dtype == th.bfloat16:  # (the caller has asked rgat_layer_bf16_ok: there is no bf16 form of anything else)
+        assert compact and halo is None, "rgat_layer_bf16_ok guards this path"
+        with th.no_grad():
+            return _forward_only_bf16(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
     if _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
         with th.no_grad():
             return _forward_only(g, direct, mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)

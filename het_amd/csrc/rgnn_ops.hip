@@ -561,6 +561,64 @@ extern "C" int het_rows_linear_bias(const int64_t* offsets, const float* x, cons
   return launch_seg_gemm_mfma(a, (hipStream_t)stream);
 }
 
+// ... with bf16 rows: x [*,K] and out [*,X] het_bf16, w and bias fp32; the bias is added in fp32 before the one rounding at the store
+extern "C" int het_rows_linear_bias_bf16(const int64_t* offsets, const het_bf16* x, const float* w, const float* bias, het_bf16* out,
+                                         int64_t num_rows, int64_t K, int64_t X, het_stream stream) {
+  const char* op = "het_rows_linear_bias_bf16";
+  HET_REQUIRE(offsets && num_rows >= 0 && K > 0 && X > 0, "%s: bad arguments", op);
+  if (num_rows == 0) return HET_OK;
+  HET_REQUIRE(x && w && out, "%s: null data pointer", op);
+  if (!((K == 32 || K == 64 || K == 128) && (X == 32 || X == 64 || X == 128) && aligned16(x, out) && aligned16(w, bias))) {
+    het_set_error("%s: K and X in {32, 64, 128} with 16-byte aligned tensors only (K=%lld X=%lld)", op, (long long)K, (long long)X);
+    return HET_ERR_UNSUPPORTED;
+  }
+  MfmaGemmArgsT<het_bf16, het_bf16> a;
+  a.A = x; a.a_ld = K; a.B = w; a.b_rel_stride = K * X; a.C = out; a.c_ld = X; a.seg_ptrs = offsets; a.num_segs = 1;
+  a.num_rows = num_rows; a.K = (int)K; a.X = (int)X; a.bias = bias;
+  return launch_seg_gemm_mfma(a, (hipStream_t)stream);
+}
+
+// out[i, (h,d)] = widen(x[gather_idx[i], :]) . weights[r(i), h, :, d]: the projection of the RGAT layer with bf16 activations onto its
+// distinct (relation, node) rows, the weight in the layer's own head-concatenated layout [R,H,K,D]; rounded once at the store
+extern "C" int het_rows_matmul_heads_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, int64_t num_rows,
+                                          const float* weights, const het_bf16* x, het_bf16* out, int64_t H, int64_t K, int64_t D,
+                                          het_stream stream) {
+  const char* op = "het_rows_matmul_heads_bf16";
+  HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rels < (1ll << 31) && num_rows >= 0 && H > 0 && K > 0 && D > 0 && H <= 128 && D <= 128,
+              "%s: bad arguments", op);
+  if (num_rows == 0) return HET_OK;
+  HET_REQUIRE(weights && x && out, "%s: null data pointer", op);
+  const int64_t X = H * D;
+  if (!((K == 32 || K == 64 || K == 128) && (X == 32 || X == 64 || X == 128) && aligned16(x, out) && aligned16(weights))) {
+    het_set_error("%s: K and H*D in {32, 64, 128} with 16-byte aligned tensors only (K=%lld H*D=%lld)", op, (long long)K, (long long)X);
+    return HET_ERR_UNSUPPORTED;
+  }
+  MfmaGemmArgsT<het_bf16, het_bf16> m;
+  m.A = x; m.a_ld = K; m.gather = gather_idx; m.B = weights; m.b_rel_stride = H * K * D; m.b_headcat = 1; m.headcat_d = (int)D;
+  m.C = out; m.c_ld = X; m.seg_ptrs = rel_ptrs; m.num_segs = (int)num_rels; m.num_rows = num_rows; m.K = (int)K; m.X = (int)X;
+  return launch_seg_gemm_mfma(m, (hipStream_t)stream);
+}
+
+// out[scatter_idx[i], h] = <widen(x[gather_idx[i], :]), weights[r(i), h, :]>: one bf16 input row against the H folded vectors of its
+// relation (er_c of the RGAT layer with bf16 activations, weights = W . attn_r); the products, sums and out are fp32
+extern "C" int het_rows_dot1h_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
+                                   int64_t num_rows, const float* weights, const het_bf16* x, float* out, int64_t H, int64_t K,
+                                   het_stream stream) {
+  const char* op = "het_rows_dot1h_bf16";
+  HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rels < (1ll << 31) && num_rows >= 0 && H > 0 && K > 0, "%s: bad arguments", op);
+  if (num_rows == 0) return HET_OK;
+  HET_REQUIRE(weights && x && out, "%s: null data pointer", op);
+  if (!(rowdot1h_supported((int)H, (int)K) && aligned16(x) && aligned16(weights))) {
+    het_set_error("%s: H in {1, 2, 4, 8} and K a power of two in [4 H, 256] with 16-byte aligned tensors only (H=%lld K=%lld)", op,
+                  (long long)H, (long long)K);
+    return HET_ERR_UNSUPPORTED;
+  }
+  RowDotArgs q;
+  q.gather = gather_idx; q.W = weights; q.out = out; q.scatter = scatter_idx; q.seg_ptrs = rel_ptrs;
+  q.num_segs = (int)num_rels; q.num_rows = num_rows; q.H = (int)H; q.K = (int)K;
+  return launch_rowdot1h_fwd_bf16(q, x, (hipStream_t)stream);
+}
+
 extern "C" int het_backward_rgnn_relational_matmul_no_scatter_gather_list(
     const int64_t* offsets, int64_t num_types, int64_t num_rows, const float* weights_t, const float* x,
     const float* gradout, float* grad_x, float* grad_w, int64_t H, int64_t K, int64_t D, int x_per_head,

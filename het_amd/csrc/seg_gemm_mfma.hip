@@ -651,13 +651,15 @@ int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s) {
 
 int launch_seg_gemm_mfma(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t s) {
   if (a.num_rows == 0) return HET_OK;
-  HET_REQUIRE((a.K == 32 || a.K == 64) && (a.X == 32 || a.X == 64 || a.X == 128) && !a.atomic && !a.dot_w && !a.b_headcat && !a.row_scale,
+  HET_REQUIRE((a.K == 32 || a.K == 64 || a.K == 128) && (a.X == 32 || a.X == 64 || a.X == 128) && !a.atomic && !a.dot_w &&
+                  a.b_headcat != 2 && !a.row_scale,
               "segment GEMM (MFMA, bf16 rows): unsupported shape K=%d X=%d or epilogue", a.K, a.X);
   if (a.X == 128) {  // two 64-wide column slabs, as the fp32 launcher runs K <= 64 into 128 columns
     for (int n0 = 0; n0 < 128; n0 += 64) {
       MfmaGemmArgsT<het_bf16, het_bf16> w = a;
       w.X = 64; w.C = a.C + n0; w.b_n0 = a.b_n0 + n0;
       w.b_kfull = a.b_kfull ? a.b_kfull : a.K; w.b_xfull = a.b_xfull ? a.b_xfull : a.X;
+      if (a.bias) w.bias = a.bias + n0;  // (the epilogue indexes the bias by the slab's own columns)
       if (int rc = launch_seg_gemm_mfma(w, s)) return rc;
     }
     return HET_OK;
@@ -667,7 +669,8 @@ int launch_seg_gemm_mfma(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t
   HET_REQUIRE(a.c_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0, "segment GEMM (MFMA, bf16 rows): C rows must be 8-byte aligned");
   HET_REQUIRE(!a.bias || aligned16(a.bias), "segment GEMM (MFMA, bf16 rows): bias must be 16-byte aligned");
   if (a.K == 32) return a.X == 32 ? launch_kx<32, 1>(a, s) : launch_kx<32, 2>(a, s);
-  return a.X == 32 ? launch_kx<64, 1>(a, s) : launch_kx<64, 2>(a, s);
+  if (a.K == 64) return a.X == 32 ? launch_kx<64, 1>(a, s) : launch_kx<64, 2>(a, s);
+  return a.X == 32 ? launch_kx<128, 1>(a, s) : launch_kx<128, 2>(a, s);  // (input widths zero-padded to 128: the RGAT layer)
 }
 
 bool mfma_dw_supported(int K, int X) {

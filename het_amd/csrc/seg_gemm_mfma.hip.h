@@ -38,8 +38,8 @@ typedef MfmaGemmArgsT<float, float> MfmaGemmArgs;
 
 bool mfma_shape_supported(int K, int X);
 int launch_seg_gemm_mfma(const MfmaGemmArgs& a, hipStream_t s);
-// bf16 A and C rows: K in {32, 64}, X in {32, 64, 128}, plain stores, plain [K][X] weights, no dot epilogue (the HGT layer's bf16
-// projections)
+// bf16 A and C rows: K, X in {32, 64, 128}, plain stores, plain [K][X] or head-concatenated weights, optional bias, no dot epilogue (the projections of
+// the HGT layer and of the RGAT layer's evaluation path with bf16 activations)
 int launch_seg_gemm_mfma(const MfmaGemmArgsT<het_bf16, het_bf16>& a, hipStream_t s);
 // C[scatter(i)] += A . B_r with the scatter rows distinct INSIDE every segment (a unique (relation, node) list) but
 // shared between segments: one launch per segment (stream order serialises them), each adding with plain

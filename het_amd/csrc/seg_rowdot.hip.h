@@ -31,5 +31,7 @@ int launch_rowdot_bwd_dw(const RowDotArgs& a, hipStream_t s);
 // A rows are [*, K]; same RowDotArgs, H <= 8, K/4 a power of two <= 64.
 bool rowdot1h_supported(int H, int K);
 int launch_rowdot1h_fwd(const RowDotArgs& a, hipStream_t s);
+// ... with the A rows given as [*, K] het_bf16 (`A`; a.A is not read): widened on load, everything else fp32
+int launch_rowdot1h_fwd_bf16(const RowDotArgs& a, const het_bf16* A, hipStream_t s);
 int launch_rowdot1h_bwd_dx(const RowDotArgs& a, hipStream_t s);
 int launch_rowdot1h_bwd_dw(const RowDotArgs& a, hipStream_t s);

@@ -799,6 +799,87 @@ def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope
           _p(ws), nbytes, _stream(h_inout))
 
 
+# ---- the RGAT layer's evaluation path with bf16 activations (backend/rgat_fused_layer.py: _forward_only_bf16) ----
+def rgat_bf16_shape_ok(H: int, K: int, D: int) -> bool:
+    """Shapes the bf16 evaluation path covers: the run-sum form's rows (32 / 64 / 128 wide, heads of at least 16), a (padded) input
+    width of 32 / 64 / 128, and er from the folded weight through the one-head row-dot (1, 2, 4 or 8 heads)."""
+    return rgat_runs_shape_ok(H, D) and K in (32, 64, 128) and H in (1, 2, 4, 8) and K >= 4 * H
+
+
+def rgat_el_from_row(H: int, D: int, num_rels: int) -> bool:
+    """Whether the run-sum walks form el from the feat row they gather (include/het_amd.h): el_c is then never read."""
+    return D == 16 and num_rels <= 8
+
+
+def rows_matmul_heads_bf16(rel_ptrs, gather_idx, weights, x, out):
+    """out[i] = x[gather_idx[i]] . weights[r(i)] (het_rows_matmul_heads_bf16): x [*,K] and out [rows,H,D] bf16, weights [R,H,K,D] fp32."""
+    _chk_bf16("rows_matmul_heads_bf16", (x, out), (weights,))
+    _chk("rows_matmul_heads_bf16", (), (rel_ptrs, gather_idx))
+    R, H, K, D = weights.shape
+    n = gather_idx.numel()
+    if x.shape[-1] != K or out.numel() != n * H * D or rel_ptrs.numel() != R + 1:
+        raise _lib.HetError(f"rows_matmul_heads_bf16: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit weights {tuple(weights.shape)} and {n} rows")
+    _call(out, "het_rows_matmul_heads_bf16", _p(rel_ptrs), R, _p(gather_idx), n, _p(weights), _p(x), _p(out), H, K, D, _stream(out))
+
+
+def rows_dot1h_bf16(rel_ptrs, gather_idx, weights, x, out):
+    """out[i, h] = <x[gather_idx[i]], weights[r(i), h]> (het_rows_dot1h_bf16): x [*,K] bf16, weights [R,H,K] and out [rows,H] fp32."""
+    _chk_bf16("rows_dot1h_bf16", (x,), (weights, out))
+    _chk("rows_dot1h_bf16", (), (rel_ptrs, gather_idx))
+    R, H, K = weights.shape
+    n = gather_idx.numel()
+    if x.shape[-1] != K or out.numel() != n * H or rel_ptrs.numel() != R + 1:
+        raise _lib.HetError(f"rows_dot1h_bf16: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit weights {tuple(weights.shape)} and {n} rows")
+    _call(out, "het_rows_dot1h_bf16", _p(rel_ptrs), R, _p(gather_idx), None, n, _p(weights), _p(x), _p(out), H, K, _stream(out))
+
+
+def rows_linear_bias_bf16(offsets, x, w, bias, out=None):
+    """rows_linear_bias with bf16 rows (het_rows_linear_bias_bf16): x and out bf16, w [K,X] and bias [X] fp32; the bias is added in
+    fp32 before the one rounding."""
+    _chk_bf16("rows_linear_bias_bf16", tuple(t for t in (x, out) if t is not None), tuple(t for t in (w, bias) if t is not None))
+    _chk("rows_linear_bias_bf16", (), (offsets,))
+    if out is None:
+        out = torch.empty((x.shape[0], w.shape[1]), dtype=torch.bfloat16, device=x.device)
+    if x.shape[-1] != w.shape[0] or out.shape != (x.shape[0], w.shape[1]):
+        raise _lib.HetError(f"rows_linear_bias_bf16: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit w {tuple(w.shape)}")
+    _call(x, "het_rows_linear_bias_bf16", _p(offsets), _p(x), _p(w), _p(bias), _p(out), x.shape[0], w.shape[0], w.shape[1], _stream(x))
+    return out
+
+
+def rgat_el_rows_bf16(rel_ptrs, feat_c, attn_l, el_c):
+    """el_c[u,h] = <feat_c[u,h,:], attn_l[r(u),h,:]> from the rounded bf16 rows (het_rgat_el_rows_bf16): feat_c [S,H,D] bf16,
+    attn_l [R,H,D] and el_c [S,H] fp32."""
+    _chk_bf16("rgat_el_rows_bf16", (feat_c,), (attn_l, el_c))
+    _chk("rgat_el_rows_bf16", (), (rel_ptrs,))
+    S, H, D = feat_c.shape
+    if attn_l.shape[1:] != (H, D) or el_c.shape != (S, H) or rel_ptrs.numel() != attn_l.shape[0] + 1:
+        raise _lib.HetError("rgat_el_rows_bf16: shapes do not match")
+    _call(el_c, "het_rgat_el_rows_bf16", _p(rel_ptrs), attn_l.shape[0], _p(feat_c), _p(attn_l), _p(el_c), S, H, D, _stream(el_c))
+
+
+def rgat_aggregate_compact_forward_bf16(groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l=None, feat_rel_ptrs=None):
+    """rgat_aggregate_compact_forward over bf16 rows (het_rgat_aggregate_compact_forward_bf16): feat_c [S,H,D] and h_inout [rows, H*D]
+    bf16, el_c / er_c / attn_l fp32.  ``el_c`` may be None where the walk forms el from the row it gathers (rgat_el_from_row)."""
+    _chk_bf16("rgat_aggregate_compact_forward_bf16", (feat_c, h_inout), tuple(t for t in (el_c, er_c) if t is not None))
+    if groupings[3] is None:
+        raise _lib.HetError("rgat_aggregate_compact_forward_bf16: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
+    H, D = feat_c.shape[1], feat_c.shape[2]
+    with torch.cuda.device(h_inout.device):
+        nbytes = int(_lib.lib().het_rgat_aggregate_compact_forward_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
+                                                                             _stream(h_inout)))
+    if nbytes < 0:
+        raise _lib.HetError("het_rgat_aggregate_compact_forward_workspace: " + _lib.lib().het_last_error().decode())
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h_inout.device) if nbytes else None
+    host_ptrs = None
+    if attn_l is not None and feat_rel_ptrs is not None:
+        _chk("rgat_aggregate_compact_forward_bf16", (attn_l,), (feat_rel_ptrs,))
+        lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
+        host_ptrs = (C.c_int64 * len(lst))(*lst)
+    _call(h_inout, "het_rgat_aggregate_compact_forward_bf16", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c),
+          _p(el_c), _p(er_c), H, D, float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None,
+          host_ptrs, _p(ws), nbytes, _stream(h_inout))
+
+
 def rows_matmul_backward_split_ok(H: int, K: int, D: int) -> bool:
     """Shapes het_rows_matmul_backward_dx / _dw cover (one input head on the matrix cores)."""
     return K in (32, 64, 128) and H * D in (32, 64, 128)

@@ -48,7 +48,17 @@ class HET_RelGraphEmbed(nn.Module):
 
 
 class HET_RGATLayer(nn.Module):
-    """Relational graph attention layer (RGAT/models.py:16-385)."""
+    """Relational graph attention layer (RGAT/models.py:16-385).
+
+    bf16 activations: a ``torch.bfloat16`` input gives a bf16 output.  Evaluation calls (``torch.no_grad()``, or nothing that
+    reaches the layer requires a gradient) on one GPU run natively in bf16 -- x, the projected rows feat_c and the output rows are
+    bf16, each rounded once where its kernel stores it; the parameters, el / er, the softmax and every sum stay fp32
+    (het_amd/backend/rgat_fused_layer.py) -- for rows of 32 / 64 / 128 (heads of 16 or more after the zero padding of
+    ``_padded_head``), 1 / 2 / 4 / 8 heads and a padded input width of 32 / 64 / 128; er always comes from the folded weight
+    (``HET_RGAT_LITERAL_ER`` does not apply).  Every other bf16 call -- a gradient is required (training still upcasts), a halo,
+    the per-edge dataflow, the op-by-op composition, ``reference_op_sequence``, CPU tensors, other shapes,
+    ``HET_RGAT_FORWARD_ONLY=0`` -- runs the fp32 layer on ``x.float()`` and casts the result; autograd casts the gradient of the
+    input back to bf16.  That fallback is correct, not faster."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_heads, *, bias=True, activation=None, self_loop=False,
                  compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
@@ -101,6 +111,9 @@ class HET_RGATLayer(nn.Module):
         the features of the owned nodes; the layer runs the halo exchange itself (``halo``: a dist.HaloContext) and overlaps
         it with the work that needs owned rows only.  Returns the owned rows, or None when the one-node path does not
         cover the configuration (the caller then exchanges first and calls forward)."""
+        if x_own.dtype == th.bfloat16:  # no bf16 form with a halo: the fp32 layer on an upcast copy, the result cast
+            h = self.forward_with_halo(g, x_own.float(), halo)
+            return None if h is None else h.to(th.bfloat16)
         if not (self.gat_edge_parallel_flag and self.self_loop and not self.reference_op_sequence and
                 FL.rgat_layer_halo_ok(g, x_own, self.conv_weights, self.leaky_relu_slope, self.compact_as_of_node_flag,
                                       self.multiply_among_weights_first_flag)):
@@ -151,9 +164,34 @@ class HET_RGATLayer(nn.Module):
             h = self.activation(h)
         return self.dropout(h)
 
+    def _bf16_native(self, g, inputs):
+        """(input width K', head width D') the bf16 evaluation path runs with -- the padding of _padded_head, zero columns -- or None:
+        the call is served by the fp32 layer on an upcast copy."""
+        if self.reference_op_sequence or self.op_by_op or not (self.gat_edge_parallel_flag and inputs.is_cuda and inputs.dim() == 2):
+            return None
+        H, D, K = self.num_heads, self.out_feat // self.num_heads, self.in_feat
+        Kp, Dp = self._padded_head(g, inputs) or (K, D)
+        shape = th.empty((self.num_rels, H, Kp, Dp), device="meta")
+        ok = FL.rgat_layer_bf16_ok(g, inputs, shape, self.leaky_relu_slope, self.compact_as_of_node_flag,
+                                   self.multiply_among_weights_first_flag, (inputs,) + tuple(self.parameters()))
+        return (Kp, Dp) if ok else None
+
     def forward(self, g, inputs: th.Tensor, num_dst=None):
         """``num_dst``: the destination nodes of ``g`` are its first ``num_dst`` nodes (a sampled block, or the owned
         nodes of a partition followed by halo nodes): only their rows are returned and the self-loop runs on them only."""
+        if inputs.dtype == th.bfloat16:
+            KDp = self._bf16_native(g, inputs)
+            if KDp is None:  # correct, not faster: the fp32 layer on an upcast copy (autograd casts the gradient of the input)
+                return self.forward(g, inputs.float(), num_dst).to(th.bfloat16)
+            if KDp != (self.in_feat, self.out_feat // self.num_heads):
+                return self._forward_padded(g, inputs, num_dst, KDp)
+            h = FL.rgat_layer_fused(g, inputs, self.conv_weights, self.attn_l, self.attn_r,
+                                    self.loop_weight if self.self_loop else None, self.h_bias if self.bias else None,
+                                    self.leaky_relu_slope, self.compact_as_of_node_flag, self.compact_direct_indexing_flag,
+                                    num_dst, self.multiply_among_weights_first_flag)
+            if self.activation:
+                h = self.activation(h)
+            return self.dropout(h)
         if self.reference_op_sequence:
             assert not self.compact_as_of_node_flag and num_dst is None and self.gat_edge_parallel_flag
             from .backend.reference_protocol import rgat_layer_reference_sequence

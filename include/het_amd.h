@@ -672,6 +672,26 @@ int het_rgat_aggregate_compact_forward(const het_grouping* by_dst, const het_gro
                                        float* h_inout, int64_t h_rows, const float* attn_l, const int64_t* feat_rel_ptrs_host,
                                        void* workspace, int64_t workspace_bytes, het_stream stream);
 
+/* ... with bf16 activation rows (the RGAT layer's evaluation path on a torch.bfloat16 input): feat_c [S_row,H,D] and h_inout
+ * [h_rows, H*D] are het_bf16, both 16-byte aligned (else HET_ERR_INVALID_ARG, nothing enqueued); el_c, er_c, attn_l, the hub records
+ * of the workspace, every maximum, exponential and sum are fp32.  Arguments, checks, shapes and workspace
+ * (het_rgat_aggregate_compact_forward_workspace) are het_rgat_aggregate_compact_forward's.  Rows are widened on load (exact); a
+ * lane holds the same 4 elements of a row as in the fp32 kernels, so the sums are formed in the same order; the one rounding (to
+ * nearest even) is at the store: h_inout[v] = round(widen(h_inout[v]) + SUM_e softmax_v(..)_e widen(feat_c[srow_e])) for every
+ * destination v < h_rows with in-edges, the other rows are not touched.  No float atomics.
+ *   el_c [S_row,H] must hold <widen(feat_c[u,h,:]), attn_l[r(u),h,:]> -- the dots of the ROUNDED rows (het_rgat_el_rows_bf16) --, which
+ *   is the function the walk itself computes where it forms el from the gathered row (attn_l and feat_rel_ptrs_host given, D == 16,
+ *   num_rels <= 8); in that case el_c is never read and may be NULL.
+ * het_rgat_el_rows_bf16: that el_c from feat_c [num_rows,H,D] het_bf16 (rows relation-major, rel_ptrs [num_rels+1] on the device) and
+ *   attn_l [num_rels,H,D]; fp32 products and sums, el_c [num_rows,H] fp32.  Same shapes. */
+int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                            const het_bf16* feat_c, const float* el_c, const float* er_c, int64_t H, int64_t D,
+                                            double slope, het_bf16* h_inout, int64_t h_rows, const float* attn_l,
+                                            const int64_t* feat_rel_ptrs_host, void* workspace, int64_t workspace_bytes,
+                                            het_stream stream);
+int het_rgat_el_rows_bf16(const int64_t* rel_ptrs, int64_t num_rels, const het_bf16* feat_c, const float* attn_l, float* el_c,
+                          int64_t num_rows, int64_t H, int64_t D, het_stream stream);
+
 /* The two halves of a2 (backward_rgnn_relational_matmul, one input head, matrix-core shapes) as separate calls, so that a
  * caller can order them around a collective (het_amd/dist.py).  Rows i in [0, num_rows) of relation-bucketed lists:
  *   dx: grad_x[gather_idx[i], :] (+)= gradout[g_rows[i], :] . Wt[r(i)]      atomic 0: "=";  1: "+=" with float atomics (rows
@@ -697,8 +717,14 @@ int het_rows_matmul_backward_dw_colsum(const int64_t* rel_ptrs, int64_t num_rels
  *   het_rows_matmul_bf16:             out[scatter_idx[i], :] = x[gather_idx[i], :] . weights[r(i)]     x [*,K], out [*,X] het_bf16 (x
  *       widened on load -- exact --, out rounded once at the store), weights [R,K,X] fp32; plain stores (the listed output rows
  *       are distinct); gather_idx / scatter_idx NULL = row i.  K in {32, 64}, X in {32, 64, 128}; else HET_ERR_UNSUPPORTED.
+ *   het_rows_matmul_heads_bf16:       out[i, (h,d)] = x[gather_idx[i], :] . weights[r(i), h, :, d]     the same product with the weight
+ *       in the RGAT layer's head-concatenated layout [R,H,K,D] and out [num_rows, H*D] in list order (feat_c on the distinct
+ *       (relation, node) rows).  K and H*D in {32, 64, 128} (an input width zero-padded to 128 included).
  *   het_rows_matmul_backward_dw_bf16: grad_w[r(i)] (+)= x[gather_idx[i], :]^T (x) gradout[g_rows[i], :]   x [*,K] het_bf16; gradout
- *       [*,X] fp32, or het_bf16 for het_rows_matmul_backward_dw_bf16_bf16; grad_w [R,K,X] fp32.  Same shapes. */
+ *       [*,X] fp32, or het_bf16 for het_rows_matmul_backward_dw_bf16_bf16; grad_w [R,K,X] fp32.  K in {32, 64}, X in {32, 64, 128}.
+ *   het_rows_dot1h_bf16:              out[scatter_idx[i], h] = <x[gather_idx[i], :], weights[r(i), h, :]>     x [*,K] het_bf16 (widened on
+ *       load), weights [R,H,K] and out [*,H] fp32, fp32 products and sums: one input row against the H vectors of its relation (er_c
+ *       of the RGAT layer from the folded weight W . attn_r, no fp32 copy of x).  H in {1, 2, 4, 8}, K a power of two in [4 H, 256]. */
 int het_rows_matmul_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
                          int64_t num_rows, const float* weights, const het_bf16* x, het_bf16* out, int64_t K, int64_t X,
                          het_stream stream);
@@ -708,6 +734,12 @@ int het_rows_matmul_backward_dw_bf16(const int64_t* rel_ptrs, int64_t num_rels, 
 int het_rows_matmul_backward_dw_bf16_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* g_rows,
                                           int64_t num_rows, const het_bf16* x, const het_bf16* gradout, float* grad_w, int64_t K,
                                           int64_t X, int accumulate, het_stream stream);
+int het_rows_matmul_heads_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, int64_t num_rows,
+                               const float* weights, const het_bf16* x, het_bf16* out, int64_t H, int64_t K, int64_t D,
+                               het_stream stream);
+int het_rows_dot1h_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
+                        int64_t num_rows, const float* weights, const het_bf16* x, float* out, int64_t H, int64_t K,
+                        het_stream stream);
 
 /* ------------------------------------------------------------------------
  * Node-major input gradient of the one-node RGAT layer (layer-level fusion; no reference op of its own).  It replaces,
@@ -812,6 +844,10 @@ int het_rgcn_layer_backward_bf16(const het_grouping* by_rel_src, const het_group
  * Matrix-core shapes only (HET_ERR_UNSUPPORTED otherwise). */
 int het_rows_linear_bias(const int64_t* offsets, const float* x, const float* w, const float* bias, float* out,
                          int64_t num_rows, int64_t K, int64_t X, het_stream stream);
+/* ... with bf16 rows: x [*,K] and out [*,X] het_bf16 (x widened on load, out rounded once at the store), w and bias fp32; the bias is
+ * added in fp32 BEFORE the rounding.  K and X in {32, 64, 128}, 16-byte aligned tensors (HET_ERR_UNSUPPORTED otherwise). */
+int het_rows_linear_bias_bf16(const int64_t* offsets, const het_bf16* x, const float* w, const float* bias, het_bf16* out,
+                              int64_t num_rows, int64_t K, int64_t X, het_stream stream);
 
 /* layer epilogue (RGAT/models.py:377-383: h + loop_message + h_bias): out[i,:] = a[i,:] (+ b[i,:]) (+ bias[:]) in one
  * pass; b and bias optional, X % 4 == 0 */
