@@ -58,6 +58,8 @@ _SIGNATURES = {
     "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
+    "het_rgat_attention_compact_workspace": [P, I64, I64, INT],  # (returns bytes: restype set in lib())
+    "het_rgat_attention_compact": [P, P, P, I64, DBL, P, P, P, P, I64, I64, P, P, P, I64, P],
     "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
     "het_rows_matmul_heads_bf16": [P, I64, P, I64, P, P, P, I64, I64, I64, P],
     "het_rows_dot1h_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
@@ -159,6 +161,7 @@ def lib() -> C.CDLL:
             f.argtypes = args
             f.restype = INT
         L.het_rgat_aggregate_compact_forward_workspace.restype = I64
+        L.het_rgat_attention_compact_workspace.restype = I64
         _lib = L
     return _lib
 

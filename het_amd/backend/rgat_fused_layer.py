@@ -35,6 +35,10 @@ weight there (HET_RGAT_LITERAL_ER does not apply: the literal form needs a secon
 ROUNDED feat_c row, so the walks that form el from the row they gather and those that gather el_c compute one function.  Every
 other bf16 call (gradients required, halo, per-edge dataflow, other shapes) is served by the fp32 layer on an upcast copy
 (het_amd/layers.py): correct, not faster.
+
+Attention weights (the layer's get_attention=True): both evaluation functions append attn [E,H] (fp32, edge-id order) to the list
+they are handed -- a pass over the ids, el_c and er_c after the aggregation (csrc/gat_attention.hip); the autograd node does not, and
+the layer composes them in torch (attention_composition): correct, not fast.
 """
 import os
 
@@ -99,12 +103,22 @@ def _compact_dicts(g, direct):
     return ss, 3, fwd, bwd
 
 
+def _eids_are_positions(eids):
+    """Whether eids[p] == p for every position (what canonicalize_eids leaves; checked once per list)."""
+    return _k._derived_get("eids_are_positions", (eids,),
+                           lambda: bool((eids == th.arange(eids.numel(), device=eids.device)).all()))
+
+
 def _edge_rows(g, ss, direct, rp, row, col, eids):
     """(feat row, er row) of every edge position, [E] int64 each: the graph's inverse indices when it carries them
     (indexed by edata id == position after canonicalize_eids), else located in the unique lists once and cached."""
     sep = getattr(g, "graph_data", {}).get("separate", {}).get("unique_node_indices_single_sided", {})
     if "inverse_indices_row" in sep and getattr(g, "sequential_eids_format", None) == "separate_coo":
-        return sep["inverse_indices_row"], sep["inverse_indices_col"]
+        if _eids_are_positions(eids):
+            return sep["inverse_indices_row"], sep["inverse_indices_col"]
+        # (edge ids renumbered after the lists were built: the inverse indices are read by edge id)
+        maps = (sep["inverse_indices_row"], None, sep["inverse_indices_col"], None)
+        return _k._src_rows_by_position(4, maps, rp, row, eids), _k._dst_rows_by_position(4, maps, rp, col, eids)
     maps = (ss["rel_ptrs_row"], ss["node_indices_row"], ss["rel_ptrs_col"], ss["node_indices_col"])
     return _k._src_rows_by_position(3, maps, rp, row, eids), _k._dst_rows_by_position(3, maps, rp, col, eids)
 
@@ -594,11 +608,20 @@ def rgat_layer_halo_ok(g, x_own, W, slope, compact, mulfirst=False):
     return c and m and _k.rows_linear_bias_ok(Kd, H * D) and _k.rows_matmul_backward_split_ok(H, Kd, D)
 
 
-def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+def _attention_rows(g, ss, direct, grp, elc, erc, slope, N):
+    """attn [E,H] in edge-id order from the tables an evaluation forward holds (csrc/gat_attention.hip): a pass over the ids, el_c
+    and er_c alone, enqueued after the aggregation."""
+    s, _, _ = _lists(g)
+    rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
+    srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
+    return _k.rgat_attention_compact(grp, elc, erc, slope, col, srow, drow, None if _eids_are_positions(eids) else eids, N)
+
+
+def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
     """RgatLayerFunction.forward on the distinct-row dataflow when no backward can follow: a plain function (no autograd node,
     nothing saved), the same projections and the same self-loop rows, and an aggregation that writes the layer output alone
     (csrc/gat_compact.hip: the _fwd kernels) -- no lse [N,H], no ret [N,H,D], no run sums [S_col,H,D].  Every output row is bit
-    for bit the training forward's."""
+    for bit the training forward's.  ``attn_out`` (a list): the attention weights [E,H] are appended to it."""
     x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
     N = x.shape[0]
     R, H, Kd, D = W.shape
@@ -615,6 +638,8 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     if not fused:  # no self-loop rows to add into (no self-loop, or widths its fused launch does not take): zeros, the tail below
         h = x.new_zeros((nd, X))
     _k.rgat_aggregate_compact_forward(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
+    if attn_out is not None:
+        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, N))
     if fused:
         return h
     loop = None
@@ -625,11 +650,12 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     return _k.rows_add_bias(h, loop, None if bias is None else bias.contiguous()) if (loop is not None or bias is not None) else h
 
 
-def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
     """_forward_only for a bf16 input (the module docstring has the precision contract): feat_c [S_row,H,D] and h [nd,X] are bf16
     rows, no fp32 copy of x, feat_c or h is made, and the aggregation rounds h once more where it adds a destination's row in place.
     The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
-    instead of the projection's epilogue."""
+    instead of the projection's epilogue.  ``attn_out`` (a list): the attention weights [E,H] (fp32) are appended to it; where the
+    walk formed el from the row it gathered, el_c is made for them by the same row-dot pass, so they are the softmax the output used."""
     x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
     s, _, _ = _lists(g)
     rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
@@ -671,6 +697,11 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp,
                                     drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
     _k.rgat_aggregate_compact_forward_bf16(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
+    if attn_out is not None:
+        if elc is None:
+            elc = th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
+            _k.rgat_el_rows_bf16(ss["rel_ptrs_row"], featc, attn_l, elc)
+        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, N))
     return h
 
 
@@ -700,15 +731,50 @@ def _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
     return _k.rgat_runs_shape_ok(H, D) and x.shape[0] * R < 2 ** 31
 
 
-def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, direct, num_dst=None, mulfirst=False, halo=None):
+def attention_composition(g, x, W, attn_l, attn_r, slope):
+    """The attention weights [E,H] (float32, edge-id order) of the layer as a plain torch composition under no_grad, in fp32 whatever
+    the input type: per-relation projections of the distinct source / destination nodes, exponentials relative to the destination's
+    maximum summed with index_add, a divide.  For every call the evaluation kernels do not serve (a gradient is required, halo,
+    per-edge dataflow, op by op, the reference's op sequence, CPU tensors, other shapes): correct, not fast -- R small GEMMs and
+    several [E,H] temporaries."""
+    with th.no_grad():
+        s = g.get_separate_coo_original()
+        rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
+        x, W, attn_l, attn_r = x.detach().float(), W.detach().float(), attn_l.detach().float(), attn_r.detach().float()
+        R, H, Kd, D = W.shape
+        E, N = row.numel(), x.shape[0]
+        z = x.new_empty((E, H))
+        for r, (a, b) in enumerate(zip(rp[:-1].tolist(), rp[1:].tolist())):
+            if a == b:
+                continue
+            Wr = W[r].permute(1, 0, 2).reshape(Kd, H * D)
+            src, isrc = th.unique(row[a:b], return_inverse=True)
+            dst, idst = th.unique(col[a:b], return_inverse=True)
+            el = ((x[src] @ Wr).view(-1, H, D) * attn_l[r]).sum(-1)
+            er = ((x[dst] @ Wr).view(-1, H, D) * attn_r[r]).sum(-1)
+            z[a:b] = el[isrc] + er[idst]
+        sc = th.where(z > 0, z, z * slope)
+        idx = col.unsqueeze(-1).expand(-1, H)
+        m = th.full((N, H), -float("inf"), dtype=sc.dtype, device=sc.device).scatter_reduce(0, idx, sc, "amax")
+        w = th.exp(sc - m[col])
+        den = th.zeros((N, H), dtype=sc.dtype, device=sc.device).index_add_(0, col, w)
+        attn = th.empty_like(w)
+        attn[eids] = w / den[col]
+        return attn
+
+
+def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, direct, num_dst=None, mulfirst=False, halo=None,
+                     attn_out=None):
+    """``attn_out`` (a list, optional): on the evaluation paths the attention weights [E,H] are appended to it (_forward_only /
+    _forward_only_bf16); the autograd node leaves it empty and the caller composes them (attention_composition)."""
     compact, direct, mulfirst = effective_flags(g, W, compact, direct, mulfirst)
     if compact and not _has_single_sided_lists(g):
         g.generate_separate_unique_node_indices_single_sided_for_each_etype()
     if x.dtype == th.bfloat16:  # (the caller has asked rgat_layer_bf16_ok: there is no bf16 form of anything else)
         assert compact and halo is None, "rgat_layer_bf16_ok guards this path"
         with th.no_grad():
-            return _forward_only_bf16(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
+            return _forward_only_bf16(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
     if _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
         with th.no_grad():
-            return _forward_only(g, direct, mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
+            return _forward_only(g, direct, mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
     return RgatLayerFunction.apply(g, compact, direct, mulfirst, float(slope), num_dst, halo, x, W, attn_l, attn_r, loop_w, bias)

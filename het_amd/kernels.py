@@ -799,6 +799,32 @@ def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope
           _p(ws), nbytes, _stream(h_inout))
 
 
+def rgat_attention_compact(groupings, el_c, er_c, slope, col, srow, drow, eids, num_nodes, lse_out=None, attn=None):
+    """The attention weights of the compact RGAT layer (include/het_amd.h: het_rgat_attention_compact): attn [E,H] float32 with
+    attn[eids[p], h] = softmax over the in-edges of col[p] of leaky(el_c[srow[p], h] + er_c[drow[p], h]) -- row p when ``eids`` is
+    None.  ``groupings``: rgat_compact_groupings of the same (col, srow, drow); el_c [S_row,H] / er_c [S_col,H] float32 (the bf16
+    layer's too).  ``lse_out`` [num_nodes,H] (optional) receives the log-sum-exp of every destination (-inf without in-edges).
+    Returns attn (allocated unless given)."""
+    ids = tuple(t for t in (col, srow, drow, eids) if t is not None)
+    _chk("rgat_attention_compact", tuple(t for t in (el_c, er_c, lse_out, attn) if t is not None), ids)
+    E, H = col.numel(), el_c.shape[1]
+    if attn is None:
+        attn = torch.empty((E, H), dtype=torch.float32, device=el_c.device)
+    if (er_c.shape[1] != H or attn.shape != (E, H) or any(t.numel() != E for t in ids)
+            or (lse_out is not None and lse_out.shape != (num_nodes, H))):
+        raise _lib.HetError(f"rgat_attention_compact: el_c {tuple(el_c.shape)}, er_c {tuple(er_c.shape)}, attn {tuple(attn.shape)} and "
+                            f"{E} edges / {num_nodes} nodes do not fit")
+    if E == 0:
+        return attn
+    nbytes = int(_lib.lib().het_rgat_attention_compact_workspace(groupings[0].handle, H, int(num_nodes), int(lse_out is not None)))
+    if nbytes < 0:
+        raise _lib.HetError(f"rgat_attention_compact: unsupported shape H={H} (1, 2, 4 or 8 heads)")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=attn.device) if nbytes else None
+    _call(attn, "het_rgat_attention_compact", groupings[0].handle, _p(el_c), _p(er_c), H, float(slope), _p(col), _p(srow), _p(drow),
+          _p(eids), E, int(num_nodes), _p(lse_out), _p(attn), _p(ws), nbytes, _stream(attn))
+    return attn
+
+
 # ---- the RGAT layer's evaluation path with bf16 activations (backend/rgat_fused_layer.py: _forward_only_bf16) ----
 def rgat_bf16_shape_ok(H: int, K: int, D: int) -> bool:
     """Shapes the bf16 evaluation path covers: the run-sum form's rows (32 / 64 / 128 wide, heads of at least 16), a (padded) input

@@ -58,7 +58,14 @@ class HET_RGATLayer(nn.Module):
     (``HET_RGAT_LITERAL_ER`` does not apply).  Every other bf16 call -- a gradient is required (training still upcasts), a halo,
     the per-edge dataflow, the op-by-op composition, ``reference_op_sequence``, CPU tensors, other shapes,
     ``HET_RGAT_FORWARD_ONLY=0`` -- runs the fp32 layer on ``x.float()`` and casts the result; autograd casts the gradient of the
-    input back to bf16.  That fallback is correct, not faster."""
+    input back to bf16.  That fallback is correct, not faster.
+
+    Attention weights: ``forward(..., get_attention=True)`` returns ``(h, attn)`` -- attn [E, num_heads] float32, detached, row i the
+    softmax weight of the edge with id i (the graph's eids, whatever order the edges are stored in) among the in-edges of its
+    destination; every row is filled, on a block too.  On the evaluation paths (fp32 and bf16) a HIP pass over the ids and the el /
+    er tables writes them after the aggregation (csrc/gat_attention.hip); every other call -- a gradient is required, a halo, the
+    per-edge dataflow, op by op, ``reference_op_sequence``, CPU tensors, other shapes -- gets them from a plain torch composition
+    in fp32 under no_grad (rgat_fused_layer.attention_composition): correct, not fast.  No gradient flows through attn."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_heads, *, bias=True, activation=None, self_loop=False,
                  compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
@@ -148,7 +155,7 @@ class HET_RGATLayer(nn.Module):
                                     self.multiply_among_weights_first_flag)
         return (Kp, Dp) if ok else None
 
-    def _forward_padded(self, g, inputs, num_dst, KDp, halo=None):
+    def _forward_padded(self, g, inputs, num_dst, KDp, halo=None, attn_out=None):
         H, D, K = self.num_heads, self.out_feat // self.num_heads, self.in_feat
         Kp, Dp = KDp
         pad = (0, Dp - D)
@@ -158,7 +165,8 @@ class HET_RGATLayer(nn.Module):
         loop = nn.functional.pad(self.loop_weight.view(K, H, D), pad + (0, 0, 0, Kp - K)).view(Kp, H * Dp) if self.self_loop else None
         bias = nn.functional.pad(self.h_bias.view(H, D), pad).view(H * Dp) if self.bias else None
         h = FL.rgat_layer_fused(g, x, W, al, ar, loop, bias, self.leaky_relu_slope, self.compact_as_of_node_flag,
-                                self.compact_direct_indexing_flag, num_dst, self.multiply_among_weights_first_flag, halo=halo)
+                                self.compact_direct_indexing_flag, num_dst, self.multiply_among_weights_first_flag, halo=halo,
+                                attn_out=attn_out)
         h = h.view(h.shape[0], H, Dp)[:, :, :D].reshape(h.shape[0], self.out_feat)
         if self.activation:
             h = self.activation(h)
@@ -176,19 +184,30 @@ class HET_RGATLayer(nn.Module):
                                    self.multiply_among_weights_first_flag, (inputs,) + tuple(self.parameters()))
         return (Kp, Dp) if ok else None
 
-    def forward(self, g, inputs: th.Tensor, num_dst=None):
+    def forward(self, g, inputs: th.Tensor, num_dst=None, get_attention=False):
         """``num_dst``: the destination nodes of ``g`` are its first ``num_dst`` nodes (a sampled block, or the owned
-        nodes of a partition followed by halo nodes): only their rows are returned and the self-loop runs on them only."""
+        nodes of a partition followed by halo nodes): only their rows are returned and the self-loop runs on them only.
+        ``get_attention``: return ``(h, attn)``, attn [E, num_heads] float32 in edge-id order (the class docstring)."""
+        if not get_attention:
+            return self._forward(g, inputs, num_dst)
+        attn_out = []
+        h = self._forward(g, inputs, num_dst, attn_out)
+        if not attn_out:  # the call did not take an evaluation path: correct, not fast
+            attn_out.append(FL.attention_composition(g, inputs, self.conv_weights, self.attn_l, self.attn_r, self.leaky_relu_slope))
+        return h, attn_out[0]
+
+    def _forward(self, g, inputs, num_dst=None, attn_out=None):
+        """forward; ``attn_out`` (a list): where the call takes an evaluation path, the attention weights are appended to it."""
         if inputs.dtype == th.bfloat16:
             KDp = self._bf16_native(g, inputs)
             if KDp is None:  # correct, not faster: the fp32 layer on an upcast copy (autograd casts the gradient of the input)
-                return self.forward(g, inputs.float(), num_dst).to(th.bfloat16)
+                return self._forward(g, inputs.float(), num_dst, attn_out).to(th.bfloat16)
             if KDp != (self.in_feat, self.out_feat // self.num_heads):
-                return self._forward_padded(g, inputs, num_dst, KDp)
+                return self._forward_padded(g, inputs, num_dst, KDp, attn_out=attn_out)
             h = FL.rgat_layer_fused(g, inputs, self.conv_weights, self.attn_l, self.attn_r,
                                     self.loop_weight if self.self_loop else None, self.h_bias if self.bias else None,
                                     self.leaky_relu_slope, self.compact_as_of_node_flag, self.compact_direct_indexing_flag,
-                                    num_dst, self.multiply_among_weights_first_flag)
+                                    num_dst, self.multiply_among_weights_first_flag, attn_out=attn_out)
             if self.activation:
                 h = self.activation(h)
             return self.dropout(h)
@@ -198,7 +217,7 @@ class HET_RGATLayer(nn.Module):
             return rgat_layer_reference_sequence(self, g, inputs)
         KDp = self._padded_head(g, inputs)
         if KDp is not None:
-            return self._forward_padded(g, inputs, num_dst, KDp)
+            return self._forward_padded(g, inputs, num_dst, KDp, attn_out=attn_out)
         if (self.gat_edge_parallel_flag and not self.op_by_op and
                 FL.rgat_layer_fused_ok(g, inputs, self.conv_weights, self.leaky_relu_slope, self.compact_as_of_node_flag,
                                        self.multiply_among_weights_first_flag)):
@@ -207,7 +226,7 @@ class HET_RGATLayer(nn.Module):
             h = FL.rgat_layer_fused(g, inputs, self.conv_weights, self.attn_l, self.attn_r,
                                     self.loop_weight if self.self_loop else None, self.h_bias if self.bias else None,
                                     self.leaky_relu_slope, self.compact_as_of_node_flag, self.compact_direct_indexing_flag,
-                                    num_dst, self.multiply_among_weights_first_flag)
+                                    num_dst, self.multiply_among_weights_first_flag, attn_out=attn_out)
             if self.activation:
                 h = self.activation(h)
             return self.dropout(h)

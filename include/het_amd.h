@@ -692,6 +692,30 @@ int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_dst, const he
 int het_rgat_el_rows_bf16(const int64_t* rel_ptrs, int64_t num_rels, const het_bf16* feat_c, const float* attn_l, float* el_c,
                           int64_t num_rows, int64_t H, int64_t D, het_stream stream);
 
+/* The attention weights the aggregations above form and discard, as an output (DGL's get_attention, PyG's
+ * return_attention_weights): a pass of its own over the ids and the two small tables -- it never reads a feat_c row, and it runs
+ * after either evaluation entry (el_c / er_c are fp32 in the bf16 layer too; everything here is fp32).
+ *   attn [num_edges, H] (required): attn[row(p), h] = exp(leaky(el_c[srow[p], h] + er_c[drow[p], h]) - lse[col[p], h]) for every edge
+ *     position p, row(p) = eids[p], or p when eids is NULL; eids must be a permutation of [0, num_edges).  Every row is written.
+ *   lse_out [num_nodes, H] (optional): lse[v, h] = log SUM_{p: col[p] == v} exp(leaky(..)), formed relative to a running maximum (any
+ *     score is safe); -inf for a destination without in-edges.  Without it the rows live in the workspace.
+ *   by_dst: the grouping of the positions by destination with payload0 = srow and payload1 = drow (the one
+ *     het_rgat_aggregate_compact_forward takes); col / srow / drow / eids [num_edges] int64 on the device are the lists it was built
+ *     from.  Destinations of more than 256 in-edges are split over work items whose {max[H], sum[H]} records meet in a finishing
+ *     launch, in a fixed order: no float atomics, the same bits from run to run.
+ *   H in {1, 2, 4, 8}, num_nodes and num_edges below 2^31: HET_ERR_UNSUPPORTED otherwise.  A null grouping, a null el_c / er_c / col /
+ *     srow / drow / attn, a pointer off its alignment (16 bytes for the float tensors and the workspace, 8 for the id lists), a
+ *     grouping of another shape and a workspace that is too small are HET_ERR_INVALID_ARG; nothing is enqueued before these checks
+ *     pass.  num_edges == 0: HET_OK, nothing is touched; by_dst is still required then (and must group no positions), no other
+ *     pointer is looked at.
+ *   workspace: het_rgat_attention_compact_workspace(by_dst, H, num_nodes, lse_out != NULL) bytes, 16-byte aligned -- the lse rows
+ *     when lse_out is NULL, and one {max[H], sum[H]} record per work item when the grouping has split destinations; -1 on error. */
+int64_t het_rgat_attention_compact_workspace(const het_grouping* by_dst, int64_t H, int64_t num_nodes, int with_lse_out);
+int het_rgat_attention_compact(const het_grouping* by_dst, const float* el_c, const float* er_c, int64_t H, double slope,
+                               const int64_t* col, const int64_t* srow, const int64_t* drow, const int64_t* eids, int64_t num_edges,
+                               int64_t num_nodes, float* lse_out, float* attn, void* workspace, int64_t workspace_bytes,
+                               het_stream stream);
+
 /* The two halves of a2 (backward_rgnn_relational_matmul, one input head, matrix-core shapes) as separate calls, so that a
  * caller can order them around a collective (het_amd/dist.py).  Rows i in [0, num_rows) of relation-bucketed lists:
  *   dx: grad_x[gather_idx[i], :] (+)= gradout[g_rows[i], :] . Wt[r(i)]      atomic 0: "=";  1: "+=" with float atomics (rows
