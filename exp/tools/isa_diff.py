@@ -2,12 +2,17 @@
 """Device code of two source trees, kernel by kernel: the proof a refactor of het_amd/csrc owes.
 
     git worktree add /tmp/parent HEAD~1
-    python3 exp/tools/isa_diff.py /tmp/parent/het_amd/csrc het_amd/csrc [--rename 8CsrItems=5Items] [--keep DIR] [-j N]
+    python3 exp/tools/isa_diff.py /tmp/parent/het_amd/csrc het_amd/csrc [--rename 8CsrItems=5Items] [--rename-re 'REGEX=REPL']
+                                  [--keep DIR] [-j N]
 
 Compiles every file of the Makefile's SRCS in both trees with the Makefile's flags plus --cuda-device-only -S and compares
 the set of kernel symbols and the text of every kernel, label to .end_amdhsa_kernel (descriptor included).  --rename
 rewrites a substring of the OLD tree's assembly first (a renamed parameter type changes the mangled names).  The
-per-translation-unit __hip_cuid_<hash> symbol lies outside the kernels and is not compared.  One summary line per file;
+--rename-re maps the OLD tree's kernels by their DEMANGLED names (c++filt), for a change that plain substitution on mangled names
+cannot follow -- a template argument added to a kernel turns parameter types into substitutions (PKT_) and renumbers the ones
+after them: e.g. --rename-re '(HET_rgat_\w+_fwd)_bf16<=\1<unsigned short, ' --rename-re '(HET_rgat_\w+_fwd)<(?!unsigned)=\1<float, '.  With
+it both trees' kernels are keyed by demangled name and the symbol in the kernel's own text (its .amdhsa_kernel line) is replaced by
+that key; everything else is compared as it is.  The per-translation-unit __hip_cuid_<hash> symbol lies outside the kernels and is not compared.  One summary line per file;
 exit status 1 when anything differs.
 
 --local-labels: block labels are .LBB<n>_<block> with n the function's ordinal in its module, so a kernel ADDED to a file renumbers
@@ -36,6 +41,19 @@ def kernels(path):  # isa_stats' parser also returns device functions and data l
     return ks
 
 
+def by_demangled(ks, renames):  # {symbol: body} -> {demangled (and renamed) name: body with the symbol replaced by it}, names changed
+    names = subprocess.run(["c++filt"], input="\n".join(ks), capture_output=True, text=True, check=True).stdout.split("\n")
+    out, changed = {}, 0
+    for (sym, body), name in zip(ks.items(), names):
+        key = name
+        for pat, to in renames:
+            key = re.sub(pat, to, key)
+        changed += key != name
+        assert key not in out, key
+        out[key] = [line.replace(sym, key) for line in body]
+    return out, changed
+
+
 def make_var(csrc, name):
     m = re.search(rf"^{name}\s*\??:?=\s*(.*)$", (Path(csrc) / "Makefile").read_text(), re.M)
     return m.group(1).strip()
@@ -53,6 +71,7 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("--rename-re", action="append", default=[], metavar="REGEX=REPL", help="on the old tree's demangled kernel names")
     ap.add_argument("--keep", help="directory for the .s files (default: a temporary one)")
     ap.add_argument("-j", type=int, default=8)
     ap.add_argument("--local-labels", action="store_true", help="ignore the function ordinal in block labels (see above)")
@@ -77,6 +96,9 @@ def main():
             text = text.replace(frm, to)
         o.write_text(text)
         ko, kn = kernels(o), kernels(n)
+        if a.rename_re:
+            ko, changed = by_demangled(ko, [r.split("=", 1) for r in a.rename_re])
+            kn, renamed = by_demangled(kn, [])[0], renamed + changed
         only_old, only_new = sorted(set(ko) - set(kn)), sorted(set(kn) - set(ko))
         differ = sorted(k for k in set(ko) & set(kn) if ko[k] != kn[k])
         same = len(set(ko) & set(kn)) - len(differ)

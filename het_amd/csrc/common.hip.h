@@ -277,6 +277,15 @@ __device__ __forceinline__ void strow2(float* p, float a, float b) { *reinterpre
 __device__ __forceinline__ void strow2(het_bf16* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = f32x2_to_bf16x2(a, b); }
 __device__ __forceinline__ void strow1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void strow1(het_bf16* p, float v) { *p = __builtin_bit_cast(het_bf16, (__bf16)v); }
+// ... at a byte offset off a wave-uniform base (ld4_at / st4_at above, for either row type)
+template <typename O, typename T>
+__device__ __forceinline__ float4 ldrow4_at(const T* base, O byte_off) {
+  return ldrow4(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off));
+}
+template <typename O, typename T>
+__device__ __forceinline__ void strow4_at(T* base, O byte_off, float4 v) {
+  strow4(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off), v);
+}
 
 constexpr int het_log2_ce(int v) { return v <= 1 ? 0 : 1 + het_log2_ce(v >> 1); }
 // rows * row_bytes fits an unsigned 32-bit byte offset (with room for the lane's piece of the row)

@@ -748,13 +748,19 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
 // stores where a run ends) and the ret / lse stores are gone; where a destination ends there is one store, h_inout[dst] = h0 + acc *
 // rcp(ssum).  Everything that reaches that row is the training kernel's arithmetic, operation for operation.  A copy and not an
 // instance of one body: as a shared __device__ body (or under `if constexpr`) the compiler scheduled the TRAINING instances
-// differently (same instructions, another order), and their code is to stay what it was measured as.
-template <int LPR, int DL, bool ELR, bool W64>
+// differently (same instructions, another order), and their code is to stay what it was measured as.  (That is about what such a
+// body REMOVES -- stores, live values.  The row type below removes nothing and re-types two pointers: its float and het_bf16
+// instances are, instruction for instruction, the code of the separate kernels they were first written as -- DESIGN.md 4.2.)
+// T: the element type of feat_c [S_row,X] and h_inout [rows,X], float or het_bf16 (het_rgat_aggregate_compact_forward_bf16).  A lane
+// holds 4 elements of a row either way (16 or 8 bytes: ldrow4 / strow4), bf16 widened on load, so every sum is the same fp32
+// arithmetic in the same order; el_c / er_c, the hub records, maxima, exponentials and sums are fp32.  The one rounding is where a
+// destination's row is stored: h_inout[v] = round(widen(h_inout[v]) + acc * rcp(sum)).
+template <typename T, int LPR, int DL, bool ELR, bool W64>
 __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd(
-    Packs pk, const int4* __restrict__ kp01, const float* __restrict__ feat, const float* __restrict__ el,
-    const float* __restrict__ er, float slope, float* __restrict__ hio, int hio_rows, int hub_min, ElFold ef) {
+    Packs pk, const int4* __restrict__ kp01, const T* __restrict__ feat, const float* __restrict__ el,
+    const float* __restrict__ er, float slope, T* __restrict__ hio, int hio_rows, int hub_min, ElFold ef) {
   constexpr int EPW = 64 / LPR, U = 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);
+  constexpr int RS = het_log2_ce(LPR * 4 * (int)sizeof(T)), HS = het_log2_ce(H * 4);  // log2 of the bytes of a feature row / of an fp32 [.,H] row
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
@@ -765,7 +771,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd(
   }
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sub = lane % LPR, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 16), hb = (O)(h * 4);
+  const O xb = (O)(sub * 4 * (int)sizeof(T)), hb = (O)(h * 4);
   const int dq = d < U ? d : U - 1;
   const int64_t pid = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW + slot;
   if (pid >= pk.n) return;
@@ -780,7 +786,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd(
     zl = ELR ? 0.f : ld1_at<O>(el, ((O)id.y << HS) | hb);
     zr = ld1_at<O>(er, ((O)id.z << HS) | hb);
 #pragma unroll
-    for (int q = 0; q < U; ++q) f[q] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RS) | xb);
+    for (int q = 0; q < U; ++q) f[q] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RS) | xb);
   };
   auto step = [&](int j0, const int4& id, const float4 (&f)[U], float zlv, float zrv) {
     const int dstv = id.x, tagv = id.w;
@@ -791,9 +797,9 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd(
         const int tagq = head_bcast_i<DL>(tagv, q, lane);
         if (tagq & HET_TAG_FIRST_KEY) {  // the destination's row of the layer output so far
           const int dstq = head_bcast_i<DL>(dstv, q, lane);
-          if (dstq < hio_rows) h0 = ld4_at<O>(hio, ((O)dstq << RS) | xb);
+          if (dstq < hio_rows) h0 = ldrow4_at<O>(hio, ((O)dstq << RS) | xb);
         }
-        if (ELR) {
+        if (ELR) {  // (bf16: el from the ROUNDED row, as the row-dot pass forms el_c for the shapes that gather it)
           const int rel = tagq >> HET_TAG_REL_SHIFT;
           if (rel != rel_cur) {
             a4 = al_s[rel * LPR + sub];
@@ -804,10 +810,10 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd(
         } else {
           online_edge(head_bcast<DL>(sv, q, lane), f[q], m, acc, ssum);
         }
-        if (tagq & HET_TAG_LAST_KEY) {  // the destination ends with this edge: its row of the layer output, nothing else
+        if (tagq & HET_TAG_LAST_KEY) {  // the destination ends with this edge: its row of the layer output (rounded once), nothing else
           const int dstq = head_bcast_i<DL>(dstv, q, lane);
           const float inv = __builtin_amdgcn_rcpf(ssum);
-          if (dstq < hio_rows) st4_at<O>(hio, ((O)dstq << RS) | xb, add_mul_rounded4(h0, acc, inv));
+          if (dstq < hio_rows) strow4_at<O>(hio, ((O)dstq << RS) | xb, add_mul_rounded4(h0, acc, inv));
           acc = make_float4(0.f, 0.f, 0.f, 0.f);
           ssum = 0.f;
           m = -INFINITY;
@@ -926,20 +932,20 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items(
   if (d == 0) { pp[2 * X + h] = m; pp[2 * X + H + h] = ssum; pp[2 * X + 2 * H + h] = sq; }
 }
 
-// ... when no backward follows: part[k] = {O[X], max[H], sum[H]}
-template <int LPR, int DL, bool ELR, bool W64>
+// ... when no backward follows: part[k] = {O[X], max[H], sum[H]}, fp32 whatever the row type T of feat
+template <typename T, int LPR, int DL, bool ELR, bool W64>
 __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items_fwd(
     Items it, const int32_t* __restrict__ hub_items, const int32_t* __restrict__ hub_order, int64_t num_hub_items,
-    const int2* __restrict__ p01, const float* __restrict__ feat, const float* __restrict__ el, const float* __restrict__ er,
+    const int2* __restrict__ p01, const T* __restrict__ feat, const float* __restrict__ el, const float* __restrict__ er,
     float slope, float* __restrict__ part, ElFold ef) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);
+  constexpr int RS = het_log2_ce(LPR * 4 * (int)sizeof(T)), HS = het_log2_ce(H * 4);
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 16), hb = (O)(h * 4);
+  const O xb = (O)(sub * 4 * (int)sizeof(T)), hb = (O)(h * 4);
   const int dq = d < U ? d : U - 1;
   const int64_t kk = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (kk >= num_hub_items) return;
@@ -958,7 +964,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items_fwd(
     float zlv = ELR ? 0.f : ld1_at<O>(el, ((O)srowv << HS) | hb);
     float4 f[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) f[u] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(srowv, u, lane) << RS) | xb);
+    for (int u = 0; u < U; ++u) f[u] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(srowv, u, lane) << RS) | xb);
     jn = j0 + (U + dq) * EPW < e ? j0 + (U + dq) * EPW : e - 1;
     idn = p01[jn];
     if (ELR) {
@@ -1120,243 +1126,11 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs(
 }
 
 // ... when no backward follows: records {O[X], max[H], sum[H]}; the first phase alone, and of it only h_inout[v] += O / sum
-template <int LPR>
+// (T = het_bf16: h_inout[v] = round(widen(h_inout[v]) + O / sum))
+template <typename T, int LPR>
 __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs_fwd(const int4* __restrict__ hub_rec, int64_t num_hubs, Items it,
                                                                    const float* __restrict__ part, int H, int D,
-                                                                   float* __restrict__ hio, int64_t hio_rows) {
-  constexpr int EPW = 64 / LPR, NW = kBlock / 64;
-  __shared__ float4 s_acc[NW][LPR];
-  __shared__ float s_m[NW][LPR], s_sum[NW][LPR];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = x / D;
-  const int64_t k = blockIdx.x;
-  if (k >= num_hubs) return;
-  const int4 hr = hub_rec[k];
-  const int64_t X = (int64_t)H * D, v = hr.w, rec = X + 2 * H;
-  const int64_t s_lo = hr.x, s_hi = hr.y, i_lo = hr.z;
-  int64_t n_all = 0;
-  for (int64_t s2 = s_lo; s2 < s_hi; ++s2) n_all += (it.seg_ptr[s2 + 1] - it.seg_ptr[s2] + HET_ITEM_MAX - 1) / HET_ITEM_MAX;
-  const int64_t i_hi = i_lo + n_all;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  float ssum = 0.f, m = -INFINITY;
-  for (int64_t i = i_lo + wave * EPW + slot; i < i_hi; i += NW * EPW) {
-    const float* pp = part + i * rec;
-    const float mi = pp[X + h], si = pp[X + H + h];
-    const float4 a = ld4(pp + x);
-    const float mn = fmaxf(m, mi), c = __expf(m - mn), ci = __expf(mi - mn);
-    acc.x = acc.x * c + a.x * ci; acc.y = acc.y * c + a.y * ci; acc.z = acc.z * c + a.z * ci; acc.w = acc.w * c + a.w * ci;
-    ssum = ssum * c + si * ci;
-    m = mn;
-  }
-  float M = m;
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
-  {
-    const float c = m == -INFINITY ? 0.f : __expf(m - M);
-    acc.x *= c; acc.y *= c; acc.z *= c; acc.w *= c; ssum *= c;
-  }
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-    acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off);
-    acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
-    ssum += __shfl_xor(ssum, off);
-  }
-  if (slot == 0) { s_acc[wave][sub] = acc; s_m[wave][sub] = M; s_sum[wave][sub] = ssum; }
-  __syncthreads();
-  if (wave == 0 && slot == 0 && v < hio_rows) {
-    float Mx = s_m[0][sub];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) Mx = fmaxf(Mx, s_m[w][sub]);
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    float ts = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float c = s_m[w][sub] == -INFINITY ? 0.f : __expf(s_m[w][sub] - Mx);
-      const float4 a = s_acc[w][sub];
-      t.x = fmaf(a.x, c, t.x); t.y = fmaf(a.y, c, t.y); t.z = fmaf(a.z, c, t.z); t.w = fmaf(a.w, c, t.w);
-      ts = fmaf(s_sum[w][sub], c, ts);
-    }
-    const float inv = 1.f / ts;
-    st4(hio + v * X + x, add_mul_rounded4(ld4(hio + v * X + x), t, inv));
-  }
-}
-
-// ---- the forward-only walk over bf16 rows (het_rgat_aggregate_compact_forward_bf16) ------------------------------------------
-// feat_c [S_row,X] and h_inout [rows,X] are het_bf16: a lane still holds 4 elements of a row (8 bytes instead of 16: ldrow4 /
-// strow4), widened on load, so every sum below is the fp32 kernels' arithmetic in the fp32 kernels' order; el_c / er_c, the hub
-// records, maxima, exponentials and sums are fp32.  The one rounding is where a destination's row is stored:
-// h_inout[v] = round(widen(h_inout[v]) + acc * rcp(sum)).  Twins of the three _fwd kernels above and, like those, copies: the fp32
-// instances stay the code they were measured as.
-template <typename O>
-__device__ __forceinline__ float4 ldrow4_at(const het_bf16* base, O byte_off) {
-  return ldrow4(reinterpret_cast<const het_bf16*>(reinterpret_cast<const char*>(base) + byte_off));
-}
-template <typename O>
-__device__ __forceinline__ void strow4_at(het_bf16* base, O byte_off, float4 v) {
-  strow4(reinterpret_cast<het_bf16*>(reinterpret_cast<char*>(base) + byte_off), v);
-}
-
-template <int LPR, int DL, bool ELR, bool W64>
-__global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed_fwd_bf16(
-    Packs pk, const int4* __restrict__ kp01, const het_bf16* __restrict__ feat, const float* __restrict__ el,
-    const float* __restrict__ er, float slope, het_bf16* __restrict__ hio, int hio_rows, int hub_min, ElFold ef) {
-  constexpr int EPW = 64 / LPR, U = 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 8), HS = het_log2_ce(H * 4);  // log2 of the bytes of a bf16 feature row / of an fp32 [.,H] row
-  typedef typename OffSel<W64>::type O;
-  static_assert(DL >= U, "a head needs at least U lanes");
-  static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
-  __shared__ float4 al_s[ELR ? kElMaxRels * LPR : 1];
-  if (ELR) {
-    for (int i = threadIdx.x; i < ef.R * LPR; i += kBlock) al_s[i] = ld4(ef.attn + (int64_t)i * 4);
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / LPR, sub = lane % LPR, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 8), hb = (O)(h * 4);
-  const int dq = d < U ? d : U - 1;
-  const int64_t pid = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW + slot;
-  if (pid >= pk.n) return;
-  const uint32_t pb = (uint32_t)pk.ptr[pid];
-  const int b = (int)(pb & 0x7fffffffu), e = (int)((uint32_t)pk.ptr[pid + 1] & 0x7fffffffu);
-  if ((pb >> 31) && e - b > hub_min) return;  // a hub: HET_rgat_aggregate_hub_items_fwd_bf16 + HET_rgat_finish_hubs_fwd_bf16
-  int rel_cur = -1;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), h0 = acc, a4 = acc;
-  float ssum = 0.f, m = -INFINITY;
-  auto ids_of = [&](int j) { return kp01[j + dq < e ? j + dq : e - 1]; };
-  auto rows_of = [&](const int4& id, float4 (&f)[U], float& zl, float& zr) {
-    zl = ELR ? 0.f : ld1_at<O>(el, ((O)id.y << HS) | hb);
-    zr = ld1_at<O>(er, ((O)id.z << HS) | hb);
-#pragma unroll
-    for (int q = 0; q < U; ++q) f[q] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RS) | xb);
-  };
-  auto step = [&](int j0, const int4& id, const float4 (&f)[U], float zlv, float zrv) {
-    const int dstv = id.x, tagv = id.w;
-    const float sv = lrelu(zlv + zrv, slope);
-#pragma unroll
-    for (int q = 0; q < U; ++q) {
-      if (j0 + q < e) {
-        const int tagq = head_bcast_i<DL>(tagv, q, lane);
-        if (tagq & HET_TAG_FIRST_KEY) {  // the destination's row of the layer output so far
-          const int dstq = head_bcast_i<DL>(dstv, q, lane);
-          if (dstq < hio_rows) h0 = ldrow4_at<O>(hio, ((O)dstq << RS) | xb);
-        }
-        if (ELR) {  // el from the ROUNDED row, as the row-dot pass forms el_c for the shapes that gather it
-          const int rel = tagq >> HET_TAG_REL_SHIFT;
-          if (rel != rel_cur) {
-            a4 = al_s[rel * LPR + sub];
-            rel_cur = rel;
-          }
-          const float zq = quad_sum(dot4(f[q], a4)) + head_bcast<DL>(zrv, q, lane);
-          online_edge(lrelu(zq, slope), f[q], m, acc, ssum);
-        } else {
-          online_edge(head_bcast<DL>(sv, q, lane), f[q], m, acc, ssum);
-        }
-        if (tagq & HET_TAG_LAST_KEY) {  // the destination ends with this edge: its row, rounded once
-          const int dstq = head_bcast_i<DL>(dstv, q, lane);
-          const float inv = __builtin_amdgcn_rcpf(ssum);
-          if (dstq < hio_rows) strow4_at<O>(hio, ((O)dstq << RS) | xb, add_mul_rounded4(h0, acc, inv));
-          acc = make_float4(0.f, 0.f, 0.f, 0.f);
-          ssum = 0.f;
-          m = -INFINITY;
-        }
-      }
-    }
-  };
-  int4 idn = ids_of(b);
-  asm volatile("" ::"v"(idn.x), "v"(idn.y), "v"(idn.z), "v"(idn.w));
-  for (int j0 = b; j0 < e; j0 += U) {
-    const int4 id = idn;
-    float4 f[U];
-    float zl, zr;
-    rows_of(id, f, zl, zr);
-    idn = ids_of(j0 + U);
-    asm volatile("" ::"v"(idn.x), "v"(idn.y), "v"(idn.z), "v"(idn.w));  // (waited for with the rows: see the training kernel)
-    step(j0, id, f, zl, zr);
-  }
-}
-
-// hub work items over bf16 feat rows: part[k] = {O[X], max[H], sum[H]} stays fp32
-template <int LPR, int DL, bool ELR, bool W64>
-__global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items_fwd_bf16(
-    Items it, const int32_t* __restrict__ hub_items, const int32_t* __restrict__ hub_order, int64_t num_hub_items,
-    const int2* __restrict__ p01, const het_bf16* __restrict__ feat, const float* __restrict__ el, const float* __restrict__ er,
-    float slope, float* __restrict__ part, ElFold ef) {
-  constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 8), HS = het_log2_ce(H * 4);
-  typedef typename OffSel<W64>::type O;
-  static_assert(DL >= U, "a head needs at least U lanes");
-  static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 8), hb = (O)(h * 4);
-  const int dq = d < U ? d : U - 1;
-  const int64_t kk = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  if (kk >= num_hub_items) return;
-  const int64_t k = hub_order ? hub_order[kk] : kk;
-  const int item = hub_items[k];
-  const int b = it.begin[item], e = it.end[item];
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  float ssum = 0.f, m = -INFINITY;
-  int jn = b + slot + dq * EPW < e ? b + slot + dq * EPW : e - 1;
-  int2 idn = p01[jn];
-  const int2 first = p01[b];
-  const float zrv = ld1_at<O>(er, ((O)first.y << HS) | hb);
-  const float4 a4 = ELR ? ld4(ef.attn + (int64_t)el_relation(ef, first.x) * X + x) : make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int j0 = b + slot; j0 < e; j0 += EPW * U) {
-    const int srowv = idn.x;
-    float zlv = ELR ? 0.f : ld1_at<O>(el, ((O)srowv << HS) | hb);
-    float4 f[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) f[u] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(srowv, u, lane) << RS) | xb);
-    jn = j0 + (U + dq) * EPW < e ? j0 + (U + dq) * EPW : e - 1;
-    idn = p01[jn];
-    if (ELR) {
-      float zl[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) zl[u] = quad_sum(dot4(f[u], a4));
-      zlv = dq == 0 ? zl[0] : dq == 1 ? zl[1] : dq == 2 ? zl[2] : zl[3];
-    }
-    const float zv = zlv + zrv;
-    const float sv = j0 + dq * EPW < e ? lrelu(zv, slope) : -INFINITY;
-    {
-      float mn = m;
-#pragma unroll
-      for (int u = 0; u < U; ++u) mn = fmaxf(mn, head_bcast<DL>(sv, u, lane));
-      const float c = __expf(m - mn);
-      acc.x *= c; acc.y *= c; acc.z *= c; acc.w *= c; ssum *= c;
-      m = mn;
-    }
-    const float wv = __expf(sv - m);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const float w = head_bcast<DL>(wv, u, lane);
-      acc.x = fmaf(w, f[u].x, acc.x); acc.y = fmaf(w, f[u].y, acc.y); acc.z = fmaf(w, f[u].z, acc.z); acc.w = fmaf(w, f[u].w, acc.w);
-      ssum += w;
-    }
-  }
-  {
-    float M = m;
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
-    const float c = m == -INFINITY ? 0.f : __expf(m - M);
-    acc.x *= c; acc.y *= c; acc.z *= c; acc.w *= c; ssum *= c;
-    m = M;
-  }
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-    acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off); acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
-    ssum += __shfl_xor(ssum, off);
-  }
-  if (slot != 0) return;
-  float* pp = part + k * (X + 2 * H);
-  st4(pp + x, acc);
-  if (d == 0) { pp[X + h] = m; pp[X + H + h] = ssum; }
-}
-
-// the fp32 records of a hub to their common maximum; h_inout[v] (bf16) = round(widen(h_inout[v]) + O / sum)
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs_fwd_bf16(const int4* __restrict__ hub_rec, int64_t num_hubs, Items it,
-                                                                        const float* __restrict__ part, int H, int D,
-                                                                        het_bf16* __restrict__ hio, int64_t hio_rows) {
+                                                                   T* __restrict__ hio, int64_t hio_rows) {
   constexpr int EPW = 64 / LPR, NW = kBlock / 64;
   __shared__ float4 s_acc[NW][LPR];
   __shared__ float s_m[NW][LPR], s_sum[NW][LPR];
@@ -1931,25 +1705,29 @@ struct RunOutputs {
   float *sum, *ret, *q_rows, *q_sum, *q_ref;
 };
 
+// whether the walk forms el from the gathered row (ElFold above), so that el_c is never read: heads of 16 floats, up to 8
+// relations, the caller names the relation boundaries of the feat rows (host array [R+1]) and attn_l [R, H*D]
+static bool rgat_el_from_row(const float* attn_l, const int64_t* feat_rel_ptrs_host, int64_t D, int64_t num_rels) {
+  return attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels && aligned16(attn_l);
+}
+
 // The launches of het_rgat_aggregate_compact_runs / _forward, arguments checked by the caller: the pack-form launch and, beside it
 // on the side stream, the two hub launches.  fwd: the instances that store h_inout alone.
-// T: the element type of feat_c and h_inout, float or het_bf16 (forward-only: the _fwd_bf16 twins).
+// T: the element type of feat_c and h_inout, float or het_bf16 (het_bf16: forward-only; the training kernels take float rows).
 template <typename T>
 static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
                                       const T* feat_c, const float* el_c, const float* er_c, const RunOutputs& o, int64_t H,
                                       int64_t D, double slope, T* h_inout, int64_t h_rows, const float* attn_l,
                                       const int64_t* feat_rel_ptrs_host, void* workspace, hipStream_t s) {
-  constexpr bool BF16 = std::is_same<T, het_bf16>::value;
+  constexpr bool F32 = std::is_same<T, float>::value;
+  if (!fwd && !F32) return HET_ERR_UNSUPPORTED;  // (no training instance over bf16 rows)
   const int64_t X = H * D;
   if (int rc = grouping_packed_ids(by_dst, true, s)) return rc;  // (builds the packs too)
   if (by_dst_rel->num_hub_items > 0)
     if (int rc = grouping_packed_ids(by_dst, false, s)) return rc;
   float* part = static_cast<float*>(workspace);
-  // el from the gathered row (ElFold above): heads of 16 floats, up to 8 relations, the caller names the relation boundaries of the
-  // feat rows (host array [R+1]) and attn_l [R, H*D]; otherwise el_c is gathered per edge
   ElFold ef{};
-  const bool elr = attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels &&
-                   aligned16(attn_l);
+  const bool elr = rgat_el_from_row(attn_l, feat_rel_ptrs_host, D, num_rels);  // (otherwise el_c is gathered per edge)
   if (elr) {
     ef.attn = attn_l; ef.R = (int)num_rels;
     for (int k = 0; k < kElMaxRels - 1; ++k)
@@ -1970,13 +1748,10 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
     const unsigned nb = (unsigned)ceil_div64(by_dst->num_packs, (int64_t)(kBlock / 64) * (64 / (X / 4)));
 #define HET_PACKS_LAUNCH2(ELRV, WV)                                                                                                \
   do {                                                                                                                             \
-    if constexpr (BF16)                                                                                                            \
-      hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed_fwd_bf16<LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk,           \
+    if (fwd)                                                                                                                       \
+      hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed_fwd<T, LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk,             \
                          by_dst->kp01, feat_c, el_c, er_c, (float)slope, h_inout, hio_rows32, rgat_hub_min(), ef);                 \
-    else if (fwd)                                                                                                                  \
-      hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed_fwd<LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk, by_dst->kp01,  \
-                         feat_c, el_c, er_c, (float)slope, h_inout, hio_rows32, rgat_hub_min(), ef);                               \
-    else                                                                                                                           \
+    else if constexpr (F32)                                                                                                        \
       hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed<LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk, by_dst->kp01,      \
                          feat_c, el_c, er_c, o.sum, o.ret, (float)slope, h_inout, hio_rows32, o.q_rows, o.q_sum, o.q_ref,          \
                          rgat_hub_min(), ef);                                                                                      \
@@ -2006,9 +1781,8 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
                       el_c, er_c, (float)slope, part, ef
 #define HET_HUBS_LAUNCH2(ELRV, WV)                                                                       \
   do {                                                                                                   \
-    if constexpr (BF16) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items_fwd_bf16<LPR, DL, ELRV, WV>), HET_HUBS_ARGS); \
-    else if (fwd) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items_fwd<LPR, DL, ELRV, WV>), HET_HUBS_ARGS);            \
-    else hipLaunchKernelGGL((HET_rgat_aggregate_hub_items<LPR, DL, ELRV, WV>), HET_HUBS_ARGS);                         \
+    if (fwd) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items_fwd<T, LPR, DL, ELRV, WV>), HET_HUBS_ARGS);              \
+    else if constexpr (F32) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items<LPR, DL, ELRV, WV>), HET_HUBS_ARGS);      \
   } while (0)
 #define HET_HUBS_LAUNCH(ELRV) do { if (w64) { HET_HUBS_LAUNCH2(ELRV, true); } else { HET_HUBS_LAUNCH2(ELRV, false); } } while (0)
       if (elr) {
@@ -2028,13 +1802,10 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
     const unsigned nbs = (unsigned)by_dst_rel->num_hub_segs;  // (a workgroup per hub)
     {
     HET_KTIME("HET_rgat_aggregate_finish", s2);
-    if constexpr (BF16) {
-      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_finish_hubs_fwd_bf16<LPR>, dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
+    if (fwd) {
+      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rgat_finish_hubs_fwd<T, LPR>), dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
                                                         by_dst_rel->num_hub_segs, it, part, (int)H, (int)D, h_inout, h_rows));
-    } else if (fwd) {
-      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_finish_hubs_fwd<LPR>, dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
-                                                        by_dst_rel->num_hub_segs, it, part, (int)H, (int)D, h_inout, h_rows));
-    } else {
+    } else if constexpr (F32) {
       HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_finish_hubs<LPR>, dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
                                                         by_dst_rel->num_hub_segs, it, by_dst->p1, part, o.sum, o.ret, (int)H, (int)D,
                                                         h_inout, h_rows, o.q_rows, o.q_sum, o.q_ref));
@@ -2077,53 +1848,23 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
 }
 
 // ---- forward only: the same walk, h_inout the only output (no sum / ret / run sums: nothing a backward could read) ----
-extern "C" int het_rgat_aggregate_compact_forward(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
-                                                  const float* feat_c, const float* el_c, const float* er_c, int64_t H, int64_t D,
-                                                  double slope, float* h_inout, int64_t h_rows, const float* attn_l,
-                                                  const int64_t* feat_rel_ptrs_host, void* workspace, int64_t workspace_bytes,
-                                                  het_stream stream) {
-  const char* op = "het_rgat_aggregate_compact_forward";
+// T = het_bf16 (het_rgat_aggregate_compact_forward_bf16): feat_c and h_inout het_bf16, everything else as for float.  That entry
+// also requires a 16-byte aligned feat_c and accepts a null el_c where the walk forms el from the row.
+template <typename T>
+static int rgat_aggregate_compact_forward(const char* op, const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                          const T* feat_c, const float* el_c, const float* er_c, int64_t H, int64_t D, double slope,
+                                          T* h_inout, int64_t h_rows, const float* attn_l, const int64_t* feat_rel_ptrs_host,
+                                          void* workspace, int64_t workspace_bytes, het_stream stream) {
+  constexpr bool BF16 = std::is_same<T, het_bf16>::value;
   hipStream_t s = (hipStream_t)stream;
   HET_REQUIRE(by_dst && by_dst_rel && num_rels > 0, "%s: null argument", op);
   HET_REQUIRE(h_inout && aligned16(h_inout) && h_rows >= 0, "%s: h_inout (16-byte aligned, h_rows >= 0) is required: it is the only output", op);
+  HET_REQUIRE(!BF16 || aligned16(feat_c), "%s: feat_c must be 16-byte aligned", op);
   if (!compact_shape_ok(H, D) || !coop_shape_ok(H, D)) {
     het_set_error("%s: unsupported shape H=%lld D=%lld", op, (long long)H, (long long)D);
     return HET_ERR_UNSUPPORTED;
   }
-  HET_REQUIRE(by_dst->R == 0 && (by_dst->E == 0 || (by_dst->p0 && by_dst->p1 && feat_c && el_c && er_c)),
-              "%s: by_dst must group the positions by destination with payload0 = feat row and payload1 = er row", op);
-  HET_REQUIRE(by_dst_rel->R == 0 && by_dst_rel->E == by_dst->E && by_dst_rel->key_bound <= by_dst->key_bound * num_rels,
-              "%s: by_dst_rel must group the same positions by destination * num_rels + relation", op);
-  if (by_dst->E == 0) return HET_OK;  // (h_inout untouched)
-  const int64_t need = het_rgat_aggregate_compact_forward_workspace(by_dst, by_dst_rel, num_rels, H, D, stream);
-  if (need < 0) return HET_ERR_INVALID_ARG;
-  HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
-              "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_aggregate_compact_forward_workspace)", op, (long long)need);
-  return rgat_aggregate_runs_launch(true, by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, RunOutputs{}, H, D, slope, h_inout, h_rows,
-                                    attn_l, feat_rel_ptrs_host, workspace, s);
-}
-
-// ---- ... over bf16 rows: feat_c and h_inout het_bf16, everything else as above (the _fwd_bf16 kernels) ----
-// whether the walk forms el from the gathered row (rgat_aggregate_runs_launch's own test): el_c is then never read
-static bool rgat_el_from_row(const float* attn_l, const int64_t* feat_rel_ptrs_host, int64_t D, int64_t num_rels) {
-  return attn_l && feat_rel_ptrs_host && D == 16 && num_rels <= kElMaxRels && aligned16(attn_l);
-}
-
-extern "C" int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
-                                                       const het_bf16* feat_c, const float* el_c, const float* er_c, int64_t H,
-                                                       int64_t D, double slope, het_bf16* h_inout, int64_t h_rows,
-                                                       const float* attn_l, const int64_t* feat_rel_ptrs_host, void* workspace,
-                                                       int64_t workspace_bytes, het_stream stream) {
-  const char* op = "het_rgat_aggregate_compact_forward_bf16";
-  hipStream_t s = (hipStream_t)stream;
-  HET_REQUIRE(by_dst && by_dst_rel && num_rels > 0, "%s: null argument", op);
-  HET_REQUIRE(h_inout && aligned16(h_inout) && h_rows >= 0, "%s: h_inout (16-byte aligned, h_rows >= 0) is required: it is the only output", op);
-  HET_REQUIRE(aligned16(feat_c), "%s: feat_c must be 16-byte aligned", op);
-  if (!compact_shape_ok(H, D) || !coop_shape_ok(H, D)) {
-    het_set_error("%s: unsupported shape H=%lld D=%lld", op, (long long)H, (long long)D);
-    return HET_ERR_UNSUPPORTED;
-  }
-  const bool el_needed = !rgat_el_from_row(attn_l, feat_rel_ptrs_host, D, num_rels);
+  const bool el_needed = !BF16 || !rgat_el_from_row(attn_l, feat_rel_ptrs_host, D, num_rels);
   HET_REQUIRE(by_dst->R == 0 && (by_dst->E == 0 || (by_dst->p0 && by_dst->p1 && feat_c && (el_c || !el_needed) && er_c)),
               "%s: by_dst must group the positions by destination with payload0 = feat row and payload1 = er row", op);
   HET_REQUIRE(by_dst_rel->R == 0 && by_dst_rel->E == by_dst->E && by_dst_rel->key_bound <= by_dst->key_bound * num_rels,
@@ -2135,6 +1876,24 @@ extern "C" int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_ds
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_aggregate_compact_forward_workspace)", op, (long long)need);
   return rgat_aggregate_runs_launch(true, by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, RunOutputs{}, H, D, slope, h_inout, h_rows,
                                     attn_l, feat_rel_ptrs_host, workspace, s);
+}
+
+extern "C" int het_rgat_aggregate_compact_forward(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                                  const float* feat_c, const float* el_c, const float* er_c, int64_t H, int64_t D,
+                                                  double slope, float* h_inout, int64_t h_rows, const float* attn_l,
+                                                  const int64_t* feat_rel_ptrs_host, void* workspace, int64_t workspace_bytes,
+                                                  het_stream stream) {
+  return rgat_aggregate_compact_forward("het_rgat_aggregate_compact_forward", by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, H, D, slope,
+                                        h_inout, h_rows, attn_l, feat_rel_ptrs_host, workspace, workspace_bytes, stream);
+}
+
+extern "C" int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                                       const het_bf16* feat_c, const float* el_c, const float* er_c, int64_t H,
+                                                       int64_t D, double slope, het_bf16* h_inout, int64_t h_rows,
+                                                       const float* attn_l, const int64_t* feat_rel_ptrs_host, void* workspace,
+                                                       int64_t workspace_bytes, het_stream stream) {
+  return rgat_aggregate_compact_forward("het_rgat_aggregate_compact_forward_bf16", by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, H, D,
+                                        slope, h_inout, h_rows, attn_l, feat_rel_ptrs_host, workspace, workspace_bytes, stream);
 }
 
 extern "C" int het_rgat_el_rows_bf16(const int64_t* rel_ptrs, int64_t num_rels, const het_bf16* feat_c, const float* attn_l,

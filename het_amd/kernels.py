@@ -775,13 +775,10 @@ def rgat_aggregate_compact(groupings, feat_c, el_c, er_c, sum, ret, slope, h_ino
     return None
 
 
-def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l=None, feat_rel_ptrs=None):
-    """The forward of rgat_aggregate_compact's run-sum form when no backward follows (include/het_amd.h:
-    het_rgat_aggregate_compact_forward): h_inout [rows, H*D] += the aggregated rows, in place, and nothing else is written -- no
-    lse, no ret, no run sums.  ``groupings``: rgat_compact_groupings with rel_ptrs (the training forward's, shared with it)."""
-    _chk("rgat_aggregate_compact_forward", (feat_c, el_c, er_c, h_inout))
+def _rgat_aggregate_compact_forward(name, groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l, feat_rel_ptrs):
+    """rgat_aggregate_compact_forward / _bf16 behind their tensor checks: the C entry is het_<name>."""
     if groupings[3] is None:
-        raise _lib.HetError("rgat_aggregate_compact_forward: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
+        raise _lib.HetError(f"{name}: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
     H, D = feat_c.shape[1], feat_c.shape[2]
     with torch.cuda.device(h_inout.device):
         nbytes = int(_lib.lib().het_rgat_aggregate_compact_forward_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
@@ -791,12 +788,21 @@ def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h_inout.device) if nbytes else None
     host_ptrs = None
     if attn_l is not None and feat_rel_ptrs is not None:
-        _chk("rgat_aggregate_compact_forward", (attn_l,), (feat_rel_ptrs,))
+        _chk(name, (attn_l,), (feat_rel_ptrs,))
         lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
         host_ptrs = (C.c_int64 * len(lst))(*lst)
-    _call(h_inout, "het_rgat_aggregate_compact_forward", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c),
-          _p(er_c), H, D, float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None, host_ptrs,
-          _p(ws), nbytes, _stream(h_inout))
+    _call(h_inout, "het_" + name, groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c), _p(er_c), H, D,
+          float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None, host_ptrs, _p(ws), nbytes,
+          _stream(h_inout))
+
+
+def rgat_aggregate_compact_forward(groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l=None, feat_rel_ptrs=None):
+    """The forward of rgat_aggregate_compact's run-sum form when no backward follows (include/het_amd.h:
+    het_rgat_aggregate_compact_forward): h_inout [rows, H*D] += the aggregated rows, in place, and nothing else is written -- no
+    lse, no ret, no run sums.  ``groupings``: rgat_compact_groupings with rel_ptrs (the training forward's, shared with it)."""
+    _chk("rgat_aggregate_compact_forward", (feat_c, el_c, er_c, h_inout))
+    _rgat_aggregate_compact_forward("rgat_aggregate_compact_forward", groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l,
+                                    feat_rel_ptrs)
 
 
 def rgat_attention_compact(groupings, el_c, er_c, slope, col, srow, drow, eids, num_nodes, lse_out=None, attn=None):
@@ -887,23 +893,8 @@ def rgat_aggregate_compact_forward_bf16(groupings, feat_c, el_c, er_c, h_inout, 
     """rgat_aggregate_compact_forward over bf16 rows (het_rgat_aggregate_compact_forward_bf16): feat_c [S,H,D] and h_inout [rows, H*D]
     bf16, el_c / er_c / attn_l fp32.  ``el_c`` may be None where the walk forms el from the row it gathers (rgat_el_from_row)."""
     _chk_bf16("rgat_aggregate_compact_forward_bf16", (feat_c, h_inout), tuple(t for t in (el_c, er_c) if t is not None))
-    if groupings[3] is None:
-        raise _lib.HetError("rgat_aggregate_compact_forward_bf16: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
-    H, D = feat_c.shape[1], feat_c.shape[2]
-    with torch.cuda.device(h_inout.device):
-        nbytes = int(_lib.lib().het_rgat_aggregate_compact_forward_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
-                                                                             _stream(h_inout)))
-    if nbytes < 0:
-        raise _lib.HetError("het_rgat_aggregate_compact_forward_workspace: " + _lib.lib().het_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h_inout.device) if nbytes else None
-    host_ptrs = None
-    if attn_l is not None and feat_rel_ptrs is not None:
-        _chk("rgat_aggregate_compact_forward_bf16", (attn_l,), (feat_rel_ptrs,))
-        lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
-        host_ptrs = (C.c_int64 * len(lst))(*lst)
-    _call(h_inout, "het_rgat_aggregate_compact_forward_bf16", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c),
-          _p(el_c), _p(er_c), H, D, float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None,
-          host_ptrs, _p(ws), nbytes, _stream(h_inout))
+    _rgat_aggregate_compact_forward("rgat_aggregate_compact_forward_bf16", groupings, feat_c, el_c, er_c, h_inout, slope, num_rels,
+                                    attn_l, feat_rel_ptrs)
 
 
 def rows_matmul_backward_split_ok(H: int, K: int, D: int) -> bool:
