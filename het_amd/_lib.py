@@ -13,23 +13,27 @@ LIB_PATH = os.environ.get("HET_AMD_LIB") or os.path.join(_HERE, "libhet_amd.so")
 
 P, I64, INT, DBL = C.c_void_p, C.c_int64, C.c_int, C.c_double
 
-# name -> argtypes, in the order of include/het_amd.h
-_SIGNATURES = {
+# The one declaration of every function of include/het_amd.h for ctypes, in the header's order (tests/test_abi.py holds each line
+# to its prototype): name -> argtypes of an entry that returns int (a status, or the yes / no of an *_ok query), or
+# (restype, argtypes) for the ones that return something else.
+_ENTRIES = {
+    "het_build_info": (C.c_char_p, []),
+    "het_last_error": (C.c_char_p, []),
+    "het_kernel_timing_enable": [INT],
+    "het_kernel_timing_read": [C.c_char_p, C.POINTER(C.c_double), C.POINTER(I64)],
+    "het_set_allocator": [P, P, P],
+    "het_allocator_is_external": [],
     "het_grouping_create": [P, I64, P, I64, I64, P, P, P, C.POINTER(P)],
+    "het_grouping_destroy": (None, [P]),
+    "het_grouping_note_stream": (None, [P, P]),
+    "het_grouping_num_segments": (I64, [P]),
+    "het_grouping_bytes": (I64, [P]),
     "het_grouping_rank_of_position": [P, P, P],
     "het_grouping_segment_map": [P, I64, P, P],
     "het_grouping_gather_payload1": [P, P, I64, P, P],
-    "het_rows_add_bias": [P, P, P, P, I64, I64, P],
-    "het_rows_gather": [P, P, I64, I64, P, P],
-    "het_rows_scatter_add": [P, P, I64, I64, P, P],
-    "het_rows_scatter_add_grouped": [P, P, I64, P, I64, P],
-    "het_layout_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
-    "het_layout_coo_to_csr": [P, P, P, P, I64, I64, P, P, P, P, P],
-    "het_layout_transpose_csr": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
-    "het_layout_unique_rel_nodes": [P, I64, P, P, I64, I64, P, P, P, P, P],
     "het_rgnn_relational_matmul": [I64, P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P, P, I64, P],
-    "het_backward_rgnn_relational_matmul_attn_dot_only": [P, I64, P, P, I64, I64, P, P, P, P, P, P, I64, I64, I64, INT, P, P, I64, P, P, P],
     "het_rgnn_relational_matmul_attn_dot": [I64, P, I64, P, P, I64, P, P, P, P, P, I64, I64, I64, P, P, I64, P, P, P],
+    "het_backward_rgnn_relational_matmul_attn_dot_only": [P, I64, P, P, I64, I64, P, P, P, P, P, P, I64, I64, I64, INT, P, P, I64, P, P, P],
     "het_backward_rgnn_relational_matmul": [I64, P, I64, P, P, I64, I64, P, P, P, P, P, I64, I64, I64, INT, INT, P, P, I64, P],
     "het_rgnn_relational_matmul_no_scatter_gather_list": [P, I64, I64, P, P, P, I64, I64, I64, INT, P],
     "het_backward_rgnn_relational_matmul_no_scatter_gather_list": [P, I64, I64, P, P, P, P, P, I64, I64, I64, INT, INT, P],
@@ -37,41 +41,6 @@ _SIGNATURES = {
     "het_backward_relational_fused_gat_separate_coo": [P, P, P, P, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, DBL, P, P, P, I64, I64, P, I64, P, P, P, P, P],
     "het_relational_fused_gat_csr": [P, P, P, P, I64, I64, P, P, I64, P, P, P, P, P, P, I64, I64, DBL, INT, P],
     "het_backward_relational_fused_gat_csr": [P, P, P, P, I64, I64, P, P, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, DBL, INT, P],
-    "het_hgt_fold_source_weights": [P, P, P, P, P, P, I64, I64, I64, I64, I64, INT, P, P],
-    "het_hgt_fold_source_weights_backward": [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, INT, P, P, P, P, P, P],
-    "het_rgat_aggregate_compact": [P, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, I64, P],
-    "het_rows_matmul_backward_dx": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
-    "het_rows_matmul_backward_dw": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
-    "het_rows_matmul_backward_dw_colsum": [P, I64, P, P, I64, P, P, P, P, I64, I64, I64, INT, P],
-    "het_rows_linear_bias": [P, P, P, P, P, I64, I64, I64, P],
-    "het_node_row_map": [P, I64, P, I64, I64, P, P],
-    "het_rgat_node_backward_dx": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
-    "het_node_rows_matmul_sum": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
-    "het_node_rows_matmul_sum_bias": [I64, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P],
-    "het_rgcn_layer_forward": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
-    "het_rgcn_layer_backward": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
-    "het_rgcn_layer_forward_bf16": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
-    "het_rgcn_layer_backward_bf16": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
-    "het_rgat_backward_compact": [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, I64, P],
-    "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
-    "het_rgat_aggregate_compact_forward_workspace": [P, P, I64, I64, I64, P],  # (returns bytes: restype set in lib())
-    "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
-    "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
-    "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
-    "het_rgat_attention_compact_workspace": [P, I64, I64, INT],  # (returns bytes: restype set in lib())
-    "het_rgat_attention_compact": [P, P, P, I64, DBL, P, P, P, P, I64, I64, P, P, P, I64, P],
-    "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
-    "het_rows_matmul_heads_bf16": [P, I64, P, I64, P, P, P, I64, I64, I64, P],
-    "het_rows_dot1h_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
-    "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
-    "het_hgt_aggregate_compact": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
-    "het_hgt_backward_compact": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
-    "het_hgt_aggregate_compact_bf16": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
-    "het_hgt_backward_compact_bf16": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
-    "het_rows_matmul_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
-    "het_rows_matmul_backward_dw_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
-    "het_rows_matmul_backward_dw_bf16_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
-    "het_node_rows_matmul_sum_bf16": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
     "het_rgcn_layer1_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, I64, I64, P, P, I64, P],
     "het_backward_rgcn_layer1_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P, I64, P],
     "het_rgcn_node_mean_aggregation_compact_as_of_node_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P, I64, INT, P, P],
@@ -89,7 +58,63 @@ _SIGNATURES = {
     "het_backward_inner_product_right_node_separatecoo": [I64, P, P, P, P, P, P, I64, I64, P, P, P, P, P, I64, I64, INT, P, P, I64, I64, P],
     "het_hgt_full_graph_hetero_attention_ops_coo": [P, P, P, P, I64, I64, P, P, P, P, P, I64, I64, I64, P],
     "het_backward_hgt_full_graph_hetero_attention_ops_coo": [P, P, P, P, I64, I64, P, P, P, P, P, P, P, P, I64, I64, I64, P, P, I64, P, I64, P],
+    "het_hgt_compact_shape_ok": [I64, I64],
+    "het_hgt_aggregate_compact": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_aggregate_compact_workspace": (I64, [P, I64, I64]),
+    "het_hgt_backward_compact_workspace": (I64, [I64, I64]),
+    "het_hgt_backward_compact": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_aggregate_compact_bf16": [P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_backward_compact_bf16": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, I64, P],
+    "het_hgt_fold_source_weights": [P, P, P, P, P, P, I64, I64, I64, I64, I64, INT, P, P],
+    "het_hgt_fold_source_weights_backward": [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, INT, P, P, P, P, P, P],
+    "het_rgat_aggregate_compact": [P, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, I64, P],
+    "het_rgat_aggregate_compact_workspace": (I64, [P, I64, I64]),
+    "het_rgat_backward_compact_workspace": (I64, [I64, I64, I64, I64, INT]),
+    "het_rgat_backward_compact": [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, I64, P],
+    "het_rgat_aggregate_compact_runs_workspace": (I64, [P, P, I64, I64, I64, P]),
+    "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
+    "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
+    "het_rgat_backward_compact_runs_workspace": (I64, [P, I64, I64, I64, I64, INT, INT, P]),
+    "het_rgat_aggregate_compact_forward_workspace": (I64, [P, P, I64, I64, I64, P]),
+    "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
+    "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
+    "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
+    "het_rgat_attention_compact_workspace": (I64, [P, I64, I64, INT]),
+    "het_rgat_attention_compact": [P, P, P, I64, DBL, P, P, P, P, I64, I64, P, P, P, I64, P],
+    "het_rows_matmul_backward_dx": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
+    "het_rows_matmul_backward_dw": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
+    "het_rows_matmul_backward_dw_colsum": [P, I64, P, P, I64, P, P, P, P, I64, I64, I64, INT, P],
+    "het_rows_matmul_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
+    "het_rows_matmul_backward_dw_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
+    "het_rows_matmul_backward_dw_bf16_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
+    "het_rows_matmul_heads_bf16": [P, I64, P, I64, P, P, P, I64, I64, I64, P],
+    "het_rows_dot1h_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
+    "het_rgat_node_gemm_ok": [I64, I64, I64, I64],
+    "het_node_row_map": [P, I64, P, I64, I64, P, P],
+    "het_rgat_node_backward_dx": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
+    "het_node_rows_matmul_sum_ok": [I64, I64, I64],
+    "het_node_rows_matmul_sum": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
+    "het_node_rows_matmul_sum_bias": [I64, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P],
+    "het_node_rows_matmul_sum_bf16": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
+    "het_rgcn_layer_ok": [I64, I64, I64],
+    "het_rgcn_layer_backward_workspace": (I64, [I64, I64]),
+    "het_rgcn_layer_forward": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
+    "het_rgcn_layer_backward": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
+    "het_rgcn_layer_forward_bf16": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
+    "het_rgcn_layer_backward_bf16": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
+    "het_rows_linear_bias": [P, P, P, P, P, I64, I64, I64, P],
+    "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
+    "het_rows_add_bias": [P, P, P, P, I64, I64, P],
+    "het_rows_gather": [P, P, I64, I64, P, P],
+    "het_rows_scatter_add": [P, P, I64, I64, P, P],
+    "het_rows_scatter_add_grouped": [P, P, I64, P, I64, P],
+    "het_layout_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
+    "het_layout_coo_to_csr": [P, P, P, P, I64, I64, P, P, P, P, P],
+    "het_layout_transpose_csr": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
+    "het_layout_unique_rel_nodes": [P, I64, P, P, I64, I64, P, P, P, P, P],
 }
+_ENTRIES = {name: decl if isinstance(decl, tuple) else (INT, decl) for name, decl in _ENTRIES.items()}  # name -> (restype, argtypes)
+_SIGNATURES = {name: args for name, (_, args) in _ENTRIES.items()}  # name -> argtypes
 
 
 class HetError(RuntimeError):
@@ -114,54 +139,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()' "
                 "or make -C het_amd/csrc). het_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        L.het_build_info.restype = C.c_char_p
-        L.het_last_error.restype = C.c_char_p
-        L.het_grouping_destroy.argtypes = [P]
-        L.het_grouping_destroy.restype = None
-        L.het_grouping_note_stream.argtypes = [P, P]
-        L.het_grouping_note_stream.restype = None
-        L.het_grouping_num_segments.argtypes = [P]
-        L.het_grouping_num_segments.restype = I64
-        L.het_grouping_bytes.argtypes = [P]
-        L.het_grouping_bytes.restype = I64
-        L.het_rgat_aggregate_compact_workspace.argtypes = [P, I64, I64]
-        L.het_rgat_aggregate_compact_workspace.restype = I64
-        L.het_rgat_aggregate_compact_runs_workspace.argtypes = [P, P, I64, I64, I64, P]
-        L.het_rgat_aggregate_compact_runs_workspace.restype = I64
-        L.het_rgat_backward_compact_runs_workspace.argtypes = [P, I64, I64, I64, I64, INT, INT, P]
-        L.het_rgat_backward_compact_runs_workspace.restype = I64
-        L.het_rgat_backward_compact_workspace.argtypes = [I64, I64, I64, I64, INT]
-        L.het_rgat_backward_compact_workspace.restype = I64
-        L.het_hgt_aggregate_compact_workspace.argtypes = [P, I64, I64]
-        L.het_hgt_aggregate_compact_workspace.restype = I64
-        L.het_hgt_backward_compact_workspace.argtypes = [I64, I64]
-        L.het_hgt_backward_compact_workspace.restype = I64
-        L.het_hgt_compact_shape_ok.argtypes = [I64, I64]
-        L.het_hgt_compact_shape_ok.restype = INT
-        L.het_node_rows_matmul_sum_ok.argtypes = [I64, I64, I64]
-        L.het_node_rows_matmul_sum_ok.restype = INT
-        L.het_rgcn_layer_ok.argtypes = [I64, I64, I64]
-        L.het_rgcn_layer_ok.restype = INT
-        L.het_rgcn_layer_backward_workspace.argtypes = [I64, I64]
-        L.het_rgcn_layer_backward_workspace.restype = I64
-        L.het_rgat_node_gemm_ok.argtypes = [I64, I64, I64, I64]
-        L.het_rgat_node_gemm_ok.restype = INT
-        L.het_set_allocator.argtypes = [P, P, P]
-        L.het_set_allocator.restype = INT
-        L.het_allocator_is_external.argtypes = []
-        L.het_allocator_is_external.restype = INT
-        L.het_kernel_timing_enable.argtypes = [INT]
-        L.het_kernel_timing_enable.restype = INT
-        L.het_kernel_timing_read.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(I64)]
-        L.het_kernel_timing_read.restype = INT
-        for name, args in _SIGNATURES.items():
+        for name, (restype, args) in _ENTRIES.items():
             f = getattr(L, name, None)
             if f is None:
                 raise HetError(f"{LIB_PATH} does not export {name}: rebuild it (make -C het_amd/csrc)")
             f.argtypes = args
-            f.restype = INT
-        L.het_rgat_aggregate_compact_forward_workspace.restype = I64
-        L.het_rgat_attention_compact_workspace.restype = I64
+            f.restype = restype
         _lib = L
     return _lib
 

@@ -145,6 +145,21 @@ def _call(dev_tensor: Tensor, cname: str, *args):
         rec.append((a, b, args))
 
 
+def _workspace(like: Tensor, query: str, *args, why: Optional[str] = None):
+    """The scratch buffer of a C entry, sized by its byte-count query (include/het_amd.h: the het_*_workspace functions), asked on
+    ``like``'s device: (float32 tensor there, or None for 0 bytes; the byte count to hand to the entry).  Every query answers in
+    whole floats.  A negative answer raises, naming the query, with ``why`` or the library's message."""
+    ask = getattr(_lib.lib(), query)
+    if like.device.index == torch.cuda.current_device():
+        nbytes = int(ask(*args))
+    else:
+        with torch.cuda.device(like.device):
+            nbytes = int(ask(*args))
+    if nbytes < 0:
+        raise _lib.HetError(f"{query}: {why or _lib.lib().het_last_error().decode()}")
+    return (torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=like.device) if nbytes else None), nbytes
+
+
 # ------------------------------------------------------------------------------------
 # info + layout converters
 # ------------------------------------------------------------------------------------
@@ -446,6 +461,13 @@ def _derived_get(tag, tensors, build):
         else:
             _derived.move_to_end(key)
         return hit[0]
+
+
+def _host_rel_ptrs(rel_ptrs: Tensor):
+    """A relation-pointer list as a host int64 array, for the entries that read it on the host: one device read per list (cached by
+    its identity), none per step."""
+    lst = _derived_get("rel_ptrs_host", (rel_ptrs,), lambda: rel_ptrs.tolist())
+    return (C.c_int64 * len(lst))(*lst)
 
 
 def _rows_by_search(rel_ptrs, nodes, ua, ub):
@@ -751,25 +773,18 @@ def rgat_aggregate_compact(groupings, feat_c, el_c, er_c, sum, ret, slope, h_ino
         S_col = er_c.shape[0]
         q_rows = torch.empty((S_col, H, D), dtype=ret.dtype, device=ret.device)
         q_sum, q_ref = torch.empty_like(er_c), torch.empty_like(er_c)
-        with torch.cuda.device(ret.device):
-            nbytes = int(_lib.lib().het_rgat_aggregate_compact_runs_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
-                                                                              _stream(ret)))
-        if nbytes < 0:
-            raise _lib.HetError("het_rgat_aggregate_compact_runs_workspace: " + _lib.lib().het_last_error().decode())
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=ret.device) if nbytes else None
+        ws, nbytes = _workspace(ret, "het_rgat_aggregate_compact_runs_workspace", groupings[0].handle, groupings[3].handle, int(num_rels),
+                                H, D, _stream(ret))
         host_ptrs = None
         if attn_l is not None and feat_rel_ptrs is not None:
             _chk("rgat_aggregate_compact", (attn_l,), (feat_rel_ptrs,))
-            # (the relation boundaries as host integers: one device read per list, cached by its identity)
-            lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
-            host_ptrs = (C.c_int64 * len(lst))(*lst)
+            host_ptrs = _host_rel_ptrs(feat_rel_ptrs)
         _call(ret, "het_rgat_aggregate_compact_runs", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c),
               _p(er_c), _p(sum), _p(ret), N, H, D, float(slope), _p(h_inout), 0 if h_inout is None else h_inout.shape[0],
               _p(q_rows), _p(q_sum), _p(q_ref), S_col, _p(attn_l) if host_ptrs is not None else None, host_ptrs, _p(ws), nbytes,
               _stream(ret))
         return q_rows, q_sum, q_ref
-    nbytes = int(_lib.lib().het_rgat_aggregate_compact_workspace(groupings[0].handle, H, D))  # (hub destinations only)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=ret.device) if nbytes else None
+    ws, nbytes = _workspace(ret, "het_rgat_aggregate_compact_workspace", groupings[0].handle, H, D)  # (hub destinations only)
     _call(ret, "het_rgat_aggregate_compact", groupings[0].handle, _p(feat_c), _p(el_c), _p(er_c), _p(sum), _p(ret), N, H, D,
           float(slope), _p(h_inout), 0 if h_inout is None else h_inout.shape[0], _p(ws), nbytes, _stream(ret))
     return None
@@ -780,17 +795,12 @@ def _rgat_aggregate_compact_forward(name, groupings, feat_c, el_c, er_c, h_inout
     if groupings[3] is None:
         raise _lib.HetError(f"{name}: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
     H, D = feat_c.shape[1], feat_c.shape[2]
-    with torch.cuda.device(h_inout.device):
-        nbytes = int(_lib.lib().het_rgat_aggregate_compact_forward_workspace(groupings[0].handle, groupings[3].handle, int(num_rels), H, D,
-                                                                             _stream(h_inout)))
-    if nbytes < 0:
-        raise _lib.HetError("het_rgat_aggregate_compact_forward_workspace: " + _lib.lib().het_last_error().decode())
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h_inout.device) if nbytes else None
+    ws, nbytes = _workspace(h_inout, "het_rgat_aggregate_compact_forward_workspace", groupings[0].handle, groupings[3].handle,
+                            int(num_rels), H, D, _stream(h_inout))
     host_ptrs = None
     if attn_l is not None and feat_rel_ptrs is not None:
         _chk(name, (attn_l,), (feat_rel_ptrs,))
-        lst = _derived_get("rel_ptrs_host", (feat_rel_ptrs,), lambda: feat_rel_ptrs.tolist())
-        host_ptrs = (C.c_int64 * len(lst))(*lst)
+        host_ptrs = _host_rel_ptrs(feat_rel_ptrs)
     _call(h_inout, "het_" + name, groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c), _p(er_c), H, D,
           float(slope), _p(h_inout), h_inout.shape[0], _p(attn_l) if host_ptrs is not None else None, host_ptrs, _p(ws), nbytes,
           _stream(h_inout))
@@ -822,10 +832,8 @@ def rgat_attention_compact(groupings, el_c, er_c, slope, col, srow, drow, eids, 
                             f"{E} edges / {num_nodes} nodes do not fit")
     if E == 0:
         return attn
-    nbytes = int(_lib.lib().het_rgat_attention_compact_workspace(groupings[0].handle, H, int(num_nodes), int(lse_out is not None)))
-    if nbytes < 0:
-        raise _lib.HetError(f"rgat_attention_compact: unsupported shape H={H} (1, 2, 4 or 8 heads)")
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=attn.device) if nbytes else None
+    ws, nbytes = _workspace(attn, "het_rgat_attention_compact_workspace", groupings[0].handle, H, int(num_nodes), int(lse_out is not None),
+                            why=f"rgat_attention_compact: unsupported shape H={H} (1, 2, 4 or 8 heads)")
     _call(attn, "het_rgat_attention_compact", groupings[0].handle, _p(el_c), _p(er_c), H, float(slope), _p(col), _p(srow), _p(drow),
           _p(eids), E, int(num_nodes), _p(lse_out), _p(attn), _p(ws), nbytes, _stream(attn))
     return attn
@@ -870,12 +878,10 @@ def rows_linear_bias_bf16(offsets, x, w, bias, out=None):
     fp32 before the one rounding."""
     _chk_bf16("rows_linear_bias_bf16", tuple(t for t in (x, out) if t is not None), tuple(t for t in (w, bias) if t is not None))
     _chk("rows_linear_bias_bf16", (), (offsets,))
-    if out is None:
-        out = torch.empty((x.shape[0], w.shape[1]), dtype=torch.bfloat16, device=x.device)
-    if x.shape[-1] != w.shape[0] or out.shape != (x.shape[0], w.shape[1]):
-        raise _lib.HetError(f"rows_linear_bias_bf16: x {tuple(x.shape)} / out {tuple(out.shape)} do not fit w {tuple(w.shape)}")
-    _call(x, "het_rows_linear_bias_bf16", _p(offsets), _p(x), _p(w), _p(bias), _p(out), x.shape[0], w.shape[0], w.shape[1], _stream(x))
-    return out
+    shape = (x.shape[0], w.shape[1]) if out is None else tuple(out.shape)
+    if x.shape[-1] != w.shape[0] or shape != (x.shape[0], w.shape[1]):
+        raise _lib.HetError(f"rows_linear_bias_bf16: x {tuple(x.shape)} / out {shape} do not fit w {tuple(w.shape)}")
+    return _rows_linear_bias("het_rows_linear_bias_bf16", offsets, x, w, bias, out)
 
 
 def rgat_el_rows_bf16(rel_ptrs, feat_c, attn_l, el_c):
@@ -1003,14 +1009,19 @@ def rows_linear_bias_ok(K: int, X: int) -> bool:
     return K in (32, 64, 128) and X in (32, 64, 128)
 
 
+def _rows_linear_bias(entry, offsets, x, w, bias, out):
+    """rows_linear_bias / _bf16 behind their tensor checks: ``out`` (allocated unless given) has x's dtype."""
+    if out is None:
+        out = torch.empty((x.shape[0], w.shape[1]), dtype=x.dtype, device=x.device)
+    _call(x, entry, _p(offsets), _p(x), _p(w), _p(bias), _p(out), x.shape[0], w.shape[0], w.shape[1], _stream(x))
+    return out
+
+
 def rows_linear_bias(offsets, x, w, bias, out=None):
     """x . w + bias for the rows [offsets[0], offsets[1]) of x (include/het_amd.h: het_rows_linear_bias).  ``out``: a tensor of the
     caller (e.g. allocated under another stream than the one the product is launched on)."""
     _chk("rows_linear_bias", tuple(t for t in (x, w, bias, out) if t is not None), (offsets,))
-    if out is None:
-        out = torch.empty((x.shape[0], w.shape[1]), dtype=x.dtype, device=x.device)
-    _call(x, "het_rows_linear_bias", _p(offsets), _p(x), _p(w), _p(bias), _p(out), x.shape[0], w.shape[0], w.shape[1], _stream(x))
-    return out
+    return _rows_linear_bias("het_rows_linear_bias", offsets, x, w, bias, out)
 
 
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
@@ -1025,19 +1036,16 @@ def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad
     N, H = sum.shape[0], sum.shape[1]
     D = ret.numel() // max(1, N * H)
     if runs:
-        with torch.cuda.device(ret.device):
-            nbytes = int(_lib.lib().het_rgat_backward_compact_runs_workspace(groupings[1].handle, N, er_c.shape[0], H, D, int(grad_bias is not None),
-                                                                             int(grad_attn_l is not None), _stream(ret)))
-        if nbytes < 0:
-            raise _lib.HetError("het_rgat_backward_compact_runs_workspace: " + _lib.lib().het_last_error().decode())
+        ws, nbytes = _workspace(ret, "het_rgat_backward_compact_runs_workspace", groupings[1].handle, N, er_c.shape[0], H, D,
+                                int(grad_bias is not None), int(grad_attn_l is not None), _stream(ret))
     else:
         assert grad_attn_l is None, "grad_attn_l comes with the run-sum form"
-        nbytes = int(_lib.lib().het_rgat_backward_compact_workspace(N, groupings[1]._keep[1].numel(), H, D, int(grad_bias is not None)))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=ret.device)
+        ws, nbytes = _workspace(ret, "het_rgat_backward_compact_workspace", N, groupings[1]._keep[1].numel(), H, D,
+                                int(grad_bias is not None))
     head = (_p(feat_c), _p(el_c), _p(er_c), _p(sum), _p(ret), _p(gradout), _p(grad_feat_c), _p(grad_el_c), _p(grad_er_c),
             _p(fold_attn_l), _p(row_rel_ptrs), 0 if row_rel_ptrs is None else row_rel_ptrs.numel() - 1, _p(grad_bias),
             int(bias_rows), N, feat_c.shape[0], er_c.shape[0], H, D, float(slope))
-    tail = (_p(ws), ws.numel() * 4, _stream(ret))
+    tail = (_p(ws), nbytes, _stream(ret))
     if runs:
         _call(ret, "het_rgat_backward_compact_runs", groupings[1].handle, _p(runs[0]), _p(runs[1]), _p(runs[2]), _p(drow_nodes), *head,
               _p(grad_attn_l), *tail)
@@ -1090,24 +1098,37 @@ def hgt_compact_groupings(col, srow, num_nodes, num_src_rows):
     return None if by_dst is None or by_srow is None else (by_dst, by_srow)
 
 
-def hgt_aggregate_compact(groupings, kv_c, q, lsum, out):
-    _chk("hgt_aggregate_compact", (kv_c, q, lsum, out))
+def _hgt_aggregate_compact(entry, groupings, kv_c, q, lsum, out, workspace=None):
+    """hgt_aggregate_compact / _bf16 behind their tensor checks (``workspace``: the caller's buffer instead of one sized by the query)."""
     N, H = lsum.shape
     D = out.numel() // max(1, N * H)
-    nbytes = int(_lib.lib().het_hgt_aggregate_compact_workspace(groupings[0].handle, H, D))  # (hub destinations only)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device) if nbytes else None
-    _call(out, "het_hgt_aggregate_compact", groupings[0].handle, _p(kv_c), _p(q), _p(lsum), _p(out), N, kv_c.shape[0], H, D,
-          _p(ws), nbytes, _stream(out))
+    if workspace is None:
+        ws, nbytes = _workspace(out, "het_hgt_aggregate_compact_workspace", groupings[0].handle, H, D)  # (hub destinations only)
+    else:
+        ws, nbytes = workspace, workspace.numel() * 4
+    _call(out, entry, groupings[0].handle, _p(kv_c), _p(q), _p(lsum), _p(out), N, kv_c.shape[0], H, D, _p(ws), nbytes, _stream(out))
+
+
+def _hgt_backward_compact(entry, groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q, workspace=None):
+    """hgt_backward_compact / _bf16 behind their tensor checks."""
+    N, H = lsum.shape
+    D = out.numel() // max(1, N * H)
+    if workspace is None:
+        ws, nbytes = _workspace(out, "het_hgt_backward_compact_workspace", N, H)
+    else:
+        ws, nbytes = workspace, workspace.numel() * 4
+    _call(out, entry, groupings[0].handle, groupings[1].handle, _p(kv_c), _p(q), _p(lsum), _p(out), _p(gradout), _p(grad_kv_c),
+          _p(grad_q), N, kv_c.shape[0], H, D, _p(ws), nbytes, _stream(out))
+
+
+def hgt_aggregate_compact(groupings, kv_c, q, lsum, out):
+    _chk("hgt_aggregate_compact", (kv_c, q, lsum, out))
+    _hgt_aggregate_compact("het_hgt_aggregate_compact", groupings, kv_c, q, lsum, out)
 
 
 def hgt_backward_compact(groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q):
     _chk("hgt_backward_compact", (kv_c, q, lsum, out, gradout, grad_kv_c, grad_q))
-    N, H = lsum.shape
-    D = out.numel() // max(1, N * H)
-    nbytes = int(_lib.lib().het_hgt_backward_compact_workspace(N, H))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
-    _call(out, "het_hgt_backward_compact", groupings[0].handle, groupings[1].handle, _p(kv_c), _p(q), _p(lsum), _p(out),
-          _p(gradout), _p(grad_kv_c), _p(grad_q), N, kv_c.shape[0], H, D, _p(ws), ws.numel() * 4, _stream(out))
+    _hgt_backward_compact("het_hgt_backward_compact", groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q)
 
 
 def gat_rank_of_position(rel_ptrs, row, col, eids, num_nodes):
@@ -1285,37 +1306,44 @@ def scale_in_rank_order(g, values):
         return out
 
 
-def rgcn_layer_forward(plan, x, weights, norm, bias):
-    """(ret [N,D], ssum [S_col,K]) of het_rgcn_layer_forward: ret = bias + SUM_r (SUM_e norm x[src]) . W[r]."""
+def _rgcn_layer_forward(entry, plan, x, weights, norm, bias):
+    """rgcn_layer_forward / _bf16 behind their tensor checks: ret has x's dtype, the kept sums are fp32."""
     gd, _, dst_map, dst_order, _, _ = plan
-    _chk("rgcn_layer_forward", tuple(t for t in (x, weights, norm, bias) if t is not None))
     R, K, D = weights.shape
     N = dst_map.shape[1]
     ssum = torch.empty((max(1, gd.num_segments), K), dtype=torch.float32, device=x.device)
-    ret = torch.empty((N, D), dtype=torch.float32, device=x.device)
-    _call(ret, "het_rgcn_layer_forward", gd.handle, R, N, _p(x), _p(weights), _p(norm), _p(scale_in_rank_order(gd, norm)), _p(bias),
-          _p(dst_map), _p(dst_order),
-          _p(ssum), _p(ret), K, D, _stream(ret))
+    ret = torch.empty((N, D), dtype=x.dtype, device=x.device)
+    _call(ret, entry, gd.handle, R, N, _p(x), _p(weights), _p(norm), _p(scale_in_rank_order(gd, norm)), _p(bias), _p(dst_map),
+          _p(dst_order), _p(ssum), _p(ret), K, D, _stream(ret))
     return ret, ssum
+
+
+def _rgcn_layer_backward(entry, plan, ssum, weights_t, norm, gradout, want_bias, want_x):
+    """rgcn_layer_backward / _bf16 behind their tensor checks: grad_x has gradout's dtype, grad_w and grad_bias are fp32."""
+    gd, gs, _, _, src_map, src_order = plan
+    R, D, K = weights_t.shape
+    N = src_map.shape[1]
+    dev = gradout.device
+    grad_x = torch.empty((N, K), dtype=gradout.dtype, device=dev) if want_x else None
+    grad_w = torch.empty((R, K, D), dtype=torch.float32, device=dev)
+    grad_bias = torch.empty((D,), dtype=torch.float32, device=dev) if want_bias else None
+    ws, nbytes = _workspace(gradout, "het_rgcn_layer_backward_workspace", gs.num_segments, D)
+    _call(gradout, entry, gs.handle, gd.handle, R, N, gradout.shape[0], _p(ssum), _p(weights_t), _p(norm),
+          _p(scale_in_rank_order(gs, norm) if want_x else None), _p(gradout), _p(src_map), _p(src_order), _p(grad_x), _p(grad_w),
+          _p(grad_bias), K, D, _p(ws), nbytes, _stream(gradout))
+    return grad_x, grad_w, grad_bias
+
+
+def rgcn_layer_forward(plan, x, weights, norm, bias):
+    """(ret [N,D], ssum [S_col,K]) of het_rgcn_layer_forward: ret = bias + SUM_r (SUM_e norm x[src]) . W[r]."""
+    _chk("rgcn_layer_forward", tuple(t for t in (x, weights, norm, bias) if t is not None))
+    return _rgcn_layer_forward("het_rgcn_layer_forward", plan, x, weights, norm, bias)
 
 
 def rgcn_layer_backward(plan, ssum, weights_t, norm, gradout, want_bias: bool, want_x: bool = True):
     """(grad_x [N,K] or None, grad_w [R,K,D], grad_bias [D] or None) of het_rgcn_layer_backward."""
-    gd, gs, _, _, src_map, src_order = plan
     _chk("rgcn_layer_backward", (ssum, weights_t, norm, gradout))
-    R, D, K = weights_t.shape
-    N = src_map.shape[1]
-    dev = gradout.device
-    grad_x = torch.empty((N, K), dtype=torch.float32, device=dev) if want_x else None
-    grad_w = torch.empty((R, K, D), dtype=torch.float32, device=dev)
-    grad_bias = torch.empty((D,), dtype=torch.float32, device=dev) if want_bias else None
-    nbytes = int(_lib.lib().het_rgcn_layer_backward_workspace(gs.num_segments, D))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    _call(gradout, "het_rgcn_layer_backward", gs.handle, gd.handle, R, N, gradout.shape[0], _p(ssum), _p(weights_t), _p(norm),
-          _p(scale_in_rank_order(gs, norm) if want_x else None),
-          _p(gradout), _p(src_map), _p(src_order), _p(grad_x), _p(grad_w), _p(grad_bias), K, D, _p(ws),
-          ws.numel() * 4, _stream(gradout))
-    return grad_x, grad_w, grad_bias
+    return _rgcn_layer_backward("het_rgcn_layer_backward", plan, ssum, weights_t, norm, gradout, want_bias, want_x)
 
 
 def _chk_bf16(name: str, rows=(), floats=()):
@@ -1330,35 +1358,15 @@ def _chk_bf16(name: str, rows=(), floats=()):
 def rgcn_layer_forward_bf16(plan, x, weights, norm, bias):
     """rgcn_layer_forward with bf16 activations (het_rgcn_layer_forward_bf16): x and the returned ret [N,D] bf16; weights, norm,
     bias and the kept sums ssum [S_col,K] fp32."""
-    gd, _, dst_map, dst_order, _, _ = plan
     _chk_bf16("rgcn_layer_forward_bf16", (x,), tuple(t for t in (weights, norm, bias) if t is not None))
-    R, K, D = weights.shape
-    N = dst_map.shape[1]
-    ssum = torch.empty((max(1, gd.num_segments), K), dtype=torch.float32, device=x.device)
-    ret = torch.empty((N, D), dtype=torch.bfloat16, device=x.device)
-    _call(ret, "het_rgcn_layer_forward_bf16", gd.handle, R, N, _p(x), _p(weights), _p(norm), _p(scale_in_rank_order(gd, norm)),
-          _p(bias), _p(dst_map), _p(dst_order), _p(ssum), _p(ret), K, D, _stream(ret))
-    return ret, ssum
+    return _rgcn_layer_forward("het_rgcn_layer_forward_bf16", plan, x, weights, norm, bias)
 
 
 def rgcn_layer_backward_bf16(plan, ssum, weights_t, norm, gradout, want_bias: bool, want_x: bool = True):
     """rgcn_layer_backward with bf16 activations (het_rgcn_layer_backward_bf16): gradout and grad_x [N,K] bf16; grad_w [R,K,D]
     and grad_bias [D] fp32."""
-    gd, gs, _, _, src_map, src_order = plan
     _chk_bf16("rgcn_layer_backward_bf16", (gradout,), (ssum, weights_t, norm))
-    R, D, K = weights_t.shape
-    N = src_map.shape[1]
-    dev = gradout.device
-    grad_x = torch.empty((N, K), dtype=torch.bfloat16, device=dev) if want_x else None
-    grad_w = torch.empty((R, K, D), dtype=torch.float32, device=dev)
-    grad_bias = torch.empty((D,), dtype=torch.float32, device=dev) if want_bias else None
-    nbytes = int(_lib.lib().het_rgcn_layer_backward_workspace(gs.num_segments, D))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    _call(gradout, "het_rgcn_layer_backward_bf16", gs.handle, gd.handle, R, N, gradout.shape[0], _p(ssum), _p(weights_t), _p(norm),
-          _p(scale_in_rank_order(gs, norm) if want_x else None),
-          _p(gradout), _p(src_map), _p(src_order), _p(grad_x), _p(grad_w), _p(grad_bias), K, D, _p(ws),
-          ws.numel() * 4, _stream(gradout))
-    return grad_x, grad_w, grad_bias
+    return _rgcn_layer_backward("het_rgcn_layer_backward_bf16", plan, ssum, weights_t, norm, gradout, want_bias, want_x)
 
 
 # ---- the HGT layer with bf16 activations (backend/hgt_fused_layer.py): activation rows bf16, everything else fp32 ----
@@ -1408,35 +1416,24 @@ def _hgt_bf16_shapes(name, kv_c, q, lsum, out):
     D = out.numel() // max(1, N * H)
     if q.numel() != N * H * D or out.numel() != N * H * D or kv_c.numel() != kv_c.shape[0] * 2 * H * D:
         raise _lib.HetError(f"{name}: kv_c {tuple(kv_c.shape)}, q {tuple(q.shape)}, out {tuple(out.shape)} do not fit lsum {tuple(lsum.shape)}")
-    return N, H, D
 
 
 def hgt_aggregate_compact_bf16(groupings, kv_c, q, lsum, out, workspace=None):
     """hgt_aggregate_compact with bf16 rows (het_hgt_aggregate_compact_bf16): kv_c, q and out bf16, lsum fp32.  ``workspace``: a
     float32 tensor of the caller instead of the one allocated here (the C entry checks its size and alignment)."""
     _chk_bf16("hgt_aggregate_compact_bf16", (kv_c, q, out), (lsum,))
-    N, H, D = _hgt_bf16_shapes("hgt_aggregate_compact_bf16", kv_c, q, lsum, out)
-    nbytes = int(_lib.lib().het_hgt_aggregate_compact_workspace(groupings[0].handle, H, D))  # (hub destinations only)
-    ws = workspace
-    if ws is None and nbytes:
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
-    _call(out, "het_hgt_aggregate_compact_bf16", groupings[0].handle, _p(kv_c), _p(q), _p(lsum), _p(out), N, kv_c.shape[0], H, D,
-          _p(ws), 0 if ws is None else ws.numel() * 4, _stream(out))
+    _hgt_bf16_shapes("hgt_aggregate_compact_bf16", kv_c, q, lsum, out)
+    _hgt_aggregate_compact("het_hgt_aggregate_compact_bf16", groupings, kv_c, q, lsum, out, workspace)
 
 
 def hgt_backward_compact_bf16(groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q, workspace=None):
     """hgt_backward_compact with bf16 rows (het_hgt_backward_compact_bf16): kv_c, q, out and gradout bf16; lsum, grad_kv_c and
     grad_q fp32."""
     _chk_bf16("hgt_backward_compact_bf16", (kv_c, q, out, gradout), (lsum, grad_kv_c, grad_q))
-    N, H, D = _hgt_bf16_shapes("hgt_backward_compact_bf16", kv_c, q, lsum, out)
+    _hgt_bf16_shapes("hgt_backward_compact_bf16", kv_c, q, lsum, out)
     if gradout.numel() != out.numel() or grad_q.numel() != q.numel() or grad_kv_c.numel() != kv_c.numel():
         raise _lib.HetError("hgt_backward_compact_bf16: gradient shapes do not match their tensors")
-    ws = workspace
-    if ws is None:
-        nbytes = int(_lib.lib().het_hgt_backward_compact_workspace(N, H))
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
-    _call(out, "het_hgt_backward_compact_bf16", groupings[0].handle, groupings[1].handle, _p(kv_c), _p(q), _p(lsum), _p(out),
-          _p(gradout), _p(grad_kv_c), _p(grad_q), N, kv_c.shape[0], H, D, _p(ws), ws.numel() * 4, _stream(out))
+    _hgt_backward_compact("het_hgt_backward_compact_bf16", groupings, kv_c, q, lsum, out, gradout, grad_kv_c, grad_q, workspace)
 
 
 def _rgcn_maps(d: Dict[str, Tensor], direct: bool):

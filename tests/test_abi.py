@@ -38,16 +38,65 @@ def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(_lib.LIB_PATH)
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
-    # every declared compute entry point has a ctypes signature (so the Python side calls it typed)
-    untyped = [n for n in names if n not in _lib._SIGNATURES and n not in
-               ("het_build_info", "het_last_error", "het_grouping_destroy", "het_grouping_note_stream", "het_grouping_num_segments", "het_grouping_bytes",
-                "het_kernel_timing_enable", "het_kernel_timing_read", "het_rgat_backward_compact_workspace",
-                "het_hgt_backward_compact_workspace", "het_hgt_compact_shape_ok", "het_rgat_node_gemm_ok", "het_rgat_aggregate_compact_workspace", "het_hgt_aggregate_compact_workspace",
-                "het_rgat_aggregate_compact_runs_workspace", "het_rgat_backward_compact_runs_workspace",
-                "het_set_allocator", "het_allocator_is_external", "het_node_rows_matmul_sum_ok", "het_rgcn_layer_ok",
-                "het_rgcn_layer_backward_workspace")]
+    # every declared function has a ctypes declaration (so the Python side calls it typed)
+    untyped = [n for n in names if n not in _lib._ENTRIES]
     assert not untyped, untyped
     assert "gfx950" in _lib.build_info()
+
+
+def _prototypes():
+    """{name: (return type, [parameter declarations])} of every function include/het_amd.h declares."""
+    src = open(os.path.join(ROOT, "include", "het_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"\b(const\s+char\s*\*|int64_t|int|void)\s*\b(het_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, name
+        params = " ".join(params.split())
+        out[name] = (re.sub(r"\s+", "", ret), [] if params == "void" else [p.strip() for p in params.split(",")])
+    return out
+
+
+def _is_pointer_sized(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def _param_fits(decl, t):
+    """Whether ctypes type ``t`` passes what the C parameter declaration ``decl`` ("const float* x") takes."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"][:-1]  # (without the parameter's name)
+    if "*" in words or words in (["het_stream"], ["het_alloc_fn"], ["het_free_fn"]):
+        return _is_pointer_sized(t)
+    scalar = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "double": ctypes.c_double}
+    assert len(words) == 1 and words[0] in scalar, f"a parameter type this test does not know: {decl!r}"
+    return t is scalar[words[0]]
+
+
+def test_ctypes_table_matches_the_header():
+    """Every prototype of include/het_amd.h against its line of _lib._ENTRIES: the return type, the number of parameters, and for
+    each parameter the class ctypes has to marshal -- a pointer (anything with a *, het_stream, the allocator callbacks) as a
+    pointer-sized type, int64_t as c_int64, int as c_int, double as c_double.  An I64 where the header has a pointer, or a
+    byte-count query left at the default int return, is silent on x86-64 until the value does not fit."""
+    from het_amd import _lib
+    protos = _prototypes()
+    # the parser may skip nothing: it yields exactly the names the looser scan of the export test finds
+    assert sorted(protos) == _declared(), sorted(set(_declared()) ^ set(protos))
+    restypes = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None, "constchar*": ctypes.c_char_p}
+    bad = [f"{name}: in the table, not in the header" for name in _lib._ENTRIES if name not in protos]
+    for name, (ret, params) in protos.items():
+        if name not in _lib._ENTRIES:
+            bad.append(f"{name}: declared in the header, no line in the table")
+            continue
+        restype, argtypes = _lib._ENTRIES[name]
+        if restype is not restypes[ret] or len(argtypes) != len(params) or not all(map(_param_fits, params, argtypes)):
+            bad.append(f"{name}\n  header: {ret} ({', '.join(params)})\n  table:  {getattr(restype, '__name__', restype)} "
+                       f"[{', '.join(t.__name__ for t in argtypes)}]")
+    assert not bad, "ctypes declarations that do not fit include/het_amd.h:\n" + "\n".join(bad)
+    assert list(_lib._ENTRIES) == list(protos), "the table keeps the header's order"
+    # and lib() applies the table as it stands
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib._ENTRIES.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == list(argtypes), name
 
 
 def test_allocator_hook_without_gpu():
