@@ -24,6 +24,9 @@ as a row-dot product on the distinct (relation, destination) rows instead of a p
 forms of er are the same real number (associativity); the reference offers the flag because it is cheaper, and so the
 node takes it whenever the one-head row-dot kernels cover the shape (HET_RGAT_LITERAL_ER=1 keeps (x . W) . attn_r).
 
+The backward of the distinct-row dataflow is ONE function for one GPU and for a partition with a halo
+(RgatLayerFunction._backward_distinct_rows): its routes differ in how the input gradient is formed, nothing else.
+
 Evaluation (torch.no_grad(), or no input that requires a gradient) on the distinct-row dataflow does not go through the node at
 all: _forward_only runs the same forward with an aggregation that keeps nothing for a backward (HET_RGAT_FORWARD_ONLY=0: the
 node's forward, as before).
@@ -88,21 +91,6 @@ def _lists(g):
     return s, by_src, by_dst
 
 
-def _compact_dicts(g, direct):
-    ss = g.get_separate_unique_node_indices_single_sided()
-    if direct:
-        inv = g.get_separate_unique_node_indices_single_sided_inverse_idx()
-        d = {"edata_idx_to_inverse_idx_row": inv["inverse_indices_row"], "edata_idx_to_inverse_idx_col": inv["inverse_indices_col"]}
-        return ss, 4, d, d
-    fwd = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_rel_ptrs_col": ss["rel_ptrs_col"],
-           "unique_srcs_and_dests_node_indices_row": ss["node_indices_row"],
-           "unique_srcs_and_dests_node_indices_col": ss["node_indices_col"]}
-    bwd = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_rel_col": ss["rel_ptrs_col"],
-           "unique_srcs_and_dests_node_indices_row": ss["node_indices_row"],
-           "unique_srcs_and_dests_node_indices_col": ss["node_indices_col"]}
-    return ss, 3, fwd, bwd
-
-
 def _eids_are_positions(eids):
     """Whether eids[p] == p for every position (what canonicalize_eids leaves; checked once per list)."""
     return _k._derived_get("eids_are_positions", (eids,),
@@ -151,11 +139,43 @@ def _side_stream(dev):
     weight-gradient passes (HBM-bound: they stream x / feat_c / gradient rows once) beside the node-major input-gradient pass
     (matrix-core-bound), the self-loop GEMM (HBM-bound) beside the projection GEMM.  The caller brackets the side work with
     events: it starts after everything it reads and the main stream waits for it before anything reads its outputs (or frees
-    its inputs), so the allocator never sees a cross-stream use."""
+    its inputs), so the allocator never sees a cross-stream use.
+    Everything the side stream WRITES is allocated before the fork (``side.wait_stream(main)``): a block handed out later may
+    have been freed by a tensor whose last main-stream kernel was enqueued after the fork -- the side stream would not wait
+    for it."""
     s = _SIDE.get(dev)
     if s is None:
         s = _SIDE[dev] = th.cuda.Stream(device=dev)
     return s
+
+
+def _unique_lists(g):
+    """(ss, d_row, d_col): the graph's unique (relation, source) / (relation, destination) lists and the argument dictionaries
+    (kind 1) of the relational products over either."""
+    ss = g.get_separate_unique_node_indices_single_sided()
+    d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_node_indices": ss["node_indices_row"]}
+    d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
+    return ss, d_row, d_col
+
+
+def _folded_weight(W, attn_r):
+    """wa[r,h,k] = SUM_d W[r,h,k,d] * attn_r[r,h,d] (RGAT/models.py:300-326): the attention vector folded into the weight, as the
+    one-input-head weight [R,H,K,1] of the relational products; its transpose [R,H,1,K] and the rows [R,H,K] of the row-dot and
+    node-major kernels are views of the same memory."""
+    R, H, Kd, D = W.shape
+    return th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1)
+
+
+def _unfold_weight_gradient(grad_wa, W, attn_r, grad_W):
+    """The gradient through _folded_weight: grad_W += grad_wa (x) attn_r in place; returns grad_attn_r.  grad_wa [R,H,K,1]."""
+    R, H, Kd, D = W.shape
+    grad_W.addcmul_(grad_wa, attn_r.view(R, H, 1, D))
+    return (W * grad_wa).sum(2)
+
+
+def _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias):
+    """What RgatLayerFunction.backward returns: nothing for (g, compact, direct, mulfirst, slope, num_dst, halo)."""
+    return None, None, None, None, None, None, None, grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
 
 
 def _halo_pieces(g, ss, plan):
@@ -194,6 +214,35 @@ def _loop_offsets(nd, device):
     return offs
 
 
+def _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst, halo=None):
+    """What every forward starts with: contiguous operands, the destination rows nd, the self-loop's pointer list and the folded
+    weight (None unless ``mulfirst``).  Returns (x, W, attn_l, attn_r, loop_w, nd, offs, wa)."""
+    x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
+    if halo is not None:
+        # multi-GPU (het_amd/dist.py): x holds the owned rows; the halo rows of x_local arrive through an all-to-all
+        # that is in flight until halo.finish_push() -- everything before that reads owned rows only
+        x = halo.start_push(x)
+    N = x.shape[0]
+    nd = N if num_dst is None else min(int(num_dst), N)
+    offs = None
+    if loop_w is not None:
+        loop_w = loop_w.contiguous()
+        offs = _loop_offsets(nd, x.device)
+    return x, W, attn_l, attn_r, loop_w, nd, offs, _folded_weight(W, attn_r) if mulfirst else None
+
+
+def _loop_and_bias_rows(rows, x, nd, offs, loop_w, bias):
+    """Without fused self-loop rows for the aggregation to add into (no self-loop, or widths its fused launch does not take):
+    ``rows`` + x[:nd] . loop_w + bias as a product and an add of their own; None when there is neither term."""
+    if loop_w is None and bias is None:
+        return None
+    loop = None
+    if loop_w is not None:
+        loop = x.new_empty((nd, loop_w.shape[1]))
+        K.rgnn_relational_matmul_no_scatter_gather_list(offs, loop_w.view(1, 1, *loop_w.shape), x[:nd], loop)
+    return _k.rows_add_bias(rows, loop, None if bias is None else bias.contiguous())
+
+
 def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias):
     """The distinct-row forward in front of its aggregation, common to RgatLayerFunction.forward and _forward_only: the
     projections feat_c / el_c / er_c on the unique (relation, node) rows, the self-loop + bias rows ``h`` the aggregation adds into
@@ -206,9 +255,7 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
     X = H * D
     new = lambda *shape: th.empty(shape, dtype=x.dtype, device=x.device)
     h = None
-    ss = g.get_separate_unique_node_indices_single_sided()
-    d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_node_indices": ss["node_indices_row"]}
-    d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
+    ss, d_row, d_col = _unique_lists(g)
     featc = new(ss["node_indices_row"].numel(), H, D)
     elc = new(featc.shape[0], H)
     erc = new(ss["node_indices_col"].numel(), H)
@@ -220,9 +267,7 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
     if OVERLAP and halo is None and fused_loop and mulfirst:
         # er_c (a row-dot) and the self-loop GEMM are HBM-bound streams of rows: on the side stream beside the projection
         main, side = th.cuda.current_stream(x.device), _side_stream(x.device)
-        # everything the side stream WRITES is allocated before the fork: a block handed out later may have been freed by
-        # a tensor whose last main-stream kernel was enqueued after the fork -- the side stream would not wait for it
-        h = x.new_empty((nd, X))
+        h = x.new_empty((nd, X))  # (with erc above: what the side stream writes, allocated before the fork -- _side_stream)
         side.wait_stream(main)
     if mulfirst:
         with th.cuda.stream(side if side is not None else th.cuda.current_stream(x.device)):
@@ -243,6 +288,8 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
             h = _k.rows_linear_bias(offs, x[:nd], loop_w, bias_c)
     dot_ok = _k.matmul_attn_dot_ok(H, Kd, D)
     piecewise = halo is not None and halo.chunks > 1 and dot_ok
+    if halo is not None and not piecewise:
+        halo.finish_push()
     if piecewise:
         # the exchange arrives in pieces (het_amd/dist.py: DistPlan.chunks): the rows whose source node is owned are
         # projected at once, the rows of piece c as soon as piece c is there -- piece c + 1 is on the wire meanwhile
@@ -250,10 +297,6 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
             halo.wait_push_piece(c)
             _k.matmul_attn_dot_rows(rp_c, nodes_c, rows_c, W, x, featc, attn_l, elc)
         halo.finish_push()
-    elif halo is not None:
-        halo.finish_push()
-    if piecewise:
-        pass  # (projected above)
     elif dot_ok:
         _k.matmul_attn_dot(d_row, 1, W, x, featc, attn_l, elc)  # el_c = <feat_c, attn_l[r]> from the GEMM epilogue
     else:  # other widths: any-shape projection, then el_c as a row-dot over the relation-bucketed rows
@@ -270,16 +313,34 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
     return ss, h, saved, grp, run_sums
 
 
+def _per_relation_front(x, loop_w, offs, grad_h, nd, H, dst_prefix):
+    """What the two backwards that add the input gradient relation by relation (generic distinct rows, per edge) start with.
+    Returns (grad_x, grad_loop, go): ONE input-gradient buffer -- the self-loop writes its rows with plain stores (and its weight
+    gradient from the same launch), the projections add to it -- and the output gradient per destination row."""
+    N, Kd = x.shape
+    X = grad_h.shape[1]
+    grad_loop = None
+    if loop_w is not None:
+        grad_x = th.empty_like(x) if nd == N else th.zeros_like(x)
+        grad_loop = th.empty_like(loop_w)
+        _k.matmul_no_scatter_gather_backward(offs, loop_w.view(1, 1, Kd, X).transpose(2, 3).contiguous(), x[:nd], grad_h,
+                                             grad_x[:nd], grad_loop.view(1, 1, Kd, X), accumulate=False)
+    else:
+        grad_x = th.zeros_like(x)
+    if nd == N or dst_prefix:
+        go = grad_h.view(nd, H, X // H)
+    else:  # rows of non-destination nodes receive no gradient
+        go = th.zeros((N, H, X // H), dtype=x.dtype, device=x.device)
+        go.view(N, X)[:nd] = grad_h
+    return grad_x, grad_loop, go
+
+
 @_consistent_plan
 class RgatLayerFunction(th.autograd.Function):
     @staticmethod
     def forward(ctx, g, compact, direct, mulfirst, slope, num_dst, halo, x, W, attn_l, attn_r, loop_w, bias):
-        x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
-        if halo is not None:
-            # multi-GPU (het_amd/dist.py): x holds the owned rows; the halo rows of x_local arrive through an all-to-all
-            # that is in flight until halo.finish_push() -- everything before that reads owned rows only
-            assert compact and mulfirst and loop_w is not None, "rgat_layer_halo_ok guards this path"
-            x = halo.start_push(x)
+        assert halo is None or (compact and mulfirst and loop_w is not None), "rgat_layer_halo_ok guards this path"
+        x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst, halo)
         s, by_src, by_dst = _lists(g)
         rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
         E, N = eids.numel(), x.shape[0]
@@ -287,14 +348,7 @@ class RgatLayerFunction(th.autograd.Function):
         X = H * D
         new = lambda *shape: th.empty(shape, dtype=x.dtype, device=x.device)
         sm, ret = new(N, H), new(N, H, D)
-        nd = N if num_dst is None else min(int(num_dst), N)
-        offs = h = None
-        if loop_w is not None:
-            loop_w = loop_w.contiguous()
-            offs = _loop_offsets(nd, x.device)
-        wa = None
-        if mulfirst:  # RGAT/models.py:300-326: the attention vector folded into the weight, [R,H,K,1]
-            wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1)
+        h = None
         if compact:
             ss, h, saved, grp, run_sums = _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
             featc, elc, erc = saved[:3]
@@ -323,11 +377,9 @@ class RgatLayerFunction(th.autograd.Function):
             ex = x.new_empty(0)
         if h is None:
             out = ret.view(N, X)[:nd]
-            loop = None
-            if loop_w is not None:
-                loop = new(nd, X)
-                K.rgnn_relational_matmul_no_scatter_gather_list(offs, loop_w.view(1, 1, Kd, X), x[:nd], loop)
-            h = _k.rows_add_bias(out, loop, None if bias is None else bias.contiguous()) if (loop is not None or bias is not None) else out.clone()
+            h = _loop_and_bias_rows(out, x, nd, offs, loop_w, bias)
+            if h is None:
+                h = out.clone()
         ctx.halo = halo
         ctx.g, ctx.compact, ctx.mulfirst, ctx.slope, ctx.nd = g, compact, mulfirst, slope, nd
         ctx.has_loop, ctx.has_bias = loop_w is not None, bias is not None
@@ -337,6 +389,9 @@ class RgatLayerFunction(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_h):
+        grad_h = grad_h.contiguous()
+        if ctx.compact:
+            return RgatLayerFunction._backward_distinct_rows(ctx, grad_h)
         x, W, attn_l, attn_r, loop_w, offs, sm, ex, ret, *saved = ctx.saved_tensors
         g, nd, slope = ctx.g, ctx.nd, ctx.slope
         s, by_src, by_dst = _lists(g)
@@ -344,139 +399,128 @@ class RgatLayerFunction(th.autograd.Function):
         N, Kd = x.shape
         E = eids.numel()
         R, H, _, D = W.shape
-        X = H * D
-        grad_h = grad_h.contiguous()
-        if ctx.halo is not None:
-            return RgatLayerFunction._backward_with_halo(ctx, grad_h)
-        grad_bias = grad_h.sum(0) if (ctx.has_bias and not ctx.compact) else None
+        grad_bias = grad_h.sum(0) if ctx.has_bias else None
         Wt = th.transpose(W, 2, 3).contiguous()
-        if ctx.compact and ctx.mulfirst and _k.rgat_node_gemm_ok(R, H, Kd, D) and _destinations_below(col, nd):
-            return RgatLayerFunction._backward_node_major(ctx, grad_h, Wt)
         grad_W = th.zeros_like(W)
-        # one input-gradient buffer: the self-loop writes its rows with plain stores, the projections add to it
-        grad_loop = None
-        if ctx.has_loop:
-            grad_x = th.empty_like(x) if nd == N else th.zeros_like(x)
-            grad_loop = th.empty_like(loop_w)
-            _k.matmul_no_scatter_gather_backward(offs, loop_w.view(1, 1, Kd, X).transpose(2, 3).contiguous(), x[:nd], grad_h,
-                                                 grad_x[:nd], grad_loop.view(1, 1, Kd, X), accumulate=False)
-        else:
-            grad_x = th.zeros_like(x)
-        # every edge points at one of the first nd nodes (blocks, partitions: checked once per graph)?  then the
-        # per-destination tensors of the distinct-row backward are their first nd rows
-        dst_prefix = ctx.compact and _destinations_below(col, nd)
-        if nd == N or dst_prefix:
-            go = grad_h.view(nd, H, D)
-        else:  # rows of non-destination nodes receive no gradient
-            go = th.zeros((N, H, D), dtype=x.dtype, device=x.device)
-            go.view(N, X)[:nd] = grad_h
-        ndp = nd if dst_prefix else N
+        grad_x, grad_loop, go = _per_relation_front(x, loop_w if ctx.has_loop else None, offs, grad_h, nd, H, False)
         mulfirst = ctx.mulfirst
         if mulfirst:
-            wa_t = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, 1, Kd)  # [R,H,K,1] transposed(2,3): same memory
+            wa_t = _folded_weight(W, attn_r).view(R, H, 1, Kd)
             grad_wa = th.zeros((R, H, Kd, 1), dtype=x.dtype, device=x.device)
-        if ctx.compact:
-            featc, elc, erc = saved[:3]
-            featd = None if mulfirst else saved[3]
-            ss = g.get_separate_unique_node_indices_single_sided()
-            d_row = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_row"], "unique_srcs_and_dests_node_indices": ss["node_indices_row"]}
-            d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
-            g_featc, g_elc, g_erc = th.empty_like(featc), th.empty_like(elc), th.empty_like(erc)  # all three overwritten
-            if ctx.has_bias:  # the bias gradient (column sums of grad_h) from the pass that reads every gradout row anyway
-                grad_bias = th.empty(X, dtype=x.dtype, device=x.device)
-            _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:ndp], ret[:ndp], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
-                                     row_rel_ptrs=ss["rel_ptrs_row"], grad_bias=grad_bias if ctx.has_bias else None, bias_rows=nd,
-                                     runs=ctx.runs, drow_nodes=ss["node_indices_col"])
-            grad_attn_l, grad_attn_r = th.empty_like(attn_l), th.empty_like(attn_r)
-            _k.matmul_no_scatter_gather_backward(ss["rel_ptrs_row"], attn_l.unsqueeze(2), featc, g_elc, None,
-                                                 grad_attn_l.unsqueeze(-1), accumulate=False)
-            _k.matmul_backward(d_row, 1, Wt, x, g_featc, grad_x, grad_W, True, accumulate=True, distinct_rows=True)
-            if mulfirst:
-                _k.matmul_backward(d_col, 1, wa_t, x, g_erc.view(-1, H, 1), grad_x, grad_wa, True, accumulate=True, distinct_rows=True)
-            else:
-                g_featd = th.empty_like(featd)
-                _k.matmul_no_scatter_gather_backward(ss["rel_ptrs_col"], attn_r.unsqueeze(2), featd, g_erc, g_featd,
-                                                     grad_attn_r.unsqueeze(-1), accumulate=False)
-                _k.matmul_backward(d_col, 1, Wt, x, g_featd, grad_x, grad_W, True, accumulate=True, distinct_rows=True)
+        feat, exs = saved[:2]
+        # the edges' grad_el (= grad_er) in the kernel's destination-grouped order: sequential stores, and the
+        # (relation, destination) sums of the er side read contiguous runs instead of scattered 16-byte pieces
+        rank = _k.gat_rank_of_position(rp, row, col, eids, N)
+        by_dst = {"separate_coo_rel_ptrs": rp, "separate_coo_node_indices": col, "separate_coo_eids": rank}
+        g_feat, g_el = th.empty_like(feat), th.empty_like(exs)
+        grad_attn_l = th.zeros_like(attn_l)
+        if R <= 8:
+            _k.fused_gat_backward(eids, rp, row, col, 0, {}, feat, None, None, sm, None, ret, go, g_feat, None, None, slope,
+                                  exs, fold_attn_l=attn_l, grad_fold_attn_l=grad_attn_l, grad_el_sorted=g_el)
         else:
-            feat, exs = saved[:2]
-            # the edges' grad_el (= grad_er) in the kernel's destination-grouped order: sequential stores, and the
-            # (relation, destination) sums of the er side read contiguous runs instead of scattered 16-byte pieces
-            rank = _k.gat_rank_of_position(rp, row, col, eids, N)
-            by_dst = {"separate_coo_rel_ptrs": rp, "separate_coo_node_indices": col, "separate_coo_eids": rank}
-            g_feat, g_el = th.empty_like(feat), th.empty_like(exs)
-            grad_attn_l = th.zeros_like(attn_l)
-            if R <= 8:
-                _k.fused_gat_backward(eids, rp, row, col, 0, {}, feat, None, None, sm, None, ret, go, g_feat, None, None, slope,
-                                      exs, fold_attn_l=attn_l, grad_fold_attn_l=grad_attn_l, grad_el_sorted=g_el)
-            else:
-                g_el_e = th.empty_like(exs)
-                _k.fused_gat_backward(eids, rp, row, col, 0, {}, feat, None, None, sm, None, ret, go, g_feat, g_el_e, g_el_e, slope,
-                                      exs, fold_attn_l=attn_l, grad_el_sorted=g_el)
-                by_eid = {"separate_coo_rel_ptrs": rp, "separate_coo_node_indices": eids, "separate_coo_eids": eids}
-                _k.matmul_backward(by_eid, 0, attn_l.unsqueeze(2), feat, g_el_e, None, grad_attn_l.unsqueeze(-1), False,
-                                   accumulate=False)
-            _k.matmul_backward(by_src, 0, Wt, x, g_feat, grad_x, grad_W, True, accumulate=True)
-            if mulfirst:
-                _k.matmul_backward(by_dst, 0, wa_t, x, g_el.view(E, H, 1), grad_x, grad_wa, True, accumulate=True)
-            else:
-                grad_attn_r = th.zeros_like(attn_r)
-                ok = _k.matmul_attn_dot_only_backward(by_dst, Wt, x, attn_r, g_el, grad_x, grad_W, comp_rows=saved[2],
-                                                      grad_dot_w=grad_attn_r, accumulate=True)
-                assert ok, "the grouping of the forward pass is gone"
-        if mulfirst:  # through wa[r,h,k] = SUM_d W[r,h,k,d] * attn_r[r,h,d]
-            grad_W.addcmul_(grad_wa, attn_r.view(R, H, 1, D))
-            grad_attn_r = (W * grad_wa).sum(2)
-        return None, None, None, None, None, None, None, grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
-
+            g_el_e = th.empty_like(exs)
+            _k.fused_gat_backward(eids, rp, row, col, 0, {}, feat, None, None, sm, None, ret, go, g_feat, g_el_e, g_el_e, slope,
+                                  exs, fold_attn_l=attn_l, grad_el_sorted=g_el)
+            by_eid = {"separate_coo_rel_ptrs": rp, "separate_coo_node_indices": eids, "separate_coo_eids": eids}
+            _k.matmul_backward(by_eid, 0, attn_l.unsqueeze(2), feat, g_el_e, None, grad_attn_l.unsqueeze(-1), False,
+                               accumulate=False)
+        _k.matmul_backward(by_src, 0, Wt, x, g_feat, grad_x, grad_W, True, accumulate=True)
+        if mulfirst:
+            _k.matmul_backward(by_dst, 0, wa_t, x, g_el.view(E, H, 1), grad_x, grad_wa, True, accumulate=True)
+            grad_attn_r = _unfold_weight_gradient(grad_wa, W, attn_r, grad_W)
+        else:
+            grad_attn_r = th.zeros_like(attn_r)
+            ok = _k.matmul_attn_dot_only_backward(by_dst, Wt, x, attn_r, g_el, grad_x, grad_W, comp_rows=saved[2],
+                                                  grad_dot_w=grad_attn_r, accumulate=True)
+            assert ok, "the grouping of the forward pass is gone"
+        return _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias)
 
     @staticmethod
-    def _backward_node_major(ctx, grad_h, Wt):
-        """The backward on the distinct-row dataflow with every term of the INPUT gradient gathered per node
-        (csrc/node_gemm.hip): one pass stores grad_x (self-loop + relation projections + the folded attention vector) -- instead
-        of a self-loop pass and one read-modify-write launch per relation and side."""
-        x, W, attn_l, attn_r, loop_w, offs, sm, ex, ret, featc, elc, erc = ctx.saved_tensors
-        g, nd, slope = ctx.g, ctx.nd, ctx.slope
+    def _backward_distinct_rows(ctx, grad_h):
+        """The backward on the distinct-row dataflow, on one GPU and on a partition.  One edge pass (rgat_backward_compact) leaves
+        the gradients of the compact tables; what differs between the routes is how the input gradient is formed from them:
+          node-major              every term of grad_x gathered per node (csrc/node_gemm.hip): one pass stores grad_x (self-loop +
+                                  relation projections + the folded attention vector) -- instead of a self-loop pass and one
+                                  read-modify-write launch per relation and side.  er from the folded weight, the shapes of
+                                  het_rgat_node_gemm_ok, every edge ending below nd.
+          node-major, partition   the same pass per node range, ordered around the reverse halo exchange: the halo rows first --
+                                  only the (relation, source) projections reach them -- so that they leave with an all-to-all
+                                  while the owned rows and the weight gradients are formed; the returned rows are added to the
+                                  owners' gradients at the end.
+          per relation            the self-loop stores its rows of grad_x, the projections add theirs relation by relation: a
+                                  partition at the other matrix-core shapes (split launches: input gradient, then weight
+                                  gradients), and every other call (``generic``: any shape, literal er, edges ending at or above
+                                  nd -- launches that form an input and a weight gradient together, "+=").
+        On all but the generic route the weight gradients are launches of their own, HBM-bound streams of rows: on the side stream
+        beside the gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once."""
+        x, W, attn_l, attn_r, loop_w, offs, sm, _, ret, featc, elc, erc, *featd = ctx.saved_tensors
+        g, nd, slope, halo, runs, has_loop, has_bias, mulfirst = ctx.g, ctx.nd, ctx.slope, ctx.halo, ctx.runs, ctx.has_loop, ctx.has_bias, ctx.mulfirst
         N, Kd = x.shape
         R, H, _, D = W.shape
         X = H * D
-        ss = g.get_separate_unique_node_indices_single_sided()
-        rp_row = ss["rel_ptrs_row"]
-        row_map = _k.node_row_map(rp_row, ss["node_indices_row"], N)
-        dst_map = _k.node_row_map(ss["rel_ptrs_col"], ss["node_indices_col"], N)
-        go = grad_h.view(nd, H, D)  # every edge points at one of the first nd nodes (checked by the caller)
-        # (the weight gradient of attn_l from the same pass when the forward left run sums: csrc/gat_compact.hip ga_block_reduce;
+        ss, d_row, d_col = _unique_lists(g)
+        rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
+        # every edge points at one of the first nd nodes (blocks, partitions: checked once per graph)?  then the
+        # per-destination tensors of the backward are their first nd rows
+        dst_prefix = _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
+        assert halo is None or dst_prefix, "a partition's edges point at owned nodes"
+        node_major = mulfirst and dst_prefix and _k.rgat_node_gemm_ok(R, H, Kd, D)
+        # (exactly one of the three routes of the docstring; the last two add to grad_x per relation)
+        generic = not node_major and halo is None
+        per_relation_halo = not node_major and halo is not None
+        # (the weight gradient of attn_l from the edge pass when the forward left run sums: csrc/gat_compact.hip ga_block_reduce;
         #  grad_el_c then has no reader left -- its other consumer, the gradient through el, is folded into grad_feat_c -- and is
         #  not written at all)
-        attn_in_pass = ctx.runs is not None and R <= 8
-        g_featc, g_erc = th.empty_like(featc), th.empty_like(erc)  # overwritten
-        g_elc = None if attn_in_pass else th.empty_like(elc)
-        grad_bias = th.empty(X, dtype=x.dtype, device=x.device) if ctx.has_bias else None
-        grad_loop = th.empty_like(loop_w) if ctx.has_loop else None
+        attn_in_pass = not generic and runs is not None and R <= 8
         # (the self-loop product names each of the nd output rows once: the column sums of its gradout rows ARE the bias gradient,
         #  from the weight-gradient launch that streams grad_h anyway instead of a pass of its own inside the gather op: 0.088 ms on
         #  ogbn-mag)
         # (offs = [0, nd] by construction in forward())
-        bias_in_dw = ctx.has_bias and ctx.has_loop
-        main, side = th.cuda.current_stream(x.device), _side_stream(x.device) if OVERLAP else None
-        if side is not None and ctx.has_loop:
+        bias_in_dw = not generic and has_bias and has_loop
+        main, side = th.cuda.current_stream(x.device), _side_stream(x.device) if OVERLAP and not generic else None
+        Wt = th.transpose(W, 2, 3).contiguous()
+        if generic:
+            grad_x, grad_loop, go = _per_relation_front(x, loop_w if has_loop else None, offs, grad_h, nd, H, dst_prefix)
+        else:
+            go = grad_h.view(nd, H, D)
+            grad_loop = th.empty_like(loop_w) if has_loop else None
+        ndp = go.shape[0]
+        g_featc, g_erc = th.empty_like(featc), th.empty_like(erc)  # overwritten
+        # (on a partition the edge pass is handed a grad_el_c it need not write: an argument of the launch, left as it was)
+        g_elc = None if attn_in_pass and halo is None else th.empty_like(elc)
+        grad_bias = th.empty(X, dtype=x.dtype, device=x.device) if has_bias else None
+
+        def loop_weight_gradient():
+            _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
+                                       colsum=grad_bias if bias_in_dw else None)
+        # Everything the side stream writes is allocated before the fork (side.wait_stream(main)) that precedes the write, for the
+        # reason _side_stream gives.  There are two forks: this one, in front of the self-loop's launch, which writes grad_loop and
+        # grad_bias alone (allocated above); and the one in front of weight_gradients() on the node-major routes, which writes
+        # grad_attn_l, grad_W and grad_wa (allocated between the two).  Nothing else is written from the side stream.
+        if side is not None and has_loop:
             # the self-loop weight gradient needs x and grad_h only: an HBM-bound stream of rows beside the gather passes below
             # (at the start of the backward: beside the node-major pass instead it stretched the two short per-destination
             #  passes, profiles/r04/default_timeline.txt: 3.97 -> 4.02 ms)
             side.wait_stream(main)
             with th.cuda.stream(side):
-                _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
-                                           colsum=grad_bias if bias_in_dw else None)
-        grad_attn_l = th.empty_like(attn_l)
-        _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:nd], ret[:nd], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
-                                 row_rel_ptrs=rp_row, grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=ctx.runs,
+                loop_weight_gradient()
+        if per_relation_halo:  # the self-loop's rows of grad_x first, plain stores
+            grad_x = th.empty_like(x)
+            grad_x[nd:].zero_()  # halo rows: only the projection's input gradient adds to them
+            _k.rows_matmul_backward_dx(offs, None, loop_w.t().contiguous().view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
+        grad_attn_l = th.empty_like(attn_l)  # (written by the edge pass on this stream, or after the second fork)
+        # the bias gradient (column sums of grad_h) from the pass that reads every gradout row anyway, unless bias_in_dw
+        _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:ndp], ret[:ndp], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
+                                 row_rel_ptrs=rp_row, grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=runs,
                                  drow_nodes=ss["node_indices_col"], grad_attn_l=grad_attn_l if attn_in_pass else None)
-        wa_t = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd)  # wa[r,h,:] = W[r,h] . attn_r[r,h]
-        grad_x = th.empty_like(x)
-        grad_W, grad_wa = th.empty_like(W), th.empty((R, H, Kd), dtype=x.dtype, device=x.device)
-        gh = grad_h if ctx.has_loop else None
-        loop_wt = loop_w.t().contiguous() if ctx.has_loop else None
-        d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
+        if mulfirst:
+            wa = _folded_weight(W, attn_r)
+        # what the launches below write: "=" outputs are allocated, "+=" outputs zero-filled
+        if node_major:
+            grad_x = th.empty_like(x)
+        grad_W = th.zeros_like(W) if generic else th.empty_like(W)
+        if mulfirst:
+            grad_wa = (th.empty if node_major else th.zeros)((R, H, Kd, 1), dtype=x.dtype, device=x.device)
 
         def weight_gradients():
             # per product (four launches; each reads its own rows of x / feat_c -- a node-major pass that reads x once was
@@ -484,118 +528,61 @@ class RgatLayerFunction(th.autograd.Function):
             if not attn_in_pass:
                 _k.matmul_no_scatter_gather_backward(rp_row, attn_l.unsqueeze(2), featc, g_elc, None, grad_attn_l.unsqueeze(-1),
                                                      accumulate=False)
-            if ctx.has_loop and side is None:
-                _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
-                                           colsum=grad_bias if bias_in_dw else None)
-            _k.rows_matmul_backward_dw(rp_row, ss["node_indices_row"], x, g_featc.view(-1, X), grad_W, accumulate=False)
-            _k.matmul_backward(d_col, 1, wa_t.view(R, H, 1, Kd), x, g_erc.view(-1, H, 1), None, grad_wa.view(R, H, Kd, 1), True,
-                               accumulate=False)
-
-        # (on a block only the first nd nodes carry the self-loop term: they stay in front, so that term's tiles are whole too)
-        order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None)
-
-        def input_gradient():
-            _k.rgat_node_backward_dx(0, N, nd, gh, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc, wa_t, dst_map, grad_x,
-                                     node_order=order)
-        if side is not None:
-            # the weight gradients (HBM-bound streams of rows) on the side stream while the node-major pass (matrix-core-bound)
-            # runs on this one; both read g_featc / g_erc / grad_h, neither writes what the other reads
-            side.wait_stream(main)
-            with th.cuda.stream(side):
-                weight_gradients()
-            input_gradient()
-            main.wait_stream(side)
-        else:
-            input_gradient()
-            weight_gradients()
-        grad_W.addcmul_(grad_wa.unsqueeze(-1), attn_r.view(R, H, 1, D))  # through wa[r,h,k] = SUM_d W[r,h,k,d] * attn_r[r,h,d]
-        grad_attn_r = (W * grad_wa.unsqueeze(-1)).sum(2)
-        return None, None, None, None, None, None, None, grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
-
-    @staticmethod
-    def _backward_with_halo(ctx, grad_h):
-        """The backward on a partition, ordered around the reverse halo exchange: the input gradient through the
-        (relation, source) projection -- the only one that reaches halo rows -- is formed first and its halo rows leave with
-        an all-to-all; the weight gradients, the destination side and the rest of the self-loop run while it is in flight;
-        the returned rows are added to the owners' gradients at the end."""
-        x, W, attn_l, attn_r, loop_w, offs, sm, ex, ret, featc, elc, erc = ctx.saved_tensors
-        g, nd, slope, halo = ctx.g, ctx.nd, ctx.slope, ctx.halo
-        N, Kd = x.shape
-        R, H, _, D = W.shape
-        X = H * D
-        ss = g.get_separate_unique_node_indices_single_sided()
-        rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
-        d_col = {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"], "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}
-        Wt = th.transpose(W, 2, 3).contiguous()
-        s_coo = g.get_separate_coo_original()
-        assert _destinations_below(s_coo["col_indices"], nd), "a partition's edges point at owned nodes"
-        go = grad_h.view(nd, H, D)  # (so the per-destination tensors of the backward are their first nd rows)
-        g_featc, g_elc, g_erc = th.empty_like(featc), th.empty_like(elc), th.empty_like(erc)
-        grad_bias = th.empty(X, dtype=x.dtype, device=x.device) if ctx.has_bias else None
-        wa_t = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, 1, Kd)
-        grad_x = th.empty_like(x)
-        grad_W, grad_loop = th.empty_like(W), th.empty_like(loop_w)
-        grad_attn_l = th.empty_like(attn_l)
-        node_major = _k.rgat_node_gemm_ok(R, H, Kd, D)
-        # as on one GPU (_backward_node_major): the weight gradients are HBM-bound streams of rows -- on the side stream beside the
-        # gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once
-        main, side = th.cuda.current_stream(x.device), (_side_stream(x.device) if OVERLAP and x.is_cuda else None)
-        bias_in_dw = ctx.has_bias  # (as in _backward_node_major)
-        if side is not None:
-            side.wait_stream(main)
-            with th.cuda.stream(side):
-                _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
-                                           colsum=grad_bias if bias_in_dw else None)
-        if not node_major:
-            grad_x[nd:].zero_()  # halo rows: only the projection's input gradient adds to them
-            _k.rows_matmul_backward_dx(offs, None, loop_w.t().contiguous().view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
-        attn_in_pass = ctx.runs is not None and R <= 8 and x.is_cuda
-        _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:nd], ret[:nd], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
-                                 row_rel_ptrs=rp_row, grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=ctx.runs,
-                                 drow_nodes=ss["node_indices_col"], grad_attn_l=grad_attn_l if attn_in_pass else None)
-        grad_wa = th.empty((R, H, Kd, 1), dtype=x.dtype, device=x.device) if node_major else th.zeros((R, H, Kd, 1), dtype=x.dtype, device=x.device)
-
-        def weight_gradients():
-            if side is None:
-                _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
-                                           colsum=grad_bias if bias_in_dw else None)
+            if generic:  # (the other three come with the input gradients below)
+                return
+            if has_loop and side is None:
+                loop_weight_gradient()
             _k.rows_matmul_backward_dw(rp_row, rows_node, x, g_featc.view(-1, X), grad_W, accumulate=False)
-            if not attn_in_pass:
-                _k.matmul_no_scatter_gather_backward(rp_row, attn_l.unsqueeze(2), featc, g_elc, None, grad_attn_l.unsqueeze(-1),
-                                                     accumulate=False)
             if node_major:  # the er side's weight gradient alone (its input gradient is a term of the node pass)
-                _k.matmul_backward(d_col, 1, wa_t, x, g_erc.view(-1, H, 1), None, grad_wa, True, accumulate=False)
+                _k.matmul_backward(d_col, 1, wa.view(R, H, 1, Kd), x, g_erc.view(-1, H, 1), None, grad_wa, True, accumulate=False)
 
         if node_major:
-            # one pass per node range (csrc/node_gemm.hip): the halo rows first -- only the (relation, source) projections reach
-            # them -- so that they leave with the all-to-all while the owned rows (self-loop + projections + folded attention
-            # vector, every term in one store) and the weight gradients are formed
             row_map = _k.node_row_map(rp_row, rows_node, N)
             dst_map = _k.node_row_map(ss["rel_ptrs_col"], ss["node_indices_col"], N)
-            loop_wt = loop_w.t().contiguous()
-            order = _k.node_order_by_presence(row_map, dst_map, split=nd)
-            args = (grad_h, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc, wa_t.view(R, H, Kd), dst_map, grad_x, order)
-            _k.rgat_node_backward_dx(nd, N, nd, *args)
-            halo.start_return(grad_x)
+            loop_wt = loop_w.t().contiguous() if has_loop else None
+            # (on a block or a partition only the first nd nodes carry the self-loop term: they stay in front, so that term's
+            #  tiles are whole too)
+            order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None)
+
+            def input_gradient(begin, end):
+                _k.rgat_node_backward_dx(begin, end, nd, grad_h if has_loop else None, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc,
+                                         wa.view(R, H, Kd), dst_map, grad_x, node_order=order)
+            if halo is not None:
+                input_gradient(nd, N)
+                halo.start_return(grad_x)
             if side is not None:
-                side.wait_stream(main)  # (g_featc / g_erc are complete)
+                # the weight gradients (HBM-bound streams of rows) on the side stream while the node-major pass (matrix-core-bound)
+                # runs on this one; both read g_featc / g_erc / grad_h, neither writes what the other reads
+                # (the second fork: grad_W / grad_wa / grad_attn_l are allocated above it)
+                side.wait_stream(main)
                 with th.cuda.stream(side):
                     weight_gradients()
-            _k.rgat_node_backward_dx(0, nd, nd, *args)
+            input_gradient(0, N if halo is None else nd)
             if side is None:
                 weight_gradients()
         else:
-            _k.rows_matmul_backward_dx(rp_row, rows_node, Wt, g_featc.view(-1, X), grad_x, atomic=2)  # rows of a relation: distinct nodes
-            halo.start_return(grad_x)
+            if halo is not None:
+                _k.rows_matmul_backward_dx(rp_row, rows_node, Wt, g_featc.view(-1, X), grad_x, atomic=2)  # rows of a relation: distinct nodes
+                halo.start_return(grad_x)
             weight_gradients()
-            # the er side's weight gradient and, on the per-relation path, its input gradient (owned rows only)
-            _k.matmul_backward(d_col, 1, wa_t, x, g_erc.view(-1, H, 1), grad_x, grad_wa, True, accumulate=True, distinct_rows=True)
+            if generic:
+                _k.matmul_backward(d_row, 1, Wt, x, g_featc, grad_x, grad_W, True, accumulate=True, distinct_rows=True)
+            if mulfirst:
+                # the er side's weight gradient and its input gradient (destination rows: owned rows only on a partition)
+                _k.matmul_backward(d_col, 1, wa.view(R, H, 1, Kd), x, g_erc.view(-1, H, 1), grad_x, grad_wa, True, accumulate=True,
+                                   distinct_rows=True)
+            else:  # literal er: through the destination-side projection table
+                g_featd, grad_attn_r = th.empty_like(featd[0]), th.empty_like(attn_r)
+                _k.matmul_no_scatter_gather_backward(ss["rel_ptrs_col"], attn_r.unsqueeze(2), featd[0], g_erc, g_featd,
+                                                     grad_attn_r.unsqueeze(-1), accumulate=False)
+                _k.matmul_backward(d_col, 1, Wt, x, g_featd, grad_x, grad_W, True, accumulate=True, distinct_rows=True)
         if side is not None:
             main.wait_stream(side)
-        grad_W.addcmul_(grad_wa, attn_r.view(R, H, 1, D))  # through wa[r,h,k] = SUM_d W[r,h,k,d] * attn_r[r,h,d]
-        grad_attn_r = (W * grad_wa).sum(2)
-        grad_own = halo.finish_return(grad_x[:nd])
-        return None, None, None, None, None, None, None, grad_own, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
+        if mulfirst:
+            grad_attn_r = _unfold_weight_gradient(grad_wa, W, attn_r, grad_W)
+        if halo is not None:
+            grad_x = halo.finish_return(grad_x[:nd])
+        return _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias)
 
 
 def rgat_layer_halo_ok(g, x_own, W, slope, compact, mulfirst=False):
@@ -622,32 +609,21 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     nothing saved), the same projections and the same self-loop rows, and an aggregation that writes the layer output alone
     (csrc/gat_compact.hip: the _fwd kernels) -- no lse [N,H], no ret [N,H,D], no run sums [S_col,H,D].  Every output row is bit
     for bit the training forward's.  ``attn_out`` (a list): the attention weights [E,H] are appended to it."""
-    x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
-    N = x.shape[0]
-    R, H, Kd, D = W.shape
-    X = H * D
-    nd = N if num_dst is None else min(int(num_dst), N)
-    offs = None
-    if loop_w is not None:
-        loop_w = loop_w.contiguous()
-        offs = _loop_offsets(nd, x.device)
-    wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1) if mulfirst else None
+    x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst)
+    R, H, _, D = W.shape
     ss, h, saved, grp, _ = _compact_tables(g, direct, mulfirst, None, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
     featc, elc, erc = saved[:3]
     fused = h is not None
     if not fused:  # no self-loop rows to add into (no self-loop, or widths its fused launch does not take): zeros, the tail below
-        h = x.new_zeros((nd, X))
+        h = x.new_zeros((nd, H * D))
     _k.rgat_aggregate_compact_forward(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
     if attn_out is not None:
-        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, N))
+        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, x.shape[0]))
     if fused:
         return h
-    loop = None
-    if loop_w is not None:
-        loop = x.new_empty((nd, X))
-        K.rgnn_relational_matmul_no_scatter_gather_list(offs, loop_w.view(1, 1, Kd, X), x[:nd], loop)
-    # (the training forward clones its view of ret here when there is nothing to add; h is already a buffer of its own)
-    return _k.rows_add_bias(h, loop, None if bias is None else bias.contiguous()) if (loop is not None or bias is not None) else h
+    # (the training forward clones its view of ret when there is nothing to add; h is already a buffer of its own)
+    rows = _loop_and_bias_rows(h, x, nd, offs, loop_w, bias)
+    return h if rows is None else rows
 
 
 def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
@@ -656,25 +632,21 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
     instead of the projection's epilogue.  ``attn_out`` (a list): the attention weights [E,H] (fp32) are appended to it; where the
     walk formed el from the row it gathered, el_c is made for them by the same row-dot pass, so they are the softmax the output used."""
-    x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
+    # (the folded weight is fp32; the cached [0, nd] list and a copy of the self-loop weight are made here, under the main stream)
+    x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, True)
     s, _, _ = _lists(g)
     rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
     N = x.shape[0]
     R, H, Kd, D = W.shape
     X = H * D
-    nd = N if num_dst is None else min(int(num_dst), N)
     dev = x.device
     ss = g.get_separate_unique_node_indices_single_sided()
-    wa = th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd)  # the folded weight, fp32
-    # (everything the side stream writes is allocated before the fork: see _compact_tables)
+    # (everything the side stream writes is allocated before the fork: _side_stream)
     featc = th.empty((ss["node_indices_row"].numel(), H, D), dtype=th.bfloat16, device=dev)
     erc = th.empty((ss["node_indices_col"].numel(), H), dtype=th.float32, device=dev)
     elc = None if _k.rgat_el_from_row(H, D, R) else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
     bias_c = None if bias is None else bias.contiguous()
-    offs = None
-    if loop_w is not None:  # (the cached [0, nd] list and a copy of the weight too: made under the main stream)
-        loop_w = loop_w.contiguous()
-        offs = _loop_offsets(nd, dev)
+    if loop_w is not None:
         h = th.empty((nd, X), dtype=th.bfloat16, device=dev)
     elif bias_c is not None:  # no self-loop: the rows the aggregation adds into hold the (rounded) bias alone
         h = bias_c.to(th.bfloat16).expand(nd, X).contiguous()
@@ -685,7 +657,7 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     if side is not None:
         side.wait_stream(main)
     with th.cuda.stream(side if side is not None else main):  # er_c and the self-loop: HBM-bound streams of rows beside the projection
-        _k.rows_dot1h_bf16(ss["rel_ptrs_col"], ss["node_indices_col"], wa, x, erc)
+        _k.rows_dot1h_bf16(ss["rel_ptrs_col"], ss["node_indices_col"], wa.view(R, H, Kd), x, erc)
         if loop_w is not None:
             _k.rows_linear_bias_bf16(offs, x[:nd], loop_w, bias_c, out=h)
     _k.rows_matmul_heads_bf16(ss["rel_ptrs_row"], ss["node_indices_row"], W, x, featc)
