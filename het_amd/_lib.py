@@ -79,6 +79,8 @@ _ENTRIES = {
     "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
+    "het_rgat_aggregate_compact_runs_bf16": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
+    "het_rgat_backward_compact_runs_bf16": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_rgat_attention_compact_workspace": (I64, [P, I64, I64, INT]),
     "het_rgat_attention_compact": [P, P, P, I64, DBL, P, P, P, P, I64, I64, P, P, P, I64, P],
     "het_rows_matmul_backward_dx": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
@@ -89,9 +91,11 @@ _ENTRIES = {
     "het_rows_matmul_backward_dw_bf16_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
     "het_rows_matmul_heads_bf16": [P, I64, P, I64, P, P, P, I64, I64, I64, P],
     "het_rows_dot1h_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, P],
+    "het_rows_dot1h_backward_dw_bf16": [P, I64, P, P, I64, P, P, P, I64, I64, INT, P],
     "het_rgat_node_gemm_ok": [I64, I64, I64, I64],
     "het_node_row_map": [P, I64, P, I64, I64, P, P],
     "het_rgat_node_backward_dx": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
+    "het_rgat_node_backward_dx_bf16": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
     "het_node_rows_matmul_sum_ok": [I64, I64, I64],
     "het_node_rows_matmul_sum": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
     "het_node_rows_matmul_sum_bias": [I64, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P],

@@ -31,13 +31,21 @@ Evaluation (torch.no_grad(), or no input that requires a gradient) on the distin
 all: _forward_only runs the same forward with an aggregation that keeps nothing for a backward (HET_RGAT_FORWARD_ONLY=0: the
 node's forward, as before).
 
-bf16 activations (a torch.bfloat16 input) exist on that evaluation path only: _forward_only_bf16 keeps x, feat_c and the layer output
+bf16 activations (a torch.bfloat16 input) on the evaluation path: _forward_only_bf16 keeps x, feat_c and the layer output
 h as bf16 rows, each rounded once (to nearest even) where its kernel stores it; W, attn_l, attn_r, the self-loop weight, the bias,
 el_c, er_c, the hub records and every sum, maximum and exponential are fp32 on widened values.  er always comes from the folded
 weight there (HET_RGAT_LITERAL_ER does not apply: the literal form needs a second projection table), and el_c is the dot of the
 ROUNDED feat_c row, so the walks that form el from the row they gather and those that gather el_c compute one function.  Every
 other bf16 call (gradients required, halo, per-edge dataflow, other shapes) is served by the fp32 layer on an upcast copy
 (het_amd/layers.py): correct, not faster.
+
+bf16 training is opt-in (the layer's bf16_training=True; rgat_layer_bf16_training_ok): RgatLayerBf16Function runs that same forward
+with the training aggregation over bf16 rows -- it also leaves lse, ret [N,H,D], the run sums and el_c, all fp32 -- and its backward is
+the node-major route of _backward_distinct_rows with the bf16 entries: the incoming gradient of h is gathered as bf16 rows and
+widened on load, grad_feat_c / grad_er_c and every parameter gradient are fp32 sums, the gradient passes straight through the
+rounding of feat_c, and grad_x is rounded once where the node-major pass stores a node's finished row.  No fp32 copy of x, feat_c,
+h, grad_h or grad_x is made.  Calls outside that one route (halo, the per-relation and generic routes, 128-wide rows or inputs,
+more than 8 relations, edges that end at or above nd) keep the upcast fallback.
 
 Attention weights (the layer's get_attention=True): both evaluation functions append attn [E,H] (fp32, edge-id order) to the list
 they are handed -- a pass over the ids, el_c and er_c after the aggregation (csrc/gat_attention.hip); the autograd node does not, and
@@ -452,7 +460,9 @@ class RgatLayerFunction(th.autograd.Function):
                                   gradients), and every other call (``generic``: any shape, literal er, edges ending at or above
                                   nd -- launches that form an input and a weight gradient together, "+=").
         On all but the generic route the weight gradients are launches of their own, HBM-bound streams of rows: on the side stream
-        beside the gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once."""
+        beside the gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once.
+        bf16 rows (RgatLayerBf16Function: x, feat_c and grad_h bf16): the node-major route alone, with the bf16 entries; every
+        gradient table and parameter gradient is fp32, grad_x bf16."""
         x, W, attn_l, attn_r, loop_w, offs, sm, _, ret, featc, elc, erc, *featd = ctx.saved_tensors
         g, nd, slope, halo, runs, has_loop, has_bias, mulfirst = ctx.g, ctx.nd, ctx.slope, ctx.halo, ctx.runs, ctx.has_loop, ctx.has_bias, ctx.mulfirst
         N, Kd = x.shape
@@ -465,6 +475,7 @@ class RgatLayerFunction(th.autograd.Function):
         dst_prefix = _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
         assert halo is None or dst_prefix, "a partition's edges point at owned nodes"
         node_major = mulfirst and dst_prefix and _k.rgat_node_gemm_ok(R, H, Kd, D)
+        bf16 = x.dtype == th.bfloat16
         # (exactly one of the three routes of the docstring; the last two add to grad_x per relation)
         generic = not node_major and halo is None
         per_relation_halo = not node_major and halo is not None
@@ -472,11 +483,13 @@ class RgatLayerFunction(th.autograd.Function):
         #  grad_el_c then has no reader left -- its other consumer, the gradient through el, is folded into grad_feat_c -- and is
         #  not written at all)
         attn_in_pass = not generic and runs is not None and R <= 8
+        assert not bf16 or (node_major and attn_in_pass and halo is None), "rgat_layer_bf16_training_ok guards this path"
         # (the self-loop product names each of the nd output rows once: the column sums of its gradout rows ARE the bias gradient,
         #  from the weight-gradient launch that streams grad_h anyway instead of a pass of its own inside the gather op: 0.088 ms on
         #  ogbn-mag)
         # (offs = [0, nd] by construction in forward())
-        bias_in_dw = not generic and has_bias and has_loop
+        # (bf16 rows: the bf16 weight-gradient entry has no column-sum form; the edge pass sums the bf16 rows on its side stream)
+        bias_in_dw = not generic and has_bias and has_loop and not bf16
         main, side = th.cuda.current_stream(x.device), _side_stream(x.device) if OVERLAP and not generic else None
         Wt = th.transpose(W, 2, 3).contiguous()
         if generic:
@@ -485,18 +498,22 @@ class RgatLayerFunction(th.autograd.Function):
             go = grad_h.view(nd, H, D)
             grad_loop = th.empty_like(loop_w) if has_loop else None
         ndp = go.shape[0]
-        g_featc, g_erc = th.empty_like(featc), th.empty_like(erc)  # overwritten
+        g_featc, g_erc = th.empty(featc.shape, dtype=W.dtype, device=x.device), th.empty_like(erc)  # overwritten
         # (on a partition the edge pass is handed a grad_el_c it need not write: an argument of the launch, left as it was)
         g_elc = None if attn_in_pass and halo is None else th.empty_like(elc)
-        grad_bias = th.empty(X, dtype=x.dtype, device=x.device) if has_bias else None
+        grad_bias = th.empty(X, dtype=W.dtype, device=x.device) if has_bias else None
 
         def loop_weight_gradient():
+            if bf16:
+                _k.rows_matmul_backward_dw_bf16(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False)
+                return
             _k.rows_matmul_backward_dw(offs, None, x[:nd], grad_h, grad_loop.view(1, 1, Kd, X), accumulate=False,
                                        colsum=grad_bias if bias_in_dw else None)
         # Everything the side stream writes is allocated before the fork (side.wait_stream(main)) that precedes the write, for the
         # reason _side_stream gives.  There are two forks: this one, in front of the self-loop's launch, which writes grad_loop and
         # grad_bias alone (allocated above); and the one in front of weight_gradients() on the node-major routes, which writes
-        # grad_attn_l, grad_W and grad_wa (allocated between the two).  Nothing else is written from the side stream.
+        # grad_attn_l, grad_W (with grad_W_kx, its [R,K,X] form on the bf16 route) and grad_wa (allocated between the two).  Nothing else
+        # is written from the side stream.
         if side is not None and has_loop:
             # the self-loop weight gradient needs x and grad_h only: an HBM-bound stream of rows beside the gather passes below
             # (at the start of the backward: beside the node-major pass instead it stretched the two short per-destination
@@ -510,9 +527,10 @@ class RgatLayerFunction(th.autograd.Function):
             _k.rows_matmul_backward_dx(offs, None, loop_w.t().contiguous().view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
         grad_attn_l = th.empty_like(attn_l)  # (written by the edge pass on this stream, or after the second fork)
         # the bias gradient (column sums of grad_h) from the pass that reads every gradout row anyway, unless bias_in_dw
-        _k.rgat_backward_compact(ctx.grp, featc, elc, erc, sm[:ndp], ret[:ndp], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l,
-                                 row_rel_ptrs=rp_row, grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=runs,
-                                 drow_nodes=ss["node_indices_col"], grad_attn_l=grad_attn_l if attn_in_pass else None)
+        (_k.rgat_backward_compact_bf16 if bf16 else _k.rgat_backward_compact)(
+            ctx.grp, featc, elc, erc, sm[:ndp], ret[:ndp], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l, row_rel_ptrs=rp_row,
+            grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=runs, drow_nodes=ss["node_indices_col"],
+            grad_attn_l=grad_attn_l if attn_in_pass else None)
         if mulfirst:
             wa = _folded_weight(W, attn_r)
         # what the launches below write: "=" outputs are allocated, "+=" outputs zero-filled
@@ -520,7 +538,9 @@ class RgatLayerFunction(th.autograd.Function):
             grad_x = th.empty_like(x)
         grad_W = th.zeros_like(W) if generic else th.empty_like(W)
         if mulfirst:
-            grad_wa = (th.empty if node_major else th.zeros)((R, H, Kd, 1), dtype=x.dtype, device=x.device)
+            grad_wa = (th.empty if node_major else th.zeros)((R, H, Kd, 1), dtype=W.dtype, device=x.device)
+        # (bf16 rows: the bf16 weight-gradient entry writes [R,K,X]; the layer's [R,H,K,D] is a transposing copy of R K X floats)
+        grad_W_kx = th.empty((R, 1, Kd, X), dtype=W.dtype, device=x.device) if bf16 else None
 
         def weight_gradients():
             # per product (four launches; each reads its own rows of x / feat_c -- a node-major pass that reads x once was
@@ -532,6 +552,11 @@ class RgatLayerFunction(th.autograd.Function):
                 return
             if has_loop and side is None:
                 loop_weight_gradient()
+            if bf16:
+                _k.rows_matmul_backward_dw_bf16(rp_row, rows_node, x, g_featc.view(-1, X), grad_W_kx, accumulate=False)
+                grad_W.copy_(grad_W_kx.view(R, Kd, H, D).transpose(1, 2))
+                _k.rows_dot1h_backward_dw_bf16(ss["rel_ptrs_col"], ss["node_indices_col"], x, g_erc, grad_wa.view(R, H, Kd), False)
+                return
             _k.rows_matmul_backward_dw(rp_row, rows_node, x, g_featc.view(-1, X), grad_W, accumulate=False)
             if node_major:  # the er side's weight gradient alone (its input gradient is a term of the node pass)
                 _k.matmul_backward(d_col, 1, wa.view(R, H, 1, Kd), x, g_erc.view(-1, H, 1), None, grad_wa, True, accumulate=False)
@@ -545,8 +570,9 @@ class RgatLayerFunction(th.autograd.Function):
             order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None)
 
             def input_gradient(begin, end):
-                _k.rgat_node_backward_dx(begin, end, nd, grad_h if has_loop else None, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc,
-                                         wa.view(R, H, Kd), dst_map, grad_x, node_order=order)
+                (_k.rgat_node_backward_dx_bf16 if bf16 else _k.rgat_node_backward_dx)(
+                    begin, end, nd, grad_h if has_loop else None, loop_wt, g_featc.view(-1, X), Wt, row_map, g_erc, wa.view(R, H, Kd),
+                    dst_map, grad_x, node_order=order)
             if halo is not None:
                 input_gradient(nd, N)
                 halo.start_return(grad_x)
@@ -626,12 +652,11 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     return h if rows is None else rows
 
 
-def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
-    """_forward_only for a bf16 input (the module docstring has the precision contract): feat_c [S_row,H,D] and h [nd,X] are bf16
-    rows, no fp32 copy of x, feat_c or h is made, and the aggregation rounds h once more where it adds a destination's row in place.
-    The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
-    instead of the projection's epilogue.  ``attn_out`` (a list): the attention weights [E,H] (fp32) are appended to it; where the
-    walk formed el from the row it gathered, el_c is made for them by the same row-dot pass, so they are the softmax the output used."""
+def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, need_el):
+    """The bf16 forward in front of its aggregation, common to _forward_only_bf16 and RgatLayerBf16Function.forward: feat_c (bf16) on
+    the unique (relation, source) rows, er_c from the folded weight, the self-loop + bias rows h (bf16) the aggregation adds into,
+    and el_c -- a row-dot pass over the rounded feat_c -- where the walk gathers it or ``need_el`` says so (else None).
+    Returns (operands, nd, ss, featc, elc, erc, h, grp, offs); operands = the contiguous (x, W, attn_l, attn_r, loop_w)."""
     # (the folded weight is fp32; the cached [0, nd] list and a copy of the self-loop weight are made here, under the main stream)
     x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, True)
     s, _, _ = _lists(g)
@@ -644,7 +669,7 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     # (everything the side stream writes is allocated before the fork: _side_stream)
     featc = th.empty((ss["node_indices_row"].numel(), H, D), dtype=th.bfloat16, device=dev)
     erc = th.empty((ss["node_indices_col"].numel(), H), dtype=th.float32, device=dev)
-    elc = None if _k.rgat_el_from_row(H, D, R) else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
+    elc = None if _k.rgat_el_from_row(H, D, R) and not need_el else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
     bias_c = None if bias is None else bias.contiguous()
     if loop_w is not None:
         h = th.empty((nd, X), dtype=th.bfloat16, device=dev)
@@ -668,13 +693,54 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
     grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp,
                                     drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
+    return (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs
+
+
+def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
+    """_forward_only for a bf16 input (the module docstring has the precision contract): feat_c [S_row,H,D] and h [nd,X] are bf16
+    rows, no fp32 copy of x, feat_c or h is made, and the aggregation rounds h once more where it adds a destination's row in place.
+    The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
+    instead of the projection's epilogue.  ``attn_out`` (a list): the attention weights [E,H] (fp32) are appended to it; where the
+    walk formed el from the row it gathered, el_c is made for them by the same row-dot pass, so they are the softmax the output used."""
+    (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, _ = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias,
+                                                                                      False)
+    R, H, _, D = W.shape
     _k.rgat_aggregate_compact_forward_bf16(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
     if attn_out is not None:
         if elc is None:
-            elc = th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
+            elc = th.empty((featc.shape[0], H), dtype=th.float32, device=x.device)
             _k.rgat_el_rows_bf16(ss["rel_ptrs_row"], featc, attn_l, elc)
-        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, N))
+        attn_out.append(_attention_rows(g, ss, direct, grp, elc, erc, slope, x.shape[0]))
     return h
+
+
+@_consistent_plan
+class RgatLayerBf16Function(th.autograd.Function):
+    """The layer's training step on bf16 rows (the module docstring): _forward_only_bf16's launches with the training aggregation,
+    which also leaves lse, ret and the run sums (fp32), and el_c always (the edge pass of the backward reads it); the backward is
+    RgatLayerFunction._backward_distinct_rows on its node-major route.  Saved: x and feat_c as bf16."""
+
+    @staticmethod
+    def forward(ctx, g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+        (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w,
+                                                                                             bias, True)
+        N = x.shape[0]
+        R, H, _, D = W.shape
+        sm = th.empty((N, H), dtype=th.float32, device=x.device)
+        ret = th.empty((N, H, D), dtype=th.float32, device=x.device)
+        ctx.runs = _k.rgat_aggregate_compact_bf16(grp, featc, elc, erc, sm, ret, slope, h, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
+        ctx.grp, ctx.halo = grp, None
+        ctx.g, ctx.compact, ctx.mulfirst, ctx.slope, ctx.nd = g, True, True, slope, nd
+        ctx.has_loop, ctx.has_bias = loop_w is not None, bias is not None
+        none = W.new_empty(0)
+        ctx.save_for_backward(x, W, attn_l, attn_r, loop_w if loop_w is not None else none, offs if offs is not None else none, sm, none,
+                              ret, featc, elc, erc)
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        grads = RgatLayerFunction._backward_distinct_rows(ctx, grad_h.contiguous())
+        return (None, None, None, None) + grads[7:]  # (g, direct, slope, num_dst; then x and the parameters)
 
 
 def rgat_layer_bf16_ok(g, x, W, slope, compact, mulfirst, tensors):
@@ -690,6 +756,25 @@ def rgat_layer_bf16_ok(g, x, W, slope, compact, mulfirst, tensors):
     R, H, Kd, D = W.shape
     compact, _, _ = effective_flags(g, W, compact, True, mulfirst)
     return compact and _k.rgat_bf16_shape_ok(H, Kd, D) and x.shape[0] * R < 2 ** 31
+
+
+def rgat_layer_bf16_training_ok(g, x, W, slope, compact, mulfirst, tensors, num_dst=None):
+    """Whether a bf16 input that needs a backward runs natively (RgatLayerBf16Function; the layer's bf16_training=True): one GPU, the
+    distinct-row dataflow, and the node-major route of _backward_distinct_rows with the attention-vector gradient from the edge pass
+    -- the shapes of the run-sum form and of het_rgat_node_gemm_ok (K and H*D each 32 or 64), at most 8 relations, every
+    destination below nd.  ``W``: a tensor of the (padded) weight's shape; ``tensors``: everything whose gradient could be asked for."""
+    if not (x.is_cuda and x.dtype == th.bfloat16 and x.dim() == 2 and th.is_grad_enabled()
+            and any(t is not None and t.requires_grad for t in tensors)):
+        return False
+    if not rgat_layer_fused_ok(g, x, W, slope, compact, mulfirst):
+        return False
+    R, H, Kd, D = W.shape
+    compact, _, _ = effective_flags(g, W, compact, True, mulfirst)
+    if not (compact and R <= 8 and x.shape[0] * R < 2 ** 31 and _k.rgat_bf16_shape_ok(H, Kd, D) and _k.rows_matmul_bf16_ok(Kd, H * D)
+            and _k.rgat_node_gemm_ok(R, H, Kd, D)):
+        return False
+    nd = x.shape[0] if num_dst is None else min(int(num_dst), x.shape[0])
+    return _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
 
 
 def _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
@@ -736,14 +821,18 @@ def attention_composition(g, x, W, attn_l, attn_r, slope):
 
 
 def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, direct, num_dst=None, mulfirst=False, halo=None,
-                     attn_out=None):
+                     attn_out=None, bf16_training=False):
     """``attn_out`` (a list, optional): on the evaluation paths the attention weights [E,H] are appended to it (_forward_only /
-    _forward_only_bf16); the autograd node leaves it empty and the caller composes them (attention_composition)."""
+    _forward_only_bf16); the autograd nodes leave it empty and the caller composes them (attention_composition).
+    ``bf16_training``: a bf16 input that needs a backward takes RgatLayerBf16Function (the caller has asked
+    rgat_layer_bf16_training_ok)."""
     compact, direct, mulfirst = effective_flags(g, W, compact, direct, mulfirst)
     if compact and not _has_single_sided_lists(g):
         g.generate_separate_unique_node_indices_single_sided_for_each_etype()
-    if x.dtype == th.bfloat16:  # (the caller has asked rgat_layer_bf16_ok: there is no bf16 form of anything else)
+    if x.dtype == th.bfloat16:  # (the caller has asked rgat_layer_bf16_ok / _training_ok: there is no bf16 form of anything else)
         assert compact and halo is None, "rgat_layer_bf16_ok guards this path"
+        if bf16_training and th.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, W, attn_l, attn_r, loop_w, bias)):
+            return RgatLayerBf16Function.apply(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
         with th.no_grad():
             return _forward_only_bf16(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
     if _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):

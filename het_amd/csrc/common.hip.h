@@ -117,6 +117,9 @@ static inline bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
 // every pointer on a 16-byte boundary (float4 accesses); NULL counts as aligned
 template <typename... P>
 static inline bool aligned16(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
+// ... on an 8-byte boundary: the 4-element accesses of bf16 rows (ldrow4 / strow4)
+template <typename... P>
+static inline bool aligned8(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 7) == 0; }
 
 // Lanes per row (a row of X floats is covered by LPR = X/4 lanes holding a float4 each) as a template argument: CALL sees
 // `constexpr int LPR`.  The shape predicates admit powers of two up to 64 only, so the default is 64.

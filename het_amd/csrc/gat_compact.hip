@@ -644,13 +644,21 @@ __device__ __forceinline__ float4 add_mul_rounded4(const float4& h, const float4
 // Measured and dropped (round 5): the feature rows of step k + 1 requested before the sums of step k are formed (two row buffers
 // that swap roles, ids two steps ahead) -- 90 VGPRs instead of 60 = 5 waves per SIMD instead of 8: 0.534 -> 0.590 ms alone.  More
 // waves, not more loads per wave, is what this pass wants.
-template <int LPR, int DL, bool ELR, bool W64>
+// T (here and in the hub kernels, the source-row kernels of the backward, HET_rgat_drow_pass and HET_rgat_colsum_rows): the element
+// type of the activation rows -- feat_c and h_inout, gradout in the backward --, float or het_bf16
+// (het_rgat_aggregate_compact_runs_bf16 / het_rgat_backward_compact_runs_bf16).  A lane holds 4 elements of a row either way, bf16
+// widened on load, so every sum is the fp32 arithmetic in the fp32 order; ret, lse, the run sums, the hub records and every gradient
+// stay fp32, and h_inout[v] = round(widen(h_inout[v]) + ret[v]) is the one rounding.  The float instances are the kernels as they
+// were measured, instruction for instruction.
+template <int LPR, int DL, bool ELR, bool W64, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
-    Packs pk, const int4* __restrict__ kp01, const float* __restrict__ feat, const float* __restrict__ el,
-    const float* __restrict__ er, float* __restrict__ lse, float* __restrict__ ret, float slope, float* __restrict__ hio,
+    Packs pk, const int4* __restrict__ kp01, const T* __restrict__ feat, const float* __restrict__ el,
+    const float* __restrict__ er, float* __restrict__ lse, float* __restrict__ ret, float slope, T* __restrict__ hio,
     int hio_rows, float* __restrict__ qrow, float* __restrict__ qsum, float* __restrict__ qref, int hub_min, ElFold ef) {
   constexpr int EPW = 64 / LPR, U = 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);  // log2 of the bytes of a feature row / of an [.,H] row
+  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);  // log2 of the bytes of an fp32 row (ret, q_rows) / of an [.,H] row
+  constexpr int RT = het_log2_ce(LPR * 4 * (int)sizeof(T));        // ... of a row of feat / h_inout (T)
+  constexpr bool F32 = std::is_same<T, float>::value;  // (the float instances keep the statements they were measured with)
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
@@ -678,7 +686,10 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
     zl = ELR ? 0.f : ld1_at<O>(el, ((O)id.y << HS) | hb);
     zr = ld1_at<O>(er, ((O)id.z << HS) | hb);
 #pragma unroll
-    for (int q = 0; q < U; ++q) f[q] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RS) | xb);
+    for (int q = 0; q < U; ++q) {
+      if constexpr (F32) f[q] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RS) | xb);
+      else f[q] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(id.y, q, lane) << RT) | (O)(sub * 4 * (int)sizeof(T)));
+    }
   };
   // the arithmetic (and the stores) of the step that starts at rank j0
   auto step = [&](int j0, const int4& id, const float4 (&f)[U], float zlv, float zrv) {
@@ -690,7 +701,11 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
         const int tagq = head_bcast_i<DL>(tagv, q, lane);
         if (hio && (tagq & HET_TAG_FIRST_KEY)) {  // the destination's row of the layer output so far: needed when the destination ends
           const int dstq = head_bcast_i<DL>(dstv, q, lane);
-          if (dstq < hio_rows) h0 = ld4_at<O>(hio, ((O)dstq << RS) | xb);
+          if constexpr (F32) {
+            if (dstq < hio_rows) h0 = ld4_at<O>(hio, ((O)dstq << RS) | xb);
+          } else {
+            if (dstq < hio_rows) h0 = ldrow4_at<O>(hio, ((O)dstq << RT) | (O)(sub * 4 * (int)sizeof(T)));
+          }
         }
         if (ELR) {  // s of the edge from its row: every lane of the head forms it (no broadcast of a gathered term)
           const int rel = tagq >> HET_TAG_REL_SHIFT;
@@ -717,8 +732,13 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_runs_packed(
             const float inv = __builtin_amdgcn_rcpf(ssum);
             const float4 r4 = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
             st4_at<O>(ret, ((O)dstq << RS) | xb, r4);
-            if (hio && dstq < hio_rows)
-              st4_at<O>(hio, ((O)dstq << RS) | xb, make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
+            if constexpr (F32) {
+              if (hio && dstq < hio_rows)
+                st4_at<O>(hio, ((O)dstq << RS) | xb, make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
+            } else {
+              if (hio && dstq < hio_rows)
+                strow4_at<O>(hio, ((O)dstq << RT) | (O)(sub * 4 * (int)sizeof(T)), make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
+            }
             if (d == 0) st1_at<O>(lse, ((O)dstq << HS) | hb, lse_fast(m, ssum));
             acc = make_float4(0.f, 0.f, 0.f, 0.f);
             ssum = 0.f;
@@ -846,19 +866,19 @@ __device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a
 // Hubs: wave per hub work item of the grouping by (destination, relation) `it` (keys destination * R + relation; same sorted
 // order as the grouping by destination whose packed ids p01 it reads; hub_items: grouping_hub_items -- a wave per item of
 // that grouping with a test for "hub" spent 1.7 ms on 1.3 M early exits).  part[k] = {O[X], Q[X], max[H], sum[H], q[H]}.
-template <int LPR, int DL, bool ELR, bool W64>
+template <int LPR, int DL, bool ELR, bool W64, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items(
     Items it, const int32_t* __restrict__ hub_items, const int32_t* __restrict__ hub_order, int64_t num_hub_items,
-    const int2* __restrict__ p01, const float* __restrict__ feat, const float* __restrict__ el, const float* __restrict__ er,
+    const int2* __restrict__ p01, const T* __restrict__ feat, const float* __restrict__ el, const float* __restrict__ er,
     float slope, float* __restrict__ part, ElFold ef) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);
+  constexpr int RS = het_log2_ce(LPR * 4 * (int)sizeof(T)), HS = het_log2_ce(H * 4);
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   static_assert(!ELR || DL == 4, "el from the row: heads of 4 lanes");
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 16), hb = (O)(h * 4);
+  const O xb = (O)(sub * 4 * (int)sizeof(T)), hb = (O)(h * 4);
   const int dq = d < U ? d : U - 1;
   const int64_t kk = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (kk >= num_hub_items) return;
@@ -879,7 +899,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items(
     float zlv = ELR ? 0.f : ld1_at<O>(el, ((O)srowv << HS) | hb);
     float4 f[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) f[u] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(srowv, u, lane) << RS) | xb);
+    for (int u = 0; u < U; ++u) f[u] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(srowv, u, lane) << RS) | xb);
     jn = j0 + (U + dq) * EPW < e ? j0 + (U + dq) * EPW : e - 1;
     idn = p01[jn];
     if (ELR) {  // el of the lane's own edge (edge dq of the step) from the rows: every lane forms all four, keeps its own
@@ -1015,11 +1035,11 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_aggregate_hub_items_fwd(
 // (Round 5: a wave per hub walked the records of the largest hub -- ~3 600 items on the ogbn-mag-like graph -- four at a time, and
 // that one wave WAS the launch: 0.135 ms at the end of the forward's critical path.  The 16 lane groups of a workgroup take the
 // records round-robin and meet in LDS; hubs of a few items leave three waves idle, which costs nothing at 17 K hubs.)
-template <int LPR>
+template <int LPR, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs(
     const int4* __restrict__ hub_rec, int64_t num_hubs, Items it, const int32_t* __restrict__ p_drow,
     const float* __restrict__ part, float* __restrict__ lse, float* __restrict__ ret, int H,
-    int D, float* __restrict__ hio, int64_t hio_rows, float* __restrict__ qrow, float* __restrict__ qsum,
+    int D, T* __restrict__ hio, int64_t hio_rows, float* __restrict__ qrow, float* __restrict__ qsum,
     float* __restrict__ qref) {
   constexpr int EPW = 64 / LPR, NW = kBlock / 64;
   __shared__ float4 s_acc[NW][LPR];
@@ -1080,8 +1100,8 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_finish_hubs(
     const float4 r4 = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
     st4(ret + v * X + x, r4);
     if (hio && v < hio_rows) {
-      const float4 h0 = ld4(hio + v * X + x);
-      st4(hio + v * X + x, make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
+      const float4 h0 = ldrow4(hio + v * X + x);
+      strow4(hio + v * X + x, make_float4(h0.x + r4.x, h0.y + r4.y, h0.z + r4.z, h0.w + r4.w));
     }
     if (x % D == 0) lse[v * H + h] = L;
   }
@@ -1285,21 +1305,21 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_attn_grad_finish(const float*
 // Round 5 (see HET_rgat_aggregate_runs_packed): where a segment starts / ends and the relation of its row come from the tag of the
 // packed id record (no carried key, no compares against the neighbours, no boundary search), addresses are 32-bit byte offsets off
 // scalar bases (W64 = false), the dot over the lanes of a head is two DPP adds instead of two ds_bpermute.  H = LPR / DL.
-template <int LPR, int DL, bool GA, bool REC, bool W64>
+template <int LPR, int DL, bool GA, bool REC, bool W64, typename T = float>
 __global__ __launch_bounds__(kBlock, GA ? 5 : 1) void HET_rgat_backward_src_coop(
-    Packs pk, const int4* __restrict__ kp01, const float* __restrict__ feat,
+    Packs pk, const int4* __restrict__ kp01, const T* __restrict__ feat,
     const float* __restrict__ el, const float* __restrict__ er, const float* __restrict__ pack2,
-    const float* __restrict__ gradout, float* __restrict__ grad_feat, float* __restrict__ grad_el,
+    const T* __restrict__ gradout, float* __restrict__ grad_feat, float* __restrict__ grad_el,
     float* __restrict__ tbuf, float slope, const float* __restrict__ fold_w,
     const idx_t* __restrict__ fold_row_rel_ptrs, int R, float* __restrict__ ga_part, int* __restrict__ ga_rel,
     float* __restrict__ ga_out) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);
+  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4), RT = het_log2_ce(LPR * 4 * (int)sizeof(T));  // (RT: rows of feat / gradout)
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 16), hb = (O)(h * 4);
+  const O xb = (O)(sub * 16), hb = (O)(h * 4), xt = (O)(sub * 4 * (int)sizeof(T));
   const int dq = d < U ? d : U - 1;
   const int64_t pid = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * EPW + slot;
   if (!GA && pid >= pk.n) return;
@@ -1334,13 +1354,13 @@ __global__ __launch_bounds__(kBlock, GA ? 5 : 1) void HET_rgat_backward_src_coop
 #pragma unroll
     for (int q = 0; q < U; ++q) tag[q] = head_bcast_i<DL>(tagv, q, lane);
 #pragma unroll
-    for (int q = 0; q < U; ++q) g[q] = ld4_at<O>(gradout, ((O)head_bcast_i<DL>(dstv, q, lane) << RS) | xb);
+    for (int q = 0; q < U; ++q) g[q] = ldrow4_at<O>(gradout, ((O)head_bcast_i<DL>(dstv, q, lane) << RT) | xt);
     // feat row of a segment that starts inside this step (uniform per lane group).  fl[q] has NO other definition: a value merged
     // with the row in hand (fq[q] = fcur; if (start) fq[q] = load) made the compiler copy the loaded registers right behind the load,
     // i.e. wait for every load in flight at each segment start
 #pragma unroll
     for (int q = 0; q < U; ++q)
-      if (j0 + q < e && (tag[q] & HET_TAG_FIRST_KEY)) fl[q] = ld4_at<O>(feat, ((O)head_bcast_i<DL>(keyv, q, lane) << RS) | xb);
+      if (j0 + q < e && (tag[q] & HET_TAG_FIRST_KEY)) fl[q] = ldrow4_at<O>(feat, ((O)head_bcast_i<DL>(keyv, q, lane) << RT) | xt);
     // ids of the next step, in flight while this step's rows arrive
     jn = j0 + U + dq < e ? j0 + U + dq : e - 1;
     idn = kp01[jn];
@@ -1409,21 +1429,21 @@ __global__ __launch_bounds__(kBlock, GA ? 5 : 1) void HET_rgat_backward_src_coop
 // graph): wave per work item (<= HET_ITEM_MAX edges of ONE feat row), the 64/LPR lane groups take its edges round-robin
 // as the forward does, scalars fetched cooperatively; feat row, el and the fold row are per item.  One store per item
 // (atomic adds only for the items of a segment longer than HET_ITEM_MAX, whose rows HET_rgat_zero_long_rows cleared).
-template <int LPR, int DL, bool GA, bool REC, bool W64>
+template <int LPR, int DL, bool GA, bool REC, bool W64, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
     Items it, const int32_t* __restrict__ long_items, int64_t num_long_items, const int2* __restrict__ p01,
-    const float* __restrict__ feat, const float* __restrict__ el,
-    const float* __restrict__ er, const float* __restrict__ pack2, const float* __restrict__ gradout,
+    const T* __restrict__ feat, const float* __restrict__ el,
+    const float* __restrict__ er, const float* __restrict__ pack2, const T* __restrict__ gradout,
     float* __restrict__ grad_feat, float* __restrict__ grad_el, float* __restrict__ tbuf, float slope,
     const float* __restrict__ fold_w, const idx_t* __restrict__ fold_row_rel_ptrs, int R, float* __restrict__ ga_part,
     int* __restrict__ ga_rel, float* __restrict__ ga_out) {
   constexpr int EPW = 64 / LPR, U = 4, X = LPR * 4, H = LPR / DL;
-  constexpr int RS = het_log2_ce(LPR * 16), HS = het_log2_ce(H * 4);
+  constexpr int RS = het_log2_ce(LPR * 4 * (int)sizeof(T)), HS = het_log2_ce(H * 4);  // (RS: rows of gradout)
   typedef typename OffSel<W64>::type O;
   static_assert(DL >= U, "a head needs at least U lanes");
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sub = lane % LPR, x = sub * 4, h = sub / DL, d = sub % DL;
-  const O xb = (O)(sub * 16), hb = (O)(h * 4);
+  const O xb = (O)(sub * 4 * (int)sizeof(T)), hb = (O)(h * 4);
   const int dq = d < U ? d : U - 1;
   const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (wid >= num_long_items) {  // (GA: the wave stays for the workgroup reduction)
@@ -1436,7 +1456,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
   int2 idn = p01[jn];
   const int64_t u = it.seg_key[seg];
   const bool whole = b == it.seg_ptr[seg] && e == it.seg_ptr[seg + 1];
-  const float4 f = ld4(feat + u * X + x);
+  const float4 f = ldrow4(feat + u * X + x);
   const float zl = el[u * H + h];
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   float acc_el = 0.f;
@@ -1453,7 +1473,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
     }
     float4 g[U];
 #pragma unroll
-    for (int q = 0; q < U; ++q) g[q] = ld4_at<O>(gradout, ((O)head_bcast_i<DL>(dstv, q, lane) << RS) | xb);
+    for (int q = 0; q < U; ++q) g[q] = ldrow4_at<O>(gradout, ((O)head_bcast_i<DL>(dstv, q, lane) << RS) | xb);
     jn = j0 + (U + dq) * EPW < e ? j0 + (U + dq) * EPW : e - 1;
     idn = p01[jn];
     const float zv = zl + zrv;
@@ -1510,9 +1530,9 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_backward_src_long(
 //   grad_er[w,h] = exp(ref[w,h] - lse[v,h]) (<gradout[v,h,:], Q[w,h,:]> - <gradout, ret>[v,h] q[w,h]),  0 for a row without edges
 // gradout / ret rows of a destination with several relations are read once per relation (adjacent work: cache hits); nodes
 // without in-edges are not visited at all.  Lane group per er row, two rows per lane group in flight.
-template <int LPR, int DL>
+template <int LPR, int DL, typename T = float>
 __global__ __launch_bounds__(kBlock) void HET_rgat_drow_pass(const float* __restrict__ er, const float* __restrict__ lse,
-                                                              const float* __restrict__ ret, const float* __restrict__ gradout,
+                                                              const float* __restrict__ ret, const T* __restrict__ gradout,
                                                               const float* __restrict__ qrow, const float* __restrict__ qsum,
                                                               const float* __restrict__ qref, const int64_t* __restrict__ drow_nodes,
                                                               const int32_t* __restrict__ order, int64_t n_rows,
@@ -1537,7 +1557,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_drow_pass(const float* __rest
   float erv[U], ls[U], qs[U], rf[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    g[u] = ld4(gradout + v[u] * X + x);
+    g[u] = ldrow4(gradout + v[u] * X + x);
     r[u] = ld4(ret + v[u] * X + x);
     q[u] = ld4(qrow + w[u] * X + x);
     erv[u] = er[w[u] * H + h];
@@ -1558,8 +1578,8 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_drow_pass(const float* __rest
 }
 
 // bias_part [gridDim.x * waves, X]: per-wave column sums of rows [0, n) of g [., X] (grid-stride; HET_rgat_colsum_finish adds them up)
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void HET_rgat_colsum_rows(const float* __restrict__ g, int64_t n, float* __restrict__ bias_part) {
+template <int LPR, typename T = float>
+__global__ __launch_bounds__(kBlock) void HET_rgat_colsum_rows(const T* __restrict__ g, int64_t n, float* __restrict__ bias_part) {
   constexpr int EPW = 64 / LPR, X = LPR * 4, U = 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slot = lane / LPR, x = (lane % LPR) * 4;
@@ -1568,7 +1588,7 @@ __global__ __launch_bounds__(kBlock) void HET_rgat_colsum_rows(const float* __re
   for (int64_t v0 = ((int64_t)blockIdx.x * (kBlock / 64) + wave) * EPW * U + slot; v0 < n; v0 += step) {
     float4 a[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) a[u] = v0 + u * EPW < n ? ld4(g + (v0 + u * EPW) * X + x) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int u = 0; u < U; ++u) a[u] = v0 + u * EPW < n ? ldrow4(g + (v0 + u * EPW) * X + x) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int u = 0; u < U; ++u) { bs.x += a[u].x; bs.y += a[u].y; bs.z += a[u].z; bs.w += a[u].w; }
   }
@@ -1713,14 +1733,12 @@ static bool rgat_el_from_row(const float* attn_l, const int64_t* feat_rel_ptrs_h
 
 // The launches of het_rgat_aggregate_compact_runs / _forward, arguments checked by the caller: the pack-form launch and, beside it
 // on the side stream, the two hub launches.  fwd: the instances that store h_inout alone.
-// T: the element type of feat_c and h_inout, float or het_bf16 (het_bf16: forward-only; the training kernels take float rows).
+// T: the element type of feat_c and h_inout, float or het_bf16.
 template <typename T>
 static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
                                       const T* feat_c, const float* el_c, const float* er_c, const RunOutputs& o, int64_t H,
                                       int64_t D, double slope, T* h_inout, int64_t h_rows, const float* attn_l,
                                       const int64_t* feat_rel_ptrs_host, void* workspace, hipStream_t s) {
-  constexpr bool F32 = std::is_same<T, float>::value;
-  if (!fwd && !F32) return HET_ERR_UNSUPPORTED;  // (no training instance over bf16 rows)
   const int64_t X = H * D;
   if (int rc = grouping_packed_ids(by_dst, true, s)) return rc;  // (builds the packs too)
   if (by_dst_rel->num_hub_items > 0)
@@ -1751,8 +1769,8 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
     if (fwd)                                                                                                                       \
       hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed_fwd<T, LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk,             \
                          by_dst->kp01, feat_c, el_c, er_c, (float)slope, h_inout, hio_rows32, rgat_hub_min(), ef);                 \
-    else if constexpr (F32)                                                                                                        \
-      hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed<LPR, DL, ELRV, WV>), dim3(nb), dim3(kBlock), 0, s, pk, by_dst->kp01,      \
+    else                                                                                                                           \
+      hipLaunchKernelGGL((HET_rgat_aggregate_runs_packed<LPR, DL, ELRV, WV, T>), dim3(nb), dim3(kBlock), 0, s, pk, by_dst->kp01,   \
                          feat_c, el_c, er_c, o.sum, o.ret, (float)slope, h_inout, hio_rows32, o.q_rows, o.q_sum, o.q_ref,          \
                          rgat_hub_min(), ef);                                                                                      \
   } while (0)
@@ -1782,7 +1800,7 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
 #define HET_HUBS_LAUNCH2(ELRV, WV)                                                                       \
   do {                                                                                                   \
     if (fwd) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items_fwd<T, LPR, DL, ELRV, WV>), HET_HUBS_ARGS);              \
-    else if constexpr (F32) hipLaunchKernelGGL((HET_rgat_aggregate_hub_items<LPR, DL, ELRV, WV>), HET_HUBS_ARGS);      \
+    else hipLaunchKernelGGL((HET_rgat_aggregate_hub_items<LPR, DL, ELRV, WV, T>), HET_HUBS_ARGS);                      \
   } while (0)
 #define HET_HUBS_LAUNCH(ELRV) do { if (w64) { HET_HUBS_LAUNCH2(ELRV, true); } else { HET_HUBS_LAUNCH2(ELRV, false); } } while (0)
       if (elr) {
@@ -1805,8 +1823,8 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
     if (fwd) {
       HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rgat_finish_hubs_fwd<T, LPR>), dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
                                                         by_dst_rel->num_hub_segs, it, part, (int)H, (int)D, h_inout, h_rows));
-    } else if constexpr (F32) {
-      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_finish_hubs<LPR>, dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
+    } else {
+      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rgat_finish_hubs<LPR, T>), dim3(nbs), dim3(kBlock), 0, s2, by_dst_rel->hub_rec,
                                                         by_dst_rel->num_hub_segs, it, by_dst->p1, part, o.sum, o.ret, (int)H, (int)D,
                                                         h_inout, h_rows, o.q_rows, o.q_sum, o.q_ref));
     }
@@ -1817,13 +1835,17 @@ static int rgat_aggregate_runs_launch(bool fwd, const het_grouping* by_dst, cons
   return HET_OK;
 }
 
-extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
-                                               const float* feat_c, const float* el_c, const float* er_c, float* sum, float* ret,
-                                               int64_t num_nodes, int64_t H, int64_t D, double slope, float* h_inout,
-                                               int64_t h_rows, float* q_rows, float* q_sum, float* q_ref, int64_t num_dst_rows,
-                                               const float* attn_l, const int64_t* feat_rel_ptrs_host, void* workspace,
-                                               int64_t workspace_bytes, het_stream stream) {
-  const char* op = "het_rgat_aggregate_compact_runs";
+// T = het_bf16 (het_rgat_aggregate_compact_runs_bf16): feat_c and h_inout het_bf16 (8-byte aligned rows), everything the backward reads
+// -- sum (the log-sum-exp), ret, the run sums -- and el_c / er_c fp32 as for float.  ret is the fp32 acc * rcp(sum); h_inout[v] =
+// round(widen(h_inout[v]) + ret[v]): the rows het_rgat_aggregate_compact_forward_bf16 stores, bit for bit.  That entry checks the
+// alignment of every table before anything is enqueued.
+template <typename T>
+static int rgat_aggregate_compact_runs(const char* op, const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                       const T* feat_c, const float* el_c, const float* er_c, float* sum, float* ret,
+                                       int64_t num_nodes, int64_t H, int64_t D, double slope, T* h_inout, int64_t h_rows,
+                                       float* q_rows, float* q_sum, float* q_ref, int64_t num_dst_rows, const float* attn_l,
+                                       const int64_t* feat_rel_ptrs_host, void* workspace, int64_t workspace_bytes, het_stream stream) {
+  constexpr bool BF16 = std::is_same<T, het_bf16>::value;
   hipStream_t s = (hipStream_t)stream;
   HET_REQUIRE(by_dst && by_dst_rel && sum && ret && q_rows && q_sum && q_ref && num_nodes >= 0 && num_rels > 0, "%s: null argument", op);
   if (!compact_shape_ok(H, D) || !coop_shape_ok(H, D)) {
@@ -1834,6 +1856,12 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
               "%s: by_dst must group the positions by destination with payload0 = feat row and payload1 = er row", op);
   HET_REQUIRE(by_dst_rel->R == 0 && by_dst_rel->E == by_dst->E && by_dst_rel->key_bound <= num_nodes * num_rels,
               "%s: by_dst_rel must group the same positions by destination * num_rels + relation", op);
+  if (BF16) {
+    HET_REQUIRE(aligned8(feat_c) && aligned8(h_inout), "%s: the bf16 rows feat_c and h_inout must be 8-byte aligned", op);
+    HET_REQUIRE(aligned16(ret, q_rows) && aligned16(sum, el_c) && aligned16(er_c, q_sum) && aligned16(q_ref),
+                "%s: the fp32 tables must be 16-byte aligned", op);
+    HET_REQUIRE(h_rows >= 0 && h_rows <= num_nodes, "%s: h_rows out of range", op);
+  }
   const int64_t need = het_rgat_aggregate_compact_runs_workspace(by_dst, by_dst_rel, num_rels, H, D, stream);
   if (need < 0) return HET_ERR_INVALID_ARG;
   HET_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && aligned16(workspace)),
@@ -1845,6 +1873,28 @@ extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const
   if (by_dst->E == 0) return HET_OK;
   return rgat_aggregate_runs_launch(false, by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, RunOutputs{sum, ret, q_rows, q_sum, q_ref},
                                     H, D, slope, h_inout, h_rows, attn_l, feat_rel_ptrs_host, workspace, s);
+}
+
+extern "C" int het_rgat_aggregate_compact_runs(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                               const float* feat_c, const float* el_c, const float* er_c, float* sum, float* ret,
+                                               int64_t num_nodes, int64_t H, int64_t D, double slope, float* h_inout,
+                                               int64_t h_rows, float* q_rows, float* q_sum, float* q_ref, int64_t num_dst_rows,
+                                               const float* attn_l, const int64_t* feat_rel_ptrs_host, void* workspace,
+                                               int64_t workspace_bytes, het_stream stream) {
+  return rgat_aggregate_compact_runs("het_rgat_aggregate_compact_runs", by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, sum, ret, num_nodes,
+                                     H, D, slope, h_inout, h_rows, q_rows, q_sum, q_ref, num_dst_rows, attn_l, feat_rel_ptrs_host, workspace,
+                                     workspace_bytes, stream);
+}
+
+extern "C" int het_rgat_aggregate_compact_runs_bf16(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                                    const het_bf16* feat_c, const float* el_c, const float* er_c, float* sum,
+                                                    float* ret, int64_t num_nodes, int64_t H, int64_t D, double slope,
+                                                    het_bf16* h_inout, int64_t h_rows, float* q_rows, float* q_sum, float* q_ref,
+                                                    int64_t num_dst_rows, const float* attn_l, const int64_t* feat_rel_ptrs_host,
+                                                    void* workspace, int64_t workspace_bytes, het_stream stream) {
+  return rgat_aggregate_compact_runs("het_rgat_aggregate_compact_runs_bf16", by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, sum, ret,
+                                     num_nodes, H, D, slope, h_inout, h_rows, q_rows, q_sum, q_ref, num_dst_rows, attn_l, feat_rel_ptrs_host,
+                                     workspace, workspace_bytes, stream);
 }
 
 // ---- forward only: the same walk, h_inout the only output (no sum / ret / run sums: nothing a backward could read) ----
@@ -1936,20 +1986,31 @@ static int64_t attn_grad_partial_rows(const PackView& pv, int64_t X) {
   return nb + nbl;
 }
 
+// T: the element type of feat_c [S_row,X] and gradout [rows,X], float or het_bf16 (het_rgat_backward_compact_runs_bf16: the run-sum
+// form on the cooperative shapes only; rows widened on load, every output and every sum fp32)
+template <typename T>
 static int rgat_backward_compact_impl(const char* op, const het_grouping* by_srow, const het_grouping* by_drow, const RunSums* runs,
-                                      float* grad_attn_l, const float* feat_c, const float* el_c, const float* er_c, const float* sum, const float* ret,
-                                      const float* gradout, float* grad_feat_c, float* grad_el_c, float* grad_er_c,
+                                      float* grad_attn_l, const T* feat_c, const float* el_c, const float* er_c, const float* sum, const float* ret,
+                                      const T* gradout, float* grad_feat_c, float* grad_el_c, float* grad_er_c,
                                       const float* fold_attn_l, const int64_t* row_rel_ptrs, int64_t num_rels,
                                       float* grad_bias, int64_t bias_rows, int64_t num_nodes, int64_t num_src_rows,
                                       int64_t num_dst_rows, int64_t H, int64_t D, double slope, void* workspace,
                                       int64_t workspace_bytes, het_stream stream) {
+  constexpr bool BF16 = std::is_same<T, het_bf16>::value;
   hipStream_t s = (hipStream_t)stream;
   HET_REQUIRE(by_srow && (by_drow || runs) && sum && ret && gradout && grad_feat_c && grad_er_c, "%s: null argument", op);
+  if (BF16) {
+    HET_REQUIRE(runs && feat_c && el_c && er_c, "%s: null argument", op);
+    HET_REQUIRE(aligned8(feat_c, gradout), "%s: the bf16 rows feat_c and gradout must be 8-byte aligned", op);
+    HET_REQUIRE(aligned16(grad_feat_c, ret, runs->q_rows) && aligned16(sum, el_c, er_c) && aligned16(grad_er_c, grad_el_c, fold_attn_l) &&
+                    aligned16(grad_attn_l, grad_bias) && aligned16(runs->q_sum, runs->q_ref),
+                "%s: the fp32 tables must be 16-byte aligned", op);
+  }
   // grad_el_c may be NULL when nobody reads it: its two consumers -- the gradient through el = <feat, attn_l> (fold_attn_l) and the
   // weight gradient of attn_l (grad_attn_l) -- are both formed inside the pass (cooperative shapes only)
   HET_REQUIRE(grad_el_c || (runs && fold_attn_l && grad_attn_l && coop_shape_ok(H, D)),
               "%s: grad_el_c may only be NULL in the run-sum form with fold_attn_l and grad_attn_l (cooperative shapes)", op);
-  if (!compact_shape_ok(H, D) || !segment_rows_supported((int)H) || slope < 0 || (runs && !coop_shape_ok(H, D))) {
+  if (!compact_shape_ok(H, D) || !segment_rows_supported((int)H) || slope < 0 || ((runs || BF16) && !coop_shape_ok(H, D))) {
     het_set_error("%s: unsupported shape H=%lld D=%lld (or slope < 0)", op, (long long)H, (long long)D);
     return HET_ERR_UNSUPPORTED;
   }
@@ -1987,7 +2048,20 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     HET_HIP(hipMemsetAsync(grad_feat_c, 0, sizeof(float) * num_src_rows * X, s));
     if (grad_el_c) HET_HIP(hipMemsetAsync(grad_el_c, 0, sizeof(float) * num_src_rows * H, s));
   }
-  if (num_nodes > 0 && !use_rec) {
+  if constexpr (BF16) {
+    if (E == 0) {  // no edge: zero gradients of the tables (grad_feat_c: by_srow->S == 0 above), the bias gradient from the rows alone
+      HET_HIP(hipMemsetAsync(grad_er_c, 0, sizeof(float) * num_dst_rows * H, s));
+      if (grad_bias && num_nodes > 0) {
+        HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rgat_colsum_rows<LPR, T>), dim3(kBiasBlocks), dim3(kBlock), 0, s, gradout,
+                                                          bias_rows < num_nodes ? bias_rows : num_nodes, bias_part));
+        hipLaunchKernelGGL(HET_rgat_colsum_finish, dim3((unsigned)X), dim3(kBlock), 0, s, bias_part, bias_part_rows, (int)X, grad_bias);
+        HET_LAUNCH_CHECK("HET_rgat_colsum_rows");
+      } else if (grad_bias) {
+        HET_HIP(hipMemsetAsync(grad_bias, 0, sizeof(float) * X, s));
+      }
+      return HET_OK;
+    }
+  } else if (num_nodes > 0 && !use_rec) {
     const unsigned nbp = grad_bias ? kBiasBlocks : grid_for(num_nodes * (X / 4));
     {
       HET_KTIME("HET_rgat_backward_dst_pack", s);
@@ -1998,6 +2072,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   } else if (grad_bias && num_nodes <= 0) {
     HET_HIP(hipMemsetAsync(grad_bias, 0, sizeof(float) * X, s));
   }
+  if (BF16 && !use_rec) return HET_ERR_INVALID_ARG;  // (edges without er rows: by_srow's payload contradicts num_dst_rows)
   if (E == 0) {
     if (grad_bias && num_nodes > 0) {
       hipLaunchKernelGGL(HET_rgat_colsum_finish, dim3((unsigned)X), dim3(kBlock), 0, s, bias_part, bias_part_rows, (int)X, grad_bias);
@@ -2014,7 +2089,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     HET_KTIME("HET_rgat_backward_drow_pass", s);
     const unsigned nbd = (unsigned)ceil_div64(num_dst_rows, (int64_t)(kBlock / 64) * (64 / (X / 4)) * 2);
     HET_DISPATCH_COOP((int)(X / 4), (int)(D / 4),
-                      hipLaunchKernelGGL((HET_rgat_drow_pass<LPR, DL>), dim3(nbd), dim3(kBlock), 0, s, er_c, sum, ret, gradout,
+                      hipLaunchKernelGGL((HET_rgat_drow_pass<LPR, DL, T>), dim3(nbd), dim3(kBlock), 0, s, er_c, sum, ret, gradout,
                                          runs->q_rows, runs->q_sum, runs->q_ref, runs->drow_nodes, by_srow->val_order, num_dst_rows, rec4,
                                          grad_er_c));
     HET_LAUNCH_CHECK("HET_rgat_drow_pass");
@@ -2045,7 +2120,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   hipStream_t s2 = fk.side;
   if (grad_bias && num_nodes > 0) {
     if (use_rec) {
-      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL(HET_rgat_colsum_rows<LPR>, dim3(kBiasBlocks), dim3(kBlock), 0, s2, gradout,
+      HET_DISPATCH_LPR((int)(X / 4), hipLaunchKernelGGL((HET_rgat_colsum_rows<LPR, T>), dim3(kBiasBlocks), dim3(kBlock), 0, s2, gradout,
                                                         bias_rows < num_nodes ? bias_rows : num_nodes, bias_part));
       HET_LAUNCH_CHECK("HET_rgat_colsum_rows");
     }
@@ -2063,7 +2138,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
       HET_KTIME("HET_rgat_backward_src_short", s);
 #define HET_SRC_COOP2(GA_, REC_, W_, gp_, gr_, go_)                                                                              \
   HET_DISPATCH_COOP((int)(X / 4), (int)(D / 4),                                                                                 \
-                    hipLaunchKernelGGL((HET_rgat_backward_src_coop<LPR, DL, GA_, REC_, W_>), dim3(nb), dim3(kBlock), 0, s, pk,   \
+                    hipLaunchKernelGGL((HET_rgat_backward_src_coop<LPR, DL, GA_, REC_, W_, T>), dim3(nb), dim3(kBlock), 0, s, pk, \
                                        by_srow->kp01, feat_c, el_c, er_arg, pack, gradout, grad_feat_c, grad_el_c, tbuf,         \
                                        (float)slope, fold_attn_l, row_rel_ptrs, (int)num_rels, gp_, gr_, go_))
 #define HET_SRC_COOP(GA_, REC_, gp_, gr_, go_) \
@@ -2084,7 +2159,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
       HET_KTIME("HET_rgat_backward_src_long", s2);
 #define HET_SRC_LONG2(GA_, REC_, W_, gp_, gr_, go_)                                                                              \
   HET_DISPATCH_COOP((int)(X / 4), (int)(D / 4),                                                                                 \
-                    hipLaunchKernelGGL((HET_rgat_backward_src_long<LPR, DL, GA_, REC_, W_>), dim3(nbl), dim3(kBlock), 0, s2, it, \
+                    hipLaunchKernelGGL((HET_rgat_backward_src_long<LPR, DL, GA_, REC_, W_, T>), dim3(nbl), dim3(kBlock), 0, s2, it, \
                                        pv.long_items, pv.num_long_items, by_srow->p01, feat_c, el_c, er_arg, pack,   \
                                        gradout, grad_feat_c, grad_el_c, tbuf, (float)slope, fold_attn_l, row_rel_ptrs,           \
                                        (int)num_rels, gp_, gr_, go_))
@@ -2099,7 +2174,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
 #undef HET_SRC_LONG
 #undef HET_SRC_LONG2
     }
-  } else {
+  } else if constexpr (!BF16) {
     const int skip_long = pv.num_long_items > 0 ? 1 : 0;
     {
       HET_KTIME("HET_rgat_backward_src_short", s);
@@ -2175,5 +2250,23 @@ extern "C" int het_rgat_backward_compact_runs(const het_grouping* by_srow, const
   const RunSums runs{q_rows, q_sum, q_ref, drow_nodes};
   return rgat_backward_compact_impl("het_rgat_backward_compact_runs", by_srow, nullptr, &runs, grad_attn_l, feat_c, el_c, er_c, sum, ret, gradout,
                                     grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows,
+                                    num_nodes, num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream);
+}
+
+// ... with bf16 rows: feat_c [S_row,H,D] and gradout [rows,H,D] het_bf16 (8-byte aligned), gathered as 2X-byte rows and widened on load;
+// el_c, er_c, sum, ret, the run sums and every gradient fp32 (16-byte aligned).  The bias gradient, when asked for, is the column sums
+// of the bf16 gradout rows.  Workspace: het_rgat_backward_compact_runs_workspace.  Every check precedes the first launch.
+extern "C" int het_rgat_backward_compact_runs_bf16(const het_grouping* by_srow, const float* q_rows, const float* q_sum,
+                                                   const float* q_ref, const int64_t* drow_nodes, const het_bf16* feat_c,
+                                                   const float* el_c, const float* er_c, const float* sum, const float* ret,
+                                                   const het_bf16* gradout, float* grad_feat_c, float* grad_el_c, float* grad_er_c,
+                                                   const float* fold_attn_l, const int64_t* row_rel_ptrs, int64_t num_rels,
+                                                   float* grad_bias, int64_t bias_rows, int64_t num_nodes, int64_t num_src_rows,
+                                                   int64_t num_dst_rows, int64_t H, int64_t D, double slope, float* grad_attn_l,
+                                                   void* workspace, int64_t workspace_bytes, het_stream stream) {
+  HET_REQUIRE(q_rows && q_sum && q_ref && (drow_nodes || num_dst_rows == 0), "het_rgat_backward_compact_runs_bf16: null argument");
+  const RunSums runs{q_rows, q_sum, q_ref, drow_nodes};
+  return rgat_backward_compact_impl("het_rgat_backward_compact_runs_bf16", by_srow, nullptr, &runs, grad_attn_l, feat_c, el_c, er_c, sum, ret,
+                                    gradout, grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows,
                                     num_nodes, num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream);
 }

@@ -16,6 +16,8 @@
 // what bounds those kernels once x is read once; five forms were measured, exp/node_dw.hip.txt.)
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hip.h"
 
 namespace {
@@ -38,7 +40,7 @@ struct NodeArgs {
   int64_t n_loop;          // nodes < n_loop carry the self-loop term (rows of grad_h)
   int64_t N;               // rows of x / grad_x = stride of the maps
   int R, H, D, rhp;        // rhp: R*H rounded up to a multiple of 8 (<= 32)
-  const float* gh;         // [n_loop, X]   gradient of the layer output (NULL: no self-loop term)
+  const void* gh;          // [n_loop, X]   gradient of the layer output (NULL: no self-loop term); rows of T (HET_node_dx)
   const float* g_rows;     // [S_row, X]    gradient of the (relation, source) rows
   const int32_t* row_map;  // [R, N]
   const float* g_er;       // [S_col, H]    gradient of er (NULL: none)
@@ -49,7 +51,7 @@ struct NodeArgs {
   const float* loop_wt;    // [X, K]  W_loop^T
   const float* wt;         // [R, X, K]  (= weights_transposed [R,H,D,K])
   const float* wa_t;       // [R, H, K]
-  float* grad_x;           // [N, K]
+  void* grad_x;            // [N, K]  rows of T
 };
 
 // ---- input gradient -------------------------------------------------------------------------------------------------------
@@ -58,7 +60,10 @@ struct NodeArgs {
 // are loaded coalesced (KS/4 lanes x float4 per row) into the wave's LDS tile, read back as MFMA A fragments and multiplied
 // into the same XO/32 accumulators; the rows of the next present source are in flight during the MFMAs.  The er term is a
 // rank-(R*H) extension of the contraction whose fragments the lanes fetch directly.
-template <int KS, int NO, int WAVES>
+// T: the element type of the activation rows grad_h (in) and grad_x (out), float or het_bf16 (het_rgat_node_backward_dx_bf16): grad_h
+// is widened where it enters the wave's LDS tile, grad_x rounded once (to nearest even) where the finished row is stored; g_rows,
+// g_er, the weights in LDS and the accumulators are fp32 either way.
+template <int KS, int NO, int WAVES, typename T = float>
 __global__ __launch_bounds__(WAVES * 64) void HET_node_dx(NodeArgs a) {
   constexpr int XO = NO * 32, KH = KS / 2;
   constexpr int LD = (KS > XO ? KS : XO) + 4;
@@ -153,11 +158,20 @@ __global__ __launch_bounds__(WAVES * 64) void HET_node_dx(NodeArgs a) {
 
     float4 areg[NITA];
     auto issue = [&](int s) {
-      const float* base = s == 0 ? a.gh : a.g_rows;
+      if constexpr (std::is_same<T, float>::value) {
+        const float* base = s == 0 ? static_cast<const float*>(a.gh) : a.g_rows;
 #pragma unroll
-      for (int it = 0; it < NITA; ++it) {
-        const int id = idsL[s * 32 + it * RPIA + ra];
-        areg[it] = ld4(base + (int64_t)(id < 0 ? 0 : id) * KS + ca);
+        for (int it = 0; it < NITA; ++it) {
+          const int id = idsL[s * 32 + it * RPIA + ra];
+          areg[it] = ld4(base + (int64_t)(id < 0 ? 0 : id) * KS + ca);
+        }
+      } else {  // (s is wave-uniform)
+#pragma unroll
+        for (int it = 0; it < NITA; ++it) {
+          const int id = idsL[s * 32 + it * RPIA + ra];
+          const int64_t off = (int64_t)(id < 0 ? 0 : id) * KS + ca;
+          areg[it] = s == 0 ? ldrow4(static_cast<const T*>(a.gh) + off) : ld4(a.g_rows + off);
+        }
       }
     };
     int s = mask ? __ffs(mask) - 1 : -1;
@@ -220,14 +234,18 @@ __global__ __launch_bounds__(WAVES * 64) void HET_node_dx(NodeArgs a) {
       const float4 v = ld4(&Ws[(it * RPIC + rc) * LD + cc]);
       // non-temporal: the rows leave in the presence-sorted order of the tiles, i.e. scattered over grad_x, and nothing reads them
       // before the step ends -- same-box A/B on the RGAT step 3.691 -> 3.642 / 3.632 ms (profiles/r05/ab_dense.txt, call 8)
-      if (node >= 0) st4_nt(a.grad_x + node * XO + cc, v);
+      if constexpr (std::is_same<T, float>::value) {
+        if (node >= 0) st4_nt(static_cast<float*>(a.grad_x) + node * XO + cc, v);
+      } else {
+        if (node >= 0) strow4(static_cast<T*>(a.grad_x) + node * XO + cc, v);
+      }
     }
   }
 }
 
 inline int pow2_heads(int64_t H) { return H == 1 || H == 2 || H == 4 || H == 8; }
 
-template <int KS, int NO>
+template <int KS, int NO, typename T>
 int launch_dx(const NodeArgs& a, hipStream_t s) {
   constexpr int XO = NO * 32, LD = (KS > XO ? KS : XO) + 4;
   const int64_t tiles = (a.n_end - a.n_begin + 31) / 32;
@@ -240,15 +258,15 @@ int launch_dx(const NodeArgs& a, hipStream_t s) {
     const size_t lds = lds_for(8);
     int64_t gx = (tiles + 8 * 4 - 1) / (8 * 4);  // ~4 tiles per wave: the weights are staged once per workgroup
     if (gx < 1) gx = 1;
-    HET_HIP(hipFuncSetAttribute((const void*)HET_node_dx<KS, NO, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((HET_node_dx<KS, NO, 8>), dim3((unsigned)gx), dim3(512), lds, s, a);
+    HET_HIP(hipFuncSetAttribute((const void*)HET_node_dx<KS, NO, 8, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((HET_node_dx<KS, NO, 8, T>), dim3((unsigned)gx), dim3(512), lds, s, a);
   } else {
     const size_t lds = lds_for(4);
     HET_REQUIRE(lds <= limit, "het_rgat_node_backward_dx: the weights of %d relations do not fit the LDS", a.R);
     int64_t gx = (tiles + 4 * 4 - 1) / (4 * 4);
     if (gx < 1) gx = 1;
-    HET_HIP(hipFuncSetAttribute((const void*)HET_node_dx<KS, NO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((HET_node_dx<KS, NO, 4>), dim3((unsigned)gx), dim3(256), lds, s, a);
+    HET_HIP(hipFuncSetAttribute((const void*)HET_node_dx<KS, NO, 4, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((HET_node_dx<KS, NO, 4, T>), dim3((unsigned)gx), dim3(256), lds, s, a);
   }
   HET_LAUNCH_CHECK("HET_node_dx");
   return HET_OK;
@@ -291,13 +309,16 @@ extern "C" int het_node_row_map(const int64_t* rel_ptrs, int64_t num_rels, const
   return HET_OK;
 }
 
-extern "C" int het_rgat_node_backward_dx(int64_t n_begin, int64_t n_end, int64_t n_loop, int64_t num_nodes, int64_t num_rels,
-                                         const float* grad_h, const float* loop_wt, const float* g_rows,
-                                         const float* weights_t, const int32_t* row_map, const float* g_er, const float* wa_t,
-                                         const int32_t* dst_map, float* grad_x, int64_t H, int64_t K, int64_t D,
-                                         const int32_t* node_order, het_stream stream) {
-  const char* op = "het_rgat_node_backward_dx";
+template <typename T>
+static int rgat_node_backward_dx(const char* op, int64_t n_begin, int64_t n_end, int64_t n_loop, int64_t num_nodes, int64_t num_rels,
+                                 const T* grad_h, const float* loop_wt, const float* g_rows, const float* weights_t,
+                                 const int32_t* row_map, const float* g_er, const float* wa_t, const int32_t* dst_map, T* grad_x, int64_t H,
+                                 int64_t K, int64_t D, const int32_t* node_order, het_stream stream) {
   if (int rc = check_node_args(op, n_begin, n_end, n_loop, num_nodes, num_rels, H, K, D)) return rc;
+  if (std::is_same<T, het_bf16>::value) {
+    HET_REQUIRE(aligned8(grad_h, grad_x), "%s: the bf16 rows grad_h and grad_x must be 8-byte aligned", op);
+    HET_REQUIRE(aligned16(g_rows, loop_wt, weights_t), "%s: the fp32 tables must be 16-byte aligned", op);
+  }
   if (n_begin == n_end) return HET_OK;
   HET_REQUIRE(grad_x && (num_rels == 0 || (g_rows && weights_t && row_map)) && (!grad_h || loop_wt) &&
                   (!g_er || (wa_t && dst_map)),
@@ -310,7 +331,26 @@ extern "C" int het_rgat_node_backward_dx(int64_t n_begin, int64_t n_end, int64_t
   a.loop_wt = loop_wt; a.wt = weights_t; a.wa_t = wa_t; a.grad_x = grad_x; a.order = node_order;
   hipStream_t s = (hipStream_t)stream;
   const int KS = (int)(H * D);
-  if (KS == 64) return K == 64 ? launch_dx<64, 2>(a, s) : launch_dx<64, 1>(a, s);
-  return K == 64 ? launch_dx<32, 2>(a, s) : launch_dx<32, 1>(a, s);
+  if (KS == 64) return K == 64 ? launch_dx<64, 2, T>(a, s) : launch_dx<64, 1, T>(a, s);
+  return K == 64 ? launch_dx<32, 2, T>(a, s) : launch_dx<32, 1, T>(a, s);
 }
 
+extern "C" int het_rgat_node_backward_dx(int64_t n_begin, int64_t n_end, int64_t n_loop, int64_t num_nodes, int64_t num_rels,
+                                         const float* grad_h, const float* loop_wt, const float* g_rows,
+                                         const float* weights_t, const int32_t* row_map, const float* g_er, const float* wa_t,
+                                         const int32_t* dst_map, float* grad_x, int64_t H, int64_t K, int64_t D,
+                                         const int32_t* node_order, het_stream stream) {
+  return rgat_node_backward_dx("het_rgat_node_backward_dx", n_begin, n_end, n_loop, num_nodes, num_rels, grad_h, loop_wt, g_rows, weights_t,
+                               row_map, g_er, wa_t, dst_map, grad_x, H, K, D, node_order, stream);
+}
+
+// ... with bf16 activation rows: grad_h [n_loop, H*D] and grad_x [num_nodes, K] het_bf16 (8-byte aligned); g_rows, g_er and the
+// weights fp32.  grad_x is rounded once, after every term of a node is summed.
+extern "C" int het_rgat_node_backward_dx_bf16(int64_t n_begin, int64_t n_end, int64_t n_loop, int64_t num_nodes, int64_t num_rels,
+                                              const het_bf16* grad_h, const float* loop_wt, const float* g_rows,
+                                              const float* weights_t, const int32_t* row_map, const float* g_er, const float* wa_t,
+                                              const int32_t* dst_map, het_bf16* grad_x, int64_t H, int64_t K, int64_t D,
+                                              const int32_t* node_order, het_stream stream) {
+  return rgat_node_backward_dx("het_rgat_node_backward_dx_bf16", n_begin, n_end, n_loop, num_nodes, num_rels, grad_h, loop_wt, g_rows,
+                               weights_t, row_map, g_er, wa_t, dst_map, grad_x, H, K, D, node_order, stream);
+}

@@ -619,6 +619,28 @@ extern "C" int het_rows_dot1h_bf16(const int64_t* rel_ptrs, int64_t num_rels, co
   return launch_rowdot1h_fwd_bf16(q, x, (hipStream_t)stream);
 }
 
+// grad_w[r, h, :] (+)= SUM_i gradout[scatter_idx[i], h] * widen(x[gather_idx[i], :]): the weight gradient of het_rows_dot1h_bf16 (the folded
+// attention vector W . attn_r of the RGAT layer's bf16 training step); gradout [*,H] and grad_w [R,H,K] fp32.  accumulate = 0: "="
+// (grad_w is cleared first; the workgroups add their partial rows with float atomics)
+extern "C" int het_rows_dot1h_backward_dw_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx,
+                                               const int64_t* scatter_idx, int64_t num_rows, const het_bf16* x, const float* gradout,
+                                               float* grad_w, int64_t H, int64_t K, int accumulate, het_stream stream) {
+  const char* op = "het_rows_dot1h_backward_dw_bf16";
+  HET_REQUIRE(rel_ptrs && num_rels > 0 && num_rels < (1ll << 31) && num_rows >= 0 && H > 0 && K > 0 && grad_w, "%s: bad arguments", op);
+  HET_REQUIRE(num_rows == 0 || (x && gradout), "%s: null data pointer", op);
+  if (!(rowdot1h_supported((int)H, (int)K) && aligned8(x) && aligned16(grad_w, gradout))) {
+    het_set_error("%s: H in {1, 2, 4, 8} and K a power of two in [4 H, 256], x 8-byte and the fp32 tensors 16-byte aligned only (H=%lld K=%lld)",
+                  op, (long long)H, (long long)K);
+    return HET_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!accumulate) HET_HIP(hipMemsetAsync(grad_w, 0, sizeof(float) * num_rels * H * K, s));
+  RowDotArgs q;
+  q.gather = gather_idx; q.scatter = scatter_idx; q.go = gradout; q.out = grad_w; q.seg_ptrs = rel_ptrs;
+  q.num_segs = (int)num_rels; q.num_rows = num_rows; q.H = (int)H; q.K = (int)K;
+  return launch_rowdot1h_bwd_dw_bf16(q, x, s);
+}
+
 extern "C" int het_backward_rgnn_relational_matmul_no_scatter_gather_list(
     const int64_t* offsets, int64_t num_types, int64_t num_rows, const float* weights_t, const float* x,
     const float* gradout, float* grad_x, float* grad_w, int64_t H, int64_t K, int64_t D, int x_per_head,

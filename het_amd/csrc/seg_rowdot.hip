@@ -374,6 +374,70 @@ __global__ __launch_bounds__(kBlock) void HET_rowdot1h_bwd_dw(RowDotArgs a, int 
   }
 }
 
+// ... with bf16 input rows (A: [*, K] het_bf16, widened on load -- exact; a lane holds 4 elements = 8 bytes); go, the sums and out stay
+// fp32.  The weight gradient of the folded attention vector (er_c = <x[dst], W . attn_r>) of the RGAT layer's bf16 training step.  A copy
+// like HET_rowdot1h_fwd_bf16: as instances of one shared body the float kernels came out with other code than they were measured with.
+template <int LPR, int H>
+__global__ __launch_bounds__(kBlock) void HET_rowdot1h_bwd_dw_bf16(RowDotArgs a, const het_bf16* __restrict__ A, int chunk) {
+  constexpr int EPW = 64 / LPR, K = LPR * 4;
+  int r;
+  idx_t rb, re;
+  if (!tile_to_relation(a.seg_ptrs, a.num_segs, chunk, blockIdx.x, r, rb, re)) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int slot = lane / LPR, sub = lane % LPR, x = sub * 4;
+  float4 acc[H];
+#pragma unroll
+  for (int h = 0; h < H; ++h) acc[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (idx_t base = rb; base < re; base += 4 * EPW * U) {
+    HET_ROWDOT_ROWS(EPW)
+    float4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = ldrow4(A + gi[u] * K + x);
+    float g[U][H];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (H == 4 && (reinterpret_cast<uintptr_t>(a.go) & 15) == 0) {  // the H gradients of a row as one 16-byte load
+        const float4 t = ld4(a.go + si[u] * H);
+        g[u][0] = t.x; g[u][1 % H] = t.y; g[u][2 % H] = t.z; g[u][3 % H] = t.w;
+      } else {
+#pragma unroll
+        for (int h = 0; h < H; ++h) g[u][h] = a.go[si[u] * H + h];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float gu = ok[u] ? g[u][h] : 0.f;
+        acc[h].x = fmaf(gu, v[u].x, acc[h].x); acc[h].y = fmaf(gu, v[u].y, acc[h].y);
+        acc[h].z = fmaf(gu, v[u].z, acc[h].z); acc[h].w = fmaf(gu, v[u].w, acc[h].w);
+      }
+    }
+  }
+  __shared__ float4 part[4][64];
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    float4 t = acc[h];
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {
+      t.x += __shfl_xor(t.x, off); t.y += __shfl_xor(t.y, off);
+      t.z += __shfl_xor(t.z, off); t.w += __shfl_xor(t.w, off);
+    }
+    __syncthreads();
+    if (slot == 0) part[wave][sub] = t;
+    __syncthreads();
+    if (wave == 0 && slot == 0) {
+      float4 o = part[0][sub];
+      for (int wv = 1; wv < 4; ++wv) {
+        const float4 q = part[wv][sub];
+        o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
+      }
+      float* p = a.out + ((int64_t)r * H + h) * K + x;
+      atomic_add4(p, o);
+    }
+  }
+}
+
 }  // namespace
 
 bool rowdot_supported(int H, int K) {
@@ -471,5 +535,16 @@ int launch_rowdot1h_bwd_dw(const RowDotArgs& a, hipStream_t s) {
   dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
   HET_ROWDOT1H_DISPATCH(HET_rowdot1h_bwd_dw, a, (int)chunk)
   HET_LAUNCH_CHECK("HET_rowdot1h_bwd_dw");
+  return HET_OK;
+}
+
+int launch_rowdot1h_bwd_dw_bf16(const RowDotArgs& a, const het_bf16* A, hipStream_t s) {
+  if (a.num_rows == 0) return HET_OK;
+  int64_t chunk = ceil_div64(a.num_rows, kDwWgs);  // see kDwWgs
+  if (chunk < kDwMinChunk) chunk = kDwMinChunk;
+  dim3 grid((unsigned)(ceil_div64(a.num_rows, chunk) + a.num_segs)), block(kBlock);
+  HET_KTIME("HET_rowdot1h_bwd_dw_bf16", s);
+  HET_ROWDOT1H_DISPATCH(HET_rowdot1h_bwd_dw_bf16, a, A, (int)chunk)
+  HET_LAUNCH_CHECK("HET_rowdot1h_bwd_dw_bf16");
   return HET_OK;
 }

@@ -35,3 +35,4 @@ int launch_rowdot1h_fwd(const RowDotArgs& a, hipStream_t s);
 int launch_rowdot1h_fwd_bf16(const RowDotArgs& a, const het_bf16* A, hipStream_t s);
 int launch_rowdot1h_bwd_dx(const RowDotArgs& a, hipStream_t s);
 int launch_rowdot1h_bwd_dw(const RowDotArgs& a, hipStream_t s);
+int launch_rowdot1h_bwd_dw_bf16(const RowDotArgs& a, const het_bf16* A, hipStream_t s);  // out += (A bf16 [*, K])

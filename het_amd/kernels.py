@@ -767,27 +767,36 @@ def rgat_aggregate_compact(groupings, feat_c, el_c, er_c, sum, ret, slope, h_ino
     for rgat_backward_compact.  attn_l [R,H,D] + feat_rel_ptrs [R+1] (relation pointers of the feat rows), run-sum form: el_c is
     <feat_c, attn_l[relation of the row]> and the pass may form it from the rows it gathers (include/het_amd.h)."""
     _chk("rgat_aggregate_compact", tuple(t for t in (feat_c, el_c, er_c, sum, ret, h_inout) if t is not None))
+    if groupings[3] is not None:
+        return _rgat_aggregate_compact_runs("rgat_aggregate_compact_runs", groupings, feat_c, el_c, er_c, sum, ret, slope, h_inout,
+                                            num_rels, attn_l, feat_rel_ptrs)
     N, H = sum.shape[0], sum.shape[1]
     D = ret.numel() // max(1, N * H)
-    if groupings[3] is not None:
-        S_col = er_c.shape[0]
-        q_rows = torch.empty((S_col, H, D), dtype=ret.dtype, device=ret.device)
-        q_sum, q_ref = torch.empty_like(er_c), torch.empty_like(er_c)
-        ws, nbytes = _workspace(ret, "het_rgat_aggregate_compact_runs_workspace", groupings[0].handle, groupings[3].handle, int(num_rels),
-                                H, D, _stream(ret))
-        host_ptrs = None
-        if attn_l is not None and feat_rel_ptrs is not None:
-            _chk("rgat_aggregate_compact", (attn_l,), (feat_rel_ptrs,))
-            host_ptrs = _host_rel_ptrs(feat_rel_ptrs)
-        _call(ret, "het_rgat_aggregate_compact_runs", groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c),
-              _p(er_c), _p(sum), _p(ret), N, H, D, float(slope), _p(h_inout), 0 if h_inout is None else h_inout.shape[0],
-              _p(q_rows), _p(q_sum), _p(q_ref), S_col, _p(attn_l) if host_ptrs is not None else None, host_ptrs, _p(ws), nbytes,
-              _stream(ret))
-        return q_rows, q_sum, q_ref
     ws, nbytes = _workspace(ret, "het_rgat_aggregate_compact_workspace", groupings[0].handle, H, D)  # (hub destinations only)
     _call(ret, "het_rgat_aggregate_compact", groupings[0].handle, _p(feat_c), _p(el_c), _p(er_c), _p(sum), _p(ret), N, H, D,
           float(slope), _p(h_inout), 0 if h_inout is None else h_inout.shape[0], _p(ws), nbytes, _stream(ret))
     return None
+
+
+def _rgat_aggregate_compact_runs(name, groupings, feat_c, el_c, er_c, sum, ret, slope, h_inout, num_rels, attn_l, feat_rel_ptrs):
+    """The run-sum form of rgat_aggregate_compact / _bf16 behind their tensor checks: the C entry is het_<name>.  Returns the run
+    sums (q_rows, q_sum, q_ref), fp32 whatever the row type."""
+    N, H = sum.shape[0], sum.shape[1]
+    D = ret.numel() // max(1, N * H)
+    S_col = er_c.shape[0]
+    q_rows = torch.empty((S_col, H, D), dtype=ret.dtype, device=ret.device)
+    q_sum, q_ref = torch.empty_like(er_c), torch.empty_like(er_c)
+    ws, nbytes = _workspace(ret, "het_rgat_aggregate_compact_runs_workspace", groupings[0].handle, groupings[3].handle, int(num_rels),
+                            H, D, _stream(ret))
+    host_ptrs = None
+    if attn_l is not None and feat_rel_ptrs is not None:
+        _chk(name, (attn_l,), (feat_rel_ptrs,))
+        host_ptrs = _host_rel_ptrs(feat_rel_ptrs)
+    _call(ret, "het_" + name, groupings[0].handle, groupings[3].handle, int(num_rels), _p(feat_c), _p(el_c),
+          _p(er_c), _p(sum), _p(ret), N, H, D, float(slope), _p(h_inout), 0 if h_inout is None else h_inout.shape[0],
+          _p(q_rows), _p(q_sum), _p(q_ref), S_col, _p(attn_l) if host_ptrs is not None else None, host_ptrs, _p(ws), nbytes,
+          _stream(ret))
+    return q_rows, q_sum, q_ref
 
 
 def _rgat_aggregate_compact_forward(name, groupings, feat_c, el_c, er_c, h_inout, slope, num_rels, attn_l, feat_rel_ptrs):
@@ -903,6 +912,73 @@ def rgat_aggregate_compact_forward_bf16(groupings, feat_c, el_c, er_c, h_inout, 
                                     attn_l, feat_rel_ptrs)
 
 
+# ---- the RGAT layer's training step with bf16 activations (backend/rgat_fused_layer.py: RgatLayerBf16Function) ----
+def rgat_aggregate_compact_bf16(groupings, feat_c, el_c, er_c, sum, ret, slope, h_inout, num_rels, attn_l=None, feat_rel_ptrs=None):
+    """rgat_aggregate_compact's run-sum form over bf16 rows (het_rgat_aggregate_compact_runs_bf16): feat_c [S,H,D] and h_inout
+    [rows, H*D] bf16; el_c (the dots of the rounded rows: rgat_el_rows_bf16), er_c, sum [N,H], ret [N,H,D] and the returned run sums
+    fp32.  h_inout receives the rows rgat_aggregate_compact_forward_bf16 would store."""
+    name = "rgat_aggregate_compact_bf16"
+    _chk_bf16(name, (feat_c, h_inout), (el_c, er_c, sum, ret))
+    if groupings[3] is None:
+        raise _lib.HetError(f"{name}: needs the groupings of the run-sum form (rgat_compact_groupings with rel_ptrs)")
+    S, H, D = feat_c.shape
+    N = sum.shape[0]
+    if (el_c.shape != (S, H) or er_c.dim() != 2 or er_c.shape[1] != H or sum.shape != (N, H) or ret.shape != (N, H, D)
+            or h_inout.dim() != 2 or h_inout.shape[1] != H * D or h_inout.shape[0] > N):
+        raise _lib.HetError(f"{name}: feat_c {tuple(feat_c.shape)}, el_c {tuple(el_c.shape)}, er_c {tuple(er_c.shape)}, sum "
+                            f"{tuple(sum.shape)}, ret {tuple(ret.shape)} and h_inout {tuple(h_inout.shape)} do not fit")
+    return _rgat_aggregate_compact_runs("rgat_aggregate_compact_runs_bf16", groupings, feat_c, el_c, er_c, sum, ret, slope, h_inout,
+                                        num_rels, attn_l, feat_rel_ptrs)
+
+
+def rgat_backward_compact_bf16(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope, runs,
+                               drow_nodes, fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, grad_attn_l=None):
+    """rgat_backward_compact's run-sum form over bf16 rows (het_rgat_backward_compact_runs_bf16): feat_c [S,H,D] and gradout [N,H,D]
+    bf16; everything else -- and every gradient -- fp32.  grad_bias [H*D]: the column sums of the first ``bias_rows`` gradout rows."""
+    name = "rgat_backward_compact_bf16"
+    _chk_bf16(name, (feat_c, gradout), tuple(t for t in (el_c, er_c, sum, ret, grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, grad_bias,
+                                                        grad_attn_l) + tuple(runs) if t is not None))
+    _chk(name, (), tuple(t for t in (row_rel_ptrs, drow_nodes) if t is not None))
+    S, H, D = feat_c.shape
+    N = sum.shape[0]
+    if (el_c.shape != (S, H) or er_c.dim() != 2 or er_c.shape[1] != H or sum.shape != (N, H) or ret.shape != (N, H, D)
+            or gradout.shape != (N, H, D) or grad_feat_c.shape != (S, H, D) or grad_er_c.shape != er_c.shape
+            or (grad_el_c is not None and grad_el_c.shape != (S, H)) or runs[0].shape != (er_c.shape[0], H, D)
+            or (grad_bias is not None and (grad_bias.numel() != H * D or bias_rows > N))):
+        raise _lib.HetError(f"{name}: feat_c {tuple(feat_c.shape)}, gradout {tuple(gradout.shape)}, sum {tuple(sum.shape)}, ret "
+                            f"{tuple(ret.shape)}, er_c {tuple(er_c.shape)} and the gradients do not fit")
+    _rgat_backward_compact("het_rgat_backward_compact_runs_bf16", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c,
+                           grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l)
+
+
+def rgat_node_backward_dx_bf16(n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weights_t, row_map, g_er, wa_t, dst_map, grad_x,
+                               node_order=None):
+    """rgat_node_backward_dx with bf16 activation rows (het_rgat_node_backward_dx_bf16): grad_h [n_loop, H*D] and grad_x [N,K] bf16,
+    g_rows, g_er and the weights fp32; grad_x is rounded once, after every term of a node is summed."""
+    name = "rgat_node_backward_dx_bf16"
+    _chk_bf16(name, tuple(t for t in (grad_h, grad_x) if t is not None), tuple(t for t in (loop_wt, g_rows, weights_t, g_er, wa_t) if t is not None))
+    R, H, D, K = weights_t.shape
+    if (grad_x.dim() != 2 or grad_x.shape[1] != K or g_rows.shape[-1] != H * D or (grad_h is not None and (grad_h.shape[-1] != H * D
+            or grad_h.shape[0] < min(int(n_loop), grad_x.shape[0]))) or row_map.shape != (R, grad_x.shape[0])):
+        raise _lib.HetError(f"{name}: grad_x {tuple(grad_x.shape)}, g_rows {tuple(g_rows.shape)} and weights_t {tuple(weights_t.shape)} do not fit")
+    _rgat_node_backward_dx("het_rgat_node_backward_dx_bf16", n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weights_t, row_map, g_er, wa_t,
+                           dst_map, grad_x, node_order)
+
+
+def rows_dot1h_backward_dw_bf16(rel_ptrs, gather_idx, x, gradout, grad_w, accumulate: bool):
+    """grad_w[r(i), h] (+)= gradout[i, h] * x[gather_idx[i]] (het_rows_dot1h_backward_dw_bf16): the weight gradient of rows_dot1h_bf16;
+    x [*,K] bf16, gradout [rows,H] and grad_w [R,H,K] fp32."""
+    _chk_bf16("rows_dot1h_backward_dw_bf16", (x,), (gradout, grad_w))
+    _chk("rows_dot1h_backward_dw_bf16", (), (rel_ptrs, gather_idx))
+    R, H, K = grad_w.shape
+    n = gather_idx.numel()
+    if x.shape[-1] != K or gradout.numel() != n * H or rel_ptrs.numel() != R + 1:
+        raise _lib.HetError(f"rows_dot1h_backward_dw_bf16: x {tuple(x.shape)} / gradout {tuple(gradout.shape)} do not fit grad_w "
+                            f"{tuple(grad_w.shape)} and {n} rows")
+    _call(grad_w, "het_rows_dot1h_backward_dw_bf16", _p(rel_ptrs), R, _p(gather_idx), None, n, _p(x), _p(gradout), _p(grad_w), H, K,
+          int(accumulate), _stream(grad_w))
+
+
 def rows_matmul_backward_split_ok(H: int, K: int, D: int) -> bool:
     """Shapes het_rows_matmul_backward_dx / _dw cover (one input head on the matrix cores)."""
     return K in (32, 64, 128) and H * D in (32, 64, 128)
@@ -971,8 +1047,15 @@ def rgat_node_backward_dx(n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weigh
     """grad_x rows [n_begin, n_end) of the one-node RGAT layer in one pass over the nodes (include/het_amd.h).  node_order
     (optional, [N] int32): the nodes of the call are the entries [n_begin, n_end) of this list."""
     _chk("rgat_node_backward_dx", tuple(t for t in (grad_h, loop_wt, g_rows, weights_t, g_er, wa_t, grad_x) if t is not None))
+    _rgat_node_backward_dx("het_rgat_node_backward_dx", n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weights_t, row_map, g_er, wa_t,
+                           dst_map, grad_x, node_order)
+
+
+def _rgat_node_backward_dx(entry, n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weights_t, row_map, g_er, wa_t, dst_map, grad_x,
+                           node_order):
+    """rgat_node_backward_dx / _bf16 behind their tensor checks."""
     R, H, D, K = weights_t.shape
-    _call(grad_x, "het_rgat_node_backward_dx", int(n_begin), int(n_end), int(n_loop), grad_x.shape[0], R, _p(grad_h), _p(loop_wt),
+    _call(grad_x, entry, int(n_begin), int(n_end), int(n_loop), grad_x.shape[0], R, _p(grad_h), _p(loop_wt),
           _p(g_rows), _p(weights_t), _p(row_map), _p(g_er), _p(wa_t), _p(dst_map), _p(grad_x), H, K, D, _p(node_order),
           _stream(grad_x))
 
@@ -1033,6 +1116,13 @@ def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad
     _chk("rgat_backward_compact", tuple(t for t in (feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c,
                                                     fold_attn_l, grad_bias, grad_attn_l) + (tuple(runs) if runs else ()) if t is not None),
          tuple(t for t in (row_rel_ptrs, drow_nodes) if t is not None))
+    _rgat_backward_compact("het_rgat_backward_compact_runs", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c,
+                           grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l)
+
+
+def _rgat_backward_compact(runs_entry, groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
+                           fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l):
+    """rgat_backward_compact / _bf16 behind their tensor checks; ``runs_entry``: the C entry of the run-sum form."""
     N, H = sum.shape[0], sum.shape[1]
     D = ret.numel() // max(1, N * H)
     if runs:
@@ -1047,7 +1137,7 @@ def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad
             int(bias_rows), N, feat_c.shape[0], er_c.shape[0], H, D, float(slope))
     tail = (_p(ws), nbytes, _stream(ret))
     if runs:
-        _call(ret, "het_rgat_backward_compact_runs", groupings[1].handle, _p(runs[0]), _p(runs[1]), _p(runs[2]), _p(drow_nodes), *head,
+        _call(ret, runs_entry, groupings[1].handle, _p(runs[0]), _p(runs[1]), _p(runs[2]), _p(drow_nodes), *head,
               _p(grad_attn_l), *tail)
     else:
         _call(ret, "het_rgat_backward_compact", groupings[1].handle, groupings[2].handle, *head, *tail)

@@ -60,6 +60,16 @@ class HET_RGATLayer(nn.Module):
     ``HET_RGAT_FORWARD_ONLY=0`` -- runs the fp32 layer on ``x.float()`` and casts the result; autograd casts the gradient of the
     input back to bf16.  That fallback is correct, not faster.
 
+    ``bf16_training=True`` (opt-in; the default keeps the fallback above for every call that needs a gradient): a bf16 input that
+    requires a gradient, or a layer whose parameters do, trains natively in bf16 -- the same forward with the training aggregation,
+    and a backward that gathers the bf16 gradient of the output, keeps every gradient sum and parameter gradient in fp32 and rounds
+    the input gradient once (rgat_fused_layer.RgatLayerBf16Function) -- on one GPU, for input widths and rows of 32 / 64 after
+    padding, at most 8 relations, every edge ending at one of the first ``num_dst`` nodes, with or without the self-loop and the
+    bias, on full graphs and blocks.  Still on the upcast fallback with the keyword on: a halo, ``HET_RGAT_PER_EDGE=1``, the
+    op-by-op composition, ``reference_op_sequence``, 128-wide rows or inputs (an input width above 64 pads to 128), more than 8
+    relations, and the shapes that take the per-relation or generic backward routes.  Evaluation calls and fp32 inputs are the same
+    with either value; ``get_attention=True`` on a training call still composes the weights in torch.
+
     Attention weights: ``forward(..., get_attention=True)`` returns ``(h, attn)`` -- attn [E, num_heads] float32, detached, row i the
     softmax weight of the edge with id i (the graph's eids, whatever order the edges are stored in) among the in-edges of its
     destination; every row is filled, on a block too.  On the evaluation paths (fp32 and bf16) a HIP pass over the ids and the el /
@@ -70,7 +80,7 @@ class HET_RGATLayer(nn.Module):
     def __init__(self, in_feat, out_feat, num_rels, num_heads, *, bias=True, activation=None, self_loop=False,
                  compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
                  multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True, dropout=0.5,
-                 leaky_relu_slope=0.2, reference_op_sequence=False):
+                 leaky_relu_slope=0.2, reference_op_sequence=False, bf16_training=False):
         super().__init__()
         assert out_feat % num_heads == 0, "out_feat must be a multiple of num_heads"
         self.in_feat, self.out_feat, self.num_rels, self.num_heads = in_feat, out_feat, num_rels, num_heads
@@ -80,6 +90,7 @@ class HET_RGATLayer(nn.Module):
         self.multiply_among_weights_first_flag = multiply_among_weights_first_flag
         self.gat_edge_parallel_flag = gat_edge_parallel_flag
         self.leaky_relu_slope = leaky_relu_slope
+        self.bf16_training = bool(bf16_training)  # a bf16 input that needs a backward: natively where covered (the class docstring)
         # True: run the reference's op sequence literally (only reference-named torch_hrt ops, the reference wrappers'
         # zero-filled "+=" buffers; het_amd/backend/reference_protocol.py) -- the drop-in path bench.py times as
         # variants.reference_op_sequence.  Non-compact flags, full graph.
@@ -166,22 +177,23 @@ class HET_RGATLayer(nn.Module):
         bias = nn.functional.pad(self.h_bias.view(H, D), pad).view(H * Dp) if self.bias else None
         h = FL.rgat_layer_fused(g, x, W, al, ar, loop, bias, self.leaky_relu_slope, self.compact_as_of_node_flag,
                                 self.compact_direct_indexing_flag, num_dst, self.multiply_among_weights_first_flag, halo=halo,
-                                attn_out=attn_out)
+                                attn_out=attn_out, bf16_training=self.bf16_training)
         h = h.view(h.shape[0], H, Dp)[:, :, :D].reshape(h.shape[0], self.out_feat)
         if self.activation:
             h = self.activation(h)
         return self.dropout(h)
 
-    def _bf16_native(self, g, inputs):
-        """(input width K', head width D') the bf16 evaluation path runs with -- the padding of _padded_head, zero columns -- or None:
-        the call is served by the fp32 layer on an upcast copy."""
+    def _bf16_native(self, g, inputs, num_dst=None):
+        """(input width K', head width D') the bf16 evaluation path -- or, with bf16_training, the bf16 training step -- runs with: the
+        padding of _padded_head, zero columns.  None: the call is served by the fp32 layer on an upcast copy."""
         if self.reference_op_sequence or self.op_by_op or not (self.gat_edge_parallel_flag and inputs.is_cuda and inputs.dim() == 2):
             return None
         H, D, K = self.num_heads, self.out_feat // self.num_heads, self.in_feat
         Kp, Dp = self._padded_head(g, inputs) or (K, D)
         shape = th.empty((self.num_rels, H, Kp, Dp), device="meta")
-        ok = FL.rgat_layer_bf16_ok(g, inputs, shape, self.leaky_relu_slope, self.compact_as_of_node_flag,
-                                   self.multiply_among_weights_first_flag, (inputs,) + tuple(self.parameters()))
+        args = (g, inputs, shape, self.leaky_relu_slope, self.compact_as_of_node_flag, self.multiply_among_weights_first_flag,
+                (inputs,) + tuple(self.parameters()))
+        ok = FL.rgat_layer_bf16_ok(*args) or (self.bf16_training and FL.rgat_layer_bf16_training_ok(*args, num_dst))
         return (Kp, Dp) if ok else None
 
     def forward(self, g, inputs: th.Tensor, num_dst=None, get_attention=False):
@@ -199,7 +211,7 @@ class HET_RGATLayer(nn.Module):
     def _forward(self, g, inputs, num_dst=None, attn_out=None):
         """forward; ``attn_out`` (a list): where the call takes an evaluation path, the attention weights are appended to it."""
         if inputs.dtype == th.bfloat16:
-            KDp = self._bf16_native(g, inputs)
+            KDp = self._bf16_native(g, inputs, num_dst)
             if KDp is None:  # correct, not faster: the fp32 layer on an upcast copy (autograd casts the gradient of the input)
                 return self._forward(g, inputs.float(), num_dst, attn_out).to(th.bfloat16)
             if KDp != (self.in_feat, self.out_feat // self.num_heads):
@@ -207,7 +219,8 @@ class HET_RGATLayer(nn.Module):
             h = FL.rgat_layer_fused(g, inputs, self.conv_weights, self.attn_l, self.attn_r,
                                     self.loop_weight if self.self_loop else None, self.h_bias if self.bias else None,
                                     self.leaky_relu_slope, self.compact_as_of_node_flag, self.compact_direct_indexing_flag,
-                                    num_dst, self.multiply_among_weights_first_flag, attn_out=attn_out)
+                                    num_dst, self.multiply_among_weights_first_flag, attn_out=attn_out,
+                                    bf16_training=self.bf16_training)
             if self.activation:
                 h = self.activation(h)
             return self.dropout(h)

@@ -32,11 +32,11 @@ class HET_RGATModel(nn.Module):
 
     def __init__(self, num_etypes, h_dim, out_dim, num_heads, num_hidden_layers=1, dropout=0.5, use_self_loop=True,
                  last_layer_act=False, compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
-                 multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True):
+                 multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True, bf16_training=False):
         super().__init__()
         flags = dict(compact_as_of_node_flag=compact_as_of_node_flag, compact_direct_indexing_flag=compact_direct_indexing_flag,
                      multiply_among_weights_first_flag=multiply_among_weights_first_flag,
-                     gat_edge_parallel_flag=gat_edge_parallel_flag, self_loop=use_self_loop)
+                     gat_edge_parallel_flag=gat_edge_parallel_flag, self_loop=use_self_loop, bf16_training=bf16_training)
         self.layers = nn.ModuleList(
             [HET_RGATLayer(h_dim, h_dim, num_etypes, num_heads, activation=F.relu, dropout=dropout, **flags)
              for _ in range(num_hidden_layers)])
@@ -124,6 +124,9 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
     p.add_argument("--inference", action="store_true",
                    help="time evaluation instead of training: every epoch is one forward under torch.no_grad() with the model in "
                         "eval(); backward is logged as 0")
+    p.add_argument("--bf16_training", action="store_true",
+                   help="RGAT only: bf16 input features and layers built with bf16_training=True (het_amd/layers.py: bf16 rows, fp32 "
+                        "parameters and sums); the loss is taken on the logits cast to fp32")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -154,6 +157,7 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
     prep_ms = []
 
     inference = getattr(args, "inference", False)
+    bf16 = getattr(args, "bf16_training", False)  # (the features enter the model as bf16 rows, the logits leave it as fp32)
 
     def one_eval(timed):
         # the evaluation pass of the reference's scripts (model.eval() + torch.no_grad()): same inputs, same event pair around
@@ -168,6 +172,8 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
                 th.cuda.synchronize()
                 prep_ms.append((time.perf_counter() - t0) * 1e3)
                 node_embed, cur_labels = node_embed[blocks[0].nodes], labels[seeds]
+            if bf16:
+                node_embed = node_embed.to(th.bfloat16)
             th.cuda.synchronize()
             ev = [th.cuda.Event(enable_timing=True) for _ in range(2)]
             ev[0].record()
@@ -177,6 +183,7 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
                 else:
                     logits = run_blocks(model.layers, blocks, node_embed, extra[0] if extra else None)
                 ev[1].record()
+                logits = logits.float()
                 loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
             th.cuda.synchronize()
         return (ev[0].elapsed_time(ev[1]), 0.0, float(loss)) if timed else None
@@ -194,6 +201,8 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
             th.cuda.synchronize()
             prep_ms.append((time.perf_counter() - t0) * 1e3)
             node_embed, cur_labels = node_embed[blocks[0].nodes], labels[seeds]
+        if bf16:
+            node_embed = node_embed.to(th.bfloat16)
         th.cuda.synchronize()
         ev = [th.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
@@ -203,6 +212,7 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
             else:
                 logits = run_blocks(model.layers, blocks, node_embed, extra[0] if extra else None)
             ev[1].record()
+            logits = logits.float()
             # = F.nll_loss(logits.log_softmax(dim=-1), labels) (RGNNUtils.py:301-302), written as gather + mean: torch's 2-d
             # nll_loss kernels reduce 1.9 M rows in ONE workgroup on ROCm (4.6 ms forward, 3.0 ms backward on ogbn-mag --
             # more than the layer's own backward inside the protocol's "backward" figure)
@@ -233,6 +243,8 @@ def main(argv=None):
     add_generic_RGNN_args(p, "het_amd_train.json")
     args = p.parse_args(argv)
     dev = th.device("cuda")
+    if args.bf16_training and args.model != "rgat":
+        raise SystemExit("--bf16_training is an option of the RGAT layer (RGCN and HGT train in bf16 on a bf16 input as they are)")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -251,7 +263,7 @@ def main(argv=None):
                               compact_as_of_node_flag=args.compact_as_of_node_flag,
                               compact_direct_indexing_flag=args.compact_direct_indexing_flag,
                               multiply_among_weights_first_flag=args.multiply_among_weights_first_flag,
-                              gat_edge_parallel_flag=args.gat_edge_parallel_flag)
+                              gat_edge_parallel_flag=args.gat_edge_parallel_flag, bf16_training=args.bf16_training)
     elif args.model == "rgcn":
         model = HET_RGCNModel(R, args.n_infeat, args.num_classes, num_layers=args.num_layers, num_bases=args.n_bases,
                               dropout=args.dropout, compact_as_of_node_flag=args.compact_as_of_node_flag,
@@ -294,6 +306,10 @@ def main(argv=None):
         res["mode"] = "inference"
     else:
         del res["args"]["inference"]  # (a training run's log line is what it was before the flag existed)
+    if args.bf16_training:
+        res["activations"] = "bf16"
+    else:
+        del res["args"]["bf16_training"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

@@ -692,6 +692,33 @@ int het_rgat_aggregate_compact_forward_bf16(const het_grouping* by_dst, const he
 int het_rgat_el_rows_bf16(const int64_t* rel_ptrs, int64_t num_rels, const het_bf16* feat_c, const float* attn_l, float* el_c,
                           int64_t num_rows, int64_t H, int64_t D, het_stream stream);
 
+/* The TRAINING pair with bf16 activation rows (the RGAT layer built with bf16_training=True): het_rgat_aggregate_compact_runs and
+ * het_rgat_backward_compact_runs with feat_c [S_row,H,D], h_inout [h_rows, H*D] and gradout [rows,H,D] as het_bf16; el_c, er_c, sum
+ * (the log-sum-exp), ret, the run sums q_rows / q_sum / q_ref, the hub records of the workspace, rec4 and every gradient are fp32.
+ * Arguments, shapes, groupings and workspaces (het_rgat_aggregate_compact_runs_workspace, het_rgat_backward_compact_runs_workspace)
+ * are the fp32 entries'.  Rows are widened on load (exact); a lane holds the same 4 elements of a row as in the fp32 kernels (8 bytes
+ * instead of 16), so every sum is formed in the fp32 order.
+ *   forward: ret[v] is the fp32 acc * rcp(sum), not rounded; h_inout[v] = round(widen(h_inout[v]) + ret[v]) (to nearest even) for
+ *     every destination v < h_rows with in-edges -- bit for bit what het_rgat_aggregate_compact_forward_bf16 stores.  el_c is required
+ *     (the backward reads it) and must hold the dots of the ROUNDED rows (het_rgat_el_rows_bf16).
+ *   backward: the run-sum form on the cooperative shapes only; grad_bias, when asked for, is the column sums of the bf16 gradout rows
+ *     [0, bias_rows).  The gradient passes straight through the rounding of feat_c: grad_feat_c is that of the widened rows.
+ *   The bf16 rows must be 8-byte aligned, every fp32 table and the workspace 16-byte aligned, h_rows <= num_nodes: else
+ *     HET_ERR_INVALID_ARG; other shapes HET_ERR_UNSUPPORTED; nothing is enqueued before these checks pass. */
+int het_rgat_aggregate_compact_runs_bf16(const het_grouping* by_dst, const het_grouping* by_dst_rel, int64_t num_rels,
+                                         const het_bf16* feat_c, const float* el_c, const float* er_c, float* sum, float* ret,
+                                         int64_t num_nodes, int64_t H, int64_t D, double slope, het_bf16* h_inout, int64_t h_rows,
+                                         float* q_rows, float* q_sum, float* q_ref, int64_t num_dst_rows, const float* attn_l,
+                                         const int64_t* feat_rel_ptrs_host, void* workspace, int64_t workspace_bytes,
+                                         het_stream stream);
+int het_rgat_backward_compact_runs_bf16(const het_grouping* by_srow, const float* q_rows, const float* q_sum, const float* q_ref,
+                                        const int64_t* drow_nodes, const het_bf16* feat_c, const float* el_c, const float* er_c,
+                                        const float* sum, const float* ret, const het_bf16* gradout, float* grad_feat_c,
+                                        float* grad_el_c, float* grad_er_c, const float* fold_attn_l, const int64_t* row_rel_ptrs,
+                                        int64_t num_rels, float* grad_bias, int64_t bias_rows, int64_t num_nodes,
+                                        int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D, double slope,
+                                        float* grad_attn_l, void* workspace, int64_t workspace_bytes, het_stream stream);
+
 /* The attention weights the aggregations above form and discard, as an output (DGL's get_attention, PyG's
  * return_attention_weights): a pass of its own over the ids and the two small tables -- it never reads a feat_c row, and it runs
  * after either evaluation entry (el_c / er_c are fp32 in the bf16 layer too; everything here is fp32).
@@ -764,6 +791,12 @@ int het_rows_matmul_heads_bf16(const int64_t* rel_ptrs, int64_t num_rels, const 
 int het_rows_dot1h_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
                         int64_t num_rows, const float* weights, const het_bf16* x, float* out, int64_t H, int64_t K,
                         het_stream stream);
+/* ... and its weight gradient: grad_w[r, h, :] (+)= SUM_i gradout[scatter_idx[i], h] * x[gather_idx[i], :]     x [*,K] het_bf16 (8-byte
+ * aligned), gradout [*,H] and grad_w [R,H,K] fp32 (16-byte aligned).  accumulate 0: grad_w is cleared first; workgroups add their
+ * partial rows with float atomics.  Same shapes. */
+int het_rows_dot1h_backward_dw_bf16(const int64_t* rel_ptrs, int64_t num_rels, const int64_t* gather_idx, const int64_t* scatter_idx,
+                                    int64_t num_rows, const het_bf16* x, const float* gradout, float* grad_w, int64_t H, int64_t K,
+                                    int accumulate, het_stream stream);
 
 /* ------------------------------------------------------------------------
  * Node-major input gradient of the one-node RGAT layer (layer-level fusion; no reference op of its own).  It replaces,
@@ -788,6 +821,12 @@ int het_rgat_node_backward_dx(int64_t n_begin, int64_t n_end, int64_t n_loop, in
                               const float* grad_h, const float* loop_wt, const float* g_rows, const float* weights_t,
                               const int32_t* row_map, const float* g_er, const float* wa_t, const int32_t* dst_map,
                               float* grad_x, int64_t H, int64_t K, int64_t D, const int32_t* node_order, het_stream stream);
+/* ... with bf16 activation rows: grad_h [n_loop, H*D] and grad_x [num_nodes, K] het_bf16 (8-byte aligned; grad_h widened on load,
+ * grad_x rounded once, to nearest even, after every term of the node is summed); g_rows, g_er and the weights fp32 (16-byte aligned). */
+int het_rgat_node_backward_dx_bf16(int64_t n_begin, int64_t n_end, int64_t n_loop, int64_t num_nodes, int64_t num_rels,
+                                   const het_bf16* grad_h, const float* loop_wt, const float* g_rows, const float* weights_t,
+                                   const int32_t* row_map, const float* g_er, const float* wa_t, const int32_t* dst_map,
+                                   het_bf16* grad_x, int64_t H, int64_t K, int64_t D, const int32_t* node_order, het_stream stream);
 
 /* Layer-level extension (no reference op of its own): the node-major sum of row x weight products
  *     out[n, :] = SUM_s rows_s[map_s[n], :] . weights_t[s]          n = node_order[p] (or p) for p in [n_begin, n_end)
