@@ -356,8 +356,11 @@ def test_rgat_compact_run_sums(K, H, D, n, e, fold, bias):
     rgat_run_sums_case(K, random_graph(seed=31, n=n, r=4, e=e), H, D, fold, bias)
 
 
-def rgat_run_sums_case(K, g, H, D, fold, bias):
-    import het_amd.kernels as k
+def rgat_run_sums_reference(g, H, D, fold, rows=lambda t: t):
+    """The CPU half of rgat_run_sums_case, shared with its bf16 twin (tests/test_gpu_bf16_ladders.py): the row maps of the run-sum
+    form, the seeded inputs -- the activation rows feat / go passed through ``rows`` (the twin rounds them to bf16 once; they stay
+    fp32 tensors here) --, the oracle's CompactAsOfNodeKind-4 pair on them in fp64 and the run sums.  Returns a namespace."""
+    from types import SimpleNamespace
     s = g.get_separate_coo_original()
     ss = g.get_separate_unique_node_indices_single_sided()
     N, E, R, slope = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels(), 0.2
@@ -371,8 +374,8 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     assert bool((ss["node_indices_col"][drow_p] == s["col_indices"]).all())
     S_row, S_col = ss["node_indices_row"].numel(), ss["node_indices_col"].numel()
     gen = torch.Generator().manual_seed(13)
-    feat, el, er = torch.randn(S_row, H, D, generator=gen), torch.randn(S_row, H, generator=gen), torch.randn(S_col, H, generator=gen)
-    go, attn = torch.randn(N, H, D, generator=gen), torch.randn(R, H, D, generator=gen)
+    feat, el, er = rows(torch.randn(S_row, H, D, generator=gen)), torch.randn(S_row, H, generator=gen), torch.randn(S_col, H, generator=gen)
+    go, attn = rows(torch.randn(N, H, D, generator=gen)), torch.randn(R, H, D, generator=gen)
     # the oracle's maps are indexed by edge id
     m_row, m_col = torch.empty(E, dtype=torch.int64), torch.empty(E, dtype=torch.int64)
     m_row[s["eids"]], m_col[s["eids"]] = srow_p, drow_p
@@ -384,25 +387,46 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     gf_r, gl_r, gr_r = torch.zeros_like(to64(feat)), torch.zeros_like(to64(el)), torch.zeros_like(to64(er))
     O.backward_relational_fused_gat_separate_coo(*idx, 4, df, to64(feat), to64(el), to64(er), sm_r, ex_r, ret_r,
                                                  to64(go), gf_r, gl_r, gr_r, slope)
+    rel_of_row = torch.repeat_interleave(torch.arange(R), ss["rel_ptrs_row"][1:] - ss["rel_ptrs_row"][:-1])
     if fold:
-        rel_of_row = torch.repeat_interleave(torch.arange(R), ss["rel_ptrs_row"][1:] - ss["rel_ptrs_row"][:-1])
         gf_r = gf_r + gl_r.unsqueeze(-1) * attn.double()[rel_of_row]
-    grp = k.rgat_compact_groupings(s["col_indices"].to(DEV), srow_p.to(DEV), drow_p.to(DEV), N, S_row, S_col, rel_ptrs=s["rel_ptrs"].to(DEV),
-                                   drow_nodes=ss["node_indices_col"].to(DEV), drow_rel_ptrs=ss["rel_ptrs_col"].to(DEV))
-    assert grp[2] is None and grp[3] is not None
-    f, l, r_ = feat.to(DEV), el.to(DEV), er.to(DEV)
     has_in = torch.zeros(N, dtype=torch.bool)
     has_in[s["col_indices"]] = True
-    sm, ret = torch.full((N, H), 7.0, device=DEV), torch.full((N, H, D), 7.0, device=DEV)
-    runs = k.rgat_aggregate_compact(grp, f, l, r_, sm, ret, slope, num_rels=R)
-    assert_close(sm[has_in.to(DEV)], torch.log(sm_r[has_in]), what="log-sum-exp")
-    assert float(sm[(~has_in).to(DEV)].abs().max() if (~has_in).any() else 0.0) == 0.0
-    assert_close(ret, ret_r, what="ret")
     # the run sums themselves: q_rows * exp(q_ref) = SUM_e exp(s_e) dl_e feat[srow_e] over the run
     z = to64(el)[srow_p] + to64(er)[drow_p]
     wd = torch.exp(torch.nn.functional.leaky_relu(z, slope)) * torch.where(z > 0, 1.0, slope)
     q_ref = torch.zeros(S_col, H, dtype=torch.float64).index_add_(0, drow_p, wd)
     Q_ref = torch.zeros(S_col, H, D, dtype=torch.float64).index_add_(0, drow_p, wd.unsqueeze(-1) * to64(feat)[srow_p])
+    # grad_attn_l[r,h,:] = SUM over the rows u of relation r of grad_el[u,h] * feat[u,h,:]
+    ga_r = torch.zeros(R, H, D, dtype=torch.float64).index_add_(0, rel_of_row, gl_r.unsqueeze(-1) * to64(feat))
+    return SimpleNamespace(s=s, ss=ss, N=N, E=E, R=R, slope=slope, srow_p=srow_p, drow_p=drow_p, S_row=S_row, S_col=S_col, gen=gen,
+                           feat=feat, el=el, er=er, go=go, attn=attn, sm_r=sm_r, ret_r=ret_r, gf_r=gf_r, gl_r=gl_r, gr_r=gr_r,
+                           rel_of_row=rel_of_row, has_in=has_in, q_ref=q_ref, Q_ref=Q_ref, ga_r=ga_r)
+
+
+def rgat_run_sums_groupings(c):
+    """The groupings of the run-sum form for the lists of rgat_run_sums_reference (checked against the edges once per list)."""
+    import het_amd.kernels as k
+    s, ss = c.s, c.ss
+    return k.rgat_compact_groupings(s["col_indices"].to(DEV), c.srow_p.to(DEV), c.drow_p.to(DEV), c.N, c.S_row, c.S_col,
+                                    rel_ptrs=s["rel_ptrs"].to(DEV), drow_nodes=ss["node_indices_col"].to(DEV),
+                                    drow_rel_ptrs=ss["rel_ptrs_col"].to(DEV))
+
+
+def rgat_run_sums_case(K, g, H, D, fold, bias):
+    import het_amd.kernels as k
+    c = rgat_run_sums_reference(g, H, D, fold)
+    s, ss, N, R, slope, srow_p, drow_p, S_row, S_col, gen = c.s, c.ss, c.N, c.R, c.slope, c.srow_p, c.drow_p, c.S_row, c.S_col, c.gen
+    feat, el, er, go, attn, rel_of_row, has_in = c.feat, c.el, c.er, c.go, c.attn, c.rel_of_row, c.has_in
+    sm_r, ret_r, gf_r, gl_r, gr_r, q_ref, Q_ref = c.sm_r, c.ret_r, c.gf_r, c.gl_r, c.gr_r, c.q_ref, c.Q_ref
+    grp = rgat_run_sums_groupings(c)
+    assert grp[2] is None and grp[3] is not None
+    f, l, r_ = feat.to(DEV), el.to(DEV), er.to(DEV)
+    sm, ret = torch.full((N, H), 7.0, device=DEV), torch.full((N, H, D), 7.0, device=DEV)
+    runs = k.rgat_aggregate_compact(grp, f, l, r_, sm, ret, slope, num_rels=R)
+    assert_close(sm[has_in.to(DEV)], torch.log(sm_r[has_in]), what="log-sum-exp")
+    assert float(sm[(~has_in).to(DEV)].abs().max() if (~has_in).any() else 0.0) == 0.0
+    assert_close(ret, ret_r, what="ret")
     sc = torch.exp(runs[2].double().cpu())
     assert_close(runs[1].double().cpu() * sc, q_ref, what="q_sum")
     assert_close(runs[0].double().cpu() * sc.unsqueeze(-1), Q_ref, what="q_rows")
@@ -440,8 +464,7 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     if bias:
         assert_close(gb, to64(go).view(N, -1)[:nb].sum(0), what="grad_bias")
     if fold:  # grad_attn_l[r,h,:] = SUM over the rows u of relation r of grad_el[u,h] * feat[u,h,:]
-        ga_r = torch.zeros(R, H, D, dtype=torch.float64).index_add_(0, rel_of_row, gl_r.unsqueeze(-1) * to64(feat))
-        assert_close(ga, ga_r, what="grad_attn_l")
+        assert_close(ga, c.ga_r, what="grad_attn_l")
     # the cache evicts and rebuilds the grouping by destination while the (destination, relation) one stays: the hub lists that
     # were built against the old object are rebuilt, same results
     import het_amd.plan as plan
