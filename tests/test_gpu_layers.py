@@ -12,17 +12,19 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0, attn_scale=1.0, oracle_dev="cpu", **layer_kw):
+def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0, attn_scale=1.0, oracle_dev="cpu", self_loop=True, bias=True,
+              **layer_kw):
     """oracle_dev: where the fp64 oracle layer is evaluated (it is plain torch: "cuda" for graphs of 1e5+ edges, where the CPU
-    takes most of a minute per case)."""
+    takes most of a minute per case).  self_loop / bias off: the layer and the oracle without that term and its parameter."""
     from het_amd.layers import HET_RGATLayer
     torch.manual_seed(seed)
     R, N = g.get_num_rels(), g.get_num_nodes()
-    layer = HET_RGATLayer(K, X, R, H, bias=True, self_loop=True, compact_as_of_node_flag=compact,
+    layer = HET_RGATLayer(K, X, R, H, bias=bias, self_loop=self_loop, compact_as_of_node_flag=compact,
                           compact_direct_indexing_flag=direct, multiply_among_weights_first_flag=mulfirst,
                           gat_edge_parallel_flag=edge_parallel, dropout=0.0, **layer_kw)
     with torch.no_grad():
-        layer.h_bias.uniform_(-0.1, 0.1)
+        if bias:
+            layer.h_bias.uniform_(-0.1, 0.1)
         layer.attn_l.mul_(attn_scale)
         layer.attn_r.mul_(attn_scale)
     x = torch.randn(N, K) * 0.5
@@ -42,8 +44,9 @@ def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0,
     p = {n: t.detach().double().to(oracle_dev).requires_grad_(True) for n, t in layer.named_parameters()}
     x64 = x.double().to(oracle_dev).requires_grad_(True)
     ref = OL.rgat_layer(x64, p["conv_weights"], p["attn_l"], p["attn_r"], s["rel_ptrs"].to(oracle_dev), s["row_indices"].to(oracle_dev),
-                        s["col_indices"].to(oracle_dev), N, 0.2, p["loop_weight"], p["h_bias"])
-    names = ["conv_weights", "attn_l", "attn_r", "loop_weight", "h_bias"]
+                        s["col_indices"].to(oracle_dev), N, 0.2, p.get("loop_weight"), p.get("h_bias"))
+    names = ["conv_weights", "attn_l", "attn_r"] + ["loop_weight"] * self_loop + ["h_bias"] * bias
+    assert set(names) == set(p)
     grads_ref = [t.cpu() for t in torch.autograd.grad(ref, [x64] + [p[n] for n in names], go.double().to(oracle_dev))]
     ref = ref.detach().cpu()
     # device
@@ -214,26 +217,28 @@ def test_rgcn_layer_many_seeds(compact):
         _run_rgcn(g, compact, compact and seed % 3 != 0, K, D, R)
 
 
-def _run_rgcn(g, compact, direct, K, D, R, oracle_dev="cpu"):
+def _run_rgcn(g, compact, direct, K, D, R, oracle_dev="cpu", num_dst=None):
+    """num_dst: the layer on a block -- the first num_dst rows of the output (the oracle's first num_dst rows: bias and sums are per row)."""
     from het_amd.layers import HET_EglRelGraphConv_EdgeParallel
     torch.manual_seed(1)
     N, E = g.get_num_nodes(), g.get_num_edges()
+    nd = N if num_dst is None else num_dst
     layer = HET_EglRelGraphConv_EdgeParallel(K, D, R, bias=True, compact_as_of_node_flag=compact,
                                              compact_direct_indexing_flag=direct)
-    x, norm, go = torch.randn(N, K), torch.rand(E, 1), torch.randn(N, D)
+    x, norm, go = torch.randn(N, K), torch.rand(E, 1), torch.randn(nd, D)
     s = g.get_separate_coo_original()
     w64 = layer.weight.detach().double().to(oracle_dev).requires_grad_(True)
     b64 = layer.h_bias.detach().double().to(oracle_dev).requires_grad_(True)
     x64 = x.double().to(oracle_dev).requires_grad_(True)
     # (the layer reads the norm of an edge by its eid; the oracle takes it in separate-COO position order)
     ref = OL.rgcn_layer(x64, w64, norm.double()[s["eids"]].to(oracle_dev), s["rel_ptrs"].to(oracle_dev), s["row_indices"].to(oracle_dev),
-                        s["col_indices"].to(oracle_dev), N, b64)
+                        s["col_indices"].to(oracle_dev), N, b64)[:nd]
     gx_r, gw_r, gb_r = (t.cpu() for t in torch.autograd.grad(ref, [x64, w64, b64], go.double().to(oracle_dev)))
     ref = ref.detach().cpu()
     g.to_(DEV)
     layer = layer.to(DEV)
     xd = x.to(DEV).requires_grad_(True)
-    out = layer(g, xd, norm.to(DEV))
+    out = layer(g, xd, norm.to(DEV)) if num_dst is None else layer(g, xd, norm.to(DEV), num_dst=num_dst)
     out.backward(go.to(DEV))
     g.cpu_()
     assert_close(out, ref, what="out")
