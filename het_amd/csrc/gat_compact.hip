@@ -1687,7 +1687,7 @@ static int rgat_hub_min() {
     //  round 5: the pack-form launch got faster (tags, 32-bit offsets) and the hub finish is a workgroup per hub;
     //  profiles/r05/ab_round5_misc.txt: 64 / 96 / 128 / 192 / 256 -> 4.03 / 3.86 / 3.78 / 3.74 / 3.72 ms per step)
     const int t = e ? atoi(e) : 256;
-    return t < HET_PACK_T ? HET_PACK_T : t;
+    return t < HET_PACK_T ? HET_PACK_T : (t > HET_ITEM_MAX ? HET_ITEM_MAX : t);  // (a work item never holds more: a hub is split first)
   }();
   return v;
 }
@@ -2100,8 +2100,8 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
     if (int rc = grouping_packed_ids(by_srow, true, s)) return rc;
     if (pv.num_long_items > 0)
       if (int rc = grouping_packed_ids(by_srow, false, s)) return rc;
-    // tags of the packed id records: segment ends + the relation of the feat row (read from the caller's device array; a grouping
-    // keeps the tags of the array it saw first -- the relation boundaries of a row list belong to the list)
+    // tags of the packed id records: segment ends + the relation of the feat row (read from the caller's device array; another
+    // array re-tags -- grouping_tag_kp01_dev)
     if (fold_attn_l) {
       if (int rc = grouping_tag_kp01_dev(by_srow, 0, row_rel_ptrs, (int)num_rels, s)) return rc;
     } else {

@@ -1,6 +1,8 @@
 // Device-side construction of het_grouping (radix sort + run-length encode via hipCUB).
 #include <hipcub/hipcub.hpp>
 
+#include <string.h>
+
 #include <atomic>
 #include <mutex>
 
@@ -217,69 +219,100 @@ struct Scratch {  // frees device temporaries on every exit path
 
 }  // namespace
 
-static std::mutex g_used_mu;
+// ---- ownership and the build-once protocol (grouping.hip.h) -------------------------------------------------------------------
+// One lock for the streams, the blocks and the lazily built lists of every grouping; recursive, because a list's build asks for
+// the lists it needs.
+static std::recursive_mutex g_mu;
 
-extern "C" void het_grouping_note_stream(const het_grouping* g, het_stream stream) {
-  if (!g) return;
-  hipStream_t s = (hipStream_t)stream;
+namespace {
+void note_stream(const het_grouping* g, hipStream_t s) {  // (lock held)
   if (s == g->home) return;
-  std::lock_guard<std::mutex> lk(g_used_mu);
   for (hipStream_t u : g->used)
     if (u == s) return;
   g->used.push_back(s);
 }
 
+// `waiter` waits for what `home` -- and, with noted_too, every noted stream -- has queued so far: an event recorded now on each of
+// them, no host synchronisation.  (Lock held, the grouping's device current.)  The library's own side stream is joined into the
+// caller's stream before an entry point returns, so the caller's streams cover it.
+void wait_for_users(const het_grouping* g, hipStream_t waiter, bool noted_too) {
+  std::vector<hipStream_t> on{g->home};
+  if (noted_too) on.insert(on.end(), g->used.begin(), g->used.end());
+  for (hipStream_t u : on) {
+    if (u == waiter) continue;
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); break; }
+    if (hipEventRecord(ev, u) != hipSuccess || hipStreamWaitEvent(waiter, ev, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipDeviceSynchronize();  // (a stream that no longer exists, a capture in progress ...: the blunt form)
+    }
+    (void)hipEventDestroy(ev);  // (released by the runtime once it has completed)
+  }
+}
+}  // namespace
+
+int grouping_alloc(const het_grouping* g, void** out, size_t bytes) {
+  if (int rc = het_dev_alloc(out, bytes, g->home)) return rc;
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  g->blocks.push_back({*out, bytes});
+  return HET_OK;
+}
+
+GroupingBuild::GroupingBuild(const het_grouping* g_, hipStream_t s_) : g(g_), s(s_) { g_mu.lock(); }
+
+void GroupingBuild::begin(bool wait_for_users_too) {
+  device.enter(g->device);
+  // the blocks come from home's pool: what `home` queued before may still use them in their previous life
+  wait_for_users(g, s, wait_for_users_too);
+  note_stream(g, s);
+  mark = g->blocks.size();
+  open = true;
+}
+
+int GroupingBuild::finish() {
+  HET_HIP(hipStreamSynchronize(s));
+  open = false;
+  return HET_OK;
+}
+
+GroupingBuild::~GroupingBuild() {
+  if (open) {  // failed between begin() and finish(): the slot stays un-built, what the build allocated goes back
+    (void)hipStreamSynchronize(s);
+    for (size_t i = mark; i < g->blocks.size(); ++i) het_dev_free(g->blocks[i].ptr);
+    g->blocks.resize(mark);
+  }
+  g_mu.unlock();
+}
+
+extern "C" void het_grouping_note_stream(const het_grouping* g, het_stream stream) {
+  if (!g) return;
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  note_stream(g, (hipStream_t)stream);
+}
+
 extern "C" void het_grouping_destroy(het_grouping* g) {
   if (!g) return;
-  // Order the release after the last use on every stream that read the arrays (see het_grouping::home): `home` waits for an event
-  // recorded now on each of them -- no host synchronisation.  With hipMalloc / hipFree (the default allocator) hipFree itself
-  // waits for the device; the waits below are then redundant and cheap.  The library's own side stream is joined into the
-  // caller's stream before an entry point returns, so the caller's streams cover it.
   {
-    std::vector<hipStream_t> used;
-    {
-      std::lock_guard<std::mutex> lk(g_used_mu);
-      used.swap(g->used);
-    }
-    for (hipStream_t u : used) {
-      hipEvent_t ev = nullptr;
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); break; }
-      if (hipEventRecord(ev, u) != hipSuccess || hipStreamWaitEvent(g->home, ev, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipDeviceSynchronize();  // (a stream that no longer exists, a capture in progress ...: the blunt form)
-      }
-      (void)hipEventDestroy(ev);  // (released by the runtime once it has completed)
-    }
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    OnDevice device;
+    device.enter(g->device);
+    // Order the release after the last use on every stream that read the arrays.  With hipMalloc / hipFree (the default allocator)
+    // hipFree itself waits for the device; the waits are then redundant and cheap.
+    wait_for_users(g, g->home, true);
+    for (const het_grouping::Block& b : g->blocks) het_dev_free(b.ptr);
   }
-  void* ptrs[] = {g->seg_key64, g->seg_rel_ptr64, g->perm, g->seg_ptr, g->seg_key, g->seg_rel_ptr, g->item_seg, g->item_begin, g->item_end,
-                  g->split_seg, g->p0, g->p1, g->seg_of_rank, g->pack_ptr, g->key_of_rank, g->long_items, g->p01, g->kp01, g->hub_items, g->hub_segs, g->hub_order, g->hub_rec, g->val_order, g->alt_pack_ptr, g->alt_long_items};
-  for (void* p : ptrs)
-    if (p) (void)het_free_e(p);
-  for (void* p : g->retired) (void)het_free_e(p);
   delete g;
 }
 
 extern "C" int64_t het_grouping_num_segments(const het_grouping* g) { return g ? g->S : -1; }
 
-// Device bytes the grouping holds right now: what a memory report has to add when they came from hipMalloc (the default);
-// with a caller's allocator (het_set_allocator) they are inside that allocator's own statistics.
+// Device bytes the grouping holds right now (lists that a rebuild replaced included): what a memory report has to add when they
+// came from hipMalloc (the default); with a caller's allocator (het_set_allocator) they are inside that allocator's own statistics.
 extern "C" int64_t het_grouping_bytes(const het_grouping* g) {
   if (!g) return 0;
-  const int64_t E = g->E, S = g->S, I = g->num_items, R = g->R;
-  int64_t b = 4 * (E > 0 ? E : 1);                                   // perm
-  b += 4 * (S + 1) + 4 * (S > 0 ? S : 1) + 8 * (S > 0 ? S : 1);      // seg_ptr, seg_key, seg_key64
-  if (R > 0) b += 4 * (R + 1) + 8 * (R + 1);                         // seg_rel_ptr, seg_rel_ptr64
-  b += 3 * 4 * (I > 0 ? I : 1) + 4 * (E / HET_ITEM_MAX + 1);         // item_seg / begin / end, split_seg
-  if (g->p0) b += 4 * E;
-  if (g->p1) b += 4 * E;
-  if (g->seg_of_rank) b += 4 * E;
-  if (g->pack_ptr) b += 4 * (g->num_packs + 1) + 4 * (g->num_long_items + 1);
-  if (g->alt_pack_ptr) b += 4 * (g->alt_num_packs + 1) + 4 * (g->alt_num_long_items + 1);
-  if (g->key_of_rank) b += 4 * (E + 1);
-  if (g->p01) b += 8 * (E > 0 ? E : 1);
-  if (g->kp01) b += 16 * (E + 1);
-  if (g->val_order) b += 4 * g->val_order_n;
-  if (g->hub_items) b += 4 * (g->num_hub_items + 1) + 4 * (g->num_hub_segs + 1) + (g->hub_order ? 4 * g->num_hub_items : 0) + (g->hub_rec ? 16 * g->num_hub_segs : 0);
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  int64_t b = 0;
+  for (const het_grouping::Block& k : g->blocks) b += (int64_t)k.bytes;
   return b;
 }
 
@@ -317,10 +350,14 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
   g->E = E; g->R = R; g->key_bound = key_bound;
   g->home = s;
   struct Guard { het_grouping* g; ~Guard() { if (g) het_grouping_destroy(g); } } guard{g};
-#define GALLOC(field, count) HET_HIP(het_malloc_e((void**)&g->field, sizeof(int32_t) * ((count) > 0 ? (count) : 1), s))
-  GALLOC(perm, E);
-  if (R > 0) GALLOC(seg_rel_ptr, R + 1);
-  if (R > 0) HET_HIP(het_malloc_e((void**)&g->seg_rel_ptr64, sizeof(idx_t) * (R + 1), s));
+  HET_HIP(hipGetDevice(&g->device));
+#define GALLOC(field, count, type)                                                                              \
+  do {                                                                                                          \
+    if (int rc__ = grouping_alloc(g, (void**)&g->field, sizeof(type) * ((count) > 0 ? (count) : 1))) return rc__; \
+  } while (0)
+  GALLOC(perm, E, int32_t);
+  if (R > 0) GALLOC(seg_rel_ptr, R + 1, int32_t);
+  if (R > 0) GALLOC(seg_rel_ptr64, R + 1, idx_t);
 
   Scratch tmp(s);
   uint64_t *keys_in = nullptr, *keys_out = nullptr, *uniq = nullptr;
@@ -359,16 +396,16 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
   }
   const int64_t S = h_runs;
   g->S = S;
-  GALLOC(seg_ptr, S + 1);
-  GALLOC(seg_key, S);
-  HET_HIP(het_malloc_e((void**)&g->seg_key64, sizeof(idx_t) * (S > 0 ? S : 1), s));
+  GALLOC(seg_ptr, S + 1, int32_t);
+  GALLOC(seg_key, S, int32_t);
+  GALLOC(seg_key64, S, idx_t);
   HET_HIP(tmp.alloc((void**)&nitems, sizeof(int32_t) * S));
   HET_HIP(tmp.alloc((void**)&item_off, sizeof(int32_t) * S));
   if (S == 0) {
     HET_HIP(hipMemsetAsync(g->seg_ptr, 0, sizeof(int32_t), s));
     if (R > 0) HET_HIP(hipMemsetAsync(g->seg_rel_ptr, 0, sizeof(int32_t) * (R + 1), s));
     if (R > 0) HET_HIP(hipMemsetAsync(g->seg_rel_ptr64, 0, sizeof(idx_t) * (R + 1), s));
-    GALLOC(item_seg, 0); GALLOC(item_begin, 0); GALLOC(item_end, 0); GALLOC(split_seg, 0);
+    GALLOC(item_seg, 0, int32_t); GALLOC(item_begin, 0, int32_t); GALLOC(item_end, 0, int32_t); GALLOC(split_seg, 0, int32_t);
   } else {
     size_t tb = 0;
     HET_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, counts, g->seg_ptr, (int)S, s));
@@ -397,10 +434,10 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
     (void)het_free_e(t0);
     HET_HIP(e);
     g->num_items = (int64_t)last_off + last_n;
-    GALLOC(item_seg, g->num_items);
-    GALLOC(item_begin, g->num_items);
-    GALLOC(item_end, g->num_items);
-    GALLOC(split_seg, E / HET_ITEM_MAX + 1);  // a split segment has > HET_ITEM_MAX positions
+    GALLOC(item_seg, g->num_items, int32_t);
+    GALLOC(item_begin, g->num_items, int32_t);
+    GALLOC(item_end, g->num_items, int32_t);
+    GALLOC(split_seg, E / HET_ITEM_MAX + 1, int32_t);  // a split segment has > HET_ITEM_MAX positions
     hipLaunchKernelGGL(HET_grouping_items, dim3(blocks_for(S)), dim3(256), 0, s, g->seg_ptr, item_off, nitems, S,
                        g->item_seg, g->item_begin, g->item_end, g->split_seg, d_scalars + 1);
     HET_LAUNCH_CHECK("HET_grouping_items");
@@ -410,7 +447,7 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
     g->num_split = h_split;
   }
   if (payload0 && E > 0) {
-    GALLOC(p0, E);
+    GALLOC(p0, E, int32_t);
     hipLaunchKernelGGL(HET_grouping_payload, dim3(blocks_for(E)), dim3(256), 0, s, g->perm, payload0, E, g->p0, d_scalars + 4);
     HET_LAUNCH_CHECK("HET_grouping_payload");
     hipLaunchKernelGGL(HET_grouping_p0_not_identity, dim3(blocks_for(E)), dim3(256), 0, s, g->p0, E, d_scalars + 2);
@@ -423,7 +460,7 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
     g->p0_max = h_max;
   }
   if (payload1 && E > 0) {
-    GALLOC(p1, E);
+    GALLOC(p1, E, int32_t);
     hipLaunchKernelGGL(HET_grouping_payload, dim3(blocks_for(E)), dim3(256), 0, s, g->perm, payload1, E, g->p1, d_scalars + 5);
     HET_LAUNCH_CHECK("HET_grouping_payload");
     int32_t h_max = 0;
@@ -438,14 +475,11 @@ extern "C" int het_grouping_create(const int64_t* rel_ptrs, int64_t num_rels, co
   return HET_OK;
 }
 
-static std::mutex g_pack_mu;
-
-// One set of packs for a threshold (caller holds g_pack_mu).  key_of_rank, which does not depend on the threshold, is built with the
-// first set and shared.
+// One set of packs for a threshold (inside the caller's build: lock held, begun).  key_of_rank, which does not depend on the
+// threshold, is built with the first set and shared.
 static int build_pack_set(const het_grouping* g, hipStream_t s, int pack_t, int32_t** pack_ptr_out, int32_t** long_items_out,
-                          int64_t* num_packs_out, int64_t* num_long_out) {
+                          int32_t** key_of_rank_out, int64_t* num_packs_out, int64_t* num_long_out) {
   const int64_t E = g->E, S = g->S;
-  if (int rc = grouping_seg_of_rank(g, s)) return rc;
   Scratch tmp(s);
   const int64_t NI = g->num_items;
   uint8_t *flag = nullptr, *is_long = nullptr;
@@ -473,91 +507,67 @@ static int build_pack_set(const het_grouping* g, hipStream_t s, int pack_t, int3
   HET_HIP(hipMemcpyAsync(h_num, d_num, sizeof(h_num), hipMemcpyDeviceToHost, s));
   HET_HIP(hipStreamSynchronize(s));
   int32_t *pack_ptr = nullptr, *key_of_rank = nullptr, *long_items = nullptr;
-  const bool need_keys = g->key_of_rank == nullptr;
-  HET_HIP(het_malloc_e((void**)&pack_ptr, sizeof(int32_t) * ((size_t)h_num[0] + 1), s));
-  hipError_t e = need_keys ? het_malloc_e((void**)&key_of_rank, sizeof(int32_t) * ((size_t)E + 1), s) : hipSuccess;
-  if (e == hipSuccess) e = het_malloc_e((void**)&long_items, sizeof(int32_t) * ((size_t)h_num[1] + 1), s);
-  if (e == hipSuccess) e = hipMemcpyAsync(pack_ptr, pack_tmp, sizeof(int32_t) * (size_t)h_num[0], hipMemcpyDeviceToDevice, s);
+  if (int rc = grouping_alloc(g, (void**)&pack_ptr, sizeof(int32_t) * ((size_t)h_num[0] + 1))) return rc;
+  if (!g->key_of_rank)
+    if (int rc = grouping_alloc(g, (void**)&key_of_rank, sizeof(int32_t) * ((size_t)E + 1))) return rc;
+  if (int rc = grouping_alloc(g, (void**)&long_items, sizeof(int32_t) * ((size_t)h_num[1] + 1))) return rc;
+  HET_HIP(hipMemcpyAsync(pack_ptr, pack_tmp, sizeof(int32_t) * (size_t)h_num[0], hipMemcpyDeviceToDevice, s));
   // (issuing the long work items in the order of their first gathered row -- as the hub items of the RGAT forward are -- was
   //  measured with (source, destination)-ordered edge lists and lost: RGAT 4.17 -> 4.28 ms, RGCN 3.02 -> 3.12; segment order stays)
-  if (e == hipSuccess) e = hipMemcpyAsync(long_items, long_tmp, sizeof(int32_t) * (size_t)h_num[1], hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(HET_grouping_pack_finish, dim3(blocks_for(h_num[0] + 1)), dim3(256), 0, s, pack_ptr, d_num, flag, E);
-    if (need_keys)
-      hipLaunchKernelGGL(HET_grouping_key_of_rank, dim3(blocks_for(E + 1)), dim3(256), 0, s, g->seg_of_rank, g->seg_key, E,
-                         key_of_rank);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // published only once complete: later users may be on other streams
-  if (e != hipSuccess) {
-    (void)het_free_e(pack_ptr); (void)het_free_e(key_of_rank); (void)het_free_e(long_items);
-    HET_HIP(e);
-  }
-  if (need_keys) g->key_of_rank = key_of_rank;
+  HET_HIP(hipMemcpyAsync(long_items, long_tmp, sizeof(int32_t) * (size_t)h_num[1], hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(HET_grouping_pack_finish, dim3(blocks_for(h_num[0] + 1)), dim3(256), 0, s, pack_ptr, d_num, flag, E);
+  if (key_of_rank)
+    hipLaunchKernelGGL(HET_grouping_key_of_rank, dim3(blocks_for(E + 1)), dim3(256), 0, s, g->seg_of_rank, g->seg_key, E, key_of_rank);
+  HET_LAUNCH_CHECK("HET_grouping_pack_finish");
   *pack_ptr_out = pack_ptr;
   *long_items_out = long_items;
+  *key_of_rank_out = key_of_rank;
   *num_packs_out = h_num[0];
   *num_long_out = h_num[1];
-  return HET_OK;
-}
-
-int grouping_packs(const het_grouping* g, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_pack_mu);
-  if (g->pack_ptr || g->E == 0 || g->S == 0) return HET_OK;
-  int32_t *pp = nullptr, *li = nullptr;
-  int64_t np = 0, nl = 0;
-  if (int rc = build_pack_set(g, s, HET_PACK_T, &pp, &li, &np, &nl)) return rc;
-  g->long_items = li;
-  g->num_long_items = nl;
-  g->num_packs = np;
-  g->pack_ptr = pp;
   return HET_OK;
 }
 
 int grouping_pack_view(const het_grouping* g, hipStream_t s, int pack_t, PackView* out) {
   *out = PackView{};
   if (g->E == 0 || g->S == 0) return HET_OK;
-  if (pack_t <= 0 || pack_t == HET_PACK_T) {
-    if (int rc = grouping_packs(g, s)) return rc;
-    *out = PackView{g->pack_ptr, g->long_items, g->num_packs, g->num_long_items};
-    return HET_OK;
-  }
-  std::lock_guard<std::mutex> lk(g_pack_mu);
-  if (g->alt_pack_t != pack_t) {
-    if (g->alt_pack_t != 0) {  // another threshold before: retired, not freed (a launch of another thread may still read it)
-      g->retired.push_back(g->alt_pack_ptr);
-      g->retired.push_back(g->alt_long_items);
+  const bool alt = pack_t > 0 && pack_t != HET_PACK_T;
+  GroupingBuild b(g, s);
+  if (alt ? g->alt_pack_t != pack_t : !g->pack_ptr) {
+    if (alt) {  // another threshold before: un-published
       g->alt_pack_ptr = g->alt_long_items = nullptr;
       g->alt_pack_t = 0;
     }
-    int32_t *pp = nullptr, *li = nullptr;
+    if (int rc = grouping_seg_of_rank(g, s)) return rc;
+    b.begin();
+    int32_t *pp = nullptr, *li = nullptr, *keys = nullptr;
     int64_t np = 0, nl = 0;
-    if (int rc = build_pack_set(g, s, pack_t, &pp, &li, &np, &nl)) return rc;
-    g->alt_pack_ptr = pp;
-    g->alt_long_items = li;
-    g->alt_num_packs = np;
-    g->alt_num_long_items = nl;
-    g->alt_pack_t = pack_t;
+    if (int rc = build_pack_set(g, s, alt ? pack_t : HET_PACK_T, &pp, &li, &keys, &np, &nl)) return rc;
+    if (int rc = b.finish()) return rc;
+    if (keys) g->key_of_rank = keys;
+    if (alt) {
+      g->alt_pack_ptr = pp; g->alt_long_items = li; g->alt_num_packs = np; g->alt_num_long_items = nl; g->alt_pack_t = pack_t;
+    } else {
+      g->long_items = li; g->num_long_items = nl; g->num_packs = np; g->pack_ptr = pp;
+    }
   }
-  *out = PackView{g->alt_pack_ptr, g->alt_long_items, g->alt_num_packs, g->alt_num_long_items};
+  *out = alt ? PackView{g->alt_pack_ptr, g->alt_long_items, g->alt_num_packs, g->alt_num_long_items}
+             : PackView{g->pack_ptr, g->long_items, g->num_packs, g->num_long_items};
   return HET_OK;
 }
 
+int grouping_packs(const het_grouping* g, hipStream_t s) {
+  PackView pv;
+  return grouping_pack_view(g, s, HET_PACK_T, &pv);
+}
+
 int grouping_hub_items(const het_grouping* g, const het_grouping* twin, int R, int hub_min, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_pack_mu);
-  if (g->num_hub_items >= 0) {
-    if (g->hub_twin_serial == twin->serial && g->hub_min == hub_min) return HET_OK;
-    // paired with another twin object before (a cache that evicted and rebuilt the grouping by key alone) or another threshold:
-    // the lists are rebuilt.  The old ones are RETIRED, not freed: another thread may be between its workspace query and its
-    // launch with the pointers it read (and a caller's allocator would hand the memory out again without waiting for the
-    // device); they go with the grouping (het_grouping_destroy).
-    for (int32_t* old : {g->hub_items, g->hub_segs, g->hub_order, reinterpret_cast<int32_t*>(g->hub_rec)})
-      if (old) g->retired.push_back(old);
-    g->hub_items = g->hub_segs = g->hub_order = nullptr;
-    g->hub_rec = nullptr;
-    g->num_hub_items = -1;
-    g->num_hub_segs = 0;
-  }
+  GroupingBuild b(g, s);
+  if (g->num_hub_items >= 0 && g->hub_twin_serial == twin->serial && g->hub_min == hub_min) return HET_OK;
+  g->hub_items = g->hub_segs = g->hub_order = nullptr;
+  g->hub_rec = nullptr;
+  g->num_hub_items = -1;
+  g->num_hub_segs = 0;
+  b.begin();
   const int64_t NI = g->num_items, TS = twin->S;
   int32_t *items = nullptr, *segs = nullptr, *order = nullptr;
   int4* rec = nullptr;
@@ -586,41 +596,36 @@ int grouping_hub_items(const het_grouping* g, const het_grouping* twin, int R, i
     HET_HIP(hipcub::DeviceSelect::Flagged(t0, tb2, ranks, is_long, sel2, d_num + 1, (int)TS, s));
     HET_HIP(hipMemcpyAsync(h_num, d_num, sizeof(h_num), hipMemcpyDeviceToHost, s));
     HET_HIP(hipStreamSynchronize(s));
-    HET_HIP(het_malloc_e((void**)&items, sizeof(int32_t) * ((size_t)h_num[0] + 1), s));
-    hipError_t e = het_malloc_e((void**)&segs, sizeof(int32_t) * ((size_t)h_num[1] + 1), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(items, sel, sizeof(int32_t) * (size_t)h_num[0], hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(segs, sel2, sizeof(int32_t) * (size_t)h_num[1], hipMemcpyDeviceToDevice, s);
+    if (int rc = grouping_alloc(g, (void**)&items, sizeof(int32_t) * ((size_t)h_num[0] + 1))) return rc;
+    if (int rc = grouping_alloc(g, (void**)&segs, sizeof(int32_t) * ((size_t)h_num[1] + 1))) return rc;
+    HET_HIP(hipMemcpyAsync(items, sel, sizeof(int32_t) * (size_t)h_num[0], hipMemcpyDeviceToDevice, s));
+    HET_HIP(hipMemcpyAsync(segs, sel2, sizeof(int32_t) * (size_t)h_num[1], hipMemcpyDeviceToDevice, s));
     // launch order of the hub items: by the first payload0 (feat row) of the item, so that items in flight together read the
     // same window of the table (within a run the rows ascend when the positions are in (relation, source) order)
-    if (e == hipSuccess && h_num[0] > 0 && twin->p0) {
-      e = het_malloc_e((void**)&order, sizeof(int32_t) * (size_t)h_num[0], s);
+    if (h_num[0] > 0 && twin->p0) {
+      if (int rc = grouping_alloc(g, (void**)&order, sizeof(int32_t) * (size_t)h_num[0])) return rc;
       uint32_t *k_in = nullptr, *k_out = nullptr;
       int32_t* v_in = nullptr;
-      if (e == hipSuccess) e = tmp.alloc((void**)&k_in, sizeof(uint32_t) * (size_t)h_num[0]);
-      if (e == hipSuccess) e = tmp.alloc((void**)&k_out, sizeof(uint32_t) * (size_t)h_num[0]);
-      if (e == hipSuccess) e = tmp.alloc((void**)&v_in, sizeof(int32_t) * (size_t)h_num[0]);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(HET_grouping_hub_first_p0, dim3(blocks_for(h_num[0])), dim3(256), 0, s, items, (int64_t)h_num[0], g->item_begin,
-                           twin->p0, k_in, v_in);
-        e = hipGetLastError();
-      }
+      HET_HIP(tmp.alloc((void**)&k_in, sizeof(uint32_t) * (size_t)h_num[0]));
+      HET_HIP(tmp.alloc((void**)&k_out, sizeof(uint32_t) * (size_t)h_num[0]));
+      HET_HIP(tmp.alloc((void**)&v_in, sizeof(int32_t) * (size_t)h_num[0]));
+      hipLaunchKernelGGL(HET_grouping_hub_first_p0, dim3(blocks_for(h_num[0])), dim3(256), 0, s, items, (int64_t)h_num[0], g->item_begin,
+                         twin->p0, k_in, v_in);
+      HET_LAUNCH_CHECK("HET_grouping_hub_first_p0");
       size_t sb = 0;
       void* st = nullptr;
-      if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, sb, k_in, k_out, v_in, order, h_num[0], 0, 32, s);
-      if (e == hipSuccess) e = tmp.alloc(&st, sb);
-      if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(st, sb, k_in, k_out, v_in, order, h_num[0], 0, 32, s);
+      HET_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, k_in, k_out, v_in, order, h_num[0], 0, 32, s));
+      HET_HIP(tmp.alloc(&st, sb));
+      HET_HIP(hipcub::DeviceRadixSort::SortPairs(st, sb, k_in, k_out, v_in, order, h_num[0], 0, 32, s));
     }
-    if (e == hipSuccess && h_num[1] > 0) {
-      e = het_malloc_e((void**)&rec, sizeof(int4) * (size_t)h_num[1], s);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(HET_grouping_hub_records, dim3(blocks_for(h_num[1])), dim3(256), 0, s, segs, (int64_t)h_num[1], twin->seg_key,
-                           g->seg_key, g->S, g->item_seg, NI, items, (int64_t)h_num[0], R, rec);
-        e = hipGetLastError();
-      }
+    if (h_num[1] > 0) {
+      if (int rc = grouping_alloc(g, (void**)&rec, sizeof(int4) * (size_t)h_num[1])) return rc;
+      hipLaunchKernelGGL(HET_grouping_hub_records, dim3(blocks_for(h_num[1])), dim3(256), 0, s, segs, (int64_t)h_num[1], twin->seg_key,
+                         g->seg_key, g->S, g->item_seg, NI, items, (int64_t)h_num[0], R, rec);
+      HET_LAUNCH_CHECK("HET_grouping_hub_records");
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)het_free_e(items); (void)het_free_e(segs); (void)het_free_e(order); (void)het_free_e(rec); HET_HIP(e); }
   }
+  if (int rc = b.finish()) return rc;
   g->hub_rec = rec;
   g->hub_order = order;
   g->hub_items = items;
@@ -675,42 +680,34 @@ __global__ __launch_bounds__(256) void HET_grouping_tag_kp01(int4* __restrict__ 
     reinterpret_cast<int*>(kp01 + j)[3] = tag;  // (only this word is written: the neighbours' reads of x / y / z do not race)
   }
 }
-}  // namespace
 
-int grouping_tag_kp01(const het_grouping* g, int which, const int* thr, hipStream_t s) {
+// Both forms of the tagging: the boundaries on the host (thr, or NULL) or on the device (dev, R).
+int tag_kp01(const het_grouping* g, int which, const int* thr, const idx_t* dev, int R, hipStream_t s) {
   if (int rc = grouping_packed_ids(g, true, s)) return rc;
-  std::lock_guard<std::mutex> lk(g_pack_mu);
+  GroupingBuild b(g, s);
   if (g->E == 0 || !g->kp01) return HET_OK;
-  if (!thr && g->tag_which >= 0) return HET_OK;  // (a user of the segment / run flags alone: they do not depend on the thresholds)
+  if (!dev && !thr && g->tag_which >= 0) return HET_OK;  // (a user of the segment / run flags alone: they do not depend on the thresholds)
   TagThr t;
-  for (int k = 0; k < 7; ++k) t.v[k] = thr ? thr[k] : 0x7fffffff;
-  thr = t.v;
-  bool same = g->tag_which == which;
-  for (int k = 0; k < 7 && same; ++k) same = g->tag_thr[k] == thr[k];
-  if (same) return HET_OK;
-  hipLaunchKernelGGL(HET_grouping_tag_kp01, dim3(blocks_for(g->E)), dim3(256), 0, s, g->kp01, g->E, which, t, nullptr, 0);
+  for (int k = 0; k < 7; ++k) t.v[k] = dev ? -1 : (thr ? thr[k] : 0x7fffffff);  // (dev: the values stay on the device)
+  if (g->tag_which == which && g->tag_dev_src == dev && g->tag_dev_R == R && memcmp(g->tag_thr, t.v, sizeof(t.v)) == 0) return HET_OK;
+  const bool retag = g->tag_which >= 0;  // word 3 is rewritten under launches on other streams that may still read it
+  g->tag_which = -1;
+  b.begin(retag);
+  hipLaunchKernelGGL(HET_grouping_tag_kp01, dim3(blocks_for(g->E)), dim3(256), 0, s, g->kp01, g->E, which, t, dev, R);
   HET_LAUNCH_CHECK("HET_grouping_tag_kp01");
-  HET_HIP(hipStreamSynchronize(s));  // published only once complete
-  for (int k = 0; k < 7; ++k) g->tag_thr[k] = thr[k];
+  if (int rc = b.finish()) return rc;
+  memcpy(g->tag_thr, t.v, sizeof(t.v));
+  g->tag_dev_src = dev;
+  g->tag_dev_R = R;
   g->tag_which = which;
-  g->tag_dev_src = nullptr;
   return HET_OK;
 }
+}  // namespace
+
+int grouping_tag_kp01(const het_grouping* g, int which, const int* thr, hipStream_t s) { return tag_kp01(g, which, thr, nullptr, 0, s); }
 
 int grouping_tag_kp01_dev(const het_grouping* g, int which, const idx_t* rel_ptrs_dev, int R, hipStream_t s) {
-  if (int rc = grouping_packed_ids(g, true, s)) return rc;
-  std::lock_guard<std::mutex> lk(g_pack_mu);
-  if (g->E == 0 || !g->kp01) return HET_OK;
-  if (g->tag_which == which && g->tag_dev_src == rel_ptrs_dev && g->tag_dev_R == R) return HET_OK;
-  TagThr t{};
-  hipLaunchKernelGGL(HET_grouping_tag_kp01, dim3(blocks_for(g->E)), dim3(256), 0, s, g->kp01, g->E, which, t, rel_ptrs_dev, R);
-  HET_LAUNCH_CHECK("HET_grouping_tag_kp01");
-  HET_HIP(hipStreamSynchronize(s));  // published only once complete
-  for (int k = 0; k < 7; ++k) g->tag_thr[k] = -1;  // (the values stay on the device)
-  g->tag_which = which;
-  g->tag_dev_src = rel_ptrs_dev;
-  g->tag_dev_R = R;
-  return HET_OK;
+  return tag_kp01(g, which, nullptr, rel_ptrs_dev, R, s);
 }
 
 namespace {
@@ -723,35 +720,27 @@ __global__ void HET_grouping_value_keys(const idx_t* __restrict__ values, int64_
 }  // namespace
 
 int grouping_value_order(const het_grouping* g, const idx_t* values, int64_t n, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_pack_mu);
+  GroupingBuild b(g, s);
   if (g->val_order && g->val_order_src == values && g->val_order_n == n) return HET_OK;
   HET_REQUIRE(values && n > 0 && n < (1ll << 31), "grouping_value_order: bad arguments");
-  if (g->val_order) {  // built from another list before: retired, not freed (see grouping_hub_items)
-    g->retired.push_back(g->val_order);
-    g->val_order = nullptr;
-  }
+  g->val_order = nullptr;
+  b.begin();
   int32_t* order = nullptr;
-  HET_HIP(het_malloc_e((void**)&order, sizeof(int32_t) * (size_t)n, s));
-  hipError_t e = hipSuccess;
-  {
-    Scratch tmp(s);
-    uint32_t *k_in = nullptr, *k_out = nullptr;
-    int32_t* v_in = nullptr;
-    e = tmp.alloc((void**)&k_in, sizeof(uint32_t) * (size_t)n);
-    if (e == hipSuccess) e = tmp.alloc((void**)&k_out, sizeof(uint32_t) * (size_t)n);
-    if (e == hipSuccess) e = tmp.alloc((void**)&v_in, sizeof(int32_t) * (size_t)n);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(HET_grouping_value_keys, dim3(blocks_for(n)), dim3(256), 0, s, values, n, k_in, v_in);
-      e = hipGetLastError();
-    }
-    size_t sb = 0;
-    void* st = nullptr;
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, sb, k_in, k_out, v_in, order, (int)n, 0, 32, s);  // (stable)
-    if (e == hipSuccess) e = tmp.alloc(&st, sb);
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(st, sb, k_in, k_out, v_in, order, (int)n, 0, 32, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // published only once complete
-  }
-  if (e != hipSuccess) { (void)het_free_e(order); HET_HIP(e); }
+  if (int rc = grouping_alloc(g, (void**)&order, sizeof(int32_t) * (size_t)n)) return rc;
+  Scratch tmp(s);
+  uint32_t *k_in = nullptr, *k_out = nullptr;
+  int32_t* v_in = nullptr;
+  HET_HIP(tmp.alloc((void**)&k_in, sizeof(uint32_t) * (size_t)n));
+  HET_HIP(tmp.alloc((void**)&k_out, sizeof(uint32_t) * (size_t)n));
+  HET_HIP(tmp.alloc((void**)&v_in, sizeof(int32_t) * (size_t)n));
+  hipLaunchKernelGGL(HET_grouping_value_keys, dim3(blocks_for(n)), dim3(256), 0, s, values, n, k_in, v_in);
+  HET_LAUNCH_CHECK("HET_grouping_value_keys");
+  size_t sb = 0;
+  void* st = nullptr;
+  HET_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, k_in, k_out, v_in, order, (int)n, 0, 32, s));  // (stable)
+  HET_HIP(tmp.alloc(&st, sb));
+  HET_HIP(hipcub::DeviceRadixSort::SortPairs(st, sb, k_in, k_out, v_in, order, (int)n, 0, 32, s));
+  if (int rc = b.finish()) return rc;
   g->val_order = order;
   g->val_order_src = values;
   g->val_order_n = n;
@@ -761,25 +750,18 @@ int grouping_value_order(const het_grouping* g, const idx_t* values, int64_t n, 
 int grouping_packed_ids(const het_grouping* g, bool with_keys, hipStream_t s) {
   if (with_keys)
     if (int rc = grouping_packs(g, s)) return rc;
-  std::lock_guard<std::mutex> lk(g_pack_mu);
+  GroupingBuild b(g, s);
   if ((with_keys ? (void*)g->kp01 : (void*)g->p01) || g->E == 0) return HET_OK;
   const int64_t E = g->E;
+  HET_REQUIRE(!with_keys || g->key_of_rank, "grouping_packed_ids: the grouping has no packs (no segments?)");
+  b.begin();
   int2* o2 = nullptr;
   int4* o4 = nullptr;
-  if (with_keys) {
-    HET_REQUIRE(g->key_of_rank, "grouping_packed_ids: the grouping has no packs (no segments?)");
-    HET_HIP(het_malloc_e((void**)&o4, sizeof(int4) * (size_t)(E + 1), s));
-  } else {
-    HET_HIP(het_malloc_e((void**)&o2, sizeof(int2) * (size_t)E, s));
-  }
+  if (int rc = with_keys ? grouping_alloc(g, (void**)&o4, sizeof(int4) * (size_t)(E + 1)) : grouping_alloc(g, (void**)&o2, sizeof(int2) * (size_t)E))
+    return rc;
   hipLaunchKernelGGL(HET_grouping_pack_ids, dim3(blocks_for(E + 1)), dim3(256), 0, s, g->key_of_rank, g->p0, g->p1, E, o2, o4);
-  hipError_t e = hipGetLastError();
-
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // published only once complete
-  if (e != hipSuccess) {
-    (void)het_free_e(o2); (void)het_free_e(o4);
-    HET_HIP(e);
-  }
+  HET_LAUNCH_CHECK("HET_grouping_pack_ids");
+  if (int rc = b.finish()) return rc;
   if (with_keys) g->kp01 = o4; else g->p01 = o2;
   return HET_OK;
 }

@@ -11,12 +11,17 @@ constexpr int HET_ITEM_MAX = 256;
 
 struct het_grouping {
   uint64_t serial = 0;     // unique per object for the life of the process (an address can come back after a destroy)
-  // Streams (round 5).  The arrays below come from the caller's allocator when one is installed (het_set_allocator): a stream-
-  // ordered pool hands a freed block out again at once to its creation stream, without waiting for kernels of OTHER streams that
-  // still read it.  `home` is the stream the grouping was built on (its blocks belong to it); `used` the other streams a binding
-  // reported through het_grouping_note_stream.  het_grouping_destroy makes `home` wait for them before it releases anything.
+  // Ownership.  Every device array below, built by het_grouping_create or on first use, comes from grouping_alloc: allocated on
+  // `home`, the stream the grouping was created on (with a stream-ordered allocator -- het_set_allocator -- the block belongs to
+  // that stream's pool), on `device`, and listed in `blocks` until het_grouping_destroy.  `used`: the other streams that read the
+  // arrays (het_grouping_note_stream, and every stream a list was built on); destroy makes `home` wait for them before it
+  // releases anything.  A list that a rebuild replaces is only un-published: its block stays in `blocks` (a launch of another
+  // thread may still read it).
+  struct Block { void* ptr; size_t bytes; };
   hipStream_t home = nullptr;
+  int device = 0;
   mutable std::vector<hipStream_t> used;
+  mutable std::vector<Block> blocks;
   int64_t E = 0;           // positions
   int64_t S = 0;           // segments
   int64_t num_items = 0;   // work items (>= S)
@@ -64,7 +69,7 @@ struct het_grouping {
   //   tag >> HET_TAG_REL_SHIFT  relation of the rank: number of relation boundaries <= its key (tag_which 0) or its p0 (tag_which 1)
   mutable int tag_which = -1;     // -1: not tagged
   mutable int tag_thr[7] = {0, 0, 0, 0, 0, 0, 0};
-  mutable const idx_t* tag_dev_src = nullptr;  // grouping_tag_kp01_dev: the device array the thresholds were read from, its length - 1
+  mutable const idx_t* tag_dev_src = nullptr;  // grouping_tag_kp01_dev: the device array the boundaries were read from (the caller pins it), its length - 1
   mutable int tag_dev_R = 0;
   // Hub items (grouping_hub_items): for a grouping by key * R + relation, the work items (ascending) whose key belongs to a
   // segment of more than hub_min positions in the twin grouping by key alone (het_rgat_aggregate_compact_runs).
@@ -78,11 +83,9 @@ struct het_grouping {
   mutable int64_t num_hub_segs = 0;
   mutable int hub_min = 0;
   mutable uint64_t hub_twin_serial = 0;       // serial of the twin the lists were built against
-  mutable std::vector<int32_t*> retired;      // hub lists replaced by a rebuild (grouping_hub_items): freed with the grouping
-  // An order of the rows of a caller's list by the list's values (grouping_value_order): ONLY a locality hint -- any permutation of
-  // [0, n) gives the same results -- so it is cached by the identity (array, length) of the list it was built from.
+  // An order of the rows of a caller's list by the list's values (grouping_value_order).
   mutable int32_t* val_order = nullptr;
-  mutable const idx_t* val_order_src = nullptr;
+  mutable const idx_t* val_order_src = nullptr;  // key: identity only -- the order is a locality hint, any permutation of [0, n) gives the same results
   mutable int64_t val_order_n = 0;
 };
 
@@ -102,34 +105,69 @@ inline Items items_of(const het_grouping* g) {
 }
 }  // namespace
 
+// ---- arrays built on first use ----------------------------------------------------------------------------------------------
+// One protocol for all of them (GroupingBuild, grouping.hip), one lock, and the ownership rule above:
+//     GroupingBuild b(g, s);                        // takes the lock
+//     if (<the slot's key is the one asked for>) return HET_OK;  // steady state: the lock and a few compares
+//     <un-publish what the slot held>;              // (its blocks stay with the grouping)
+//     b.begin();                                    // g's device current; `s` ordered after `home`, noted as a user
+//     grouping_alloc(g, &p, bytes); launches on s;  // any early return releases what was allocated since begin()
+//     if (int rc = b.finish()) return rc;           // hipStreamSynchronize(s): users may be on other streams
+//     <publish pointers, counts and key>;
+// A list that needs another one builds that one BEFORE its own begin() (the lock is recursive; packs need seg_of_rank, kp01
+// needs the packs, tags need kp01).
+int grouping_alloc(const het_grouping* g, void** out, size_t bytes);  // on g->home, recorded in g->blocks
+struct OnDevice {  // makes a device current until the end of a scope
+  int prev = -1;
+  void enter(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess || prev == dev || hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  }
+  ~OnDevice() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+struct GroupingBuild {
+  GroupingBuild(const het_grouping* g, hipStream_t s);
+  ~GroupingBuild();
+  // wait_for_users: `s` also waits for every noted stream (a rebuild IN PLACE: launches there may still read the old contents)
+  void begin(bool wait_for_users = false);
+  int finish();
+  GroupingBuild(const GroupingBuild&) = delete;
+  GroupingBuild& operator=(const GroupingBuild&) = delete;
+
+ private:
+  const het_grouping* g;
+  hipStream_t s;
+  OnDevice device;
+  size_t mark = 0;       // g->blocks.size() at begin()
+  bool open = false;
+};
+
 constexpr int HET_PACK_T = 32;
-// Builds g->pack_ptr / key_of_rank / long_items (threshold HET_PACK_T) once (thread-safe; synchronises `s` before publishing them).
+// g->pack_ptr / key_of_rank / long_items for the threshold HET_PACK_T.  Key: pack_ptr set.
 int grouping_packs(const het_grouping* g, hipStream_t s);
 // The packs of a grouping for a threshold: HET_PACK_T (or <= 0) = the default set above; any other value = the second set
-// (built on first use; a grouping keeps one other threshold -- asking for a third retires the second).  key_of_rank is shared.
+// (key: alt_pack_t; a grouping keeps one other threshold -- asking for a third replaces the second).  key_of_rank is shared.
 struct PackView {
   const int32_t* pack_ptr = nullptr;
   const int32_t* long_items = nullptr;
   int64_t num_packs = 0, num_long_items = 0;
 };
 int grouping_pack_view(const het_grouping* g, hipStream_t s, int pack_t, PackView* out);
-// Builds g->p01 (with_keys == false) or g->kp01 (true; builds the packs first) once, thread-safe, published after a sync.
+// g->p01 (with_keys == false) or g->kp01 (true; builds the packs first).  Key: the pointer set.
 int grouping_packed_ids(const het_grouping* g, bool with_keys, hipStream_t s);
 constexpr int HET_TAG_FIRST_KEY = 1, HET_TAG_LAST_RUN = 2, HET_TAG_LAST_KEY = 4, HET_TAG_REL_SHIFT = 8;
-// Fills the fourth word of g->kp01 (builds kp01 first; thread-safe; synchronises `s`).  thr[0..6]: ascending first values of relations
-// 1 .. 7 (INT_MAX beyond the last relation), or NULL: the caller reads the segment / run flags only (any tagging will do);
-// which = 0: the relation follows the key, 1: payload0.  A grouping tagged with other thresholds before is re-tagged in place (the
-// flags are rewritten with the same values; the thresholds of a graph's unique lists do not change between calls).
+// Fills the fourth word of g->kp01 (builds kp01 first).  thr[0..6]: ascending first values of relations 1 .. 7 (INT_MAX beyond the
+// last relation), or NULL: the caller reads the segment / run flags only (any tagging will do); which = 0: the relation follows the
+// key, 1: payload0.  Key: (which, thr).  Another key re-tags IN PLACE (the flags are rewritten with the same values), ordered
+// after every stream that uses the grouping.
 int grouping_tag_kp01(const het_grouping* g, int which, const int* thr, hipStream_t s);
-// The same with the relation boundaries read on the device: rel_ptrs_dev [R+1] (int64), any R < 2^23 (a search above 8).  No host copy,
-// so "tagged already" is decided by the identity of (array, R): the boundaries of a row list belong to the list the grouping sorts,
-// a caller does not hand the same grouping different boundaries.
+// The same with the relation boundaries read on the device: rel_ptrs_dev [R+1] (int64), any R < 2^23 (a search above 8).  No host
+// copy (a synchronisation per call), so the key is the identity (which, array, R): the caller keeps the array alive and unchanged
+// while the grouping lives (het_amd/kernels.py pins it on the Grouping and refuses an in-place edit).
 int grouping_tag_kp01_dev(const het_grouping* g, int which, const idx_t* rel_ptrs_dev, int R, hipStream_t s);
-// Builds g_rel->hub_items once (thread-safe, published after a sync): g_rel groups the same positions as `twin` by
-// key * R + relation.  Rebuilt when g_rel was paired with another twin object (or threshold) before.
+// g_rel->hub_items / hub_segs / hub_order / hub_rec: g_rel groups the same positions as `twin` by key * R + relation.  Key: (serial
+// of the twin object, hub_min) -- a cache that evicted and rebuilt the grouping by key alone gets new lists.
 int grouping_hub_items(const het_grouping* g_rel, const het_grouping* twin, int R, int hub_min, hipStream_t s);
-// g->val_order [n]: the indices of values[0..n) (device, 0 <= values < 2^31) in ascending order of the value, ties in index order;
-// built once per (array, n), thread-safe, published after a sync.  A pass over the rows of a (relation, node) list in this order
-// visits the rows of one node together (het_rgat_backward_compact_runs: the two rows of a destination read the same gradout /
-// ret rows).
+// g->val_order [n]: the indices of values[0..n) (device, 0 <= values < 2^31) in ascending order of the value, ties in index order.
+// Key: (array, n).  A pass over the rows of a (relation, node) list in this order visits the rows of one node together
+// (het_rgat_backward_compact_runs: the two rows of a destination read the same gradout / ret rows).
 int grouping_value_order(const het_grouping* g, const idx_t* values, int64_t n, hipStream_t s);

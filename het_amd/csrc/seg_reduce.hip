@@ -1,5 +1,4 @@
 // Segmented sum of gathered rows, one lane group per work item (no atomics except for split hub segments).
-#include <mutex>
 
 #include "seg_reduce.hip.h"
 
@@ -550,26 +549,17 @@ __global__ __launch_bounds__(kBlock) void HET_segment_broadcast(const int32_t* _
 }
 }  // namespace
 
-static std::mutex g_seg_of_rank_mu;
-
 int grouping_seg_of_rank(const het_grouping* g, hipStream_t s) {
-  // one-time, cached in the grouping.  Built under a lock and published only after the fill kernel has finished, so a
-  // second stream or thread that finds the pointer set never reads a half-written buffer
-  std::lock_guard<std::mutex> lk(g_seg_of_rank_mu);
+  GroupingBuild b(g, s);
   if (g->seg_of_rank || g->E == 0) return HET_OK;
+  b.begin();
   int32_t* p = nullptr;
-  HET_HIP(het_malloc_e((void**)&p, sizeof(int32_t) * g->E, s));
+  if (int rc = grouping_alloc(g, (void**)&p, sizeof(int32_t) * g->E)) return rc;
   int64_t nb0 = ceil_div64(g->E, kBlock);
   hipLaunchKernelGGL(HET_grouping_seg_of_rank, dim3((unsigned)(nb0 > 65536 ? 65536 : nb0)), dim3(kBlock), 0, s, g->seg_ptr,
                      g->S, g->E, p);
-  if (hipGetLastError() != hipSuccess) {
-    (void)het_free_e(p);
-    HET_REQUIRE(false, "HET_grouping_seg_of_rank: launch failed");
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    (void)het_free_e(p);
-    HET_REQUIRE(false, "HET_grouping_seg_of_rank: kernel failed");
-  }
+  HET_LAUNCH_CHECK("HET_grouping_seg_of_rank");
+  if (int rc = b.finish()) return rc;
   g->seg_of_rank = p;
   return HET_OK;
 }

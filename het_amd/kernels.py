@@ -1125,6 +1125,8 @@ def _rgat_backward_compact(runs_entry, groupings, feat_c, el_c, er_c, sum, ret, 
     """rgat_backward_compact / _bf16 behind their tensor checks; ``runs_entry``: the C entry of the run-sum form."""
     N, H = sum.shape[0], sum.shape[1]
     D = ret.numel() // max(1, N * H)
+    if runs and row_rel_ptrs is not None:
+        groupings[1].pin_key(runs_entry, row_rel_ptrs)
     if runs:
         ws, nbytes = _workspace(ret, "het_rgat_backward_compact_runs_workspace", groupings[1].handle, N, er_c.shape[0], H, D,
                                 int(grad_bias is not None), int(grad_attn_l is not None), _stream(ret))

@@ -73,6 +73,7 @@ class Grouping:
     def __init__(self, handle: C.c_void_p, keep):
         self.handle = handle
         self._keep = keep  # source tensors, kept alive with the handle
+        self._pinned = None  # (tensor, _ident): the device array the library keys a lazily built list on (pin_key)
 
     @property
     def num_segments(self) -> int:
@@ -83,6 +84,17 @@ class Grouping:
         """Device bytes the grouping holds (inside torch's allocator statistics when _lib.use_torch_allocator() is in effect --
         the default of het_amd.kernels -- else hipMalloc'ed by the library and invisible to them)."""
         return int(_lib.lib().het_grouping_bytes(self.handle)) if self.handle else 0
+
+    def pin_key(self, op: str, t: torch.Tensor):
+        """The library decides "built already" for the relation tags of this grouping by the ADDRESS of the device array ``t`` it
+        read them from (csrc/grouping.hip.h: grouping_tag_kp01_dev -- a host copy would cost a synchronisation per call).  Holding the
+        tensor makes that key sound: while the grouping lives the address cannot be recycled, so another tensor has another address
+        and is read afresh.  The same array edited in place cannot be seen by the library: it is refused here."""
+        ident = _ident(t)
+        if self._pinned is not None and self._pinned[1][:2] == ident[:2] and self._pinned[1][2] != ident[2]:
+            raise _lib.HetError(f"{op}: the relation boundaries were edited in place after this grouping was tagged with them; "
+                                "the grouping must be rebuilt (het_amd.plan.clear())")
+        self._pinned = (t, ident)
 
     def __del__(self):
         # (the library may already be unloaded at interpreter exit: nothing left to free then; and with torch's allocator

@@ -96,16 +96,20 @@ int het_grouping_create(const int64_t* rel_ptrs /* [R+1] or NULL */, int64_t num
                         const int64_t* payload0, const int64_t* payload1,
                         het_stream stream, het_grouping** out);
 void het_grouping_destroy(het_grouping* g);
-/* Lifetime across streams.  A grouping's arrays belong to the stream it was created on.  With the default allocator
+/* Lifetime across streams.  All arrays of a grouping -- the lists the library builds on first use included -- belong to the
+ * stream (and device) it was created on: a list first needed on another stream is allocated on the creation stream all the same,
+ * and its build on that other stream is ordered after the creation stream's earlier work.  With the default allocator
  * het_grouping_destroy ends in hipFree, which waits for the device.  With a stream-ordered allocator installed
  * (het_set_allocator: torch's caching allocator in both torch registrations) a freed block is handed out again to that stream
  * at once, so a binding that runs ops with the grouping on ANOTHER stream reports that stream here (cheap; idempotent): destroy
  * then makes the creation stream wait for an event on every reported stream before it releases anything -- no host
- * synchronisation.  Both registrations call it on every cache lookup (het_amd/plan.py, csrc/torch_export.cpp). */
+ * synchronisation -- whichever device is current when it is called.  Both registrations call it on every cache lookup
+ * (het_amd/plan.py, csrc/torch_export.cpp). */
 void het_grouping_note_stream(const het_grouping* g, het_stream stream);
 /* number of segments (distinct (relation, key) pairs) */
 int64_t het_grouping_num_segments(const het_grouping* g);
-/* device bytes the grouping currently holds (with the default hipMalloc they are outside the caller's allocator statistics) */
+/* device bytes the grouping currently holds: the sum of its allocations, the lists built on first use so far and the ones a
+ * rebuild replaced included (with the default hipMalloc they are outside the caller's allocator statistics) */
 int64_t het_grouping_bytes(const het_grouping* g);
 /* out[i] = sorted rank of position i (the inverse of the grouping's permutation), [E] */
 int het_grouping_rank_of_position(const het_grouping* g, int64_t* out, het_stream stream);

@@ -487,6 +487,47 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
                                  drow_nodes=ss["node_indices_col"].to(DEV), drow_rel_ptrs=ss["rel_ptrs_col"].to(DEV))
 
 
+def test_rgat_backward_follows_the_relation_boundaries_it_is_handed(K):
+    """The run-sum backward with fold_attn_l reads the relation of every feat row from tags it leaves in the grouping, keyed by
+    the ADDRESS of the boundaries' device array (csrc/grouping.hip.h: grouping_tag_kp01_dev).  The grouping holds that tensor
+    (het_amd/plan.py: Grouping.pin_key), so a second call with ANOTHER tensor holding other boundaries is tagged afresh -- both calls
+    match the oracle's gradients (rgat_run_sums_reference; its fold terms re-formed for the boundaries of the call) -- and the
+    same tensor edited in place, which the library could not tell from the unedited one, is refused."""
+    import het_amd.kernels as k
+    from het_amd import _lib, plan
+    H, D = 4, 32
+    c = rgat_run_sums_reference(random_graph(seed=31, n=300, r=4, e=700), H, D, True)  # (the smallest graph of the test above)
+    grp = rgat_run_sums_groupings(c)
+    f, l, r_, go, attn = (t.to(DEV) for t in (c.feat, c.el, c.er, c.go, c.attn))
+    sm, ret = torch.empty(c.N, H, device=DEV), torch.empty(c.N, H, D, device=DEV)
+    runs = k.rgat_aggregate_compact(grp, f, l, r_, sm, ret, c.slope, num_rels=c.R)
+    drow_nodes = c.ss["node_indices_col"].to(DEV)
+    own = c.ss["rel_ptrs_row"]
+    other = own.clone()
+    other[1:-1] = own[1:-1] // 2  # other boundaries of the same rows: ascending, same ends
+    assert not torch.equal(own, other)
+    gl_feat, gl_attn = c.gl_r.unsqueeze(-1) * to64(c.feat), lambda rel: c.gl_r.unsqueeze(-1) * c.attn.double()[rel]
+
+    def check(ptrs_dev, ptrs, what):
+        gf, gl, gr = torch.full_like(f, float("nan")), torch.full_like(l, float("nan")), torch.full_like(r_, float("nan"))
+        ga = torch.full((c.R, H, D), float("nan"), device=DEV)
+        k.rgat_backward_compact(grp, f, l, r_, sm, ret, go, gf, gl, gr, c.slope, fold_attn_l=attn, row_rel_ptrs=ptrs_dev, runs=runs,
+                                drow_nodes=drow_nodes, grad_attn_l=ga)
+        rel = torch.repeat_interleave(torch.arange(c.R), ptrs[1:] - ptrs[:-1])
+        assert_close(gf, c.gf_r - gl_attn(c.rel_of_row) + gl_attn(rel), what=f"grad_feat ({what})")
+        assert_close(gl, c.gl_r, what=f"grad_el ({what})")
+        assert_close(gr, c.gr_r, what=f"grad_er ({what})")
+        assert_close(ga, torch.zeros(c.R, H, D, dtype=torch.float64).index_add_(0, rel, gl_feat), what=f"grad_attn_l ({what})")
+
+    check(own.to(DEV), own, "the list's own boundaries")
+    other_dev = other.to(DEV)
+    check(other_dev, other, "another tensor, other boundaries")
+    other_dev[1] += 1  # in place: same address, new _version
+    with pytest.raises(_lib.HetError, match="rebuilt"):
+        check(other_dev, other, "edited in place")
+    plan.clear()
+
+
 def test_rgat_backward_packs_do_not_depend_on_the_groupings_first_user():
     """The RGAT backward walks the (relation, source) segments of its grouping in packs of its own threshold (64), kept beside the
     library-wide packs (32) that e.g. a segment sum over the SAME grouping object uses (csrc/grouping.hip: grouping_pack_view).
