@@ -13,15 +13,18 @@ DEV = "cuda"
 
 
 def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0, attn_scale=1.0, oracle_dev="cpu", self_loop=True, bias=True,
-              **layer_kw):
+              slope=0.2, case=None, forward_only=False, **layer_kw):
     """oracle_dev: where the fp64 oracle layer is evaluated (it is plain torch: "cuda" for graphs of 1e5+ edges, where the CPU
-    takes most of a minute per case).  self_loop / bias off: the layer and the oracle without that term and its parameter."""
+    takes most of a minute per case).  self_loop / bias off: the layer and the oracle without that term and its parameter.
+    case: pre-made inputs and parameters (tests/util.py: exact_rgat_case) in place of the random draw -- they stay ON the
+    leaky-ReLU kink (no nudge), and that they are is asserted.  forward_only: the evaluation call (torch.no_grad()) on the same
+    input too, against the same oracle output."""
     from het_amd.layers import HET_RGATLayer
     torch.manual_seed(seed)
     R, N = g.get_num_rels(), g.get_num_nodes()
     layer = HET_RGATLayer(K, X, R, H, bias=bias, self_loop=self_loop, compact_as_of_node_flag=compact,
                           compact_direct_indexing_flag=direct, multiply_among_weights_first_flag=mulfirst,
-                          gat_edge_parallel_flag=edge_parallel, dropout=0.0, **layer_kw)
+                          gat_edge_parallel_flag=edge_parallel, dropout=0.0, leaky_relu_slope=slope, **layer_kw)
     with torch.no_grad():
         if bias:
             layer.h_bias.uniform_(-0.1, 0.1)
@@ -31,20 +34,24 @@ def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0,
     go = torch.randn(N, X)
     # oracle (fp64, autograd)
     s = g.get_separate_coo_original()
+    if case is not None:
+        from tests.util import assert_ties_on_hub_edges, load_rgat_case
+        x, go = load_rgat_case(layer, case)
+        assert_ties_on_hub_edges(case, s, N)
     if oracle_dev != "cpu":  # (1e5+ edges: the per-node nudge of tests/util.py, on the device)
         from tests.util import rgat_nudge_off_kink
         xd_, zmin = rgat_nudge_off_kink(x.to(oracle_dev), layer.conv_weights.to(oracle_dev), layer.attn_l.to(oracle_dev),
                                         layer.attn_r.to(oracle_dev), s)
         assert zmin >= 2e-6, zmin
         x = xd_.cpu()
-    for _ in range(64 if oracle_dev == "cpu" else 0):  # no (edge, head) on the leaky-ReLU kink (see tests/util.py); fp32 rounding of el + er is ~3e-7
+    for _ in range(64 if oracle_dev == "cpu" and case is None else 0):  # no (edge, head) on the leaky-ReLU kink (see tests/util.py); fp32 rounding of el + er is ~3e-7
         if rgat_min_abs_preactivation(x, layer.conv_weights, layer.attn_l, layer.attn_r, s) >= 2e-6:
             break
         x = x + 1e-3 * torch.randn(N, K)
     p = {n: t.detach().double().to(oracle_dev).requires_grad_(True) for n, t in layer.named_parameters()}
     x64 = x.double().to(oracle_dev).requires_grad_(True)
     ref = OL.rgat_layer(x64, p["conv_weights"], p["attn_l"], p["attn_r"], s["rel_ptrs"].to(oracle_dev), s["row_indices"].to(oracle_dev),
-                        s["col_indices"].to(oracle_dev), N, 0.2, p.get("loop_weight"), p.get("h_bias"))
+                        s["col_indices"].to(oracle_dev), N, slope, p.get("loop_weight"), p.get("h_bias"))
     names = ["conv_weights", "attn_l", "attn_r"] + ["loop_weight"] * self_loop + ["h_bias"] * bias
     assert set(names) == set(p)
     grads_ref = [t.cpu() for t in torch.autograd.grad(ref, [x64] + [p[n] for n in names], go.double().to(oracle_dev))]
@@ -55,11 +62,17 @@ def _run_rgat(g, H, K, X, compact, direct, mulfirst, edge_parallel=True, seed=0,
     xd = x.to(DEV).requires_grad_(True)
     out = layer(g, xd)
     out.backward(go.to(DEV))
+    if forward_only:
+        with torch.no_grad():
+            out_eval = layer(g, x.to(DEV))
     g.cpu_()
     assert_close(out, ref, what="out")
     assert_close(xd.grad, grads_ref[0], what="grad_x")
     for n, gr in zip(names, grads_ref[1:]):
         assert_close(dict(layer.named_parameters())[n].grad, gr, what="grad_" + n)
+    if forward_only:
+        assert out_eval.grad_fn is None
+        assert_close(out_eval, ref, what="out (forward-only)")
 
 
 @pytest.mark.parametrize("compact,direct,mulfirst", [(False, False, False), (False, False, True), (True, False, False),
@@ -74,10 +87,10 @@ def test_rgat_layer_large_preactivations_stay_finite(compact):
     reference-named a4 here, would return inf / inf); the one-node layer subtracts a running maximum per (destination, head)
     and must agree with the fp64 oracle (whose raw exp is finite up to 709).  Graphs with and without destinations of more than
     256 in-edges (several work items that have to agree on one maximum)."""
-    from tests.util import rgat_min_abs_preactivation
     for g in (mag_graph(scale=5e-3), random_graph(seed=44, n=300, r=4, e=5000, shuffle=False)):
         s = g.get_separate_coo_original()
-        _run_rgat(g, H=4, K=64, X=64, compact=compact, direct=compact, mulfirst=False, attn_scale=300.0, seed=5)
+        for mulfirst in (False, True):  # (the forward-only fp32 call on the same input: _run_rgat's forward_only)
+            _run_rgat(g, H=4, K=64, X=64, compact=compact, direct=compact, mulfirst=mulfirst, attn_scale=300.0, seed=5, forward_only=True)
     # the scale really produces such values
     from het_amd.layers import HET_RGATLayer
     torch.manual_seed(5)

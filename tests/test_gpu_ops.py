@@ -207,10 +207,13 @@ def test_fused_gat_separate_coo(K, plan_mode, kind, H, D, n):
     fused_gat_case(K, random_graph(seed=21, n=n, r=4, e=5000), kind, H, D)
 
 
-def fused_gat_case(K, g, kind, H, D):
-    """relational_fused_gat_separate_coo and its backward on graph g against the oracle (also tests/test_gpu_thresholds.py)."""
+def fused_gat_case(K, g, kind, H, D, inputs=None, slope=0.2):
+    """relational_fused_gat_separate_coo and its backward on graph g against the oracle (also tests/test_gpu_thresholds.py).
+    inputs: (feat, el, er, go) in place of the seeded random ones (tests/test_gpu_rgat_kink.py)."""
     s, feat, el, er, go, df, db = _gat_case(g, kind, H, D, seed=9)
-    N, E, slope = g.get_num_nodes(), g.get_num_edges(), 0.2
+    if inputs is not None:
+        feat, el, er, go = inputs
+    N, E = g.get_num_nodes(), g.get_num_edges()
     idx = (s["eids"], s["rel_ptrs"], s["row_indices"], s["col_indices"])
     sm_r, ex_r, ret_r = (torch.empty(N, H, dtype=torch.float64), torch.empty(E, H, dtype=torch.float64),
                          torch.empty(N, H, D, dtype=torch.float64))
@@ -240,15 +243,21 @@ def test_gat_backward_streams_the_sorted_exp_its_forward_left(K, H, D):
     the backward streams it when (exp, el, er) come back untouched -- and falls back to gathering by edge id after an in-place
     edit of exp, with other el / er tensors, or with another exp: every case against the oracle (what the backward computes
     from the tensors it is GIVEN), hit / miss asserted through the Python registration's counter."""
+    sorted_exp_stream_case(K, random_graph(seed=23, n=300, r=4, e=5000), H, D)
+
+
+def sorted_exp_stream_case(K, g, H, D, inputs=None, slope=0.2):
+    """inputs: (feat, el, er, go) in place of the seeded random ones (tests/test_gpu_rgat_kink.py)."""
     import het_amd.kernels as k
     import het_amd.plan as plan
     old = plan.enabled
     plan.enabled = True
     plan.clear()
     try:
-        g = random_graph(seed=23, n=300, r=4, e=5000)
         s, feat, el, er, go, df, db = _gat_case(g, 0, H, D, seed=13)
-        N, E, slope = g.get_num_nodes(), g.get_num_edges(), 0.2
+        if inputs is not None:
+            feat, el, er, go = inputs
+        N, E = g.get_num_nodes(), g.get_num_edges()
         idx = (s["eids"], s["rel_ptrs"], s["row_indices"], s["col_indices"])
         didx = tuple(t.to(DEV) for t in idx)
         f, l, r_, god = feat.to(DEV), el.to(DEV), er.to(DEV), go.to(DEV)
@@ -294,10 +303,13 @@ def test_rgat_compact_passes(K, H, D, n, e, fold, bias):
     rgat_compact_case(K, random_graph(seed=27, n=n, r=4, e=e), H, D, fold, bias)
 
 
-def rgat_compact_case(K, g, H, D, fold, bias):
+def rgat_compact_case(K, g, H, D, fold, bias, inputs=None, slope=0.2):
+    """inputs: (feat, el, er, go) in place of the seeded random ones (tests/test_gpu_rgat_kink.py)."""
     import het_amd.kernels as k
     s, feat, el, er, go, df, db = _gat_case(g, 4, H, D, seed=11)
-    N, E, slope = g.get_num_nodes(), g.get_num_edges(), 0.2
+    if inputs is not None:
+        feat, el, er, go = inputs
+    N, E = g.get_num_nodes(), g.get_num_edges()
     idx = (s["eids"], s["rel_ptrs"], s["row_indices"], s["col_indices"])
     sm_r, ex_r, ret_r = (torch.empty(N, H, dtype=torch.float64), torch.empty(E, H, dtype=torch.float64),
                          torch.empty(N, H, D, dtype=torch.float64))
@@ -356,14 +368,15 @@ def test_rgat_compact_run_sums(K, H, D, n, e, fold, bias):
     rgat_run_sums_case(K, random_graph(seed=31, n=n, r=4, e=e), H, D, fold, bias)
 
 
-def rgat_run_sums_reference(g, H, D, fold, rows=lambda t: t):
+def rgat_run_sums_reference(g, H, D, fold, rows=lambda t: t, inputs=None, slope=0.2):
     """The CPU half of rgat_run_sums_case, shared with its bf16 twin (tests/test_gpu_bf16_ladders.py): the row maps of the run-sum
     form, the seeded inputs -- the activation rows feat / go passed through ``rows`` (the twin rounds them to bf16 once; they stay
-    fp32 tensors here) --, the oracle's CompactAsOfNodeKind-4 pair on them in fp64 and the run sums.  Returns a namespace."""
+    fp32 tensors here) --, the oracle's CompactAsOfNodeKind-4 pair on them in fp64 and the run sums.  inputs: a function (srow, drow) -> (feat, el, er, go)
+    of the edges' row maps, in place of the seeded random tensors.  Returns a namespace."""
     from types import SimpleNamespace
     s = g.get_separate_coo_original()
     ss = g.get_separate_unique_node_indices_single_sided()
-    N, E, R, slope = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels(), 0.2
+    N, E, R = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels()
     rel = torch.repeat_interleave(torch.arange(R), s["rel_ptrs"][1:] - s["rel_ptrs"][:-1])
 
     def rows_of(ptrs, nodes, ids):  # row of (relation, node) of every position in a unique (relation, node) list
@@ -376,6 +389,8 @@ def rgat_run_sums_reference(g, H, D, fold, rows=lambda t: t):
     gen = torch.Generator().manual_seed(13)
     feat, el, er = rows(torch.randn(S_row, H, D, generator=gen)), torch.randn(S_row, H, generator=gen), torch.randn(S_col, H, generator=gen)
     go, attn = rows(torch.randn(N, H, D, generator=gen)), torch.randn(R, H, D, generator=gen)
+    if inputs is not None:
+        feat, el, er, go = inputs(srow_p, drow_p)
     # the oracle's maps are indexed by edge id
     m_row, m_col = torch.empty(E, dtype=torch.int64), torch.empty(E, dtype=torch.int64)
     m_row[s["eids"]], m_col[s["eids"]] = srow_p, drow_p
@@ -413,9 +428,9 @@ def rgat_run_sums_groupings(c):
                                     drow_rel_ptrs=ss["rel_ptrs_col"].to(DEV))
 
 
-def rgat_run_sums_case(K, g, H, D, fold, bias):
+def rgat_run_sums_case(K, g, H, D, fold, bias, inputs=None, slope=0.2):
     import het_amd.kernels as k
-    c = rgat_run_sums_reference(g, H, D, fold)
+    c = rgat_run_sums_reference(g, H, D, fold, inputs=inputs, slope=slope)
     s, ss, N, R, slope, srow_p, drow_p, S_row, S_col, gen = c.s, c.ss, c.N, c.R, c.slope, c.srow_p, c.drow_p, c.S_row, c.S_col, c.gen
     feat, el, er, go, attn, rel_of_row, has_in = c.feat, c.el, c.er, c.go, c.attn, c.rel_of_row, c.has_in
     sm_r, ret_r, gf_r, gl_r, gr_r, q_ref, Q_ref = c.sm_r, c.ret_r, c.gf_r, c.gl_r, c.gr_r, c.q_ref, c.Q_ref
@@ -430,7 +445,7 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     sc = torch.exp(runs[2].double().cpu())
     assert_close(runs[1].double().cpu() * sc, q_ref, what="q_sum")
     assert_close(runs[0].double().cpu() * sc.unsqueeze(-1), Q_ref, what="q_rows")
-    if D == 16:
+    if D == 16 and R <= 8:  # (more than 8 relations: the pass gathers el_c as handed over -- "may form it", include/het_amd.h)
         # el_c that IS <feat_c, attn_l[relation of the row]> (the layer's case): with attn_l and the relation pointers of the rows the
         # pass forms it from the rows it gathers -- the el_c handed over is not read (NaN here) -- same sums as the gathered form
         rel_of_row_ = torch.repeat_interleave(torch.arange(R), ss["rel_ptrs_row"][1:] - ss["rel_ptrs_row"][:-1])
@@ -454,7 +469,8 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     gf, gl, gr = torch.full_like(f, float("nan")), torch.full_like(l, float("nan")), torch.full_like(r_, float("nan"))
     gb = torch.full((H * D,), float("nan"), device=DEV) if bias else None
     nb = N - 3
-    ga = torch.full((R, H, D), float("nan"), device=DEV) if fold else None  # (the attention-vector gradient from the same pass)
+    # (the attention-vector gradient from the same pass: the library takes it for up to 8 relations)
+    ga = torch.full((R, H, D), float("nan"), device=DEV) if fold and R <= 8 else None
     k.rgat_backward_compact(grp, f, l, r_, sm, ret, go.to(DEV), gf, gl, gr, slope, fold_attn_l=attn.to(DEV) if fold else None,
                             row_rel_ptrs=ss["rel_ptrs_row"].to(DEV) if fold else None, grad_bias=gb, bias_rows=nb, runs=runs,
                             drow_nodes=ss["node_indices_col"].to(DEV), grad_attn_l=ga)
@@ -463,7 +479,7 @@ def rgat_run_sums_case(K, g, H, D, fold, bias):
     assert_close(gr, gr_r, what="grad_er")
     if bias:
         assert_close(gb, to64(go).view(N, -1)[:nb].sum(0), what="grad_bias")
-    if fold:  # grad_attn_l[r,h,:] = SUM over the rows u of relation r of grad_el[u,h] * feat[u,h,:]
+    if fold and R <= 8:  # grad_attn_l[r,h,:] = SUM over the rows u of relation r of grad_el[u,h] * feat[u,h,:]
         assert_close(ga, c.ga_r, what="grad_attn_l")
     # the cache evicts and rebuilds the grouping by destination while the (destination, relation) one stays: the hub lists that
     # were built against the old object are rebuilt, same results
@@ -638,13 +654,20 @@ def test_fused_gat_hub_destination(K, plan_mode):
 
 @pytest.mark.parametrize("compact", [False, True])
 def test_fused_gat_csr(K, plan_mode, compact):
-    g = random_graph(seed=23, n=200, r=3, e=2500, empty_rel=False)
+    fused_gat_csr_case(K, plan_mode, random_graph(seed=23, n=200, r=3, e=2500, empty_rel=False), compact, 2, 8)
+
+
+def fused_gat_csr_case(K, plan_mode, g, compact, H, D, inputs=None, slope=0.2):
+    """The CSR pair on graph g against the oracle.  inputs: a function (n_rows) -> (feat, el, er, go) in place of the seeded random
+    tensors (tests/test_gpu_rgat_kink.py)."""
     i, o, u = g.get_in_csr(), g.get_out_csr(), g.get_separate_unique_node_indices()
-    N, E, H, D, slope = g.get_num_nodes(), g.get_num_edges(), 2, 8, 0.2
+    N, E = g.get_num_nodes(), g.get_num_edges()
     n_rows = int(u["rel_ptrs"][-1]) if compact else E
     gen = torch.Generator().manual_seed(1)
     feat, el, er = torch.randn(n_rows, H, D, generator=gen), torch.randn(n_rows, H, generator=gen), torch.randn(n_rows, H, generator=gen)
     go = torch.randn(N, H, D, generator=gen)
+    if inputs is not None:
+        feat, el, er, go = inputs(n_rows)
     sm_r, ex_r, ret_r = (torch.empty(N, H, dtype=torch.float64), torch.empty(E, H, dtype=torch.float64), torch.empty(N, H, D, dtype=torch.float64))
     O.relational_fused_gat_csr(i["row_ptrs"], i["col_indices"], i["eids"], i["rel_types"], u["rel_ptrs"], u["node_indices"],
                                to64(feat), to64(el), to64(er), sm_r, ex_r, ret_r, slope, compact)
@@ -673,7 +696,9 @@ def test_fused_gat_csr(K, plan_mode, compact):
     bwd_grouped = HL.kernel_timing_read("HET_gat_backward_grouped")[1] + HL.kernel_timing_read("HET_gat_backward_src")[1]
     HL.kernel_timing(False)
     import het_amd.kernels as k
-    if k.COMPILED_LIB:
+    if not k.gat_grouped_shape_ok(H, D):  # (a head width the grouped kernels do not take, e.g. 5: the edge kernels in either mode)
+        assert fwd_grouped == 0 and bwd_grouped == 0
+    elif k.COMPILED_LIB:
         # the compiled registration object has its own switch (HET_SHIM_GROUPINGS in its environment, not het_amd.plan): both CSR
         # pairs on the grouped kernels whatever plan_mode says
         assert fwd_grouped >= 1 and bwd_grouped >= 1, (fwd_grouped, bwd_grouped)
@@ -942,7 +967,8 @@ def test_fused_gat_with_folded_attn_l(H, D, nrel):
     folded_attn_l_case(random_graph(seed=77, n=300, r=nrel, e=5000, empty_rel=False), H, D)  # > 8 relations: separate weight-gradient pass
 
 
-def folded_attn_l_case(g, H, D):
+def folded_attn_l_case(g, H, D, inputs=None, slope=0.2):
+    """inputs: a function (E, R) -> (feat [E,H,D], attn [R,H,D], er [E,H], go) in place of the seeded random tensors."""
     import het_amd.backend as B
     s = g.get_separate_coo_original()
     assert not torch.equal(s["eids"], torch.arange(s["eids"].numel()))
@@ -952,6 +978,8 @@ def folded_attn_l_case(g, H, D):
     attn = (0.5 * torch.randn(R, H, D, generator=gen)).to(DEV)
     er = (0.5 * torch.randn(E, H, generator=gen)).to(DEV)
     go = torch.randn(g.get_num_nodes(), H, D, generator=gen).to(DEV)
+    if inputs is not None:
+        feat, attn, er, go = (t.to(DEV) for t in inputs(E, R))
     g.to_(DEV)
     sd = g.get_separate_coo_original()
     by_eid = {"separate_coo_rel_ptrs": sd["rel_ptrs"], "separate_coo_node_indices": sd["eids"],
@@ -960,11 +988,11 @@ def folded_attn_l_case(g, H, D):
     for fused in (False, True):
         f, a, r = (t.clone().requires_grad_(True) for t in (feat, attn, er))
         if fused:
-            assert B.relational_fused_gat_separate_coo_with_attn_l_ok(g, f, a, 0.2)
-            out = B.relational_fused_gat_separate_coo_with_attn_l(g, f, a, r, 0.2)
+            assert B.relational_fused_gat_separate_coo_with_attn_l_ok(g, f, a, slope)
+            out = B.relational_fused_gat_separate_coo_with_attn_l(g, f, a, r, slope)
         else:
             el = B.rgnn_relational_matmul(by_eid, a.unsqueeze(-1), f, False, 0).view(E, H)
-            out = B.relational_fused_gat_separate_coo(g, f, el, r, 0.2)
+            out = B.relational_fused_gat_separate_coo(g, f, el, r, slope)
         out.backward(go)
         outs.append((out.detach(), f.grad, a.grad, r.grad))
     g.cpu_()

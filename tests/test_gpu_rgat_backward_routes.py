@@ -21,17 +21,33 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GRAPHS = {"whole": (("random", 41, 400, 4, 6000), None),          # tests/test_gpu_layers.py: test_rgat_layer_variants
           "block": (("block", 5, 900, 4, 7000, 200), 200),        # every edge ends below num_dst = 200
-          "whole_num_dst": (("random", 41, 400, 4, 6000), 200)}   # num_dst < N and edges that end at or above it
+          "whole_num_dst": (("random", 41, 400, 4, 6000), 200),   # num_dst < N and edges that end at or above it
+          # tests/test_gpu_rgat_kink.py: the ladder graph (hubs of 257 .. 769 in-edges), the block a sampler makes of its first 120
+          # nodes (all the destination rungs) with all their in-edges, and num_dst = its 43 destination rungs with the edges into the pool kept
+          "ladder": (("ladder", 5, 0), None),
+          "ladder_block": (("ladder_block", 5, 0, 120), 120),
+          "ladder_num_dst": (("ladder", 5, 0), 43)}
 NAMES = ["conv_weights", "attn_l", "attn_r", "loop_weight", "h_bias"]
 
 
+def _build(spec):
+    if spec[0] != "ladder_block":
+        return build_graph(spec)
+    from het_amd.sampling import NeighborSampler
+    _, R, seed, nd = spec
+    block = NeighborSampler(build_graph(("ladder", R, seed)), [-1]).sample_block(torch.arange(nd), -1)
+    assert block.num_dst == nd
+    return block.graph
+
+
 @functools.lru_cache(maxsize=None)
-def _case(graph, H, K, X, mulfirst, self_loop, bias):
+def _case(graph, H, K, X, mulfirst, self_loop, bias, slope=0.2, case=None):
     """(layer state, x, gradout, oracle output [nd,X], oracle gradients by name) of a case, computed once: the cases that differ in
-    the side stream alone share it.  Nothing here is changed by a test."""
+    the side stream alone share it.  Nothing here is changed by a test.  case: the seed of pre-made inputs and parameters ON the
+    leaky-ReLU kink (tests/util.py: exact_rgat_case) in place of the random draw: no nudge, and the ties are asserted."""
     from het_amd.layers import HET_RGATLayer
     spec, nd = GRAPHS[graph]
-    g = build_graph(spec)
+    g = _build(spec)
     R, N = g.get_num_rels(), g.get_num_nodes()
     nd = N if nd is None else nd
     torch.manual_seed(7)
@@ -43,29 +59,35 @@ def _case(graph, H, K, X, mulfirst, self_loop, bias):
     x = torch.randn(N, K) * 0.5
     go = torch.randn(nd, X)
     s = g.get_separate_coo_original()
-    for _ in range(64):  # no (edge, head) on the leaky-ReLU kink (tests/util.py)
+    if case is not None:
+        from tests.util import assert_ties_on_hub_edges, exact_rgat_case, load_rgat_case
+        c = exact_rgat_case(g, H, K, X // H, case, bias=bias, self_loop=self_loop)
+        x, go = load_rgat_case(layer, c)
+        go = go[:nd]
+        assert_ties_on_hub_edges(c, s, N)
+    for _ in range(64 if case is None else 0):  # no (edge, head) on the leaky-ReLU kink (tests/util.py)
         if rgat_min_abs_preactivation(x, layer.conv_weights, layer.attn_l, layer.attn_r, s) >= 2e-6:
             break
         x = x + 1e-3 * torch.randn(N, K)
     p = {n: t.detach().double().requires_grad_(True) for n, t in layer.named_parameters()}
     x64 = x.double().requires_grad_(True)
-    ref = OL.rgat_layer(x64, p["conv_weights"], p["attn_l"], p["attn_r"], s["rel_ptrs"], s["row_indices"], s["col_indices"], N, 0.2,
+    ref = OL.rgat_layer(x64, p["conv_weights"], p["attn_l"], p["attn_r"], s["rel_ptrs"], s["row_indices"], s["col_indices"], N, slope,
                         p.get("loop_weight"), p.get("h_bias"))[:nd]
     wrt = {"x": x64, **p}
     grads = dict(zip(wrt, torch.autograd.grad(ref, list(wrt.values()), go.double())))
     return {n: t.detach().clone() for n, t in layer.state_dict().items()}, x, go, ref.detach(), grads
 
 
-def _run(monkeypatch, route, graph, H, K, X, mulfirst, self_loop, bias, overlap):
+def _run(monkeypatch, route, graph, H, K, X, mulfirst, self_loop, bias, overlap, slope=0.2, case=None):
     from het_amd import kernels as _k
     from het_amd.backend import rgat_fused_layer as FL
     from het_amd.layers import HET_RGATLayer
     monkeypatch.setattr(FL, "OVERLAP", overlap)
     monkeypatch.setattr(FL, "LITERAL_ER", not mulfirst)  # (False: er from the folded weight whatever the layer flag says)
     monkeypatch.setattr(FL, "PER_EDGE", False)
-    state, x, go, ref, grads_ref = _case(graph, H, K, X, mulfirst, self_loop, bias)
+    state, x, go, ref, grads_ref = _case(graph, H, K, X, mulfirst, self_loop, bias, slope, case)
     spec, nd = GRAPHS[graph]
-    g = build_graph(spec)
+    g = _build(spec)
     R = g.get_num_rels()
     assert _k.rgat_node_gemm_ok(R, H, K, X // H) == (X == 64), "the shapes of the routes are not what this file assumes"
     calls = {"node-major": 0, "generic": 0}
@@ -82,7 +104,7 @@ def _run(monkeypatch, route, graph, H, K, X, mulfirst, self_loop, bias, overlap)
     monkeypatch.setattr(_k, "rgat_node_backward_dx", counted_node_dx)
     monkeypatch.setattr(_k, "matmul_backward", counted_matmul_backward)
     layer = HET_RGATLayer(K, X, R, H, bias=bias, self_loop=self_loop, compact_as_of_node_flag=True, compact_direct_indexing_flag=True,
-                          multiply_among_weights_first_flag=mulfirst, dropout=0.0)
+                          multiply_among_weights_first_flag=mulfirst, dropout=0.0, leaky_relu_slope=slope)
     layer.load_state_dict(state)
     g.to_(DEV)
     layer = layer.to(DEV)

@@ -259,3 +259,162 @@ def check_round5_gat_pins(ops, dev, gold, lists, inputs, slope, rtol_exp=1e-6, a
         # atomics when the groupings are off) on the other: the repository's fp32 tolerance, not the 5e-5 that
         # the kind-0 pin happens to meet -- 1 element of 589 104 on the full topology differs by 8.4e-5 relative with atomics
         torch.testing.assert_close(per_node, gold[key], rtol=2e-4, atol=2e-5)
+
+
+# ---------------------------------------------------------------- inputs ON the leaky-ReLU kink, exact in every number format
+TINY = 2.0 ** -30  # expf(TINY) rounds to 1.0f in fp32 (half an ulp of 1 is 2^-24)
+
+
+def _grid(shape, values, gen):
+    """A tensor of `shape` drawn uniformly from the list `values`."""
+    v = torch.tensor(values, dtype=torch.float32)
+    return v[torch.randint(0, len(values), shape, generator=gen)]
+
+
+def exact_rgat_case(g, H, K, D, seed, zero_rows=0.15, bias=True, self_loop=True):
+    """Inputs of one RGAT layer on graph g drawn from small integer grids, so that every quantity a route forms on the way to the
+    pre-activation z = el + er is exact in fp32 and in bf16, in any association: x in {-1, 0, 1} (a fraction `zero_rows` of the
+    rows all zero: el = er = 0 there in every relation, so every edge between two such nodes sits exactly ON the leaky-ReLU
+    kink), W in {-1, 0, 1} / 4 (feat = x . W: multiples of 1/4 up to K / 4, 7 significant bits at K = 64), attn_l / attn_r in
+    {-1, 0, 1} / 2 (W . attn: multiples of 1/8; el, er, z: multiples of 1/8 below 2^11 / 8).  fp32, bf16 and fp64 therefore take the
+    same branch at every (edge, head), and the derivative AT z == 0 is `slope` (oracle: z > 0 ? 1 : slope).  Returns a dict of
+    fp32 CPU tensors: x [N,K], W [R,H,K,D], attn_l / attn_r [R,H,D], loop_weight [K,H*D] or None, h_bias [H*D] or None, go [N,H*D]
+    (multiples of 1/4 in [-2, 2]: exact in bf16)."""
+    gen = torch.Generator().manual_seed(seed)
+    N, R = g.get_num_nodes(), g.get_num_rels()
+    x = _grid((N, K), [-1.0, 0.0, 1.0], gen)
+    x[torch.rand(N, generator=gen) < zero_rows] = 0.0
+    return {"x": x,
+            "W": _grid((R, H, K, D), [-0.25, 0.0, 0.25], gen),
+            "attn_l": _grid((R, H, D), [-0.5, 0.0, 0.5], gen),
+            "attn_r": _grid((R, H, D), [-0.5, 0.0, 0.5], gen),
+            "loop_weight": _grid((K, H * D), [-0.25, 0.0, 0.25], gen) if self_loop else None,
+            "h_bias": _grid((H * D,), [i / 8 for i in range(-8, 9)], gen) if bias else None,
+            "go": _grid((N, H * D), [i / 4 for i in range(-8, 9)], gen)}
+
+
+def rgat_case_preactivations(c, sep, dtype=torch.float64, folded=False, bf16_feat=False):
+    """z [E,H] of an exact_rgat_case in `dtype`, as (x . W) . attn (literal) or x . (W . attn) (folded); bf16_feat: with the
+    projected rows rounded to bf16 before the dot with attn (literal form only)."""
+    R = c["W"].shape[0]
+    rel = torch.repeat_interleave(torch.arange(R), sep["rel_ptrs"][1:] - sep["rel_ptrs"][:-1])
+    x, W, al, ar = (c[n].to(dtype) for n in ("x", "W", "attn_l", "attn_r"))
+    if folded:
+        el_n = torch.einsum("nk,rhk->rnh", x, torch.einsum("rhkd,rhd->rhk", W, al))
+        er_n = torch.einsum("nk,rhk->rnh", x, torch.einsum("rhkd,rhd->rhk", W, ar))
+    else:
+        feat = torch.einsum("nk,rhkd->rnhd", x, W)
+        if bf16_feat:
+            feat = feat.to(torch.bfloat16).to(dtype)
+        el_n = (feat * al[:, None]).sum(-1)
+        er_n = (feat * ar[:, None]).sum(-1)
+    return el_n[rel, sep["row_indices"]] + er_n[rel, sep["col_indices"]]
+
+
+def rgat_case_tie_stats(c, sep, num_nodes):
+    """Where the ties of an exact_rgat_case sit: {"z": fp64 z [E,H], "tied_edges": edges with a tied head, "hub": tied edges ending
+    at a destination of more than 256 in-edges, "deg1": ... of exactly one in-edge}."""
+    z = rgat_case_preactivations(c, sep)
+    tied = (z == 0).any(1)
+    indeg = torch.bincount(sep["col_indices"], minlength=num_nodes)[sep["col_indices"]]
+    return {"z": z, "tied_edges": int(tied.sum()), "hub": int((tied & (indeg > 256)).sum()), "deg1": int((tied & (indeg == 1)).sum())}
+
+
+def assert_ties_on_hub_edges(c, sep, num_nodes, hub=1):
+    """The property that makes a layer test a test AT the kink: its input has exact ties, `hub` of them on edges into destinations of
+    more than 256 in-edges.  Asserted by every such test before it compares, so that a change of generator cannot quietly turn them
+    back into off-kink tests."""
+    st = rgat_case_tie_stats(c, sep, num_nodes)
+    assert st["tied_edges"] > 0 and st["hub"] >= hub, f"no ties on hub edges: {st['tied_edges']} tied edges, {st['hub']} into hubs"
+    return st
+
+
+GAT_Z_CLASSES = ("tie", "tiny+", "tiny-", "ordinary")
+
+
+def gat_z_class(z):
+    """Class index (GAT_Z_CLASSES) of every pre-activation: 0 tie, 1 z = +2^-30, 2 z = -2^-30, 3 |z| >= 1/8; -1 anything else."""
+    out = torch.full(z.shape, -1, dtype=torch.int64)
+    out[z == 0] = 0
+    out[z == TINY] = 1
+    out[z == -TINY] = 2
+    out[z.abs() >= 0.125] = 3
+    return out
+
+
+def exact_gat_case(srow, drow, col, ns, nd, num_nodes, H, D, seed, min_deg=8):
+    """Op-level inputs at the kink for the fused-GAT pairs: feat [ns,H,D], el [ns,H], er [nd,H], go [num_nodes,H,D] for edges whose
+    el / er rows are srow / drow (by position) and whose destinations are col.  Every z = el[srow] + er[drow] is an exact fp32 sum
+    of one of four classes (GAT_Z_CLASSES): an exact tie z == 0; z = +2^-30 (expf rounds to 1.0f: the grouped kernels have to
+    recover z > 0 from a stored exp that would be 1); z = -2^-30; an ordinary multiple of 1/8 with 1/8 <= |z| <= 4.  To keep the
+    sums exact a row holding +-2^-30 only meets rows holding 0: the er rows of every destination of `min_deg` in-edges or more
+    are 0 (its classes come from el: 0, +-2^-30, k/8), the other er rows are 0 or k/8, and an el row is +-2^-30 only where all
+    its edges meet er == 0.  Every class occurs among the in-edges of every destination of `min_deg` or more in-edges, for every
+    head: four of its source rows are pinned to the four classes (asserted).  feat in {-1, -1/2, 0, 1/2, 1}, go multiples of
+    1/4 in [-2, 2] (both exact in bf16)."""
+    gen = torch.Generator().manual_seed(seed)
+    ordinary = [k / 8 for k in range(-16, 17) if k != 0]
+    indeg = torch.bincount(col, minlength=num_nodes)
+    big_edge = indeg[col] >= min_deg
+    er = torch.where(torch.rand(nd, H, generator=gen) < 0.3, torch.zeros(nd, H), _grid((nd, H), ordinary, gen))
+    er[drow[big_edge]] = 0.0
+    meets_nonzero = torch.zeros(ns, H).index_add_(0, srow, (er[drow] != 0).float()) > 0  # [ns,H]
+    u = torch.rand(ns, H, generator=gen)
+    ordin = _grid((ns, H), ordinary, gen)
+    el_free = torch.where(u < 0.3, torch.zeros(ns, H), torch.where(u < 0.55, torch.full((ns, H), TINY),
+                          torch.where(u < 0.8, torch.full((ns, H), -TINY), ordin)))
+    el = torch.where(meets_nonzero, torch.where(u < 0.15, torch.zeros(ns, H), ordin), el_free)
+    # pin the four classes at every destination of min_deg or more in-edges (their er rows are 0: z = el there)
+    pinned = torch.zeros(ns, H, dtype=torch.bool)
+    order = torch.argsort(col, stable=True)
+    ptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(indeg, 0)])
+    want = (0.0, TINY, -TINY, 0.5)
+    for v in torch.nonzero(indeg >= min_deg).flatten().tolist():
+        rows = torch.unique(srow[order[ptr[v]:ptr[v + 1]]])
+        for h in range(H):
+            free = rows[~pinned[rows, h] & ~meets_nonzero[rows, h]][:4]
+            assert free.numel() == 4, f"destination {v}, head {h}: fewer than four source rows that can take any class"
+            el[free, h] = torch.tensor(want)
+            pinned[free, h] = True
+    feat = _grid((ns, H, D), [-1.0, -0.5, 0.0, 0.5, 1.0], gen)
+    go = _grid((num_nodes, H, D), [i / 4 for i in range(-8, 9)], gen)
+    return feat, el, er, go
+
+
+def load_rgat_case(layer, c):
+    """Copy the parameters of an exact_rgat_case into a HET_RGATLayer (same shapes; a parameter the case leaves out must be one the
+    layer does not have); returns (x, go)."""
+    have = dict(layer.named_parameters())
+    with torch.no_grad():
+        for name, key in (("conv_weights", "W"), ("attn_l", "attn_l"), ("attn_r", "attn_r"), ("loop_weight", "loop_weight"), ("h_bias", "h_bias")):
+            assert (c[key] is not None) == (name in have), name
+            if c[key] is not None:
+                have[name].copy_(c[key].view(have[name].shape))
+    return c["x"].clone(), c["go"].clone()
+
+
+def gat_rows_of_kind(g, kind):
+    """(srow, drow) by edge position: the rows of el / feat and of er that the fused-GAT pair of CompactAsOfNodeKind `kind` reads on
+    graph g, and (ns, nd), the row counts."""
+    from oracle import ops as O
+    from tests.test_oracle import _gat_dict, _gat_sizes
+    s = g.get_separate_coo_original()
+    srow, drow = O._gat_rows(kind, _gat_dict(g, kind)[0], s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"])
+    return srow, drow, _gat_sizes(g, kind)
+
+
+def assert_gat_ties_on_hub_edges(el, er, srow, drow, col, num_nodes):
+    """An op-level input has exact ties and the +-2^-30 classes on edges into destinations of more than 256 in-edges."""
+    cls = gat_z_class(el.double()[srow] + er.double()[drow])
+    hub = (torch.bincount(col, minlength=num_nodes) > 256)[col]
+    for k in (0, 1, 2):
+        assert int((cls[hub] == k).sum()) > 0, f"no z of class {GAT_Z_CLASSES[k]} on a hub edge"
+
+
+def exact_gat_case_of_kind(g, kind, H, D, seed):
+    """exact_gat_case for the rows of CompactAsOfNodeKind `kind` on graph g (ties on hub edges asserted)."""
+    srow, drow, (ns, nd) = gat_rows_of_kind(g, kind)
+    col, N = g.get_separate_coo_original()["col_indices"], g.get_num_nodes()
+    feat, el, er, go = exact_gat_case(srow, drow, col, ns, nd, N, H, D, seed)
+    assert_gat_ties_on_hub_edges(el, er, srow, drow, col, N)
+    return feat, el, er, go
