@@ -109,6 +109,12 @@ _ENTRIES = {
     "het_rows_linear_bias": [P, P, P, P, P, I64, I64, I64, P],
     "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
     "het_rows_add_bias": [P, P, P, P, I64, I64, P],
+    "het_rows_layer_norm_ok": [I64],
+    "het_rows_layer_norm_backward_workspace_bytes": (I64, [I64, I64, I64]),
+    "het_rows_layer_norm": [P, I64, P, P, P, DBL, P, P, P, I64, I64, P],
+    "het_rows_layer_norm_backward": [P, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P],
+    "het_rows_layer_norm_bf16": [P, I64, P, P, P, DBL, P, P, P, I64, I64, P],
+    "het_rows_layer_norm_backward_bf16": [P, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P],
     "het_rows_gather": [P, P, I64, I64, P, P],
     "het_rows_scatter_add": [P, P, I64, I64, P, P],
     "het_rows_scatter_add_grouped": [P, P, I64, P, I64, P],

@@ -383,6 +383,57 @@ class RowsLinearBf16(th.autograd.Function):
         return None, None, None, g_x, g_w
 
 
+def _typed_layer_norm_kernel_ok(y):
+    """Rows the layer-norm kernels take: a contiguous fp32 or bf16 [N, X] GPU tensor of a served width whose rows are 16-byte
+    (bf16: 8-byte) aligned."""
+    return (y.is_cuda and y.dim() == 2 and y.dtype in (th.float32, th.bfloat16) and y.is_contiguous()
+            and _k.rows_layer_norm_ok(y.shape[1]) and y.data_ptr() % (4 * y.element_size()) == 0)
+
+
+@_consistent_plan
+class TypedLayerNormFunction(th.autograd.Function):
+    """out[v] = LayerNorm(y[v]) * gamma[t(v)] + beta[t(v)] over the runs ``offs`` [T+1] of the rows, as one HIP launch and its
+    backward as two (csrc/rows_layer_norm.hip).  y and out share a row type (fp32, or bf16 with out and grad_y each rounded once at
+    the store); gamma / beta [T,X], the row statistics and both parameter gradients are fp32.  Keeps y, mean and rstd for the
+    backward; a call that needs no gradient (torch.no_grad()) passes NULL statistics and saves nothing."""
+
+    @staticmethod
+    def forward(ctx, offs, y, gamma, beta, eps, train):
+        """``train`` False (the caller runs under torch.no_grad(), or nothing needs a gradient): the statistics are not written."""
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        fwd = _k.rows_layer_norm_bf16 if y.dtype == th.bfloat16 else _k.rows_layer_norm
+        out, mean, rstd = fwd(offs, y, gamma, beta, eps, save_stats=train)
+        if train:
+            ctx.save_for_backward(y, gamma, mean, rstd, offs)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        y, gamma, mean, rstd, offs = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        if grad_out.data_ptr() % (4 * grad_out.element_size()):
+            grad_out = grad_out.clone()
+        bwd = _k.rows_layer_norm_backward_bf16 if y.dtype == th.bfloat16 else _k.rows_layer_norm_backward
+        g_y, g_gamma, g_beta = bwd(offs, y, gamma, mean, rstd, grad_out, want_y=ctx.needs_input_grad[1])
+        return None, g_y, (g_gamma if ctx.needs_input_grad[2] else None), (g_beta if ctx.needs_input_grad[3] else None), None, None
+
+
+def typed_layer_norm(y, offs, gamma, beta, eps=1e-5):
+    """The per-node-type LayerNorm of HGT's use_norm on the rows y [N, X]: row v of run t of ``offs`` [T+1] is normalised over its
+    columns (biased variance, eps inside the root) and meets gamma[t] / beta[t] ([T, X], one pair per run).  On the GPU, for
+    contiguous aligned fp32 / bf16 rows of a width that is a multiple of 4 up to 1024, this is TypedLayerNormFunction.  Everything
+    else (a width like 10, CPU tensors, non-contiguous or unaligned rows) is a plain torch composition -- F.layer_norm per run,
+    in fp32, cast back to y's dtype: correct, not fast."""
+    if _typed_layer_norm_kernel_ok(y) and gamma.is_cuda and gamma.dtype == th.float32 and beta.dtype == th.float32:
+        train = th.is_grad_enabled() and (y.requires_grad or gamma.requires_grad or beta.requires_grad)
+        return TypedLayerNormFunction.apply(offs, y, gamma, beta, float(eps), train)
+    bounds = offs.tolist()
+    X = y.shape[1]
+    parts = [th.nn.functional.layer_norm(y[a:b].float(), (X,), gamma[t].float(), beta[t].float(), eps)
+             for t, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])) if b > a]
+    return (th.cat(parts, dim=0) if parts else y.float()).to(y.dtype)
+
+
 def hgt_bf16_native_ok(G, K_in, num_heads, d_k, proj_in, out_dim):
     """Whether a bf16 layer input runs on the bf16 kernels: a full graph (one run per node type), input width and row width
     X = H * d_pad (heads zero-padded to a power of two >= 8) both 32 or 64, one head group, and an output projection of

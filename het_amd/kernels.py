@@ -1107,6 +1107,79 @@ def rows_linear_bias(offsets, x, w, bias, out=None):
     return _rows_linear_bias("het_rows_linear_bias", offsets, x, w, bias, out)
 
 
+# ---- typed LayerNorm over rows (HGT's use_norm; csrc/rows_layer_norm.hip): rows fp32 or bf16, everything else fp32 ----
+def rows_layer_norm_ok(X: int) -> bool:
+    """Row widths het_rows_layer_norm / _backward cover (a multiple of 4 in 4 .. 1024)."""
+    return bool(_lib.lib().het_rows_layer_norm_ok(int(X)))
+
+
+def _chk_f32_rows(name, rows, floats):
+    _chk(name, tuple(rows) + tuple(floats))
+
+
+def _ln_chk(name, chk_rows, offsets, rows, params, stats=()):
+    """Tensor checks of the four layer-norm wrappers: ``rows`` [N,X] of the entry's row type, ``params`` [T,X] and ``stats`` [N] fp32."""
+    chk_rows(name, rows, params + stats)
+    _chk(name, (), (offsets,))
+    N = rows[0].shape[0]
+    if (params[0].dim() != 2 or any(t.shape != params[0].shape for t in params) or offsets.numel() != params[0].shape[0] + 1
+            or any(t.shape != (N, params[0].shape[1]) for t in rows) or any(t.shape != (N,) for t in stats)):
+        raise _lib.HetError(f"{name}: rows {[tuple(t.shape) for t in rows]}, statistics {[tuple(t.shape) for t in stats]} and offsets "
+                            f"[{offsets.numel()}] do not fit the parameters {[tuple(t.shape) for t in params]}")
+
+
+def _rows_layer_norm(entry, offsets, y, gamma, beta, eps, save_stats):
+    N, T, X = y.shape[0], *gamma.shape
+    out = torch.empty_like(y)
+    mean = rstd = None
+    if save_stats:
+        mean = torch.empty(N, dtype=torch.float32, device=y.device)
+        rstd = torch.empty(N, dtype=torch.float32, device=y.device)
+    _call(y, entry, _p(offsets), T, _p(y), _p(gamma), _p(beta), float(eps), _p(out), _p(mean), _p(rstd), N, X, _stream(y))
+    return out, mean, rstd
+
+
+def _rows_layer_norm_backward(entry, offsets, y, gamma, mean, rstd, grad_out, want_y):
+    N, T, X = y.shape[0], *gamma.shape
+    grad_y = torch.empty_like(y) if want_y else None
+    if N == 0:
+        return grad_y, torch.zeros_like(gamma), torch.zeros_like(gamma)
+    grad_gamma, grad_beta = torch.empty_like(gamma), torch.empty_like(gamma)
+    ws, nbytes = _workspace(y, "het_rows_layer_norm_backward_workspace_bytes", N, T, X)
+    _call(y, entry, _p(offsets), T, _p(y), _p(gamma), _p(mean), _p(rstd), _p(grad_out), _p(grad_y), _p(grad_gamma), _p(grad_beta),
+          _p(ws), nbytes, N, X, _stream(y))
+    return grad_y, grad_gamma, grad_beta
+
+
+def rows_layer_norm(offsets, y, gamma, beta, eps=1e-5, save_stats=True):
+    """(out [N,X], mean [N], rstd [N]) of het_rows_layer_norm: row v of run t of ``offsets`` [T+1] normalised over its X columns
+    (biased variance) and scaled by gamma[t] / shifted by beta[t] ([T,X]).  ``save_stats=False``: mean and rstd are None and
+    nothing is written for a backward."""
+    _ln_chk("rows_layer_norm", _chk_f32_rows, offsets, (y,), (gamma, beta))
+    return _rows_layer_norm("het_rows_layer_norm", offsets, y, gamma, beta, eps, save_stats)
+
+
+def rows_layer_norm_backward(offsets, y, gamma, mean, rstd, grad_out, want_y=True):
+    """(grad_y [N,X] or None, grad_gamma [T,X], grad_beta [T,X]) of het_rows_layer_norm_backward; the parameter gradients are summed
+    without float atomics (the same bits every run)."""
+    _ln_chk("rows_layer_norm_backward", _chk_f32_rows, offsets, (y, grad_out), (gamma,), (mean, rstd))
+    return _rows_layer_norm_backward("het_rows_layer_norm_backward", offsets, y, gamma, mean, rstd, grad_out, want_y)
+
+
+def rows_layer_norm_bf16(offsets, y, gamma, beta, eps=1e-5, save_stats=True):
+    """rows_layer_norm with bf16 rows (het_rows_layer_norm_bf16): y and out bf16 (out rounded once at the store); gamma, beta, mean
+    and rstd fp32."""
+    _ln_chk("rows_layer_norm_bf16", _chk_bf16, offsets, (y,), (gamma, beta))
+    return _rows_layer_norm("het_rows_layer_norm_bf16", offsets, y, gamma, beta, eps, save_stats)
+
+
+def rows_layer_norm_backward_bf16(offsets, y, gamma, mean, rstd, grad_out, want_y=True):
+    """rows_layer_norm_backward with bf16 rows (het_rows_layer_norm_backward_bf16): y, grad_out and grad_y bf16; gamma, mean, rstd
+    and both parameter gradients fp32."""
+    _ln_chk("rows_layer_norm_backward_bf16", _chk_bf16, offsets, (y, grad_out), (gamma,), (mean, rstd))
+    return _rows_layer_norm_backward("het_rows_layer_norm_backward_bf16", offsets, y, gamma, mean, rstd, grad_out, want_y)
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None):

@@ -468,7 +468,19 @@ class HET_HGTLayerHetero(nn.Module):
         than 32 / 64.
     One branch inside the bf16 path keeps an fp32 buffer: a graph with more relations per node type than the node-major input
     gradient keeps in LDS (4 and more) adds a node's gradient terms relation by relation in an fp32 [N, in] buffer and rounds
-    it once; ``h``, ``kv_c``, ``q`` and ``new_h`` are bf16 there too."""
+    it once; ``h``, ``kv_c``, ``q`` and ``new_h`` are bf16 there too.
+
+    ``use_norm`` (the HGT paper's x = norm_t(W[t] . Agg(x)); HGT/models_dgl.py:131-138 applies the per-type ``LayerNorm(out_dim)`` the
+    HET class only builds, HGT/models.py:92-97): the layer's output y, on the full [N, out] result and before the ``num_dst`` slice,
+    becomes (y - mean) * rsqrt(var + norm_eps) * norm_weight[t] + norm_bias[t] per row, t the row's node type, var biased --
+    one HIP launch forward, two backward (backend/hgt_fused_layer.py: typed_layer_norm), at the end of every path above.
+    ``norm_weight`` (ones) and ``norm_bias`` (zeros) [T, out_dim] exist only with ``use_norm``; ``self.drop`` stays unapplied, as
+    in the reference's HET class.  A node without in-edges has y = 0, so its row is ``norm_bias[t]`` exactly.  Output widths that are
+    no multiple of 4 (10 classes) take F.layer_norm per type: correct, not fast.  bf16 activations add two roundings to the
+    contract above: on the bf16 kernels' path the norm reads the bf16 y the output projection stored, computes in fp32 and rounds
+    ``out`` once at its store, and its backward rounds ``grad_y`` once (the row statistics, norm_weight / norm_bias and their
+    gradients are fp32); on the upcast paths the norm runs in fp32 with the rest and the layer's one rounding follows it.  y is
+    kept for the backward: N * out * sizeof(row type) more memory than without the norm."""
 
     def __init__(self, num_ntypes, num_rels, in_dim, out_dim, num_heads=1, dropout=0.2, use_norm=False,
                  hgt_fused_attn_score_flag=False, compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
@@ -476,7 +488,6 @@ class HET_HGTLayerHetero(nn.Module):
         super().__init__()
         if not fused_message_mean_aggregation_flag:  # (the reference's HGT/models.py:251-277 branch)
             B.hgt_full_graph_edge_softmax_and_message_mean_aggregation_csr(None, None, None, None)  # raises HetUnsupported, named
-        assert not use_norm, "use_norm is off in the reference scripts"
         self.num_ntypes, self.num_relations, self.in_dim, self.out_dim = num_ntypes, num_rels, in_dim, out_dim
         self.num_heads, self.d_k = num_heads, out_dim // num_heads
         self.sqrt_dk = math.sqrt(self.d_k)
@@ -493,6 +504,10 @@ class HET_HGTLayerHetero(nn.Module):
         self.relation_msg = nn.Parameter(th.Tensor(num_rels, num_heads, self.d_k, self.d_k))
         self.skip = nn.Parameter(th.ones(num_ntypes, 1, 1, 1))
         self.drop = nn.Dropout(dropout)
+        self.use_norm, self.norm_eps = bool(use_norm), 1e-5
+        if self.use_norm:  # (registered only then: a layer without the norm keeps the state_dict it had)
+            self.norm_weight = nn.Parameter(th.ones(num_ntypes, out_dim))
+            self.norm_bias = nn.Parameter(th.zeros(num_ntypes, out_dim))
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -502,12 +517,22 @@ class HET_HGTLayerHetero(nn.Module):
     def forward(self, G, h, num_dst=None):
         """``num_dst``: ``G`` is a sampled block whose first ``num_dst`` nodes are its destinations (only their rows are
         returned); its nodes are runs of equal type (``node_segment_types``, het_amd/sampling.py) instead of one run per type."""
-        if h.dtype == th.bfloat16 and not _hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k):
-            # no bf16 kernels behind the op-by-op composition: fp32 on an upcast copy, one final rounding (class docstring)
+        if h.dtype == th.bfloat16 and not (_hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k) and (
+                not self.use_norm or _hgt_fused.hgt_bf16_native_ok(G, _padded_in_width(self.in_dim), self.num_heads, self.d_k,
+                                                                   self.out_dim, self.out_dim))):
+            # no bf16 kernels behind the op-by-op composition: fp32 on an upcast copy, one final rounding (class docstring).  With
+            # use_norm the fused path's own upcast (graphs and shapes without bf16 kernels) is taken here as well, so that the norm
+            # runs in fp32 inside the recursion and its result is the one value that is rounded.
             return self.forward(G, h.float(), num_dst).to(th.bfloat16)
         offs = G.get_original_node_type_offsets()
         seg_types = G.graph_data["original"].get("node_segment_types") if hasattr(G, "graph_data") else None
         per_run = (lambda w: w) if seg_types is None else (lambda w: w.index_select(0, seg_types))
+
+        def finish(out):
+            """use_norm on the full [N, out] result (one affine pair per run of ``offs``), then the destinations' rows."""
+            if self.use_norm:
+                out = _hgt_fused.typed_layer_norm(out, offs, per_run(self.norm_weight), per_run(self.norm_bias), self.norm_eps)
+            return out if num_dst is None else out[:num_dst]
         if _hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k):
             # attention + aggregation as one node on the distinct (relation, source) rows (backend/hgt_fused_layer.py): the
             # same function of the parameters for every flag combination below, without the per-edge tensors
@@ -520,9 +545,9 @@ class HET_HGTLayerHetero(nn.Module):
             out = _hgt_fused.hgt_layer_fused(G, h, offs, per_run(q_w), per_run(th.sigmoid(self.skip) * self.a_linears),
                                              k_w, v_w, self.relation_att, self.relation_msg,
                                              self.relation_pri, self.num_heads, self.hgt_fused_attn_score_flag)
-            return out if num_dst is None else out[:num_dst]
+            return finish(out)
         if self.multiply_among_weights_first_flag:
-            return self._forward_weights_first(G, h, offs, per_run, num_dst)
+            return finish(self._forward_weights_first(G, h, offs, per_run))
         k = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.k_linears), h).view(-1, self.num_heads, self.d_k)
         q = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.q_linears), h).view(-1, self.num_heads, self.d_k)
         v = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.v_linears), h).view(-1, self.num_heads, self.d_k)
@@ -551,9 +576,9 @@ class HET_HGTLayerHetero(nn.Module):
             self.relation_msg, v, G, (self.relation_pri / self.sqrt_dk), attn_score)
         out = B.rgnn_relational_matmul_no_scatter_gather_list(
             offs, per_run(th.sigmoid(self.skip) * self.a_linears), new_h.view(-1, self.out_dim))
-        return out if num_dst is None else out[:num_dst]
+        return finish(out)
 
-    def _forward_weights_first(self, G, h, offs, per_run, num_dst):
+    def _forward_weights_first(self, G, h, offs, per_run):
         """--multiply_among_weights_first_flag (see the class docstring): two small batched products per step replace the three
         typed projections of the nodes; the per-relation [in,in] / [in,dk] weights then meet the layer input directly."""
         H, dk = self.num_heads, self.d_k
@@ -578,6 +603,5 @@ class HET_HGTLayerHetero(nn.Module):
             attn_score = B.rgnn_inner_product_right_node(G, per_edge, hh, 0, "_col")
         new_h = B.hgt_full_graph_message_calc_edge_softmax_and_message_mean_aggregation_coo(
             w_msg.contiguous(), hh, G, (self.relation_pri / self.sqrt_dk), attn_score)
-        out = B.rgnn_relational_matmul_no_scatter_gather_list(
+        return B.rgnn_relational_matmul_no_scatter_gather_list(
             offs, per_run(th.sigmoid(self.skip) * self.a_linears), new_h.view(-1, self.out_dim))
-        return out if num_dst is None else out[:num_dst]

@@ -74,12 +74,13 @@ class HET_HGTModel(nn.Module):
     """hrt/python/HGT/models.py:246-347 (stack of HET_HGTLayerHetero)."""
 
     def __init__(self, num_ntypes, num_rels, h_dim, out_dim, num_heads, num_layers=1, dropout=0.2,
-                 multiply_among_weights_first_flag=False, hgt_fused_attn_score_flag=False):
+                 multiply_among_weights_first_flag=False, hgt_fused_attn_score_flag=False, use_norm=False):
         super().__init__()
         dims = [h_dim] * num_layers + [out_dim]
         self.layers = nn.ModuleList([HET_HGTLayerHetero(num_ntypes, num_rels, dims[i], dims[i + 1], num_heads=num_heads,
                                                         dropout=dropout, hgt_fused_attn_score_flag=hgt_fused_attn_score_flag,
-                                                        multiply_among_weights_first_flag=multiply_among_weights_first_flag)
+                                                        multiply_among_weights_first_flag=multiply_among_weights_first_flag,
+                                                        use_norm=use_norm)
                                      for i in range(num_layers)])
 
     def forward(self, g, h):
@@ -127,6 +128,8 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
     p.add_argument("--bf16_training", action="store_true",
                    help="RGAT only: bf16 input features and layers built with bf16_training=True (het_amd/layers.py: bf16 rows, fp32 "
                         "parameters and sums); the loss is taken on the logits cast to fp32")
+    p.add_argument("--use_norm", action="store_true",
+                   help="HGT only: the per-node-type LayerNorm after every layer's output projection (het_amd/layers.py)")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -245,6 +248,8 @@ def main(argv=None):
     dev = th.device("cuda")
     if args.bf16_training and args.model != "rgat":
         raise SystemExit("--bf16_training is an option of the RGAT layer (RGCN and HGT train in bf16 on a bf16 input as they are)")
+    if args.use_norm and args.model != "hgt":
+        raise SystemExit("--use_norm is an option of the HGT layer")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -273,7 +278,7 @@ def main(argv=None):
         model = HET_HGTModel(g.get_num_ntypes(), R, args.n_infeat, args.num_classes, args.num_heads,
                              num_layers=args.num_layers, dropout=args.dropout,
                              multiply_among_weights_first_flag=args.multiply_among_weights_first_flag,
-                             hgt_fused_attn_score_flag=getattr(args, "hgt_fused_attn_score_flag", False))
+                             hgt_fused_attn_score_flag=getattr(args, "hgt_fused_attn_score_flag", False), use_norm=args.use_norm)
     model = model.to(dev)
     labels = th.randint(0, args.num_classes, (N,), device=dev)  # random labels as train_dgl.py:132-148
     params = list(model.parameters()) + list(embed.parameters())
@@ -310,6 +315,8 @@ def main(argv=None):
         res["activations"] = "bf16"
     else:
         del res["args"]["bf16_training"]
+    if not args.use_norm:
+        del res["args"]["use_norm"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

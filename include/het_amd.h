@@ -921,6 +921,38 @@ int het_rows_linear_bias_bf16(const int64_t* offsets, const het_bf16* x, const f
 int het_rows_add_bias(const float* a, const float* b, const float* bias, float* out, int64_t num_rows, int64_t X,
                       het_stream stream);
 
+/* Typed LayerNorm over rows (HGT's use_norm, HGT/models_dgl.py:131-138: one LayerNorm(out_dim) per node type after the typed output
+ * projection).  Row v of the run t of offsets [T+1] (device array, non-decreasing, offsets[0] = 0, offsets[T] = num_rows) that holds it:
+ *   mean_v = SUM_j y[v,j] / X    var_v = SUM_j (y[v,j] - mean_v)^2 / X  (biased, as torch.nn.LayerNorm; two-pass in registers)
+ *   out[v,:] = (y[v,:] - mean_v) * rsqrt(var_v + eps) * gamma[t,:] + beta[t,:]          gamma, beta [T,X] fp32
+ * Shapes: X % 4 == 0, 4 <= X <= 1024, y / out rows 16-byte aligned (8-byte for the bf16 entries), gamma / beta 16-byte aligned:
+ * HET_ERR_UNSUPPORTED otherwise, before any launch (het_rows_layer_norm_ok answers for the width).  Null data pointers are
+ * HET_ERR_INVALID_ARG; num_rows == 0 is HET_OK.  Rows outside [0, num_rows) are never touched whatever offsets holds. */
+int het_rows_layer_norm_ok(int64_t X);
+/* bytes of the backward's workspace (one partial row pair [2,X] per row tile, fp32); -1 for an unsupported width */
+int64_t het_rows_layer_norm_backward_workspace_bytes(int64_t num_rows, int64_t num_types, int64_t X);
+/* forward: writes out [num_rows,X] and, when both are given, mean / rstd [num_rows] fp32 for the backward (both NULL: an
+ * evaluation pass, nothing is saved) */
+int het_rows_layer_norm(const int64_t* offsets, int64_t num_types, const float* y, const float* gamma, const float* beta, double eps,
+                        float* out, float* mean, float* rstd, int64_t num_rows, int64_t X, het_stream stream);
+/* backward, one pass over y, grad_out, mean, rstd: with xhat = (y - mean) * rstd and a = grad_out * gamma[t],
+ *   grad_y = rstd * (a - mean_j(a) - xhat * mean_j(a * xhat))                      (grad_y NULL: not wanted)
+ *   grad_gamma[t,:] = SUM_v grad_out[v,:] * xhat[v,:]    grad_beta[t,:] = SUM_v grad_out[v,:]     over the rows v of type t
+ * The column sums leave the pass as one partial per row tile (workspace) and a second small launch adds a type's partials in a
+ * fixed order: no float atomics, the same bits every run.  grad_gamma / grad_beta [T,X] are written whole (zeros for an empty type);
+ * num_rows == 0 writes nothing. */
+int het_rows_layer_norm_backward(const int64_t* offsets, int64_t num_types, const float* y, const float* gamma, const float* mean,
+                                 const float* rstd, const float* grad_out, float* grad_y, float* grad_gamma, float* grad_beta,
+                                 void* workspace, int64_t workspace_bytes, int64_t num_rows, int64_t X, het_stream stream);
+/* ... with bf16 rows: y, out, grad_out and grad_y het_bf16 (widened on load, each result rounded once, to nearest even, at its
+ * store); gamma, beta, mean, rstd, every sum and both parameter gradients fp32 */
+int het_rows_layer_norm_bf16(const int64_t* offsets, int64_t num_types, const het_bf16* y, const float* gamma, const float* beta,
+                             double eps, het_bf16* out, float* mean, float* rstd, int64_t num_rows, int64_t X, het_stream stream);
+int het_rows_layer_norm_backward_bf16(const int64_t* offsets, int64_t num_types, const het_bf16* y, const float* gamma,
+                                      const float* mean, const float* rstd, const het_bf16* grad_out, het_bf16* grad_y,
+                                      float* grad_gamma, float* grad_beta, void* workspace, int64_t workspace_bytes, int64_t num_rows,
+                                      int64_t X, het_stream stream);
+
 /* Halo pack / unpack of the multi-GPU path (no reference counterpart: het_amd/dist.py pushes the features of remote source
  * nodes with an all-to-all before the forward and returns their gradients after the backward).
  *   het_rows_gather:       out[i, :] = x[idx[i], :]        i in [0, num_rows)   (X % 4 == 0, 16-byte aligned rows)
