@@ -75,12 +75,15 @@ _ENTRIES = {
     "het_rgat_aggregate_compact_runs": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
     "het_rgat_backward_compact_runs": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_rgat_backward_compact_runs_workspace": (I64, [P, I64, I64, I64, I64, INT, INT, P]),
+    "het_rgat_backward_compact_runs_edges": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
+    "het_rgat_attn_grad_finish": [P, I64, I64, I64, I64, I64, INT, P, P, I64, P],
     "het_rgat_aggregate_compact_forward_workspace": (I64, [P, P, I64, I64, I64, P]),
     "het_rgat_aggregate_compact_forward": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_aggregate_compact_forward_bf16": [P, P, I64, P, P, P, I64, I64, DBL, P, I64, P, P, P, I64, P],
     "het_rgat_el_rows_bf16": [P, I64, P, P, P, I64, I64, I64, P],
     "het_rgat_aggregate_compact_runs_bf16": [P, P, I64, P, P, P, P, P, I64, I64, I64, DBL, P, I64, P, P, P, I64, P, P, P, I64, P],
     "het_rgat_backward_compact_runs_bf16": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
+    "het_rgat_backward_compact_runs_edges_bf16": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, DBL, P, P, I64, P],
     "het_rgat_attention_compact_workspace": (I64, [P, I64, I64, INT]),
     "het_rgat_attention_compact": [P, P, P, I64, DBL, P, P, P, P, I64, I64, P, P, P, I64, P],
     "het_rows_matmul_backward_dx": [P, I64, P, P, I64, P, P, P, I64, I64, I64, INT, P],
@@ -96,6 +99,8 @@ _ENTRIES = {
     "het_node_row_map": [P, I64, P, I64, I64, P, P],
     "het_rgat_node_backward_dx": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
     "het_rgat_node_backward_dx_bf16": [I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, P],
+    "het_rgat_transpose_weights": [P, I64, I64, I64, I64, P, P, I64, P, P],
+    "het_rgat_unfold_weight_gradient": [P, P, P, I64, I64, I64, I64, P, P, P],
     "het_node_rows_matmul_sum_ok": [I64, I64, I64],
     "het_node_rows_matmul_sum": [I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, P, P],
     "het_node_rows_matmul_sum_bias": [I64, I64, I64, I64, P, P, P, P, P, P, P, I64, I64, P, P],

@@ -150,7 +150,14 @@ def _side_stream(dev):
     its inputs), so the allocator never sees a cross-stream use.
     Everything the side stream WRITES is allocated before the fork (``side.wait_stream(main)``): a block handed out later may
     have been freed by a tensor whose last main-stream kernel was enqueued after the fork -- the side stream would not wait
-    for it."""
+    for it.
+    Everything the side stream READS that no output of the step keeps alive stays referenced until the join
+    (``main.wait_stream(side)``) has been enqueued: the workspace of the backward's edge pass, whose partial rows of grad_attn_l the
+    side stream sums (kernels.rgat_attn_grad_finish) -- released earlier, its block could go to a main-stream allocation made
+    between the fork and the join, and that tensor's kernels would not wait for the side stream's read.
+    What runs there, per step: forward -- the er row-dot and the self-loop GEMM beside the projection;
+    backward -- the self-loop's weight gradient beside the gather passes (first fork), then the attention-gradient finish and the
+    weight gradients of W and W.attn_r beside the node-major pass (second fork)."""
     s = _SIDE.get(dev)
     if s is None:
         s = _SIDE[dev] = th.cuda.Stream(device=dev)
@@ -169,16 +176,15 @@ def _unique_lists(g):
 def _folded_weight(W, attn_r):
     """wa[r,h,k] = SUM_d W[r,h,k,d] * attn_r[r,h,d] (RGAT/models.py:300-326): the attention vector folded into the weight, as the
     one-input-head weight [R,H,K,1] of the relational products; its transpose [R,H,1,K] and the rows [R,H,K] of the row-dot and
-    node-major kernels are views of the same memory."""
+    node-major kernels are views of the same memory.  Once per step, in the forward; the backward takes it from the context."""
     R, H, Kd, D = W.shape
     return th.bmm(W.view(-1, Kd, D), attn_r.view(-1, D, 1)).view(R, H, Kd, 1)
 
 
 def _unfold_weight_gradient(grad_wa, W, attn_r, grad_W):
-    """The gradient through _folded_weight: grad_W += grad_wa (x) attn_r in place; returns grad_attn_r.  grad_wa [R,H,K,1]."""
-    R, H, Kd, D = W.shape
-    grad_W.addcmul_(grad_wa, attn_r.view(R, H, 1, D))
-    return (W * grad_wa).sum(2)
+    """The gradient through _folded_weight: grad_W += grad_wa (x) attn_r in place; returns grad_attn_r.  grad_wa [R,H,K,1].  One
+    launch, sums in a fixed order (csrc/node_gemm.hip: HET_rgat_unfold_weight_gradient)."""
+    return _k.rgat_unfold_weight_gradient(grad_wa, W, attn_r, grad_W)
 
 
 def _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias):
@@ -222,9 +228,9 @@ def _loop_offsets(nd, device):
     return offs
 
 
-def _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst, halo=None):
-    """What every forward starts with: contiguous operands, the destination rows nd, the self-loop's pointer list and the folded
-    weight (None unless ``mulfirst``).  Returns (x, W, attn_l, attn_r, loop_w, nd, offs, wa)."""
+def _prologue(x, W, attn_l, attn_r, loop_w, num_dst, halo=None):
+    """What every forward starts with: contiguous operands, the destination rows nd and the self-loop's pointer list.  Returns
+    (x, W, attn_l, attn_r, loop_w, nd, offs)."""
     x, W, attn_l, attn_r = x.contiguous(), W.contiguous(), attn_l.contiguous(), attn_r.contiguous()
     if halo is not None:
         # multi-GPU (het_amd/dist.py): x holds the owned rows; the halo rows of x_local arrive through an all-to-all
@@ -236,7 +242,7 @@ def _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst, halo=None):
     if loop_w is not None:
         loop_w = loop_w.contiguous()
         offs = _loop_offsets(nd, x.device)
-    return x, W, attn_l, attn_r, loop_w, nd, offs, _folded_weight(W, attn_r) if mulfirst else None
+    return x, W, attn_l, attn_r, loop_w, nd, offs
 
 
 def _loop_and_bias_rows(rows, x, nd, offs, loop_w, bias):
@@ -251,11 +257,15 @@ def _loop_and_bias_rows(rows, x, nd, offs, loop_w, bias):
     return _k.rows_add_bias(rows, loop, None if bias is None else bias.contiguous())
 
 
-def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias):
+def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, loop_w, bias, for_backward=False):
     """The distinct-row forward in front of its aggregation, common to RgatLayerFunction.forward and _forward_only: the
     projections feat_c / el_c / er_c on the unique (relation, node) rows, the self-loop + bias rows ``h`` the aggregation adds into
     (None when there is no self-loop or its fused launch does not take the widths) and the groupings of the edges.  Returns
-    (ss, h, saved, grp, run_sums); saved = (feat_c, el_c, er_c[, feat_d])."""
+    (ss, h, saved, grp, run_sums, forms); saved = (feat_c, el_c, er_c[, feat_d]).
+    ``forms`` = (W^T [R,H,D,K], loop_w^T [X,K] or None, wa [R,H,K,1] or None), the forms of the parameters the step's kernels read:
+    the folded weight wa (``mulfirst``), once per step; the transposes -- ``for_backward`` alone, else None: only the backward reads
+    them -- as one launch behind the projection, on the stream that has slack there (the projection ends before the self-loop's
+    launch beside it does: profiles/r11/default_timeline_after.txt)."""
     s, _, _ = _lists(g)
     rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
     N = x.shape[0]
@@ -276,6 +286,10 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
         # er_c (a row-dot) and the self-loop GEMM are HBM-bound streams of rows: on the side stream beside the projection
         main, side = th.cuda.current_stream(x.device), _side_stream(x.device)
         h = x.new_empty((nd, X))  # (with erc above: what the side stream writes, allocated before the fork -- _side_stream)
+    # (in front of the fork: on the side stream, in front of its one reader here, the bmm's 16 workgroups waited 0.09 ms for a
+    #  slot behind the projection's 1 857 and the row-dot started that much later -- DESIGN.md 4.2)
+    wa = _folded_weight(W, attn_r) if mulfirst else None
+    if side is not None:
         side.wait_stream(main)
     if mulfirst:
         with th.cuda.stream(side if side is not None else th.cuda.current_stream(x.device)):
@@ -310,6 +324,7 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
     else:  # other widths: any-shape projection, then el_c as a row-dot over the relation-bucketed rows
         K.rgnn_relational_matmul(d_row, 1, W, x, featc, True)
         K.rgnn_relational_matmul_no_scatter_gather_list(ss["rel_ptrs_row"], attn_l.unsqueeze(-1), featc, elc.view(-1, H, 1))
+    Wt, loop_wt = _k.rgat_transpose_weights(W, loop_w) if for_backward else (None, None)
     if side is not None:
         th.cuda.current_stream(x.device).wait_stream(side)
     # edge softmax + aggregation straight from the compact tables: no exp [E,H] tensor (csrc/gat_compact.hip)
@@ -318,7 +333,7 @@ def _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, w
     run_sums = _k.rgat_runs_shape_ok(H, D)
     grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp if run_sums else None,
                                     drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
-    return ss, h, saved, grp, run_sums
+    return ss, h, saved, grp, run_sums, (Wt, loop_wt, wa)
 
 
 def _per_relation_front(x, loop_w, offs, grad_h, nd, H, dst_prefix):
@@ -348,7 +363,7 @@ class RgatLayerFunction(th.autograd.Function):
     @staticmethod
     def forward(ctx, g, compact, direct, mulfirst, slope, num_dst, halo, x, W, attn_l, attn_r, loop_w, bias):
         assert halo is None or (compact and mulfirst and loop_w is not None), "rgat_layer_halo_ok guards this path"
-        x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst, halo)
+        x, W, attn_l, attn_r, loop_w, nd, offs = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, halo)
         s, by_src, by_dst = _lists(g)
         rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
         E, N = eids.numel(), x.shape[0]
@@ -358,7 +373,8 @@ class RgatLayerFunction(th.autograd.Function):
         sm, ret = new(N, H), new(N, H, D)
         h = None
         if compact:
-            ss, h, saved, grp, run_sums = _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
+            ss, h, saved, grp, run_sums, ctx.forms = _compact_tables(g, direct, mulfirst, halo, nd, offs, x, W, attn_l, attn_r, loop_w, bias,
+                                                                      for_backward=True)
             featc, elc, erc = saved[:3]
             # (elc IS <featc, attn_l[relation of the row]>: the pass may form it from the rows it gathers -- kernels.py)
             ctx.runs = _k.rgat_aggregate_compact(grp, featc, elc, erc, sm, ret, slope, h_inout=h, num_rels=R,
@@ -373,7 +389,7 @@ class RgatLayerFunction(th.autograd.Function):
             feat, el_s, er_s, exs = new(E, H, D), new(E, H), new(E, H), new(E, H)
             _k.matmul_attn_dot(by_src, 0, W, x, feat, attn_l, el_s, dot_rows=rank)
             if mulfirst:
-                K.rgnn_relational_matmul(by_dst_s, 0, wa, x, er_s.view(E, H, 1), True)
+                K.rgnn_relational_matmul(by_dst_s, 0, _folded_weight(W, attn_r), x, er_s.view(E, H, 1), True)
                 saved = (feat, exs)
             else:
                 comp = _k.matmul_attn_dot(by_dst_s, 0, W, x, None, attn_r, er_s)
@@ -461,9 +477,17 @@ class RgatLayerFunction(th.autograd.Function):
                                   nd -- launches that form an input and a weight gradient together, "+=").
         On all but the generic route the weight gradients are launches of their own, HBM-bound streams of rows: on the side stream
         beside the gather passes and the matrix-core-bound node pass; the self-loop's needs x and grad_h only and starts at once.
+        Nothing that depends on the parameters alone is made here: W^T, loop_w^T and the folded weight wa come from the forward
+        (ctx.forms, _compact_tables) -- as launches of the backward they stood where the whole chip waited for them, in front of the
+        edge pass and between it and the node-major pass.  On the node-major routes with the side stream the edge pass also leaves
+        the sum of grad_attn_l's partial rows to the side stream (after the second fork, in front of the weight gradients): the
+        node-major pass starts where the edge pass ends.  The fold of grad_wa back into grad_W / grad_attn_r behind the last join is
+        one launch (_unfold_weight_gradient).
         bf16 rows (RgatLayerBf16Function: x, feat_c and grad_h bf16): the node-major route alone, with the bf16 entries; every
         gradient table and parameter gradient is fp32, grad_x bf16."""
         x, W, attn_l, attn_r, loop_w, offs, sm, _, ret, featc, elc, erc, *featd = ctx.saved_tensors
+        # (the forms of the parameters the forward made for this step: W^T [R,H,D,K], loop_w^T [X,K], wa [R,H,K,1] -- _compact_tables)
+        Wt, loop_wt, wa = ctx.forms
         g, nd, slope, halo, runs, has_loop, has_bias, mulfirst = ctx.g, ctx.nd, ctx.slope, ctx.halo, ctx.runs, ctx.has_loop, ctx.has_bias, ctx.mulfirst
         N, Kd = x.shape
         R, H, _, D = W.shape
@@ -491,7 +515,6 @@ class RgatLayerFunction(th.autograd.Function):
         # (bf16 rows: the bf16 weight-gradient entry has no column-sum form; the edge pass sums the bf16 rows on its side stream)
         bias_in_dw = not generic and has_bias and has_loop and not bf16
         main, side = th.cuda.current_stream(x.device), _side_stream(x.device) if OVERLAP and not generic else None
-        Wt = th.transpose(W, 2, 3).contiguous()
         if generic:
             grad_x, grad_loop, go = _per_relation_front(x, loop_w if has_loop else None, offs, grad_h, nd, H, dst_prefix)
         else:
@@ -524,15 +547,16 @@ class RgatLayerFunction(th.autograd.Function):
         if per_relation_halo:  # the self-loop's rows of grad_x first, plain stores
             grad_x = th.empty_like(x)
             grad_x[nd:].zero_()  # halo rows: only the projection's input gradient adds to them
-            _k.rows_matmul_backward_dx(offs, None, loop_w.t().contiguous().view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
+            _k.rows_matmul_backward_dx(offs, None, loop_wt.view(1, 1, X, Kd), grad_h, grad_x[:nd], atomic=False)
         grad_attn_l = th.empty_like(attn_l)  # (written by the edge pass on this stream, or after the second fork)
         # the bias gradient (column sums of grad_h) from the pass that reads every gradout row anyway, unless bias_in_dw
-        (_k.rgat_backward_compact_bf16 if bf16 else _k.rgat_backward_compact)(
+        # (the sum of grad_attn_l's partial rows is left to the side stream where the second fork follows: the node-major pass, which
+        #  does not read it, starts where the edge pass ends.  ``attn_finish`` holds the workspace with those rows: it stays referenced
+        #  until this function returns, i.e. past main.wait_stream(side), so no later allocation is handed its block -- _side_stream)
+        attn_finish = (_k.rgat_backward_compact_bf16 if bf16 else _k.rgat_backward_compact)(
             ctx.grp, featc, elc, erc, sm[:ndp], ret[:ndp], go, g_featc, g_elc, g_erc, slope, fold_attn_l=attn_l, row_rel_ptrs=rp_row,
             grad_bias=None if bias_in_dw else grad_bias, bias_rows=nd, runs=runs, drow_nodes=ss["node_indices_col"],
-            grad_attn_l=grad_attn_l if attn_in_pass else None)
-        if mulfirst:
-            wa = _folded_weight(W, attn_r)
+            grad_attn_l=grad_attn_l if attn_in_pass else None, finish_attn_grad=not (attn_in_pass and node_major and side is not None))
         # what the launches below write: "=" outputs are allocated, "+=" outputs zero-filled
         if node_major:
             grad_x = th.empty_like(x)
@@ -564,7 +588,6 @@ class RgatLayerFunction(th.autograd.Function):
         if node_major:
             row_map = _k.node_row_map(rp_row, rows_node, N)
             dst_map = _k.node_row_map(ss["rel_ptrs_col"], ss["node_indices_col"], N)
-            loop_wt = loop_w.t().contiguous() if has_loop else None
             # (on a block or a partition only the first nd nodes carry the self-loop term: they stay in front, so that term's
             #  tiles are whole too)
             order = _k.node_order_by_presence(row_map, dst_map, split=nd if nd < N else None)
@@ -582,6 +605,8 @@ class RgatLayerFunction(th.autograd.Function):
                 # (the second fork: grad_W / grad_wa / grad_attn_l are allocated above it)
                 side.wait_stream(main)
                 with th.cuda.stream(side):
+                    if attn_finish is not None:
+                        _k.rgat_attn_grad_finish(attn_finish)
                     weight_gradients()
             input_gradient(0, N if halo is None else nd)
             if side is None:
@@ -635,9 +660,9 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     nothing saved), the same projections and the same self-loop rows, and an aggregation that writes the layer output alone
     (csrc/gat_compact.hip: the _fwd kernels) -- no lse [N,H], no ret [N,H,D], no run sums [S_col,H,D].  Every output row is bit
     for bit the training forward's.  ``attn_out`` (a list): the attention weights [E,H] are appended to it."""
-    x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, mulfirst)
+    x, W, attn_l, attn_r, loop_w, nd, offs = _prologue(x, W, attn_l, attn_r, loop_w, num_dst)
     R, H, _, D = W.shape
-    ss, h, saved, grp, _ = _compact_tables(g, direct, mulfirst, None, nd, offs, x, W, attn_l, attn_r, wa, loop_w, bias)
+    ss, h, saved, grp, _, _ = _compact_tables(g, direct, mulfirst, None, nd, offs, x, W, attn_l, attn_r, loop_w, bias)
     featc, elc, erc = saved[:3]
     fused = h is not None
     if not fused:  # no self-loop rows to add into (no self-loop, or widths its fused launch does not take): zeros, the tail below
@@ -652,13 +677,14 @@ def _forward_only(g, direct, mulfirst, slope, num_dst, x, W, attn_l, attn_r, loo
     return h if rows is None else rows
 
 
-def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, need_el):
+def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, training):
     """The bf16 forward in front of its aggregation, common to _forward_only_bf16 and RgatLayerBf16Function.forward: feat_c (bf16) on
     the unique (relation, source) rows, er_c from the folded weight, the self-loop + bias rows h (bf16) the aggregation adds into,
-    and el_c -- a row-dot pass over the rounded feat_c -- where the walk gathers it or ``need_el`` says so (else None).
-    Returns (operands, nd, ss, featc, elc, erc, h, grp, offs); operands = the contiguous (x, W, attn_l, attn_r, loop_w)."""
-    # (the folded weight is fp32; the cached [0, nd] list and a copy of the self-loop weight are made here, under the main stream)
-    x, W, attn_l, attn_r, loop_w, nd, offs, wa = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, True)
+    and el_c -- a row-dot pass over the rounded feat_c -- where the walk gathers it or a backward follows (``training``; else None).
+    Returns (operands, nd, ss, featc, elc, erc, h, grp, offs, forms); operands = the contiguous (x, W, attn_l, attn_r, loop_w),
+    forms = the parameter forms of _compact_tables (all fp32) when ``training``, else None."""
+    # (the cached [0, nd] list and a copy of the self-loop weight are made here, under the main stream)
+    x, W, attn_l, attn_r, loop_w, nd, offs = _prologue(x, W, attn_l, attn_r, loop_w, num_dst)
     s, _, _ = _lists(g)
     rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
     N = x.shape[0]
@@ -669,7 +695,7 @@ def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, need_el
     # (everything the side stream writes is allocated before the fork: _side_stream)
     featc = th.empty((ss["node_indices_row"].numel(), H, D), dtype=th.bfloat16, device=dev)
     erc = th.empty((ss["node_indices_col"].numel(), H), dtype=th.float32, device=dev)
-    elc = None if _k.rgat_el_from_row(H, D, R) and not need_el else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
+    elc = None if _k.rgat_el_from_row(H, D, R) and not training else th.empty((featc.shape[0], H), dtype=th.float32, device=dev)
     bias_c = None if bias is None else bias.contiguous()
     if loop_w is not None:
         h = th.empty((nd, X), dtype=th.bfloat16, device=dev)
@@ -677,6 +703,7 @@ def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, need_el
         h = bias_c.to(th.bfloat16).expand(nd, X).contiguous()
     else:
         h = th.zeros((nd, X), dtype=th.bfloat16, device=dev)
+    wa = _folded_weight(W, attn_r)  # (fp32; in front of the fork, as in _compact_tables)
     main = th.cuda.current_stream(dev)
     side = _side_stream(dev) if OVERLAP else None
     if side is not None:
@@ -688,12 +715,14 @@ def _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias, need_el
     _k.rows_matmul_heads_bf16(ss["rel_ptrs_row"], ss["node_indices_row"], W, x, featc)
     if elc is not None:
         _k.rgat_el_rows_bf16(ss["rel_ptrs_row"], featc, attn_l, elc)
+    # (the transposes of the parameters, for the backward: one launch on the main stream, which has slack here -- _compact_tables)
+    forms = _k.rgat_transpose_weights(W, loop_w) + (wa,) if training else None
     if side is not None:
         main.wait_stream(side)
     srow, drow = _edge_rows(g, ss, direct, rp, row, col, eids)
     grp = _k.rgat_compact_groupings(col, srow, drow, N, featc.shape[0], erc.shape[0], rel_ptrs=rp,
                                     drow_nodes=ss["node_indices_col"], drow_rel_ptrs=ss["rel_ptrs_col"])
-    return (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs
+    return (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs, forms
 
 
 def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out=None):
@@ -702,8 +731,8 @@ def _forward_only_bf16(g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, 
     The same launches as the fp32 path except that el_c, where the walk gathers it, is a row-dot pass over the rounded feat_c
     instead of the projection's epilogue.  ``attn_out`` (a list): the attention weights [E,H] (fp32) are appended to it; where the
     walk formed el from the row it gathered, el_c is made for them by the same row-dot pass, so they are the softmax the output used."""
-    (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, _ = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w, bias,
-                                                                                      False)
+    (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, _, _ = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w,
+                                                                                         bias, False)
     R, H, _, D = W.shape
     _k.rgat_aggregate_compact_forward_bf16(grp, featc, elc, erc, h, slope, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
     if attn_out is not None:
@@ -722,8 +751,8 @@ class RgatLayerBf16Function(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
-        (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r, loop_w,
-                                                                                             bias, True)
+        (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs, ctx.forms = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r,
+                                                                                                        loop_w, bias, True)
         N = x.shape[0]
         R, H, _, D = W.shape
         sm = th.empty((N, H), dtype=th.float32, device=x.device)

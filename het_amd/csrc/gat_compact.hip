@@ -1868,7 +1868,10 @@ static int rgat_aggregate_compact_runs(const char* op, const het_grouping* by_ds
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_aggregate_compact_runs_workspace)", op, (long long)need);
   const int64_t X = H * D;
   HET_HIP(hipMemsetAsync(sum, 0, sizeof(float) * num_nodes * H, s));
-  HET_HIP(hipMemsetAsync(q_sum, 0, sizeof(float) * num_dst_rows * H, s));  // er rows without edges: q == 0 marks them
+  // er rows without edges: q == 0 marks them.  An er row IS a (relation, destination) pair and every run stores its row's q_sum, so
+  // when the positions have as many distinct (destination, relation) keys as there are er rows (a graph's own lists) every row is
+  // stored and the fill is a launch nobody reads (the backward makes the same test for grad_feat_c)
+  if (by_dst_rel->S != num_dst_rows) HET_HIP(hipMemsetAsync(q_sum, 0, sizeof(float) * num_dst_rows * H, s));
   if (!h_inout) HET_HIP(hipMemsetAsync(ret, 0, sizeof(float) * num_nodes * X, s));
   if (by_dst->E == 0) return HET_OK;
   return rgat_aggregate_runs_launch(false, by_dst, by_dst_rel, num_rels, feat_c, el_c, er_c, RunOutputs{sum, ret, q_rows, q_sum, q_ref},
@@ -1986,11 +1989,34 @@ static int64_t attn_grad_partial_rows(const PackView& pv, int64_t X) {
   return nb + nbl;
 }
 
+constexpr int kBiasBlocks = 2048;  // workgroups (and partial rows per wave) of the bias gradient's column sums
+// The pieces of the backward's workspace, 16-byte aligned each, in this order (floats): pack [N, 2H], tbuf [E, H] (per-edge form only),
+// the bias gradient's partial rows, the attention gradient's partial rows [ga_rows, X] with their relation tags [ga_rows], the records
+// [S_col, H, 4] (run-sum form).  One function, so that the edge pass and het_rgat_attn_grad_finish name the same partial rows.
+struct BackwardWorkspace {
+  int64_t n_pack, n_tbuf, bias_part_rows, ga_rows, n_ga, n_rec;
+  int64_t floats(int64_t X) const { return n_pack + n_tbuf + bias_part_rows * X + n_ga + n_rec; }
+  float* ga_part(void* ws, int64_t X) const { return ga_rows ? (float*)ws + n_pack + n_tbuf + bias_part_rows * X : nullptr; }
+  int* ga_rel(void* ws, int64_t X) const { return ga_rows ? reinterpret_cast<int*>(ga_part(ws, X) + ga_rows * X) : nullptr; }
+};
+static BackwardWorkspace backward_workspace(const PackView& pv, int64_t E, int64_t num_nodes, int64_t num_dst_rows, int64_t H, int64_t X,
+                                            bool runs, bool with_bias, bool with_attn_grad) {
+  BackwardWorkspace w;
+  w.n_pack = (num_nodes * 2 * H + 3) / 4 * 4;
+  w.n_tbuf = runs ? 0 : (E * H + 3) / 4 * 4;
+  w.bias_part_rows = with_bias ? (int64_t)kBiasBlocks * (kBlock / 64) : 0;
+  w.ga_rows = (with_attn_grad && E > 0) ? attn_grad_partial_rows(pv, X) : 0;
+  w.n_ga = (w.ga_rows * (X + 1) + 3) / 4 * 4;
+  w.n_rec = runs ? num_dst_rows * H * 4 : 0;
+  return w;
+}
+
 // T: the element type of feat_c [S_row,X] and gradout [rows,X], float or het_bf16 (het_rgat_backward_compact_runs_bf16: the run-sum
 // form on the cooperative shapes only; rows widened on load, every output and every sum fp32)
+// finish_attn_grad == false (the _edges entries): the partial rows of grad_attn_l stay in the workspace, for het_rgat_attn_grad_finish
 template <typename T>
 static int rgat_backward_compact_impl(const char* op, const het_grouping* by_srow, const het_grouping* by_drow, const RunSums* runs,
-                                      float* grad_attn_l, const T* feat_c, const float* el_c, const float* er_c, const float* sum, const float* ret,
+                                      bool finish_attn_grad, float* grad_attn_l, const T* feat_c, const float* el_c, const float* er_c, const float* sum, const float* ret,
                                       const T* gradout, float* grad_feat_c, float* grad_el_c, float* grad_er_c,
                                       const float* fold_attn_l, const int64_t* row_rel_ptrs, int64_t num_rels,
                                       float* grad_bias, int64_t bias_rows, int64_t num_nodes, int64_t num_src_rows,
@@ -2025,23 +2051,20 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   // the backward's own packs of by_srow (threshold rgat_bwd_pack_t(): a second set beside the library-wide one, grouping.hip.h)
   PackView pv;
   if (int rc = grouping_pack_view(by_srow, s, rgat_bwd_pack_t(), &pv)) return rc;
-  constexpr int kBiasBlocks = 2048;
-  const int64_t bias_part_rows = grad_bias ? (int64_t)kBiasBlocks * (kBlock / 64) : 0;
-  const int64_t ga_rows = (grad_attn_l && E > 0) ? attn_grad_partial_rows(pv, X) : 0, n_ga = (ga_rows * (X + 1) + 3) / 4 * 4;
-  const int64_t n_pack = (num_nodes * 2 * H + 3) / 4 * 4, n_tbuf = runs ? 0 : (E * H + 3) / 4 * 4;  // 16-byte aligned pieces
+  const BackwardWorkspace wl = backward_workspace(pv, E, num_nodes, num_dst_rows, H, X, runs != nullptr, grad_bias != nullptr, grad_attn_l != nullptr);
+  const int64_t bias_part_rows = wl.bias_part_rows, ga_rows = wl.ga_rows, n_ga = wl.n_ga, n_pack = wl.n_pack, n_tbuf = wl.n_tbuf;
   // Run-sum form (runs implies coop): one pass over the er rows (HET_rgat_drow_pass) leaves both the records the source-row kernels
   // read and grad_er, instead of dst pack + record pack + grad_er pass; the bias gradient's column sums then are a pass of their own
   // on the side stream
   const bool use_rec = runs && E > 0 && num_dst_rows > 0;
-  const int64_t n_rec = runs ? num_dst_rows * H * 4 : 0;
-  const int64_t need = (int64_t)sizeof(float) * (n_pack + n_tbuf + bias_part_rows * X + n_ga + n_rec);
+  const int64_t need = (int64_t)sizeof(float) * wl.floats(X);
   HET_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace),
               "%s: a 16-byte aligned workspace of %lld bytes is needed (het_rgat_backward_compact_workspace)", op, (long long)need);
   float* pack = (float*)workspace;  // [N, 2H]
   float* tbuf = runs ? nullptr : pack + n_pack;  // [E, H], rank order of by_srow
   float* bias_part = grad_bias ? pack + n_pack + n_tbuf : nullptr;
-  float* ga_part = ga_rows ? pack + n_pack + n_tbuf + bias_part_rows * X : nullptr;  // [ga_rows, X] then [ga_rows] relation tags
-  int* ga_rel = ga_rows ? reinterpret_cast<int*>(ga_part + ga_rows * X) : nullptr;
+  float* ga_part = wl.ga_part(workspace, X);  // [ga_rows, X] then [ga_rows] relation tags
+  int* ga_rel = wl.ga_rel(workspace, X);
   float* rec4 = use_rec ? pack + n_pack + n_tbuf + bias_part_rows * X + n_ga : nullptr;  // [S_col, H, 4]
   if (grad_attn_l) HET_HIP(hipMemsetAsync(grad_attn_l, 0, sizeof(float) * num_rels * X, s));  // (boundary pieces add atomically)
   if (by_srow->S != num_src_rows) {  // feat rows without an edge (none when the lists come from the graph): zero gradient
@@ -2197,7 +2220,7 @@ static int rgat_backward_compact_impl(const char* op, const het_grouping* by_sro
   }
   HET_LAUNCH_CHECK("HET_rgat_backward_src_packed");
   HET_HIP(fk.join());
-  if (ga_rows) {
+  if (ga_rows && finish_attn_grad) {
     hipLaunchKernelGGL(HET_rgat_attn_grad_finish, dim3((unsigned)ceil_div64(ga_rows, kAttnFinishRows)), dim3(kBlock), 0, s, ga_part, ga_rel, ga_rows,
                        (int)X, grad_attn_l);
     HET_LAUNCH_CHECK("HET_rgat_attn_grad_finish");
@@ -2215,7 +2238,7 @@ extern "C" int het_rgat_backward_compact(const het_grouping* by_srow, const het_
                                          int64_t num_dst_rows, int64_t H, int64_t D, double slope, void* workspace,
                                          int64_t workspace_bytes, het_stream stream) {
   HET_REQUIRE(by_drow, "het_rgat_backward_compact: null argument");
-  return rgat_backward_compact_impl("het_rgat_backward_compact", by_srow, by_drow, nullptr, nullptr, feat_c, el_c, er_c, sum, ret, gradout,
+  return rgat_backward_compact_impl("het_rgat_backward_compact", by_srow, by_drow, nullptr, true, nullptr, feat_c, el_c, er_c, sum, ret, gradout,
                                     grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows,
                                     num_nodes, num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream);
 }
@@ -2238,35 +2261,81 @@ extern "C" int64_t het_rgat_backward_compact_runs_workspace(const het_grouping* 
   return bytes;
 }
 
-extern "C" int het_rgat_backward_compact_runs(const het_grouping* by_srow, const float* q_rows, const float* q_sum, const float* q_ref,
-                                              const int64_t* drow_nodes, const float* feat_c, const float* el_c, const float* er_c,
-                                              const float* sum, const float* ret, const float* gradout, float* grad_feat_c,
-                                              float* grad_el_c, float* grad_er_c, const float* fold_attn_l,
-                                              const int64_t* row_rel_ptrs, int64_t num_rels, float* grad_bias, int64_t bias_rows,
-                                              int64_t num_nodes, int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D,
-                                              double slope, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
-                                              het_stream stream) {
-  HET_REQUIRE(q_rows && q_sum && q_ref && (drow_nodes || num_dst_rows == 0), "het_rgat_backward_compact_runs: null argument");
+// The second half of the run-sum backward: grad_attn_l[r, :] += the partial rows tagged r that the edge pass (the _edges entries)
+// left in `workspace`.  Ordered after that pass by the caller -- on its stream, or on another one that waits for it; the workspace
+// must not be reused in between.  The arguments are the edge pass's own: they say where the partial rows lie.
+static int rgat_attn_grad_finish(const char* op, const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t num_rels,
+                                 int64_t H, int64_t D, bool with_bias, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
+                                 hipStream_t s) {
+  HET_REQUIRE(by_srow && grad_attn_l && num_nodes >= 0 && num_dst_rows >= 0 && num_rels > 0 && num_rels <= 8 && coop_shape_ok(H, D),
+              "%s: grad_attn_l needs the grouping by feat row, the cooperative shapes and <= 8 relations", op);
+  const int64_t X = H * D;
+  PackView pv;  // (built by the edge pass: nothing is enqueued here)
+  if (int rc = grouping_pack_view(by_srow, s, rgat_bwd_pack_t(), &pv)) return rc;
+  const BackwardWorkspace wl = backward_workspace(pv, by_srow->E, num_nodes, num_dst_rows, H, X, true, with_bias, true);
+  if (!wl.ga_rows) return HET_OK;  // (no edge: the edge pass has zero-filled grad_attn_l)
+  HET_REQUIRE(workspace && workspace_bytes >= (int64_t)sizeof(float) * wl.floats(X) && aligned16(workspace),
+              "%s: the workspace of the edge pass is needed (het_rgat_backward_compact_runs_workspace)", op);
+  hipLaunchKernelGGL(HET_rgat_attn_grad_finish, dim3((unsigned)ceil_div64(wl.ga_rows, kAttnFinishRows)), dim3(kBlock), 0, s,
+                     wl.ga_part(workspace, X), wl.ga_rel(workspace, X), wl.ga_rows, (int)X, grad_attn_l);
+  HET_LAUNCH_CHECK("HET_rgat_attn_grad_finish");
+  return HET_OK;
+}
+
+extern "C" int het_rgat_attn_grad_finish(const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t num_rels, int64_t H,
+                                         int64_t D, int with_bias, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
+                                         het_stream stream) {
+  return rgat_attn_grad_finish("het_rgat_attn_grad_finish", by_srow, num_nodes, num_dst_rows, num_rels, H, D, with_bias != 0, grad_attn_l,
+                               workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// het_rgat_backward_compact_runs / _bf16 and their first halves (finish == false: the _edges entries)
+template <typename T>
+static int rgat_backward_compact_runs(const char* op, bool finish, const het_grouping* by_srow, const float* q_rows, const float* q_sum,
+                                      const float* q_ref, const int64_t* drow_nodes, const T* feat_c, const float* el_c, const float* er_c,
+                                      const float* sum, const float* ret, const T* gradout, float* grad_feat_c, float* grad_el_c,
+                                      float* grad_er_c, const float* fold_attn_l, const int64_t* row_rel_ptrs, int64_t num_rels,
+                                      float* grad_bias, int64_t bias_rows, int64_t num_nodes, int64_t num_src_rows, int64_t num_dst_rows,
+                                      int64_t H, int64_t D, double slope, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
+                                      het_stream stream) {
+  HET_REQUIRE(q_rows && q_sum && q_ref && (drow_nodes || num_dst_rows == 0), "%s: null argument", op);
   const RunSums runs{q_rows, q_sum, q_ref, drow_nodes};
-  return rgat_backward_compact_impl("het_rgat_backward_compact_runs", by_srow, nullptr, &runs, grad_attn_l, feat_c, el_c, er_c, sum, ret, gradout,
-                                    grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows,
-                                    num_nodes, num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream);
+  if (int rc = rgat_backward_compact_impl(op, by_srow, nullptr, &runs, false, grad_attn_l, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c,
+                                          grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows, num_nodes,
+                                          num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream))
+    return rc;
+  if (!finish || !grad_attn_l) return HET_OK;
+  return rgat_attn_grad_finish(op, by_srow, num_nodes, num_dst_rows, num_rels, H, D, grad_bias != nullptr, grad_attn_l, workspace,
+                               workspace_bytes, (hipStream_t)stream);
+}
+
+#define HET_RUNS_PARAMS(T)                                                                                                           \
+  const het_grouping *by_srow, const float *q_rows, const float *q_sum, const float *q_ref, const int64_t *drow_nodes, const T *feat_c, \
+      const float *el_c, const float *er_c, const float *sum, const float *ret, const T *gradout, float *grad_feat_c, float *grad_el_c, \
+      float *grad_er_c, const float *fold_attn_l, const int64_t *row_rel_ptrs, int64_t num_rels, float *grad_bias, int64_t bias_rows, \
+      int64_t num_nodes, int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D, double slope, float *grad_attn_l,          \
+      void *workspace, int64_t workspace_bytes, het_stream stream
+#define HET_RUNS_ARGS                                                                                                                  \
+  by_srow, q_rows, q_sum, q_ref, drow_nodes, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, fold_attn_l,    \
+      row_rel_ptrs, num_rels, grad_bias, bias_rows, num_nodes, num_src_rows, num_dst_rows, H, D, slope, grad_attn_l, workspace,       \
+      workspace_bytes, stream
+
+extern "C" int het_rgat_backward_compact_runs(HET_RUNS_PARAMS(float)) {
+  return rgat_backward_compact_runs("het_rgat_backward_compact_runs", true, HET_RUNS_ARGS);
+}
+// ... its first half: everything but the sum of grad_attn_l's partial rows, which stay in the workspace for het_rgat_attn_grad_finish
+extern "C" int het_rgat_backward_compact_runs_edges(HET_RUNS_PARAMS(float)) {
+  return rgat_backward_compact_runs("het_rgat_backward_compact_runs_edges", false, HET_RUNS_ARGS);
 }
 
 // ... with bf16 rows: feat_c [S_row,H,D] and gradout [rows,H,D] het_bf16 (8-byte aligned), gathered as 2X-byte rows and widened on load;
 // el_c, er_c, sum, ret, the run sums and every gradient fp32 (16-byte aligned).  The bias gradient, when asked for, is the column sums
 // of the bf16 gradout rows.  Workspace: het_rgat_backward_compact_runs_workspace.  Every check precedes the first launch.
-extern "C" int het_rgat_backward_compact_runs_bf16(const het_grouping* by_srow, const float* q_rows, const float* q_sum,
-                                                   const float* q_ref, const int64_t* drow_nodes, const het_bf16* feat_c,
-                                                   const float* el_c, const float* er_c, const float* sum, const float* ret,
-                                                   const het_bf16* gradout, float* grad_feat_c, float* grad_el_c, float* grad_er_c,
-                                                   const float* fold_attn_l, const int64_t* row_rel_ptrs, int64_t num_rels,
-                                                   float* grad_bias, int64_t bias_rows, int64_t num_nodes, int64_t num_src_rows,
-                                                   int64_t num_dst_rows, int64_t H, int64_t D, double slope, float* grad_attn_l,
-                                                   void* workspace, int64_t workspace_bytes, het_stream stream) {
-  HET_REQUIRE(q_rows && q_sum && q_ref && (drow_nodes || num_dst_rows == 0), "het_rgat_backward_compact_runs_bf16: null argument");
-  const RunSums runs{q_rows, q_sum, q_ref, drow_nodes};
-  return rgat_backward_compact_impl("het_rgat_backward_compact_runs_bf16", by_srow, nullptr, &runs, grad_attn_l, feat_c, el_c, er_c, sum, ret,
-                                    gradout, grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, row_rel_ptrs, num_rels, grad_bias, bias_rows,
-                                    num_nodes, num_src_rows, num_dst_rows, H, D, slope, workspace, workspace_bytes, stream);
+extern "C" int het_rgat_backward_compact_runs_bf16(HET_RUNS_PARAMS(het_bf16)) {
+  return rgat_backward_compact_runs("het_rgat_backward_compact_runs_bf16", true, HET_RUNS_ARGS);
 }
+extern "C" int het_rgat_backward_compact_runs_edges_bf16(HET_RUNS_PARAMS(het_bf16)) {
+  return rgat_backward_compact_runs("het_rgat_backward_compact_runs_edges_bf16", false, HET_RUNS_ARGS);
+}
+#undef HET_RUNS_PARAMS
+#undef HET_RUNS_ARGS

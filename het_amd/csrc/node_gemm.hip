@@ -354,3 +354,100 @@ extern "C" int het_rgat_node_backward_dx_bf16(int64_t n_begin, int64_t n_end, in
   return rgat_node_backward_dx("het_rgat_node_backward_dx_bf16", n_begin, n_end, n_loop, num_nodes, num_rels, grad_h, loop_wt, g_rows,
                                weights_t, row_map, g_er, wa_t, dst_map, grad_x, H, K, D, node_order, stream);
 }
+
+// ---- the parameter forms of one RGAT step ---------------------------------------------------------------------------------------
+// What the step's kernels read of the parameters in another layout than the layer keeps them in, and the gradient through the
+// folded weight wa[r,h,k] = SUM_d W[r,h,k,d] attn_r[r,h,d].  R*H*K*D floats each (64 KB on ogbn-mag): a launch apiece is
+// all they cost, which is why they are single launches and not torch compositions.
+namespace {
+
+// wt[m, d, k] = w[m, k, d] for the M = R*H matrices [K, D], and loop_wt[x, k] = loop_w[k, x]: exact copies, one thread per output
+// element (coalesced stores, strided loads of tables that stay in L2).  Scalar accesses: no alignment is asked of w.
+__global__ __launch_bounds__(kBlock) void HET_rgat_transpose_weights(const float* __restrict__ w, int64_t n_w, int K, int D,
+                                                                     float* __restrict__ wt, const float* __restrict__ loop_w,
+                                                                     int64_t n_loop, int X, float* __restrict__ loop_wt) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n_w) {
+    const int64_t kd = (int64_t)K * D, m = i / kd;
+    const int rem = (int)(i - m * kd), d = rem / K, k = rem - d * K;
+    wt[i] = w[m * kd + (int64_t)k * D + d];
+  } else if (i - n_w < n_loop) {
+    const int j = (int)(i - n_w), x = j / K, k = j - x * K;
+    loop_wt[j] = loop_w[(int64_t)k * X + x];
+  }
+}
+
+// One workgroup per matrix m = (r, h):  grad_w[m, k, d] += grad_wa[m, k] * attn_r[m, d]  and
+// grad_attn_r[m, d] = SUM_k w[m, k, d] * grad_wa[m, k].  The sum: column d is cut into nsl = kBlock / CW slices of k (k = s, s + nsl,
+// ..), each summed in ascending k by one thread, and the slices added in ascending s by one thread -- a fixed order, no atomics.
+__global__ __launch_bounds__(kBlock) void HET_rgat_unfold_weight_gradient(const float* __restrict__ grad_wa,
+                                                                          const float* __restrict__ w,
+                                                                          const float* __restrict__ attn_r, int K, int D,
+                                                                          float* __restrict__ grad_w, float* __restrict__ grad_attn_r) {
+  __shared__ float part[kBlock];
+  const int64_t m = blockIdx.x;
+  const float* ga = grad_wa + m * K;
+  const float* wm = w + m * K * D;
+  const float* ar = attn_r + m * D;
+  float* gw = grad_w + m * K * D;
+  const int t = threadIdx.x;
+  for (int i = t; i < K * D; i += kBlock) {
+    const int k = i / D, d = i - k * D;
+    gw[i] += ga[k] * ar[d];
+  }
+  const int CW = D < kBlock ? D : kBlock, nsl = kBlock / CW, s = t / CW, c = t - s * CW;
+  for (int d0 = 0; d0 < D; d0 += CW) {  // (one trip unless D > kBlock)
+    const int d = d0 + c;
+    float a = 0.f;
+    if (s < nsl && d < D)
+      for (int k = s; k < K; k += nsl) a += wm[(int64_t)k * D + d] * ga[k];
+    if (s < nsl) part[s * CW + c] = a;
+    __syncthreads();
+    if (s == 0 && d < D) {
+      float sum = part[c];
+      for (int q = 1; q < nsl; ++q) sum += part[q * CW + c];
+      grad_attn_r[m * D + d] = sum;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+extern "C" int het_rgat_transpose_weights(const float* weights, int64_t num_rels, int64_t H, int64_t K, int64_t D, float* weights_t,
+                                          const float* loop_w, int64_t X, float* loop_wt, het_stream stream) {
+  const char* op = "het_rgat_transpose_weights";
+  hipStream_t s = (hipStream_t)stream;
+  HET_REQUIRE(num_rels >= 0 && H >= 0 && K > 0 && D > 0 && K < (1 << 15) && D < (1 << 15) && (!loop_w || (X > 0 && X < (1 << 15))),
+              "%s: bad sizes", op);
+  const int64_t n_w = num_rels * H * K * D, n_loop = loop_w ? K * X : 0;
+  HET_REQUIRE((n_w == 0 || (weights && weights_t)) && (!loop_w || loop_wt), "%s: null argument", op);
+  HET_REQUIRE(weights != weights_t && (!loop_w || loop_w != loop_wt), "%s: the copies cannot be made in place", op);
+  const int64_t nb = ceil_div64(n_w + n_loop, kBlock);
+  HET_REQUIRE(nb < (1ll << 31), "%s: too many elements", op);
+  if (nb == 0) return HET_OK;
+  {
+    HET_KTIME("HET_rgat_transpose_weights", s);
+    hipLaunchKernelGGL(HET_rgat_transpose_weights, dim3((unsigned)nb), dim3(kBlock), 0, s, weights, n_w, (int)K, (int)D, weights_t, loop_w,
+                       n_loop, (int)X, loop_wt);
+  }
+  HET_LAUNCH_CHECK("HET_rgat_transpose_weights");
+  return HET_OK;
+}
+
+extern "C" int het_rgat_unfold_weight_gradient(const float* grad_wa, const float* weights, const float* attn_r, int64_t num_rels,
+                                               int64_t H, int64_t K, int64_t D, float* grad_weights, float* grad_attn_r,
+                                               het_stream stream) {
+  const char* op = "het_rgat_unfold_weight_gradient";
+  hipStream_t s = (hipStream_t)stream;
+  HET_REQUIRE(num_rels >= 0 && H >= 0 && K > 0 && D > 0 && K * D < (1ll << 31) && num_rels * H < (1ll << 31), "%s: bad sizes", op);
+  if (num_rels * H == 0) return HET_OK;
+  HET_REQUIRE(grad_wa && weights && attn_r && grad_weights && grad_attn_r, "%s: null argument", op);
+  {
+    HET_KTIME("HET_rgat_unfold_weight_gradient", s);
+    hipLaunchKernelGGL(HET_rgat_unfold_weight_gradient, dim3((unsigned)(num_rels * H)), dim3(kBlock), 0, s, grad_wa, weights, attn_r, (int)K,
+                       (int)D, grad_weights, grad_attn_r);
+  }
+  HET_LAUNCH_CHECK("HET_rgat_unfold_weight_gradient");
+  return HET_OK;
+}

@@ -932,9 +932,11 @@ def rgat_aggregate_compact_bf16(groupings, feat_c, el_c, er_c, sum, ret, slope, 
 
 
 def rgat_backward_compact_bf16(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope, runs,
-                               drow_nodes, fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, grad_attn_l=None):
+                               drow_nodes, fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, grad_attn_l=None,
+                               finish_attn_grad=True):
     """rgat_backward_compact's run-sum form over bf16 rows (het_rgat_backward_compact_runs_bf16): feat_c [S,H,D] and gradout [N,H,D]
-    bf16; everything else -- and every gradient -- fp32.  grad_bias [H*D]: the column sums of the first ``bias_rows`` gradout rows."""
+    bf16; everything else -- and every gradient -- fp32.  grad_bias [H*D]: the column sums of the first ``bias_rows`` gradout rows.
+    ``finish_attn_grad``: as for rgat_backward_compact."""
     name = "rgat_backward_compact_bf16"
     _chk_bf16(name, (feat_c, gradout), tuple(t for t in (el_c, er_c, sum, ret, grad_feat_c, grad_el_c, grad_er_c, fold_attn_l, grad_bias,
                                                         grad_attn_l) + tuple(runs) if t is not None))
@@ -947,8 +949,9 @@ def rgat_backward_compact_bf16(groupings, feat_c, el_c, er_c, sum, ret, gradout,
             or (grad_bias is not None and (grad_bias.numel() != H * D or bias_rows > N))):
         raise _lib.HetError(f"{name}: feat_c {tuple(feat_c.shape)}, gradout {tuple(gradout.shape)}, sum {tuple(sum.shape)}, ret "
                             f"{tuple(ret.shape)}, er_c {tuple(er_c.shape)} and the gradients do not fit")
-    _rgat_backward_compact("het_rgat_backward_compact_runs_bf16", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c,
-                           grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l)
+    return _rgat_backward_compact("het_rgat_backward_compact_runs%s_bf16", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c,
+                                  grad_el_c, grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l,
+                                  finish_attn_grad)
 
 
 def rgat_node_backward_dx_bf16(n_begin, n_end, n_loop, grad_h, loop_wt, g_rows, weights_t, row_map, g_er, wa_t, dst_map, grad_x,
@@ -1182,20 +1185,27 @@ def rows_layer_norm_backward_bf16(offsets, y, gamma, mean, rstd, grad_out, want_
 
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
-                          grad_attn_l=None):
+                          grad_attn_l=None, finish_attn_grad=True):
     """runs = (q_rows, q_sum, q_ref) of rgat_aggregate_compact in the run-sum form, drow_nodes [S_col] int64 the destination of
     every er row: grad_er_c from the run sums (het_rgat_backward_compact_runs).  grad_attn_l [R,H,D] (run-sum form, with
-    fold_attn_l): also the weight gradient of el_c = <feat_c, attn_l[r]>, from the same pass."""
+    fold_attn_l): also the weight gradient of el_c = <feat_c, attn_l[r]>, from the same pass.
+    ``finish_attn_grad=False`` (with grad_attn_l): the edge pass alone (het_rgat_backward_compact_runs_edges) -- grad_attn_l's partial
+    rows stay in the workspace, and what is returned goes to rgat_attn_grad_finish, on this stream or on one that waits for it.  The
+    returned tuple holds the workspace: keep it until the finishing launch is ordered before whatever allocates next."""
     _chk("rgat_backward_compact", tuple(t for t in (feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c,
                                                     fold_attn_l, grad_bias, grad_attn_l) + (tuple(runs) if runs else ()) if t is not None),
          tuple(t for t in (row_rel_ptrs, drow_nodes) if t is not None))
-    _rgat_backward_compact("het_rgat_backward_compact_runs", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c,
-                           grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l)
+    return _rgat_backward_compact("het_rgat_backward_compact_runs%s", groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c,
+                                  grad_el_c, grad_er_c, slope, fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l,
+                                  finish_attn_grad)
 
 
 def _rgat_backward_compact(runs_entry, groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
-                           fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l):
-    """rgat_backward_compact / _bf16 behind their tensor checks; ``runs_entry``: the C entry of the run-sum form."""
+                           fold_attn_l, row_rel_ptrs, grad_bias, bias_rows, runs, drow_nodes, grad_attn_l, finish_attn_grad=True):
+    """rgat_backward_compact / _bf16 behind their tensor checks; ``runs_entry``: the C entry of the run-sum form, with a %s where its
+    first half has "_edges".  Returns what rgat_attn_grad_finish takes when the finishing pass is left to the caller, else None."""
+    split = bool(runs) and grad_attn_l is not None and not finish_attn_grad
+    runs_entry = runs_entry % ("_edges" if split else "")
     N, H = sum.shape[0], sum.shape[1]
     D = ret.numel() // max(1, N * H)
     if runs and row_rel_ptrs is not None:
@@ -1214,8 +1224,46 @@ def _rgat_backward_compact(runs_entry, groupings, feat_c, el_c, er_c, sum, ret, 
     if runs:
         _call(ret, runs_entry, groupings[1].handle, _p(runs[0]), _p(runs[1]), _p(runs[2]), _p(drow_nodes), *head,
               _p(grad_attn_l), *tail)
+        if split:
+            return (groupings[1], N, er_c.shape[0], row_rel_ptrs.numel() - 1, H, D, int(grad_bias is not None), grad_attn_l, ws, nbytes)
     else:
         _call(ret, "het_rgat_backward_compact", groupings[1].handle, groupings[2].handle, *head, *tail)
+
+
+def rgat_attn_grad_finish(pending):
+    """The second half of rgat_backward_compact(..., finish_attn_grad=False), on the current stream (het_rgat_attn_grad_finish):
+    grad_attn_l += the partial rows the edge pass left in its workspace."""
+    by_srow, N, S_col, R, H, D, with_bias, grad_attn_l, ws, nbytes = pending
+    _call(grad_attn_l, "het_rgat_attn_grad_finish", by_srow.handle, N, S_col, R, H, D, with_bias, _p(grad_attn_l), _p(ws), nbytes,
+          _stream(grad_attn_l))
+
+
+def rgat_transpose_weights(W, loop_w=None):
+    """(W^T [R,H,D,K], loop_w^T [X,K] or None) of W [R,H,K,D] and loop_w [K,X] in one launch (het_rgat_transpose_weights): exact
+    copies, what transpose(...).contiguous() gives."""
+    _chk("rgat_transpose_weights", (W,) if loop_w is None else (W, loop_w))
+    R, H, Kd, D = W.shape
+    if loop_w is not None and (loop_w.dim() != 2 or loop_w.shape[0] != Kd):
+        raise _lib.HetError(f"rgat_transpose_weights: loop_w {tuple(loop_w.shape)} does not fit W {tuple(W.shape)}")
+    Wt = torch.empty((R, H, D, Kd), dtype=W.dtype, device=W.device)
+    X = 0 if loop_w is None else loop_w.shape[1]
+    loop_wt = None if loop_w is None else torch.empty((X, Kd), dtype=W.dtype, device=W.device)
+    _call(W, "het_rgat_transpose_weights", _p(W), R, H, Kd, D, _p(Wt), _p(loop_w), X, _p(loop_wt), _stream(W))
+    return Wt, loop_wt
+
+
+def rgat_unfold_weight_gradient(grad_wa, W, attn_r, grad_W):
+    """The gradient through wa = W . attn_r in one launch (het_rgat_unfold_weight_gradient): grad_W [R,H,K,D] += grad_wa (x) attn_r in
+    place; returns grad_attn_r [R,H,D].  grad_wa: R*H*K floats ([R,H,K,1] or [R,H,K])."""
+    _chk("rgat_unfold_weight_gradient", (grad_wa, W, attn_r, grad_W))
+    R, H, Kd, D = W.shape
+    if grad_wa.numel() != R * H * Kd or attn_r.numel() != R * H * D or grad_W.shape != W.shape:
+        raise _lib.HetError(f"rgat_unfold_weight_gradient: grad_wa {tuple(grad_wa.shape)}, attn_r {tuple(attn_r.shape)} and grad_W "
+                            f"{tuple(grad_W.shape)} do not fit W {tuple(W.shape)}")
+    grad_attn_r = torch.empty((R, H, D), dtype=W.dtype, device=W.device)
+    torch.autograd.graph.increment_version(grad_W)
+    _call(W, "het_rgat_unfold_weight_gradient", _p(grad_wa), _p(W), _p(attn_r), R, H, Kd, D, _p(grad_W), _p(grad_attn_r), _stream(W))
+    return grad_attn_r
 
 
 def hgt_fold_source_weights(k_lin, v_lin, rel_att, rel_msg, rel_pri, src_type, transpose_att: bool):

@@ -655,6 +655,25 @@ int het_rgat_backward_compact_runs(const het_grouping* by_srow, const float* q_r
  *   kernels fetch everything they need from the destination side of an edge with one load instead of two (round 4). */
 int64_t het_rgat_backward_compact_runs_workspace(const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t H,
                                                  int64_t D, int with_bias, int with_attn_grad, het_stream stream);
+/* het_rgat_backward_compact_runs in two halves, for a caller whose next launch needs grad_feat_c / grad_er_c but not grad_attn_l (the
+ * RGAT layer: its node-major input gradient starts where the edge pass ends, the finishing pass runs beside it on another stream):
+ *   het_rgat_backward_compact_runs_edges: the same arguments, the same launches and the same values, except that the partial rows of
+ *     grad_attn_l are left in the workspace.  grad_attn_l then holds the zero fill plus the few boundary pieces added atomically.
+ *   het_rgat_attn_grad_finish: grad_attn_l[r, :] += the partial rows tagged r.  by_srow, num_nodes, num_dst_rows, num_rels, H, D and
+ *     with_bias (= grad_bias != NULL) as the edge pass was given them -- they say where the partial rows lie in `workspace`, which
+ *     nobody may have written since.  `stream` must be ordered after the edge pass (its own stream, or one that waits for it).
+ *     Nothing to do (HET_OK) when the grouping has no position.
+ * het_rgat_backward_compact_runs is the one followed by the other on `stream`: bit for bit what the two calls leave. */
+int het_rgat_backward_compact_runs_edges(const het_grouping* by_srow, const float* q_rows, const float* q_sum, const float* q_ref,
+                                         const int64_t* drow_nodes, const float* feat_c, const float* el_c, const float* er_c,
+                                         const float* sum, const float* ret, const float* gradout, float* grad_feat_c,
+                                         float* grad_el_c, float* grad_er_c, const float* fold_attn_l, const int64_t* row_rel_ptrs,
+                                         int64_t num_rels, float* grad_bias, int64_t bias_rows, int64_t num_nodes,
+                                         int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D, double slope,
+                                         float* grad_attn_l, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_rgat_attn_grad_finish(const het_grouping* by_srow, int64_t num_nodes, int64_t num_dst_rows, int64_t num_rels, int64_t H,
+                              int64_t D, int with_bias, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
+                              het_stream stream);
 
 /* The forward of that pair when no backward will follow (evaluation, torch.no_grad()): the same groupings -- by_dst and by_dst_rel
  * as for het_rgat_aggregate_compact_runs, so a training step and an evaluation pass over one graph share them --, the same feat_c /
@@ -722,6 +741,15 @@ int het_rgat_backward_compact_runs_bf16(const het_grouping* by_srow, const float
                                         int64_t num_rels, float* grad_bias, int64_t bias_rows, int64_t num_nodes,
                                         int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D, double slope,
                                         float* grad_attn_l, void* workspace, int64_t workspace_bytes, het_stream stream);
+/* ... its first half (het_rgat_backward_compact_runs_edges above; the second half, het_rgat_attn_grad_finish, is fp32 either way) */
+int het_rgat_backward_compact_runs_edges_bf16(const het_grouping* by_srow, const float* q_rows, const float* q_sum, const float* q_ref,
+                                              const int64_t* drow_nodes, const het_bf16* feat_c, const float* el_c, const float* er_c,
+                                              const float* sum, const float* ret, const het_bf16* gradout, float* grad_feat_c,
+                                              float* grad_el_c, float* grad_er_c, const float* fold_attn_l,
+                                              const int64_t* row_rel_ptrs, int64_t num_rels, float* grad_bias, int64_t bias_rows,
+                                              int64_t num_nodes, int64_t num_src_rows, int64_t num_dst_rows, int64_t H, int64_t D,
+                                              double slope, float* grad_attn_l, void* workspace, int64_t workspace_bytes,
+                                              het_stream stream);
 
 /* The attention weights the aggregations above form and discard, as an output (DGL's get_attention, PyG's
  * return_attention_weights): a pass of its own over the ids and the two small tables -- it never reads a feat_c row, and it runs
@@ -831,6 +859,19 @@ int het_rgat_node_backward_dx_bf16(int64_t n_begin, int64_t n_end, int64_t n_loo
                                    const het_bf16* grad_h, const float* loop_wt, const float* g_rows, const float* weights_t,
                                    const int32_t* row_map, const float* g_er, const float* wa_t, const int32_t* dst_map,
                                    het_bf16* grad_x, int64_t H, int64_t K, int64_t D, const int32_t* node_order, het_stream stream);
+/* The parameter forms of one step of that layer, a launch each (they depend on the parameters alone: the layer makes them once per
+ * step, in the forward, and keeps them for the backward).
+ * het_rgat_transpose_weights: weights_t [R,H,D,K] = weights [R,H,K,D] with the last two axes swapped, and -- loop_w given --
+ *   loop_wt [X,K] = loop_w [K,X] transposed, both in ONE launch.  Exact copies (bit for bit a transposed contiguous copy); no
+ *   alignment is asked of any pointer; the copies cannot be made in place.  K, D, X < 32768.
+ * het_rgat_unfold_weight_gradient: the gradient through the folded weight wa[r,h,k] = SUM_d weights[r,h,k,d] attn_r[r,h,d], from
+ *   grad_wa [R,H,K]:  grad_weights[r,h,k,d] += grad_wa[r,h,k] attn_r[r,h,d] in place, and grad_attn_r[r,h,d] = SUM_k
+ *   weights[r,h,k,d] grad_wa[r,h,k], overwritten.  One workgroup per (r, h); fp32 sums over k in a fixed order, no float atomics: the
+ *   same bits every call. */
+int het_rgat_transpose_weights(const float* weights, int64_t num_rels, int64_t H, int64_t K, int64_t D, float* weights_t,
+                               const float* loop_w, int64_t X, float* loop_wt, het_stream stream);
+int het_rgat_unfold_weight_gradient(const float* grad_wa, const float* weights, const float* attn_r, int64_t num_rels, int64_t H,
+                                    int64_t K, int64_t D, float* grad_weights, float* grad_attn_r, het_stream stream);
 
 /* Layer-level extension (no reference op of its own): the node-major sum of row x weight products
  *     out[n, :] = SUM_s rows_s[map_s[n], :] . weights_t[s]          n = node_order[p] (or p) for p in [n_begin, n_end)
