@@ -24,28 +24,27 @@ as a row-dot product on the distinct (relation, destination) rows instead of a p
 forms of er are the same real number (associativity); the reference offers the flag because it is cheaper, and so the
 node takes it whenever the one-head row-dot kernels cover the shape (HET_RGAT_LITERAL_ER=1 keeps (x . W) . attn_r).
 
+Which of the functions below serves a call -- and which dataflow, which form of er, which route of the backward -- is decided once
+per call, by rgat_route.decide: the table of its module docstring has every path with its conditions.  rgat_layer_fused runs the
+record it is handed (``Route``), the autograd nodes keep it on their context.
+
 The backward of the distinct-row dataflow is ONE function for one GPU and for a partition with a halo
 (RgatLayerFunction._backward_distinct_rows): its routes differ in how the input gradient is formed, nothing else.
 
-Evaluation (torch.no_grad(), or no input that requires a gradient) on the distinct-row dataflow does not go through the node at
-all: _forward_only runs the same forward with an aggregation that keeps nothing for a backward (HET_RGAT_FORWARD_ONLY=0: the
-node's forward, as before).
+Evaluation (path ``eval``) does not go through the node at all: _forward_only runs the same forward with an aggregation that keeps
+nothing for a backward.
 
-bf16 activations (a torch.bfloat16 input) on the evaluation path: _forward_only_bf16 keeps x, feat_c and the layer output
-h as bf16 rows, each rounded once (to nearest even) where its kernel stores it; W, attn_l, attn_r, the self-loop weight, the bias,
-el_c, er_c, the hub records and every sum, maximum and exponential are fp32 on widened values.  er always comes from the folded
-weight there (HET_RGAT_LITERAL_ER does not apply: the literal form needs a second projection table), and el_c is the dot of the
-ROUNDED feat_c row, so the walks that form el from the row they gather and those that gather el_c compute one function.  Every
-other bf16 call (gradients required, halo, per-edge dataflow, other shapes) is served by the fp32 layer on an upcast copy
-(het_amd/layers.py): correct, not faster.
+bf16 activations (a torch.bfloat16 input) on the evaluation path (``eval_bf16``): _forward_only_bf16 keeps x, feat_c and the layer
+output h as bf16 rows, each rounded once (to nearest even) where its kernel stores it; W, attn_l, attn_r, the self-loop weight, the
+bias, el_c, er_c, the hub records and every sum, maximum and exponential are fp32 on widened values.  er always comes from the
+folded weight there, and el_c is the dot of the ROUNDED feat_c row, so the walks that form el from the row they gather and those
+that gather el_c compute one function.
 
-bf16 training is opt-in (the layer's bf16_training=True; rgat_layer_bf16_training_ok): RgatLayerBf16Function runs that same forward
-with the training aggregation over bf16 rows -- it also leaves lse, ret [N,H,D], the run sums and el_c, all fp32 -- and its backward is
-the node-major route of _backward_distinct_rows with the bf16 entries: the incoming gradient of h is gathered as bf16 rows and
-widened on load, grad_feat_c / grad_er_c and every parameter gradient are fp32 sums, the gradient passes straight through the
-rounding of feat_c, and grad_x is rounded once where the node-major pass stores a node's finished row.  No fp32 copy of x, feat_c,
-h, grad_h or grad_x is made.  Calls outside that one route (halo, the per-relation and generic routes, 128-wide rows or inputs,
-more than 8 relations, edges that end at or above nd) keep the upcast fallback.
+bf16 training (``train_bf16``): RgatLayerBf16Function runs that same forward with the training aggregation over bf16 rows -- it also
+leaves lse, ret [N,H,D], the run sums and el_c, all fp32 -- and its backward is the node-major route of _backward_distinct_rows with
+the bf16 entries: the incoming gradient of h is gathered as bf16 rows and widened on load, grad_feat_c / grad_er_c and every
+parameter gradient are fp32 sums, the gradient passes straight through the rounding of feat_c, and grad_x is rounded once where the
+node-major pass stores a node's finished row.  No fp32 copy of x, feat_c, h, grad_h or grad_x is made.
 
 Attention weights (the layer's get_attention=True): both evaluation functions append attn [E,H] (fp32, edge-id order) to the list
 they are handed -- a pass over the ids, el_c and er_c after the aggregation (csrc/gat_attention.hip); the autograd node does not, and
@@ -59,6 +58,7 @@ from ..plan import consistent as _consistent_plan
 
 from .. import kernels as _k
 from ..kernels import K
+from . import rgat_route
 
 
 _OFFS = {}
@@ -68,23 +68,8 @@ OVERLAP = os.environ.get("HET_RGAT_OVERLAP", "1") != "0"  # independent launches
 FORWARD_ONLY = os.environ.get("HET_RGAT_FORWARD_ONLY", "1") != "0"  # no backward in sight: the forward that keeps nothing for one
 
 
-def _mulfirst_shape_ok(H, Kd):
-    """er = x[dst] . (W . attn_r) through the one-head row-dot kernels (seg_rowdot.hip)."""
-    return H in (1, 2, 4, 8) and Kd >= 4 * H and Kd & (Kd - 1) == 0 and Kd <= 256
-
-
 def _has_single_sided_lists(g):
     return "unique_node_indices_single_sided" in getattr(g, "graph_data", {}).get("separate", {})
-
-
-def effective_flags(g, W, compact, direct, mulfirst):
-    """(compact, direct, mulfirst) the node runs with for the layer flags given (see the module docstring)."""
-    R, H, Kd, D = W.shape
-    if not compact and not PER_EDGE and (_has_single_sided_lists(g) or hasattr(g, "generate_separate_unique_node_indices_single_sided_for_each_etype")):
-        compact, direct = True, True
-    if not mulfirst and not LITERAL_ER and _mulfirst_shape_ok(H, Kd):
-        mulfirst = True
-    return bool(compact), bool(direct), bool(mulfirst)
 
 
 def _destinations_below(col, nd):
@@ -119,24 +104,19 @@ def _edge_rows(g, ss, direct, rp, row, col, eids):
     return _k._src_rows_by_position(3, maps, rp, row, eids), _k._dst_rows_by_position(3, maps, rp, col, eids)
 
 
-def rgat_layer_fused_ok(g, x, W, slope, compact, mulfirst=False):
-    """Shapes / state for which every op of the node runs on its fast path (else use the op-by-op composition)."""
-    R, H, Kd, D = W.shape
-    if not (_k._plan.is_enabled() and x.is_cuda and x.dim() == 2 and slope >= 0 and g.get_num_edges() > 0
-            and _k.gat_grouped_shape_ok(H, D)):
-        return False
-    compact, _, mulfirst_eff = effective_flags(g, W, compact, True, mulfirst)
-    if mulfirst and not _mulfirst_shape_ok(H, Kd):
-        return False
-    mulfirst = mulfirst_eff
-    if not _k.matmul_attn_dot_ok(H, Kd, D):
-        # widths the matrix-core projection does not take (e.g. the 8 output classes of the reference CLI's defaults): the
-        # distinct-row dataflow with er from the folded weight runs on the any-shape GEMM + a row-dot for el
-        return compact and mulfirst and H & (H - 1) == 0
-    if compact or mulfirst:
-        return True
-    _, _, by_dst = _lists(g)
-    return _k.matmul_attn_dot_only_ok(by_dst, W, x)
+def rgat_layer_fused_ok():
+    """The ``plan`` fact of rgat_route.decide: the groupings are on (het_amd.plan), without which nothing in this module runs.
+    (Tests replace it with a constant False: the op-by-op composition of layers.py with the groupings still on.)"""
+    return _k._plan.is_enabled()
+
+
+def graph_facts(g, x):
+    """What rgat_route.decide is told about the graph, (lists, dst_below, attn_dot_only): whether it has, or can generate, the
+    single-sided unique lists, and the two facts that may read its lists, as callables for decide to ask where they matter."""
+    lists = _has_single_sided_lists(g) or hasattr(g, "generate_separate_unique_node_indices_single_sided_for_each_etype")
+    dst_below = lambda nd: _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
+    attn_dot_only = lambda R, H, Kd, D: _k.matmul_attn_dot_only_ok(_lists(g)[2], th.empty((R, H, Kd, D), device="meta"), x)
+    return lists, dst_below, attn_dot_only
 
 
 _SIDE = {}
@@ -188,8 +168,8 @@ def _unfold_weight_gradient(grad_wa, W, attn_r, grad_W):
 
 
 def _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias):
-    """What RgatLayerFunction.backward returns: nothing for (g, compact, direct, mulfirst, slope, num_dst, halo)."""
-    return None, None, None, None, None, None, None, grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
+    """What RgatLayerFunction.backward returns: nothing for (g, route, slope, num_dst, halo)."""
+    return None, None, None, None, None, grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias
 
 
 def _halo_pieces(g, ss, plan):
@@ -361,8 +341,8 @@ def _per_relation_front(x, loop_w, offs, grad_h, nd, H, dst_prefix):
 @_consistent_plan
 class RgatLayerFunction(th.autograd.Function):
     @staticmethod
-    def forward(ctx, g, compact, direct, mulfirst, slope, num_dst, halo, x, W, attn_l, attn_r, loop_w, bias):
-        assert halo is None or (compact and mulfirst and loop_w is not None), "rgat_layer_halo_ok guards this path"
+    def forward(ctx, g, route, slope, num_dst, halo, x, W, attn_l, attn_r, loop_w, bias):
+        compact, direct, mulfirst = route.compact, route.direct, route.mulfirst
         x, W, attn_l, attn_r, loop_w, nd, offs = _prologue(x, W, attn_l, attn_r, loop_w, num_dst, halo)
         s, by_src, by_dst = _lists(g)
         rp, row, col, eids = s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"]
@@ -405,7 +385,7 @@ class RgatLayerFunction(th.autograd.Function):
             if h is None:
                 h = out.clone()
         ctx.halo = halo
-        ctx.g, ctx.compact, ctx.mulfirst, ctx.slope, ctx.nd = g, compact, mulfirst, slope, nd
+        ctx.g, ctx.route, ctx.slope, ctx.nd = g, route, slope, nd
         ctx.has_loop, ctx.has_bias = loop_w is not None, bias is not None
         ctx.save_for_backward(x, W, attn_l, attn_r, loop_w if loop_w is not None else x.new_empty(0), offs if offs is not None else eids,
                               sm, ex, ret, *saved)
@@ -414,7 +394,7 @@ class RgatLayerFunction(th.autograd.Function):
     @staticmethod
     def backward(ctx, grad_h):
         grad_h = grad_h.contiguous()
-        if ctx.compact:
+        if ctx.route.compact:
             return RgatLayerFunction._backward_distinct_rows(ctx, grad_h)
         x, W, attn_l, attn_r, loop_w, offs, sm, ex, ret, *saved = ctx.saved_tensors
         g, nd, slope = ctx.g, ctx.nd, ctx.slope
@@ -427,7 +407,7 @@ class RgatLayerFunction(th.autograd.Function):
         Wt = th.transpose(W, 2, 3).contiguous()
         grad_W = th.zeros_like(W)
         grad_x, grad_loop, go = _per_relation_front(x, loop_w if ctx.has_loop else None, offs, grad_h, nd, H, False)
-        mulfirst = ctx.mulfirst
+        mulfirst = ctx.route.mulfirst
         if mulfirst:
             wa_t = _folded_weight(W, attn_r).view(R, H, 1, Kd)
             grad_wa = th.zeros((R, H, Kd, 1), dtype=x.dtype, device=x.device)
@@ -488,7 +468,7 @@ class RgatLayerFunction(th.autograd.Function):
         x, W, attn_l, attn_r, loop_w, offs, sm, _, ret, featc, elc, erc, *featd = ctx.saved_tensors
         # (the forms of the parameters the forward made for this step: W^T [R,H,D,K], loop_w^T [X,K], wa [R,H,K,1] -- _compact_tables)
         Wt, loop_wt, wa = ctx.forms
-        g, nd, slope, halo, runs, has_loop, has_bias, mulfirst = ctx.g, ctx.nd, ctx.slope, ctx.halo, ctx.runs, ctx.has_loop, ctx.has_bias, ctx.mulfirst
+        g, nd, slope, halo, runs, has_loop, has_bias = ctx.g, ctx.nd, ctx.slope, ctx.halo, ctx.runs, ctx.has_loop, ctx.has_bias
         N, Kd = x.shape
         R, H, _, D = W.shape
         X = H * D
@@ -498,16 +478,16 @@ class RgatLayerFunction(th.autograd.Function):
         # per-destination tensors of the backward are their first nd rows
         dst_prefix = _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
         assert halo is None or dst_prefix, "a partition's edges point at owned nodes"
-        node_major = mulfirst and dst_prefix and _k.rgat_node_gemm_ok(R, H, Kd, D)
-        bf16 = x.dtype == th.bfloat16
-        # (exactly one of the three routes of the docstring; the last two add to grad_x per relation)
-        generic = not node_major and halo is None
-        per_relation_halo = not node_major and halo is not None
+        # (exactly one of the three routes of the docstring; the last two add to grad_x per relation.  The bf16 node's was resolved
+        #  when the call was routed -- from the same cached fact, by the same function)
+        route = rgat_route.with_backward(ctx.route, lambda: dst_prefix)
+        assert route.run_sums == (runs is not None) and route.halo == (halo is not None), "the forward ran another route than ctx.route"
+        mulfirst, bf16 = route.mulfirst, x.dtype == th.bfloat16
+        node_major, generic, per_relation_halo = (route.backward == name for name in ("node_major", "generic", "per_relation"))
         # (the weight gradient of attn_l from the edge pass when the forward left run sums: csrc/gat_compact.hip ga_block_reduce;
         #  grad_el_c then has no reader left -- its other consumer, the gradient through el, is folded into grad_feat_c -- and is
         #  not written at all)
-        attn_in_pass = not generic and runs is not None and R <= 8
-        assert not bf16 or (node_major and attn_in_pass and halo is None), "rgat_layer_bf16_training_ok guards this path"
+        attn_in_pass = route.attn_in_pass
         # (the self-loop product names each of the nd output rows once: the column sums of its gradout rows ARE the bias gradient,
         #  from the weight-gradient launch that streams grad_h anyway instead of a pass of its own inside the gather op: 0.088 ms on
         #  ogbn-mag)
@@ -636,16 +616,6 @@ class RgatLayerFunction(th.autograd.Function):
         return _gradients(grad_x, grad_W, grad_attn_l, grad_attn_r, grad_loop, grad_bias)
 
 
-def rgat_layer_halo_ok(g, x_own, W, slope, compact, mulfirst=False):
-    """Whether the one-node layer can run the halo exchange itself (forward_with_halo): the distinct-row dataflow with er
-    from the folded weight, and the matrix-core shapes of the split backward GEMMs."""
-    R, H, Kd, D = W.shape
-    if not rgat_layer_fused_ok(g, x_own, W, slope, compact, mulfirst):
-        return False
-    c, _, m = effective_flags(g, W, compact, True, mulfirst)
-    return c and m and _k.rows_linear_bias_ok(Kd, H * D) and _k.rows_matmul_backward_split_ok(H, Kd, D)
-
-
 def _attention_rows(g, ss, direct, grp, elc, erc, slope, N):
     """attn [E,H] in edge-id order from the tables an evaluation forward holds (csrc/gat_attention.hip): a pass over the ids, el_c
     and er_c alone, enqueued after the aggregation."""
@@ -750,16 +720,16 @@ class RgatLayerBf16Function(th.autograd.Function):
     RgatLayerFunction._backward_distinct_rows on its node-major route.  Saved: x and feat_c as bf16."""
 
     @staticmethod
-    def forward(ctx, g, direct, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
-        (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs, ctx.forms = _bf16_tables(g, direct, num_dst, x, W, attn_l, attn_r,
-                                                                                                        loop_w, bias, True)
+    def forward(ctx, g, route, slope, num_dst, x, W, attn_l, attn_r, loop_w, bias):
+        (x, W, attn_l, attn_r, loop_w), nd, ss, featc, elc, erc, h, grp, offs, ctx.forms = _bf16_tables(g, route.direct, num_dst, x, W, attn_l,
+                                                                                                        attn_r, loop_w, bias, True)
         N = x.shape[0]
         R, H, _, D = W.shape
         sm = th.empty((N, H), dtype=th.float32, device=x.device)
         ret = th.empty((N, H, D), dtype=th.float32, device=x.device)
         ctx.runs = _k.rgat_aggregate_compact_bf16(grp, featc, elc, erc, sm, ret, slope, h, R, attn_l=attn_l, feat_rel_ptrs=ss["rel_ptrs_row"])
         ctx.grp, ctx.halo = grp, None
-        ctx.g, ctx.compact, ctx.mulfirst, ctx.slope, ctx.nd = g, True, True, slope, nd
+        ctx.g, ctx.route, ctx.slope, ctx.nd = g, route, slope, nd
         ctx.has_loop, ctx.has_bias = loop_w is not None, bias is not None
         none = W.new_empty(0)
         ctx.save_for_backward(x, W, attn_l, attn_r, loop_w if loop_w is not None else none, offs if offs is not None else none, sm, none,
@@ -769,52 +739,7 @@ class RgatLayerBf16Function(th.autograd.Function):
     @staticmethod
     def backward(ctx, grad_h):
         grads = RgatLayerFunction._backward_distinct_rows(ctx, grad_h.contiguous())
-        return (None, None, None, None) + grads[7:]  # (g, direct, slope, num_dst; then x and the parameters)
-
-
-def rgat_layer_bf16_ok(g, x, W, slope, compact, mulfirst, tensors):
-    """Whether a bf16 input runs natively (_forward_only_bf16): no backward can follow, the one-node layer covers the call on the
-    distinct-row dataflow, and the shapes are those of the bf16 entries (kernels.rgat_bf16_shape_ok).  ``W``: a tensor of the
-    (padded) weight's shape; ``tensors``: everything whose gradient could be asked for."""
-    if not (FORWARD_ONLY and x.is_cuda and x.dtype == th.bfloat16):
-        return False
-    if th.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        return False
-    if not rgat_layer_fused_ok(g, x, W, slope, compact, mulfirst):
-        return False
-    R, H, Kd, D = W.shape
-    compact, _, _ = effective_flags(g, W, compact, True, mulfirst)
-    return compact and _k.rgat_bf16_shape_ok(H, Kd, D) and x.shape[0] * R < 2 ** 31
-
-
-def rgat_layer_bf16_training_ok(g, x, W, slope, compact, mulfirst, tensors, num_dst=None):
-    """Whether a bf16 input that needs a backward runs natively (RgatLayerBf16Function; the layer's bf16_training=True): one GPU, the
-    distinct-row dataflow, and the node-major route of _backward_distinct_rows with the attention-vector gradient from the edge pass
-    -- the shapes of the run-sum form and of het_rgat_node_gemm_ok (K and H*D each 32 or 64), at most 8 relations, every
-    destination below nd.  ``W``: a tensor of the (padded) weight's shape; ``tensors``: everything whose gradient could be asked for."""
-    if not (x.is_cuda and x.dtype == th.bfloat16 and x.dim() == 2 and th.is_grad_enabled()
-            and any(t is not None and t.requires_grad for t in tensors)):
-        return False
-    if not rgat_layer_fused_ok(g, x, W, slope, compact, mulfirst):
-        return False
-    R, H, Kd, D = W.shape
-    compact, _, _ = effective_flags(g, W, compact, True, mulfirst)
-    if not (compact and R <= 8 and x.shape[0] * R < 2 ** 31 and _k.rgat_bf16_shape_ok(H, Kd, D) and _k.rows_matmul_bf16_ok(Kd, H * D)
-            and _k.rgat_node_gemm_ok(R, H, Kd, D)):
-        return False
-    nd = x.shape[0] if num_dst is None else min(int(num_dst), x.shape[0])
-    return _destinations_below(g.get_separate_coo_original()["col_indices"], nd)
-
-
-def _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
-    """No backward can follow (autograd is off, or nothing that reaches the layer asks for a gradient) and the call is one the
-    forward-only kernels cover: one GPU, the distinct-row dataflow, the shapes and the int32 key range of the run-sum form."""
-    if not FORWARD_ONLY or halo is not None or not compact:
-        return False
-    if th.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, W, attn_l, attn_r, loop_w, bias)):
-        return False
-    R, H, _, D = W.shape
-    return _k.rgat_runs_shape_ok(H, D) and x.shape[0] * R < 2 ** 31
+        return (None, None, None, None) + grads[5:]  # (g, route, slope, num_dst; then x and the parameters)
 
 
 def attention_composition(g, x, W, attn_l, attn_r, slope):
@@ -849,22 +774,19 @@ def attention_composition(g, x, W, attn_l, attn_r, slope):
         return attn
 
 
-def rgat_layer_fused(g, x, W, attn_l, attn_r, loop_w, bias, slope, compact, direct, num_dst=None, mulfirst=False, halo=None,
-                     attn_out=None, bf16_training=False):
-    """``attn_out`` (a list, optional): on the evaluation paths the attention weights [E,H] are appended to it (_forward_only /
-    _forward_only_bf16); the autograd nodes leave it empty and the caller composes them (attention_composition).
-    ``bf16_training``: a bf16 input that needs a backward takes RgatLayerBf16Function (the caller has asked
-    rgat_layer_bf16_training_ok)."""
-    compact, direct, mulfirst = effective_flags(g, W, compact, direct, mulfirst)
-    if compact and not _has_single_sided_lists(g):
+def rgat_layer_fused(route, g, x, W, attn_l, attn_r, loop_w, bias, slope, num_dst=None, halo=None, attn_out=None):
+    """Run ``route`` (rgat_route.decide's answer for this call; the operands at its widths).  ``attn_out`` (a list, optional): on the
+    evaluation paths the attention weights [E,H] are appended to it (_forward_only / _forward_only_bf16); the autograd nodes leave
+    it empty and the caller composes them (attention_composition)."""
+    if route.compact and not _has_single_sided_lists(g):
         g.generate_separate_unique_node_indices_single_sided_for_each_etype()
-    if x.dtype == th.bfloat16:  # (the caller has asked rgat_layer_bf16_ok / _training_ok: there is no bf16 form of anything else)
-        assert compact and halo is None, "rgat_layer_bf16_ok guards this path"
-        if bf16_training and th.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, W, attn_l, attn_r, loop_w, bias)):
-            return RgatLayerBf16Function.apply(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
-        with th.no_grad():
-            return _forward_only_bf16(g, direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
-    if _forward_only_ok(g, halo, compact, x, W, attn_l, attn_r, loop_w, bias):
-        with th.no_grad():
-            return _forward_only(g, direct, mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
-    return RgatLayerFunction.apply(g, compact, direct, mulfirst, float(slope), num_dst, halo, x, W, attn_l, attn_r, loop_w, bias)
+    if route.path == "node":
+        return RgatLayerFunction.apply(g, route, float(slope), num_dst, halo, x, W, attn_l, attn_r, loop_w, bias)
+    if route.path == "train_bf16":
+        return RgatLayerBf16Function.apply(g, route, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias)
+    with th.no_grad():
+        if route.path == "eval":
+            return _forward_only(g, route.direct, route.mulfirst, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
+        if route.path == "eval_bf16":
+            return _forward_only_bf16(g, route.direct, float(slope), num_dst, x, W, attn_l, attn_r, loop_w, bias, attn_out)
+    raise _k._lib.HetError(f"rgat_layer_fused: no kernels behind the path {route.path!r}")

@@ -172,7 +172,7 @@ def test_rgat_layer_small_and_odd_widths(H, K, X, compact, mulfirst, pad, monkey
     """Output widths outside the matrix-core shapes -- 64 -> 8 is the layer of the reference CLI's defaults (--n_infeat 64
     --num_classes 8 --num_heads 1), 128 -> 8 over 8 heads the reference's RGAT experiment -- and heads of 1 - 8 floats or of a
     width that is not a power of two.  pad: the layer zero-pads every head to the row kernels' widths (het_amd/layers.py
-    _padded_head) and runs the one-node layer on the distinct-row dataflow; a spy checks that the row kernels ran, not the
+    _fused) and runs the one-node layer on the distinct-row dataflow; a spy checks that the row kernels ran, not the
     op-by-op composition.  Without the padding (HET_RGAT_PAD_HEADS=0): any-shape projection + row-dot and the non-cooperative
     gather kernels where the shapes allow, the op-by-op composition elsewhere.  n = 40: rows with hundreds of edges."""
     import het_amd.kernels as k

@@ -147,7 +147,7 @@ def test_cpu_bf16_input_is_handed_to_the_fp32_layer():
     import het_amd.kernels as k
     case = REF._case("cpu", ("random", 720, 350, 4, 6000), 4, 64, 64)
     g, layer, x = REF.build_case(case)
-    assert layer._bf16_native(g, x) is None
+    assert layer._route(g, x, None, False).path == "upcast"
     with torch.no_grad(), pytest.raises(k._lib.HetError, match="float32 GPU tensors, got torch.float32 on cpu"):
         layer(g, x)
 
@@ -159,15 +159,24 @@ def test_halo_call_with_bf16_rows_goes_through_the_fp32_layer(monkeypatch):
     case = REF._case("halo", ("random", 720, 350, 4, 6000), 4, 64, 64)
     g, layer, x = REF.build_case(case)
     seen = []
-    monkeypatch.setattr(FL, "rgat_layer_halo_ok", lambda g_, x_, *a, **k: seen.append(x_.dtype) or True)
+    decide = FL.rgat_route.decide
 
-    def fused(g_, x_, *a, **k):
-        assert x_.dtype == torch.float32 and k.get("halo") is not None
+    def served(facts, *lazy):  # (the real decision for the bf16 call; the fp32 halo call it hands on is "served" by the stub)
+        if facts.bf16:
+            return decide(facts, *lazy)
+        assert facts.halo
+        return FL.rgat_route.Route("node", facts.R, facts.H, facts.K, facts.D, True, True, True, True, True)
+
+    def fused(route, g_, x_, *a, **k):
+        seen.append(x_.dtype)
+        assert route.path == "node" and k.get("halo") is not None
         return x_ * 2.0
 
+    monkeypatch.setattr(FL.rgat_route, "decide", served)
     monkeypatch.setattr(FL, "rgat_layer_fused", fused)
     with torch.no_grad():
         out = layer.forward_with_halo(g, x, object())
     assert seen == [torch.float32] and out.dtype == torch.bfloat16 and torch.equal(out, (x.float() * 2.0).to(torch.bfloat16))
-    monkeypatch.setattr(FL, "rgat_layer_halo_ok", lambda *a, **k: False)
+    monkeypatch.setattr(FL.rgat_route, "decide", lambda facts, *lazy: decide(facts, *lazy) if facts.bf16 else
+                        FL.rgat_route.Route("composition", facts.R, facts.H, facts.K, facts.D))
     assert layer.forward_with_halo(g, x, object()) is None
