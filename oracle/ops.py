@@ -26,6 +26,10 @@ unpinned", except:
     tests/test_mag01_full.py, tests/test_gpu_mag01_full.py; toy graph, slice and the whole shipped topology).
     Pinned by the reference: a4 forward kinds 0 / 1 / 2 (sum) / 4, a5 ``grad_feat`` kinds 0 / 1 / 4.  Kind 3 is kind 4 with the
     rows found by search instead of read from the inverse index (same rows: tests/test_oracle.py::test_gat_kind3_rows_equal_kind4).
+  * a9 (RGCN compact aggregation) forward and backward (ref_rgcn.py:63-100), the KEYING of a10's softmax (ref_hgt.py:78-136,
+    :269-296: denominator per destination over all E positions, relation -> mu row; not its exp and sum) and a10c's message
+    aggregation and its backward (ref_hgt.py:299-337): tests/golden/*_rgcn_hgt.npz, tests/test_rgcn_hgt_golden.py,
+    tests/test_gpu_rgcn_hgt_golden.py (DESIGN.md section 3 states what each vector does and does not pin).
     NOT pinned, because the reference holds nothing comparable: a4's ``ret`` (ref_rgat.py never writes it), a5's
     ``grad_el`` / ``grad_er`` (ref_rgat.py:64-65 adds ``slope`` to the leaky-ReLU derivative and drops the dot product
     over the feature dimension -- it disagrees with the CUDA kernel it mirrors; its two backward WRAPPERS, :117-180 and

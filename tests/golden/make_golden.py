@@ -51,7 +51,53 @@ mag01_full.npz: the edges as one [3, E] int32 array, the reference builders'
 layouts as SHA-256 digests, the reference's float outputs in full; its float
 inputs are regenerated from seeds on the test side (tests/golden/recipe.py).
 
-Usage: python tests/golden/make_golden.py
+RGCN compact aggregation and HGT softmax / message aggregation (main_rgcn_hgt;
+NEW files toy_rgcn_hgt.npz, mag01_slice_rgcn_hgt.npz, mag01_full_rgcn_hgt.npz on
+the same three graphs and layouts; float arrays only).  ref_rgcn.py and
+ref_hgt.py are loaded UNMODIFIED (load_lite: synthetic parent package, an empty
+module of ours for ref_rgnn, the adjacency_manipulation loaded above) and
+called with eids = arange(E) on position-ordered edge data; H = 2, D = 4
+(recipe.H / recipe.D), RGCN width 16 (8 on the whole topology):
+  * ``rgcnc_ret [N,X]``: ref_rgcn.py:63-77 on feat_node [N,X], enorm [E], ret = 0
+    -- ret[col] += feat_src[row] * enorm, feat_src by NODE id, enorm by position;
+  * ``rgcncb_grad_feat_src [N,X]``: its backward (:80-100) on gradout [N,X];
+  * ``hgts_a [E,H]``: the normalisation stage of ref_hgt.py's softmax, from both
+    twins (separate COO :100-136 and in-CSR :269-296, both through :78-97), which
+    must agree exactly in edge-id order.  That file has no exp (m = score * mu,
+    :91-93) and takes the sum as an INPUT, so the generator forms m = exp(score *
+    mu) (fp32) and sum = index_add of m by destination (added in fp64, rounded
+    once) ITSELF and hands over unnormalized := m / mu.  Pinned: the denominator
+    keyed by the destination, all E positions visited, the relation -> mu row
+    lookup.  NOT pinned: the exp and the sum;
+  * ``hgta_new_h [N,H,D]``: ref_hgt.py:299-321 on message [E,H,D] and normalized
+    := hgts_a, both read by in-CSR POSITION (its eids argument is ignored);
+  * ``hgtab_grad_message [E,H,D]`` (toy, slice): ref_hgt.py:324-337 on gradout
+    [N,H,D]: grad_message[outcsr_eids] = gradout[outcsr_col_idx] * normalized, the
+    latter by out-CSR position; the canonical id handed over for an out-CSR entry
+    is its separate-COO position.
+The CSR arguments are the reference builders' own csr_* / tcsr_* arrays.  A
+committed file holds at most 1 MiB: the outputs are stored on the rows of
+recipe.pinned_rows (every row on the toy graph), the float inputs are
+regenerated from seeds (recipe.rgcn_hgt_inputs) and only their digests stored
+(the toy file also holds them in full).
+What these two files cannot pin, run as written on the toy graph by
+probe_not_pinnable (printed by main_rgcn_hgt):
+  - ref_hgt.backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr
+    (:217-264): RUNS, DEVIATES.  It multiplies the per-destination sum of
+    grad * normalized by grad_normalized (:247-248, :258-259) where the softmax
+    derivative of its own comment (:229) needs normalized, and sizes that sum
+    [E,H] (:239-242).  On the toy graph max |grad_score - derivative| = 2.77
+    where |derivative| <= 0.484;
+  - ref_hgt.backward_hgt_full_graph_edge_softmax_ops_csr (:340-373): RAISES
+    (RuntimeError, [E,H,D] * [E,H] at :363-366); grad_mu is rebound locally (:359);
+  - ref_rgcn.rgcn_layer1_separate_coo and its backward (:6-22, :25-60): RAISE here
+    (AttributeError on the empty ref_rgnn; the real one needs DGL's SEGMENTMM);
+  - ref_hgt's attention (:8-36, :39-75) and fused-message functions (:139-166,
+    :169-214): the same.
+
+Usage: python tests/golden/make_golden.py        the *_rgcn_hgt.npz files only
+       python tests/golden/make_golden.py gat    toy.npz, mag01_slice.npz, mag01_full.npz
+       python tests/golden/make_golden.py all
 """
 import importlib.util
 import os
@@ -216,15 +262,20 @@ def probe_backward_wrappers(lay, num_nodes, H, D):
     return notes
 
 
-def main_full():
-    """The whole shipped topology (SURVEY.md section 8c, fixture 2)."""
-    import json
+def full_coo3():
+    """[3, E] int32: row (source), col (destination), relation of the whole shipped topology, in file order."""
     parts = []
     for r, n in enumerate(recipe.MAG01_RELATIONS):
         a = np.load(os.path.join(REF, "data/ogbn_mag_0.1", f"{n}_coo_2.npy"))
         assert a.dtype == np.int32 and a.shape[0] == 2
         parts.append(np.concatenate([a, np.full((1, a.shape[1]), r, dtype=np.int32)], axis=0))
-    coo3 = np.ascontiguousarray(np.concatenate(parts, axis=1))  # [3, E]: row (source), col (destination), relation; file order
+    return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+def main_full():
+    """The whole shipped topology (SURVEY.md section 8c, fixture 2)."""
+    import json
+    coo3 = full_coo3()
     row, col, rel, eids, n, R = recipe.integrated_coo(coo3)
     E = row.numel()
     lay = layouts(row, col, rel, eids, R)
@@ -287,13 +338,197 @@ def save(name, d):
     print(name, {k: tuple(a.shape) for k, a in arrs.items()})
 
 
-def main():
-    # toy graph
+# ---------------------------------------------------------------- RGCN compact aggregation, HGT softmax / message aggregation
+def load_lite(name):
+    """ref_kernels_lite/<name>.py, UNMODIFIED, with its relative imports resolved: a synthetic parent package stands where
+    hrt/python/testing would, ``from .. import adjacency_manipulation`` finds the module loaded above, and ``from . import
+    ref_rgnn`` finds an EMPTY module of ours (the real one needs DGL) -- so every function that goes through ref_rgnn raises
+    AttributeError, and every other one runs as written."""
+    import types
+    top, sub = "ref_testing", "ref_testing.ref_kernels_lite"
+    if top not in sys.modules:
+        t, s_, stand_in = types.ModuleType(top), types.ModuleType(sub), types.ModuleType(sub + ".ref_rgnn")
+        t.__path__, s_.__path__ = [], []
+        t.adjacency_manipulation, t.ref_kernels_lite, s_.ref_rgnn = adj, s_, stand_in
+        sys.modules.update({top: t, sub: s_, sub + ".ref_rgnn": stand_in, top + ".adjacency_manipulation": adj})
+    spec = importlib.util.spec_from_file_location(f"{sub}.{name}", os.path.join(REF, "python/testing/ref_kernels_lite", name + ".py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+ref_rgcn = load_lite("ref_rgcn")
+ref_hgt = load_lite("ref_hgt")
+
+
+def position_of_csr_entries(lay):
+    """Separate-COO position (= canonical edge id) of every entry of the reference builders' out-CSR and transposed (in-) CSR."""
+    pos_of_eid = torch.empty_like(lay["sep_eids"])
+    pos_of_eid[lay["sep_eids"]] = torch.arange(lay["sep_eids"].numel())
+    return pos_of_eid[lay["csr_eids"]], pos_of_eid[lay["tcsr_eids"]]
+
+
+def rgcn_hgt_pins(lay, n, R, inp):
+    """The reference's outputs on position-ordered inputs ``inp`` (recipe.rgcn_hgt_inputs), every function called as written
+    with eids = arange(E) where it reads edge data through them; see the module docstring for what each vector pins."""
+    E, H, D = lay["sep_row"].numel(), recipe.H, recipe.D
+    ar = torch.arange(E)
+    rp, row, col = lay["sep_rel_ptrs"], lay["sep_row"], lay["sep_col"]
+    out = {}
+    # ---- RGCN compact aggregation, forward and backward (ref_rgcn.py:63-77, :80-100)
+    ret = torch.zeros(n, inp["rgcnc_feat_node"].shape[1])
+    ref_rgcn.rgcn_node_mean_aggregation_compact_as_of_node_separate_coo(
+        ar, rp, row, col, lay["ss_rel_ptrs_row"], lay["ss_node_indices_row"], inp["rgcnc_feat_node"], inp["rgcnc_enorm"], ret)
+    out["rgcnc_ret"] = ret
+    gfs = torch.zeros_like(ret)
+    ref_rgcn.backward_rgcn_node_mean_aggregation_compact_as_of_node_separate_coo(
+        ar, rp, row, col, lay["ss_rel_ptrs_row"], lay["ss_node_indices_row"], inp["rgcnc_feat_node"], inp["rgcnc_enorm"], ret,
+        inp["rgcncb_gradout"], gfs)
+    out["rgcncb_grad_feat_src"] = gfs
+    # ---- HGT softmax normalisation.  Ours (NOT pinned): m = exp(score * mu) in fp32, sum by destination (added up in fp64 and
+    # rounded once, so that the stored a = m / sum is within fp32 rounding of the exact quotient).  The reference's: the
+    # relation -> mu row lookup, all E positions, sum keyed by the destination.
+    rel = torch.repeat_interleave(torch.arange(R), rp[1:] - rp[:-1])
+    mu = inp["hgts_mu"]
+    m = torch.exp(inp["hgts_score"] * mu[rel])
+    sm = torch.zeros(n, H, dtype=torch.float64).index_add_(0, col, m.double()).float()
+    unnorm = m / mu[rel]
+    m1, a1 = torch.zeros(E, H), torch.zeros(E, H)
+    ref_hgt.hgt_full_graph_edge_softmax_ops_separate_coo(row, col, ar, rp, unnorm, mu, sm, m1, a1)
+    out_pos, in_pos = position_of_csr_entries(lay)
+    m2, a2 = torch.zeros(E, H), torch.zeros(E, H)
+    ref_hgt.hgt_full_graph_edge_softmax_ops_csr(lay["tcsr_row_ptrs"], lay["tcsr_col"], ar, lay["tcsr_rel"], unnorm[in_pos], mu, sm, m2, a2)
+    a2_by_id = torch.empty_like(a2)
+    a2_by_id[in_pos] = a2
+    assert torch.equal(a1, a2_by_id), "the reference's separate-COO and in-CSR softmax twins disagree"
+    out["hgts_a"] = a1
+    # ---- HGT message aggregation (ref_hgt.py:299-321: message and normalized by in-CSR POSITION) and its backward (:324-337:
+    # normalized by out-CSR position, grad_message written by edge id -- the canonical id of an entry is its separate-COO position)
+    new_h = torch.zeros(n, H, D)
+    ref_hgt.hgt_full_graph_message_mean_aggregation_csr(lay["tcsr_row_ptrs"], lay["tcsr_col"], lay["tcsr_rel"], ar,
+                                                        inp["hgta_message"][in_pos], a1[in_pos], sm, mu, new_h)
+    out["hgta_new_h"] = new_h
+    gm = torch.zeros(E, H, D)
+    ref_hgt.backward_hgt_full_graph_message_mean_aggregation_csr(lay["csr_row_ptrs"], lay["csr_col"], out_pos, lay["csr_rel"], sm,
+                                                                 a1[out_pos], inp["hgtab_gradout"], gm)
+    out["hgtab_grad_message"] = gm
+    return out
+
+
+def probe_not_pinnable(lay, n, R, inp, pins):
+    """Runs, as written, the four groups of ref_rgcn.py / ref_hgt.py that pin nothing and returns what they raise or by how much
+    they deviate (module docstring)."""
+    E, H, D = lay["sep_row"].numel(), recipe.H, recipe.D
+    ar = torch.arange(E)
+    rp, row, col = lay["sep_rel_ptrs"], lay["sep_row"], lay["sep_col"]
+    out_pos, in_pos = position_of_csr_entries(lay)
+    rel = torch.repeat_interleave(torch.arange(R), rp[1:] - rp[:-1])
+    a, mu, score = pins["hgts_a"], inp["hgts_mu"], inp["hgts_score"]
+    notes = []
+
+    def attempt(what, fn):
+        try:
+            notes.append(f"{what}: {fn() or 'ran'}")
+        except Exception as e:  # noqa: BLE001
+            notes.append(f"{what}: {type(e).__name__}: {e}")
+
+    def enorm_backward():
+        ga = recipe.normal(5, E, H)
+        gs, gmu = torch.zeros(E, H), torch.zeros(R, H)
+        ref_hgt.backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr(
+            lay["tcsr_row_ptrs"], lay["tcsr_col"], ar, lay["tcsr_rel"], score[in_pos], a[in_pos], ga[in_pos], mu, gs, gmu)
+        gs_by_id = torch.empty_like(gs)
+        gs_by_id[in_pos] = gs
+        t = torch.zeros(n, H).index_add_(0, col, a * ga)
+        want = (ga - t[col]) * a * mu[rel]  # the softmax derivative its own comment (:229) states
+        return f"ran; max |grad_score - softmax derivative| = {float((gs_by_id - want).abs().max()):.3g} (max |derivative| {float(want.abs().max()):.3g})"
+
+    attempt("ref_hgt.backward_hgt_full_graph_enorm_to_unnormalized_attn_score_csr (:217-264)", enorm_backward)
+    attempt("ref_hgt.backward_hgt_full_graph_edge_softmax_ops_csr (:340-373)",
+            lambda: ref_hgt.backward_hgt_full_graph_edge_softmax_ops_csr(
+                lay["csr_row_ptrs"], lay["csr_col"], out_pos, lay["csr_rel"], inp["hgta_message"], score, a, pins["hgta_new_h"],
+                inp["hgtab_gradout"], mu, torch.zeros(E, H), torch.zeros(R, H)))
+    X = inp["rgcnc_feat_node"].shape[1]
+    attempt("ref_rgcn.rgcn_layer1_separate_coo (:6-22)",
+            lambda: ref_rgcn.rgcn_layer1_separate_coo(rp, ar, row, col, inp["rgcnc_feat_node"], torch.zeros(R, X, X), inp["rgcnc_enorm"],
+                                                      torch.zeros(n, X)))
+    attempt("ref_rgcn.backward_rgcn_layer1_separate_coo (:25-60)",
+            lambda: ref_rgcn.backward_rgcn_layer1_separate_coo(rp, ar, row, col, inp["rgcnc_feat_node"], torch.zeros(R, X, X),
+                                                               inp["rgcnc_enorm"], torch.zeros(E), torch.zeros(n, X),
+                                                               inp["rgcncb_gradout"], torch.zeros(X, X)))
+    kq = torch.zeros(n, H, D)
+    attempt("ref_hgt.hgt_full_graph_hetero_attention_ops_coo (:8-36)",
+            lambda: ref_hgt.hgt_full_graph_hetero_attention_ops_coo(row, col, ar, rp, kq, kq, torch.zeros(R, H, D, D), torch.zeros(E, H, D),
+                                                                    torch.zeros(E, H)))
+    attempt("ref_hgt.backward_hgt_full_graph_hetero_attention_ops_coo (:39-75)",
+            lambda: ref_hgt.backward_hgt_full_graph_hetero_attention_ops_coo(
+                lay["tcsr_row_ptrs"], lay["tcsr_col"], ar, lay["tcsr_rel"], row, col, ar, rp, torch.zeros(R, H, D, D), torch.zeros(R, H, D, D),
+                kq, kq, torch.zeros(E, H, D), torch.zeros(E, H), torch.zeros(n, H, D), torch.zeros(n, H, D)))
+    attempt("ref_hgt.hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo (:139-166)",
+            lambda: ref_hgt.hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo(rp, ar, row, col, kq, torch.zeros(R, H, D, D), a,
+                                                                                                torch.zeros(n, H, D)))
+    attempt("ref_hgt.backward_hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo (:169-214)",
+            lambda: ref_hgt.backward_hgt_full_graph_fused_message_calc_and_mean_aggregation_separate_coo(
+                rp, ar, row, col, kq, torch.zeros(R, H, D, D), a, torch.zeros(n, H, D), torch.zeros(n, H, D), torch.zeros(R, H, D, D),
+                torch.zeros(E, H), inp["hgtab_gradout"]))
+    return notes
+
+
+def main_rgcn_hgt():
+    """toy_rgcn_hgt.npz, mag01_slice_rgcn_hgt.npz, mag01_full_rgcn_hgt.npz: float arrays only (the layouts are those of toy.npz,
+    mag01_slice.npz and mag01_full.npz).  Every input is regenerated on the test side (recipe.rgcn_hgt_inputs) and checked against
+    the digests stored here; the toy file also holds them in full.  The outputs are stored on the rows of recipe.pinned_rows."""
+    import json
+    for which, coo in (("toy", toy_coo), ("mag01_slice", slice_coo), ("mag01_full", lambda: recipe.integrated_coo(full_coo3()))):
+        row, col, rel, eids, n, R = coo()
+        lay = layouts(row, col, rel, eids, R)
+        E = row.numel()
+        inp = recipe.rgcn_hgt_inputs(which, E, n, R)
+        pins = rgcn_hgt_pins(lay, n, R, inp)
+        if which == "toy":
+            for note in probe_not_pinnable(lay, n, R, inp, pins):
+                print("reference, as written, on the toy graph --", note)
+        rows = recipe.pinned_rows(which, lay["sep_row"], lay["sep_col"], n)
+        dig = {"input_" + k: recipe.digest(v) for k, v in inp.items()}
+        dig.update({"rows_" + k: recipe.digest(v) for k, v in rows.items()})
+        out = dict(inp) if which == "toy" else {}
+        for k, v in pins.items():
+            r = rows[recipe.PIN_ROWS[k]]
+            if r.numel():
+                out[k] = v[r]
+        out["digests_json"] = np.array(json.dumps(dig, sort_keys=True))
+        save(which + "_rgcn_hgt.npz", out)
+        size = os.path.getsize(os.path.join(HERE, which + "_rgcn_hgt.npz"))
+        assert size <= 1 << 20, f"{which}_rgcn_hgt.npz: {size} bytes"
+
+
+def toy_coo():
+    """(row, col, rel, eids, num_nodes, num_rels) of the toy graph."""
     row = torch.tensor([0, 1, 2, 2, 3, 0])
     col = torch.tensor([1, 2, 0, 3, 1, 3])
     rel = torch.tensor([0, 0, 1, 1, 0, 1])
-    eids = torch.arange(6)
-    lay = layouts(row, col, rel, eids, 2)
+    return row, col, rel, torch.arange(6), 4, 2
+
+
+def slice_coo():
+    """Slice of the shipped ogbn_mag_0.1 topology; the relations are interleaved so the integrated COO is NOT relation-sorted
+    and the eids are a non-trivial permutation."""
+    rows, cols, rels = [], [], []
+    for r, n in enumerate(recipe.MAG01_RELATIONS):
+        a = np.load(os.path.join(REF, "data/ogbn_mag_0.1", f"{n}_coo_2.npy"))[:, :4096].astype(np.int64)
+        rows.append(a[0]); cols.append(a[1]); rels.append(np.full(a.shape[1], r, dtype=np.int64))
+    row = torch.from_numpy(np.concatenate(rows)); col = torch.from_numpy(np.concatenate(cols))
+    rel = torch.from_numpy(np.concatenate(rels))
+    perm = torch.randperm(row.numel(), generator=torch.Generator().manual_seed(7))
+    row, col, rel = row[perm], col[perm], rel[perm]
+    eids = torch.randperm(row.numel(), generator=torch.Generator().manual_seed(8))
+    return row, col, rel, eids, int(max(row.max(), col.max())) + 1, 6
+
+
+def main_gat():
+    """toy.npz, mag01_slice.npz, mag01_full.npz: the layouts and the fused-GAT pins."""
+    row, col, rel, eids, n, R = toy_coo()
+    lay = layouts(row, col, rel, eids, R)
     lay.update(gat_exp_sum(lay, 4, 2, seed=1))
     lay.update(gat_backward_grad_feat_src(lay, 4, 2, 3, seed=11))
     lay.update(gat_compact_exp_sum(lay, 4, 2, seed=21))
@@ -303,20 +538,8 @@ def main():
     lay["num_nodes"], lay["num_rels"] = torch.tensor(4), torch.tensor(2)
     save("toy.npz", lay)
 
-    # slice of the shipped ogbn_mag_0.1 topology; interleave the relations so the
-    # integrated COO is NOT relation-sorted and eids are a non-trivial permutation
-    names = ["cited", "citing", "has", "is-about", "writing", "written-by"]
-    rows, cols, rels = [], [], []
-    for r, n in enumerate(names):
-        a = np.load(os.path.join(REF, "data/ogbn_mag_0.1", f"{n}_coo_2.npy"))[:, :4096].astype(np.int64)
-        rows.append(a[0]); cols.append(a[1]); rels.append(np.full(a.shape[1], r, dtype=np.int64))
-    row = torch.from_numpy(np.concatenate(rows)); col = torch.from_numpy(np.concatenate(cols))
-    rel = torch.from_numpy(np.concatenate(rels))
-    perm = torch.randperm(row.numel(), generator=torch.Generator().manual_seed(7))
-    row, col, rel = row[perm], col[perm], rel[perm]
-    eids = torch.randperm(row.numel(), generator=torch.Generator().manual_seed(8))
-    lay = layouts(row, col, rel, eids, 6)
-    n = int(max(row.max(), col.max())) + 1
+    row, col, rel, eids, n, R = slice_coo()
+    lay = layouts(row, col, rel, eids, R)
     lay.update(gat_exp_sum(lay, n, 4, seed=2))
     lay.update(gat_backward_grad_feat_src(lay, n, 4, 4, seed=12))
     lay.update(gat_compact_exp_sum(lay, n, 4, seed=22))
@@ -324,6 +547,17 @@ def main():
     lay["num_nodes"], lay["num_rels"] = torch.tensor(n), torch.tensor(6)
     save("mag01_slice.npz", lay)
     main_full()
+
+
+def main(argv=None):
+    """No argument: the RGCN / HGT pins only (NEW files; toy.npz, mag01_slice.npz and mag01_full.npz are left as they are).
+    ``gat``: those three.  ``all``: both."""
+    what = (sys.argv[1:] if argv is None else argv) or ["rgcn_hgt"]
+    assert set(what) <= {"rgcn_hgt", "gat", "all"}, what
+    if "gat" in what or "all" in what:
+        main_gat()
+    if "rgcn_hgt" in what or "all" in what:
+        main_rgcn_hgt()
 
 
 if __name__ == "__main__":

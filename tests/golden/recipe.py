@@ -6,7 +6,10 @@ loads whole: hrt/src/test_hyb.cu.cc:26-36) as ONE [3, E] int32 array in file ord
 digests (+ the small pointer arrays in full) and the reference's float outputs.  Everything else -- the shuffled integrated COO,
 the edge numbering, the float inputs -- comes from numpy's PCG64 streams below (stable across platforms by numpy's
 compatibility policy; the fixture also stores digests of the regenerated float inputs, checked first by every test that uses
-them, so a drifted stream fails as "inputs differ" rather than as a parity error)."""
+them, so a drifted stream fails as "inputs differ" rather than as a parity error).
+
+The *_rgcn_hgt.npz fixtures (make_golden.py::main_rgcn_hgt) use the same scheme on all three graphs: rgcn_hgt_inputs() regenerates
+their float inputs, pinned_rows() the rows of the reference's outputs that they store."""
 import hashlib
 
 import numpy as np
@@ -90,6 +93,56 @@ def gat_inputs_round5(ts_rows):
     """el / er per row of the two-sided unique list: the kind-1 forward (dual wrapper fed the two-sided inverse index) and the
     kind-2 forward (single-list wrapper) of the reference."""
     return {"gatk1_el": normal(SEED_GATK1, ts_rows, H), "gatk1_er": normal(SEED_GATK1 + 100, ts_rows, H)}
+
+
+# ---- RGCN compact aggregation and HGT softmax / message aggregation pins (*_rgcn_hgt.npz; make_golden.py::main_rgcn_hgt)
+SEED_RGCNC, SEED_HGTS, SEED_HGTA, SEED_PINNED = 42, 52, 62, 72
+# per graph: (seed offset, RGCN width X, pinned node rows, pinned edge rows of hgts_a, of hgtab_grad_message (0: not stored))
+RGCN_HGT_GRAPHS = {"toy": (0, 16, 1 << 30, 1 << 30, 1 << 30), "mag01_slice": (1000, 16, 3000, 1 << 30, 6000),
+                   "mag01_full": (2000, 8, 6000, 40000, 0)}
+# which row set of pinned_rows() every stored output is restricted to
+PIN_ROWS = {"rgcnc_ret": "node", "rgcncb_grad_feat_src": "node", "hgta_new_h": "node", "hgts_a": "edge_a", "hgtab_grad_message": "edge_gm"}
+
+
+def uniform(seed, lo, hi, *shape):
+    return torch.from_numpy(_rng(seed).random(shape, dtype=np.float32) * np.float32(hi - lo) + np.float32(lo))
+
+
+def rgcn_hgt_inputs(which, E, n, R):
+    """Float inputs of the reference runs behind the *_rgcn_hgt.npz fixtures, all in separate-COO POSITION order (= by edge id
+    under the canonical numbering the reference's files are written for): feat_node / gradout per NODE for the RGCN compact
+    aggregation (ref_rgcn.py indexes node rows), enorm per edge; score / mu in [0.5, 1.5], message per edge and gradout per node
+    for HGT's softmax normalisation and message aggregation."""
+    off, X = RGCN_HGT_GRAPHS[which][:2]
+    return {"rgcnc_feat_node": normal(SEED_RGCNC + off, n, X), "rgcnc_enorm": uniform(SEED_RGCNC + off + 100, 0.1, 1.1, E),
+            "rgcncb_gradout": normal(SEED_RGCNC + off + 200, n, X),
+            "hgts_score": uniform(SEED_HGTS + off, 0.5, 1.5, E, H), "hgts_mu": uniform(SEED_HGTS + off + 100, 0.5, 1.5, R, H),
+            "hgta_message": normal(SEED_HGTA + off, E, H, D), "hgtab_gradout": normal(SEED_HGTA + off + 100, n, H, D)}
+
+
+def _pick(seed, pool, k):
+    pool = np.asarray(pool, dtype=np.int64)
+    return pool if k >= pool.size else pool[_rng(seed).choice(pool.size, size=k, replace=False)]
+
+
+def pinned_rows(which, row, col, n):
+    """The rows of the reference's outputs that a *_rgcn_hgt.npz fixture stores (a committed file holds at most 1 MiB; the toy
+    graph stores every row): {"node": node ids, "edge_a": positions of hgts_a, "edge_gm": positions of hgtab_grad_message},
+    sorted int64.  Nodes: the 128 destinations of highest in-degree, the 128 sources of highest out-degree, a draw from the
+    other nodes with an edge and 64 nodes without one (their rows are zero: the ops overwrite them).  Positions: the first, the
+    last (the reference's CUDA launcher never visits it: SURVEY Q6) and a draw.  The ops under test always run on the WHOLE
+    graph; only the comparison is restricted to these rows."""
+    off, _, k_node, k_a, k_gm = RGCN_HGT_GRAPHS[which]
+    row, col = np.asarray(row), np.asarray(col)
+    E = row.size
+    indeg, outdeg = np.bincount(col, minlength=n), np.bincount(row, minlength=n)
+    hubs = np.concatenate([np.argsort(-indeg, kind="stable")[:128], np.argsort(-outdeg, kind="stable")[:128]])
+    touched = np.nonzero(indeg + outdeg > 0)[0]
+    node = np.concatenate([hubs, _pick(SEED_PINNED + off, touched, k_node), _pick(SEED_PINNED + off + 1, np.nonzero(indeg + outdeg == 0)[0], 64)])
+    ends = np.array([0, E - 1], dtype=np.int64)
+    out = {"node": node, "edge_a": np.concatenate([ends, _pick(SEED_PINNED + off + 2, np.arange(E), k_a)]),
+           "edge_gm": np.concatenate([ends, _pick(SEED_PINNED + off + 3, np.arange(E), k_gm)]) if k_gm else ends[:0]}
+    return {k: torch.from_numpy(np.unique(v.astype(np.int64))) for k, v in out.items()}
 
 
 def canonical_csr(row_ptrs, col, rel, eids):
