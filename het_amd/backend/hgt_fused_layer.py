@@ -17,6 +17,10 @@ canonical edge types (one source node type each -- what the reference's HGT requ
 att' = relation_att for --hgt_fused_attn_score_flag (s = <k . att, q>), its transpose otherwise (s = <q . att, k>).
 Same function of the parameters as the composition (associativity of the matrix products): tests/ check both against
 oracle/layers.py::hgt_layer.  HET_HGT_FUSED=0 keeps the composition.
+
+Which calls run here, at which widths, with which output projection and which form of the backward is decided once per call, by
+hgt_route.decide: the table of its module docstring has every path with its conditions.  hgt_layer_fused runs the record it is
+given, and HgtAttentionFunction keeps it on its context for the backward.
 """
 import os
 
@@ -32,58 +36,54 @@ from .rgnn_layers_and_funcs import rgnn_relational_matmul_no_scatter_gather_list
 FUSED = os.environ.get("HET_HGT_FUSED", "1") != "0"
 
 
-def _node_dx_plan(G, ss, offs, K_in, X, dst):
+def _node_dx_plan(G, rp_row, rows_node, offs, K_in, X, dst):
     """Per graph, cached on it: what the node-major input gradient needs -- [R,N] int32 row maps of the (relation, source) list,
-    the rank of every node in the list of destinations with in-edges (compact form), the nodes sorted by (node type, which
-    sources they have rows in) so that 32-node tiles are homogeneous, and per node type its position range + relations.
-    None when the graph or the shapes are outside the pass (sampled blocks with type runs, too many relations per type)."""
+    the rank of every node in the list of destinations with in-edges (``dst`` = (dst_nodes, run_ptrs): the compact form), the nodes
+    sorted by (node type, which sources they have rows in) so that 32-node tiles are homogeneous, and per node type its position
+    range + relations.
+    (Whether the pass serves the graph and the shapes: ``dx`` of hgt_route.decide.)"""
     key = ("hgt_node_dx", K_in, X, dst is not None)
-    hit = G._plans.get(key)
-    if hit is not None:
-        return hit or None
-    plan = False
-    orig = G.graph_data["original"]
-    if orig.get("node_segment_types") is None and X in (32, 64) and K_in in (32, 64):
-        st, _ = G.get_rel_node_types()
-        st_l, offs_l = st.tolist(), offs.tolist()
-        T, R, N = len(offs_l) - 1, len(st_l), offs_l[-1]
-        rels_of = [[r for r in range(R) if st_l[r] == t] for t in range(T)]
-        if all(_k.node_rows_matmul_sum_ok(1 + 2 * len(rs), X, K_in) for rs in rels_of):
-            row_map = _k.node_row_map(ss["rel_ptrs_row"], ss["node_indices_row"], N)
-            dev = row_map.device
-            dst_rank = None
-            has_dst = [True] * T
-            if dst is not None:
-                dst_nodes, _, run_ptrs = dst
-                dst_rank = th.full((N,), -1, dtype=th.int32, device=dev)
-                dst_rank[dst_nodes] = th.arange(dst_nodes.numel(), dtype=th.int32, device=dev)
-                rl = run_ptrs.tolist()
-                has_dst = [rl[t + 1] > rl[t] for t in range(T)]
-            w = (1 << th.arange(R, device=dev, dtype=th.int64)).view(R, 1)
-            mask = ((row_map >= 0).to(th.int64) * w).sum(0)
-            if dst_rank is not None:
-                mask = mask | ((dst_rank >= 0).to(th.int64) << R)
-            typ = th.searchsorted(offs[1:].contiguous().to(dev), th.arange(N, device=dev), right=True)
-            order = th.argsort(mask | (typ << (R + 1)), stable=True).to(th.int32).contiguous()
-            plan = dict(row_map=row_map, dst_rank=dst_rank, order=order, offs=offs_l, rels_of=rels_of, has_dst=has_dst)
-    G._plans[key] = plan
-    return plan or None
+    plan = G._plans.get(key)
+    if plan is not None:
+        return plan
+    st_l, offs_l = G.get_rel_node_types()[0].tolist(), offs.tolist()
+    T, R, N = len(offs_l) - 1, len(st_l), offs_l[-1]
+    row_map = _k.node_row_map(rp_row, rows_node, N)
+    dev = row_map.device
+    dst_rank, has_dst = None, [True] * T
+    if dst is not None:
+        dst_nodes, run_ptrs = dst
+        dst_rank = th.full((N,), -1, dtype=th.int32, device=dev)
+        dst_rank[dst_nodes] = th.arange(dst_nodes.numel(), dtype=th.int32, device=dev)
+        has_dst = (run_ptrs[1:] > run_ptrs[:-1]).tolist()
+    w = (1 << th.arange(R, device=dev, dtype=th.int64)).view(R, 1)
+    mask = ((row_map >= 0).to(th.int64) * w).sum(0)
+    if dst_rank is not None:
+        mask = mask | ((dst_rank >= 0).to(th.int64) << R)
+    typ = th.searchsorted(offs[1:].contiguous().to(dev), th.arange(N, device=dev), right=True)
+    order = th.argsort(mask | (typ << (R + 1)), stable=True).to(th.int32).contiguous()
+    plan = G._plans[key] = dict(row_map=row_map, dst_rank=dst_rank, order=order, offs=offs_l, has_dst=has_dst,
+                                rels_of=[[r for r in range(R) if st_l[r] == t] for t in range(T)])
+    return plan
 
 
-def hgt_fused_ok(G, h, num_heads, d_k):
-    """Graphs (full, or sampled blocks large enough to keep their groupings) with the unique (relation, node) lists (built on
-    demand) and canonical relations, on the GPU, shapes the row kernels are built for."""
-    if not (FUSED and _k._plan.is_enabled() and h.is_cuda and h.dim() == 2 and hasattr(G, "graph_data") and G.get_num_edges() > 0):
-        return False
-    if not (_has_single_sided_lists(G) or hasattr(G, "generate_separate_unique_node_indices_single_sided_for_each_etype")):
-        return False
-    if _head_groups(num_heads, _padded_head(d_k)) is None:
-        return False
-    try:
-        G.get_rel_node_types()
-    except ValueError:  # a relation mixes node types: no single K / V projection per relation to fold
-        return False
-    return True
+def graph_facts(G, offs):
+    """What hgt_route.decide is told about the graph: the ``edges``, ``lists``, ``lists_present`` and ``typed_runs`` of its
+    Facts, and the three facts that read the graph's arrays, as callables for decide to ask where they matter."""
+    graph, present = hasattr(G, "graph_data"), _has_single_sided_lists(G)
+    facts = dict(edges=graph and G.get_num_edges() > 0, lists_present=present,
+                 lists=present or hasattr(G, "generate_separate_unique_node_indices_single_sided_for_each_etype"),
+                 typed_runs=graph and G.graph_data["original"].get("node_segment_types") is not None)
+
+    def canonical():
+        try:
+            return bool(G.get_rel_node_types())
+        except ValueError:  # a relation mixes node types: no single K / V projection per relation to fold
+            return False
+    # (read back to the host once per graph)
+    rels_per_type = lambda: _k._derived_get("hgt_rels_per_type", (G.get_rel_node_types()[0], offs),
+                                            lambda: th.bincount(G.get_rel_node_types()[0], minlength=offs.numel() - 1).tolist())
+    return facts, canonical, lambda: _k.destination_lists(G.get_separate_coo_original()["col_indices"], offs)[0].numel(), rels_per_type
 
 
 def _head_groups(num_heads: int, d_pad: int):
@@ -148,6 +148,11 @@ def fold_source_weights(k_lin, v_lin, rel_att, rel_msg, rel_pri, src_type, num_h
     return th.cat([flat(wk), flat(wm)], dim=2).unsqueeze(1).contiguous()
 
 
+def _row_lists(rel_ptrs, rows):
+    """A (relation, node) list whose rows are distinct inside every relation, as the segment GEMM entries take it."""
+    return {"unique_srcs_and_dests_rel_ptrs": rel_ptrs, "unique_srcs_and_dests_node_indices": rows}
+
+
 # Destinations WITHOUT in-edges receive nothing: their rows of new_h are zero, and so are their rows of the layer output
 # (the typed output projection has no bias).  When they are many (on the ogbn-mag-like graph 58 % of the nodes), q, lsum,
 # new_h and the output projection live on the S_dst destinations that do have in-edges: the row kernels are agnostic (their
@@ -158,170 +163,164 @@ COMPACT_DST_BELOW = float(os.environ.get("HET_HGT_COMPACT_DST", "0.8"))  # use t
 @_consistent_plan
 class HgtAttentionFunction(th.autograd.Function):
     @staticmethod
-    def forward(ctx, G, num_heads, offs, h, w_kv, q_w, dst):
+    def forward(ctx, G, route, num_heads, offs, h, w_kv, q_w, dst):
         """h [N,in]; w_kv [R,1,in,2X]; q_w [T,1,in,X] typed projection of the destination side (one weight per run of offs).
-        dst = None: rows of the result are nodes.  dst = (dst_nodes, rank_of_edge, run_ptrs) (kernels.destination_lists):
-        rows are the destinations with in-edges, in that order."""
+        dst = None: rows of the result are nodes.  dst = (dst_nodes, rank_of_edge, run_ptrs) (kernels.destination_lists, with
+        ``route.compact_dst``): rows are the destinations with in-edges, in that order.  ``route``: hgt_route.decide's answer for the
+        call -- a bf16 h only with ``native_bf16``, so in the shapes of the bf16 kernels; the backward reads its own route from it."""
         h, w_kv, q_w = h.contiguous(), w_kv.contiguous(), q_w.contiguous()
-        N, K_in = h.shape
-        X = q_w.shape[3]
-        H = num_heads
+        N, X = h.shape[0], q_w.shape[3]
         s = G.get_separate_coo_original()
         ss = G.get_separate_unique_node_indices_single_sided()
         rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
         S_row = rows_node.numel()
         bf16 = h.dtype == th.bfloat16  # activation rows (h, kv_c, q, out) bf16; lsum and every parameter fp32 (hgt_layer_fused)
-        if bf16 and not (_k.rows_matmul_bf16_ok(K_in, 2 * X) and _k.rows_matmul_backward_split_ok(1, K_in, 2 * X)
-                         and _k.rows_matmul_backward_split_ok(1, K_in, X)):  # (hgt_layer_fused sends such shapes through fp32)
-            raise _k._lib.HetError(f"HgtAttentionFunction: no bf16 kernels for input width {K_in} and row width {X} (hgt_bf16_native_ok)")
         new = lambda *shape: th.empty(shape, dtype=h.dtype, device=h.device)
         # the destination-side projection beside the source-row one (rgat_fused_layer._side_stream: independent launches, the
         # tensors are allocated and freed under the main stream)
         main, side = th.cuda.current_stream(h.device), (_side_stream(h.device) if OVERLAP and h.is_cuda else None)
-        if dst is None:
-            ND, keys = N, s["col_indices"]
-            q = new(ND, X)
-        else:
-            dst_nodes, keys, run_ptrs = dst
-            ND = dst_nodes.numel()
-            q = new(ND, 1, X)
-        kv_c = new(S_row, 1, 2 * X)
+        dst_nodes, keys, run_ptrs = (None, s["col_indices"], offs) if dst is None else dst  # (the rows of q: every node, in runs of offs)
+        ND = N if dst is None else dst_nodes.numel()
+        q, kv_c = new(ND, X) if dst is None else new(ND, 1, X), new(S_row, 1, 2 * X)
         if side is not None:
             side.wait_stream(main)
         with th.cuda.stream(side if side is not None else main):
             if bf16:
-                _k.rows_matmul_bf16(offs if dst is None else run_ptrs, None if dst is None else dst_nodes, None, q_w, h, q.view(ND, X))
+                _k.rows_matmul_bf16(run_ptrs, dst_nodes, None, q_w, h, q.view(ND, X))
             elif dst is None:
                 K.rgnn_relational_matmul_no_scatter_gather_list(offs, q_w, h, q)
             else:
-                K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": run_ptrs, "unique_srcs_and_dests_node_indices": dst_nodes},
-                                         1, q_w, h, q, True)
+                K.rgnn_relational_matmul(_row_lists(run_ptrs, dst_nodes), 1, q_w, h, q, True)
         q = q.view(ND, X)
         if bf16:
             _k.rows_matmul_bf16(rp_row, rows_node, None, w_kv, h, kv_c.view(S_row, 2 * X))
         else:
-            K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": rp_row, "unique_srcs_and_dests_node_indices": rows_node},
-                                     1, w_kv, h, kv_c, True)
+            K.rgnn_relational_matmul(_row_lists(rp_row, rows_node), 1, w_kv, h, kv_c, True)
         if side is not None:
             main.wait_stream(side)
         srow, _ = _edge_rows(G, ss, True, s["rel_ptrs"], s["row_indices"], s["col_indices"], s["eids"])
         grp = _k.hgt_compact_groupings(keys, srow, ND, S_row)
-        lsum, out = th.empty((ND, H), dtype=th.float32, device=h.device), new(ND, X)
+        lsum, out = th.empty((ND, num_heads), dtype=th.float32, device=h.device), new(ND, X)
         (_k.hgt_aggregate_compact_bf16 if bf16 else _k.hgt_aggregate_compact)(grp, kv_c, q, lsum, out)
-        ctx.G, ctx.H, ctx.grp, ctx.compact_dst = G, H, grp, dst is not None
+        ctx.G, ctx.route, ctx.grp = G, route, grp
         ctx.save_for_backward(h, w_kv, q_w, offs, q, kv_c, lsum, out, *(() if dst is None else (dst[0], dst[2])))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         h, w_kv, q_w, offs, q, kv_c, lsum, out, *lists = ctx.saved_tensors
-        G, H = ctx.G, ctx.H
-        N, K_in = h.shape
-        X = q_w.shape[3]
-        ss = G.get_separate_unique_node_indices_single_sided()
-        rp_row, rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
-        grad_out = grad_out.contiguous()
-        bf16 = h.dtype == th.bfloat16
         # sums over edges, hub rows met by float atomics, streamed once into the fp32 parameter gradients: fp32 for either row type
         g_kv, g_q = th.empty_like(kv_c, dtype=th.float32), th.empty_like(q, dtype=th.float32)
-        (_k.hgt_backward_compact_bf16 if bf16 else _k.hgt_backward_compact)(ctx.grp, kv_c, q, lsum, out, grad_out, g_kv, g_q)
-        rows_dw = _k.rows_matmul_backward_dw_bf16 if bf16 else _k.rows_matmul_backward_dw
-        node_sum = _k.node_rows_matmul_sum_bf16 if bf16 else _k.node_rows_matmul_sum
+        bwd = _k.hgt_backward_compact_bf16 if h.dtype == th.bfloat16 else _k.hgt_backward_compact
+        bwd(ctx.grp, kv_c, q, lsum, out, grad_out.contiguous(), g_kv, g_q)
+        return (None,) * 4 + _DenseBackward(ctx.route, ctx.G, h, w_kv, q_w, offs, lists, g_kv, g_q).run() + (None,)
+
+
+class _DenseBackward:
+    """The dense half of HgtAttentionFunction.backward: from g_kv [S_row,1,2X] and g_q [ND,X], the gradients of h, w_kv and q_w on
+    the route of the call (hgt_route.decide: ``dx``, ``split_kv``, ``split_q``, ``compact_dst``).
+    The two weight gradients (HBM-bound streams of rows; ``dw`` has their one launch) follow one rule in every form of the input
+    gradient.  With a side stream (HET_RGAT_OVERLAP; rgat_fused_layer._side_stream) they run there, beside the input-gradient chain:
+    w_kv's right after the first fork (where the route has ``split_kv``), q's after a second fork that follows the allocation of its
+    buffer.  Without one, each runs on the main stream where the form places its ``dw``."""
+
+    def __init__(self, route, G, h, w_kv, q_w, offs, lists, g_kv, g_q):
+        self.route, self.G, self.h, self.w_kv, self.q_w, self.offs, self.lists, self.g_kv, self.g_q = route, G, h, w_kv, q_w, offs, lists, g_kv, g_q
+        self.X = X = q_w.shape[3]
+        ss = G.get_separate_unique_node_indices_single_sided()
+        self.rp_row, self.rows_node = ss["rel_ptrs_row"], ss["node_indices_row"]
+        # the rows of the destination-side projection: the destinations with in-edges in runs of a node type, or every node
+        self.rp_q, self.rows_q = (lists[1], lists[0]) if route.compact_dst else (offs, None)
+        self.g_kv2 = g_kv.view(-1, 2 * X)
+        self.pending = {"kv": (self.rp_row, self.rows_node, self.g_kv2), "q": (self.rp_q, self.rows_q, g_q)}
         # one input-gradient buffer for both consumers of h
-        qwt = q_w.transpose(2, 3).contiguous()
-        wt = w_kv.transpose(2, 3).contiguous()
-        split_kv = _k.rows_matmul_backward_split_ok(1, K_in, 2 * X)
-        # the weight gradients (HBM-bound streams of rows) on the side stream beside the input-gradient chain
-        main, side = th.cuda.current_stream(h.device), (_side_stream(h.device) if OVERLAP and h.is_cuda else None)
-        grad_wkv = th.empty_like(w_kv) if split_kv else None
-        if side is not None and split_kv:
-            side.wait_stream(main)
-            with th.cuda.stream(side):
-                rows_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
-        nplan = _node_dx_plan(G, ss, offs, K_in, X, (lists[0], None, lists[1]) if ctx.compact_dst else None) if split_kv else None
-        if nplan is not None:
-            # every consumer of h adds its term in ONE pass over the nodes (csrc/node_sum.hip) -- instead of one read-modify-write
-            # launch per relation on the 2X-wide source rows + the destination-side projection's own pass (the round-3 form): the
-            # destination-side projection's gradient rows (g_q . Q_t^T) and, per relation the node is a source of, the two halves
-            # of its [k' | m] gradient row
-            grad_h, grad_qw = th.empty_like(h), th.empty_like(q_w)  # (allocated under the main stream)
-            g_kv2, g_q2 = g_kv.view(-1, 2 * X), g_q.view(-1, X)
-            wt2 = wt.view(-1, 2 * X, K_in)
-            if side is not None:
-                # grad_qw (and, on a graph seen for the first time, the plan's temporaries) were allocated AFTER the fork above: the
-                # allocator may have handed out blocks whose previous main-stream use was enqueued after that fork (the kernels
-                # that build the plan), and the side stream would write grad_qw while they still run -- seen once in ~40 cold
-                # runs as rows of grad_h missing (the node order came out corrupted).  Fork again: free when nothing is pending.
-                side.wait_stream(main)
-            with th.cuda.stream(side if side is not None else main):  # the other two weight gradients beside the node pass
-                if side is None:
-                    rows_dw(rp_row, rows_node, h, g_kv2, grad_wkv, accumulate=False)
-                if ctx.compact_dst:
-                    rows_dw(lists[1], lists[0], h, g_q2, grad_qw, accumulate=False)
-                else:
-                    rows_dw(offs, None, h, g_q2, grad_qw, accumulate=False)
-            for t, rels in enumerate(nplan["rels_of"]):
-                a, b = nplan["offs"][t], nplan["offs"][t + 1]
-                srcs = []
-                if nplan["has_dst"][t]:
-                    srcs.append((g_q2, 0, nplan["dst_rank"], qwt[t, 0]))
-                for r in rels:
-                    srcs.append((g_kv2, 0, nplan["row_map"][r], wt2[r, :X]))
-                    srcs.append((g_kv2, X, nplan["row_map"][r], wt2[r, X:]))
-                if not srcs:
-                    grad_h[a:b].zero_()  # (a node type that neither sends nor receives: its rows of the gradient are zero)
-                elif b > a:
-                    node_sum(a, b, srcs, grad_h, nplan["order"])
-            if side is not None:
-                main.wait_stream(side)
-            return None, None, None, grad_h, grad_wkv, grad_qw, None
-        if bf16:
-            # more relations per node type than the node-major pass keeps in LDS: the per-relation launches add a node's terms in an
-            # fp32 buffer, which is rounded once (the only fp32 [N, in] tensor of the bf16 step; h itself is never widened)
-            rp_q, rows_q = (lists[1], lists[0]) if ctx.compact_dst else (offs, None)
-            grad_h32 = (th.zeros if ctx.compact_dst else th.empty)(h.shape, dtype=th.float32, device=h.device)
-            grad_qw = th.empty_like(q_w)
-            if side is not None:
-                side.wait_stream(main)  # (grad_qw was allocated after the first fork: see the node-major branch)
-            with th.cuda.stream(side if side is not None else main):
-                if side is None:
-                    rows_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
-                rows_dw(rp_q, rows_q, h, g_q.view(-1, X), grad_qw, accumulate=False)
-            _k.rows_matmul_backward_dx(rp_q, rows_q, qwt, g_q.view(-1, X), grad_h32, atomic=False)
-            _k.rows_matmul_backward_dx(rp_row, rows_node, wt, g_kv.view(-1, 2 * X), grad_h32, atomic=2)
-            if side is not None:
-                main.wait_stream(side)
-            return None, None, None, grad_h32.to(th.bfloat16), grad_wkv, grad_qw, None
-        if not ctx.compact_dst:  # the typed projection writes every row with plain stores, the source-row GEMM adds to it
-            grad_h, grad_qw = th.empty_like(h), th.empty_like(q_w)
-            _k.matmul_no_scatter_gather_backward(offs, qwt, h, g_q, grad_h, grad_qw, accumulate=False)
+        self.qwt, self.wt = q_w.transpose(2, 3).contiguous(), w_kv.transpose(2, 3).contiguous()
+        self.main, self.side = th.cuda.current_stream(h.device), (_side_stream(h.device) if OVERLAP and h.is_cuda else None)
+
+    def dw(self, early=False, **grad_w):
+        """Launch the weight gradients (which=buffer) that are not launched yet: on the side stream, forked here, or without one on
+        the main stream -- unless ``early``: a place where only the side stream launches."""
+        todo = [which for which in grad_w if which in self.pending and not (early and self.side is None)]
+        if todo and self.side is not None:
+            # A fork per place: grad_qw (and, on a graph seen for the first time, the node-major plan's temporaries) are allocated AFTER
+            # the first fork, so the allocator may have handed out blocks whose previous main-stream use was enqueued after that fork
+            # (the kernels that build the plan), and the side stream would write grad_qw while they still run -- seen once in ~40 cold
+            # runs as rows of grad_h missing (the node order came out corrupted).  A fork is free when nothing is pending.
+            self.side.wait_stream(self.main)
+        rows_dw = _k.rows_matmul_backward_dw_bf16 if self.h.dtype == th.bfloat16 else _k.rows_matmul_backward_dw
+        with th.cuda.stream(self.main if self.side is None else self.side):
+            for which in todo:
+                rel_ptrs, rows, g = self.pending.pop(which)
+                rows_dw(rel_ptrs, rows, self.h, g, grad_w[which], accumulate=False)
+
+    def run(self):
+        grad_wkv = th.empty_like(self.w_kv) if self.route.split_kv else None
+        if self.route.split_kv:
+            self.dw(early=True, kv=grad_wkv)
+        grad_h, grad_wkv, grad_qw = getattr(self, self.route.dx)(grad_wkv)
+        if self.side is not None:
+            self.main.wait_stream(self.side)  # (a wait for a stream without new work is free)
+        return grad_h.to(self.h.dtype), grad_wkv, grad_qw
+
+    def node_major(self, grad_wkv):
+        """Every consumer of h adds its term in ONE pass over the nodes (csrc/node_sum.hip) -- instead of one read-modify-write
+        launch per relation on the 2X-wide source rows + the destination-side projection's own pass (the round-3 form): the
+        destination-side projection's gradient rows (g_q . Q_t^T) and, per relation the node is a source of, the two halves of its
+        [k' | m] gradient row."""
+        h, X = self.h, self.X
+        nplan = _node_dx_plan(self.G, self.rp_row, self.rows_node, self.offs, h.shape[1], X, self.lists or None)
+        grad_h, grad_qw = th.empty_like(h), th.empty_like(self.q_w)  # (allocated under the main stream)
+        self.dw(kv=grad_wkv, q=grad_qw)  # the other two weight gradients beside the node pass
+        node_sum = _k.node_rows_matmul_sum_bf16 if h.dtype == th.bfloat16 else _k.node_rows_matmul_sum
+        wt2 = self.wt.view(-1, 2 * X, h.shape[1])
+        for t, rels in enumerate(nplan["rels_of"]):
+            a, b = nplan["offs"][t], nplan["offs"][t + 1]
+            srcs = []
+            if nplan["has_dst"][t]:
+                srcs.append((self.g_q, 0, nplan["dst_rank"], self.qwt[t, 0]))
+            for r in rels:
+                srcs.append((self.g_kv2, 0, nplan["row_map"][r], wt2[r, :X]))
+                srcs.append((self.g_kv2, X, nplan["row_map"][r], wt2[r, X:]))
+            if not srcs:
+                grad_h[a:b].zero_()  # (a node type that neither sends nor receives: its rows of the gradient are zero)
+            elif b > a:
+                node_sum(a, b, srcs, grad_h, nplan["order"])
+        return grad_h, grad_wkv, grad_qw
+
+    def fp32_buffer(self, grad_wkv):
+        """bf16 rows and more relations per node type than the node-major pass keeps in LDS: the per-relation launches add a node's
+        terms in an fp32 buffer, which ``run`` rounds once (the only fp32 [N, in] tensor of the bf16 step; h itself is never widened)."""
+        grad_h32 = (th.zeros if self.route.compact_dst else th.empty)(self.h.shape, dtype=th.float32, device=self.h.device)
+        grad_qw = th.empty_like(self.q_w)
+        self.dw(kv=grad_wkv, q=grad_qw)
+        _k.rows_matmul_backward_dx(self.rp_q, self.rows_q, self.qwt, self.g_q, grad_h32, atomic=False)
+        _k.rows_matmul_backward_dx(self.rp_row, self.rows_node, self.wt, self.g_kv2, grad_h32, atomic=2)
+        return grad_h32, grad_wkv, grad_qw
+
+    def per_relation(self, grad_wkv):
+        """fp32 rows outside the node-major pass: the destination-side projection writes its rows of grad_h, the source-row GEMM adds
+        to them relation by relation; widths outside rows_matmul_backward_split_ok take the any-shape dX + dW launch."""
+        r, h = self.route, self.h
+        if not r.compact_dst:  # the typed projection writes every row with plain stores
+            grad_h, grad_qw = th.empty_like(h), th.empty_like(self.q_w)
+            _k.matmul_no_scatter_gather_backward(self.offs, self.qwt, h, self.g_q, grad_h, grad_qw, accumulate=False)
+        elif r.split_q:
+            grad_h, grad_qw = th.zeros_like(h), th.empty_like(self.q_w)
+            self.dw(early=True, q=grad_qw)
+            _k.rows_matmul_backward_dx(self.rp_q, self.rows_q, self.qwt, self.g_q, grad_h, atomic=False)  # distinct nodes, first writer: "="
+            self.dw(q=grad_qw)
         else:
-            dst_nodes, run_ptrs = lists
-            grad_h = th.zeros_like(h)
-            if _k.rows_matmul_backward_split_ok(1, K_in, X):
-                grad_qw = th.empty_like(q_w)
-                if side is not None:
-                    side.wait_stream(main)  # (grad_qw was allocated after the first fork: see the node-major branch)
-                    with th.cuda.stream(side):
-                        _k.rows_matmul_backward_dw(run_ptrs, dst_nodes, h, g_q, grad_qw, accumulate=False)
-                _k.rows_matmul_backward_dx(run_ptrs, dst_nodes, qwt, g_q, grad_h, atomic=False)  # distinct nodes, first writer: "="
-                if side is None:
-                    _k.rows_matmul_backward_dw(run_ptrs, dst_nodes, h, g_q, grad_qw, accumulate=False)
-            else:
-                grad_qw = th.zeros_like(q_w)
-                _k.matmul_backward({"unique_srcs_and_dests_rel_ptrs": run_ptrs, "unique_srcs_and_dests_node_indices": dst_nodes}, 1,
-                                   qwt, h, g_q.view(-1, 1, X), grad_h, grad_qw, True, accumulate=True, distinct_rows=True)
-        if split_kv:
-            _k.rows_matmul_backward_dx(rp_row, rows_node, wt, g_kv.view(-1, 2 * X), grad_h, atomic=2)  # rows of a relation: distinct nodes
-            if side is None:
-                _k.rows_matmul_backward_dw(rp_row, rows_node, h, g_kv.view(-1, 2 * X), grad_wkv, accumulate=False)
+            grad_h, grad_qw = th.zeros_like(h), th.zeros_like(self.q_w)
+            _k.matmul_backward(_row_lists(self.rp_q, self.rows_q), 1, self.qwt, h, self.g_q.view(-1, 1, self.X), grad_h, grad_qw, True,
+                               accumulate=True, distinct_rows=True)
+        if r.split_kv:
+            _k.rows_matmul_backward_dx(self.rp_row, self.rows_node, self.wt, self.g_kv2, grad_h, atomic=2)  # rows of a relation: distinct nodes
+            self.dw(kv=grad_wkv)
         else:
-            grad_wkv = th.zeros_like(w_kv)
-            _k.matmul_backward({"unique_srcs_and_dests_rel_ptrs": rp_row, "unique_srcs_and_dests_node_indices": rows_node}, 1, wt, h,
-                               g_kv, grad_h, grad_wkv, True, accumulate=True, distinct_rows=True)
-        if side is not None:
-            main.wait_stream(side)  # (a wait for a stream without new work is free)
-        return None, None, None, grad_h, grad_wkv, grad_qw, None
+            grad_wkv = th.zeros_like(self.w_kv)
+            _k.matmul_backward(_row_lists(self.rp_row, self.rows_node), 1, self.wt, h, self.g_kv, grad_h, grad_wkv, True, accumulate=True,
+                               distinct_rows=True)
+        return grad_h, grad_wkv, grad_qw
 
 
 @_consistent_plan
@@ -345,8 +344,8 @@ class RowsLinearScatter(th.autograd.Function):
         grad_out = grad_out.contiguous()
         T, _, K_in, X_out = w.shape
         g_x = th.empty((x_c.shape[0], 1, K_in), dtype=w.dtype, device=w.device)
-        K.rgnn_relational_matmul({"unique_srcs_and_dests_rel_ptrs": run_ptrs, "unique_srcs_and_dests_node_indices": rows}, 1,
-                                 w.transpose(2, 3).contiguous(), grad_out, g_x, True)  # g_x[i] = grad_out[rows[i]] . w[t]^T
+        # g_x[i] = grad_out[rows[i]] . w[t]^T
+        K.rgnn_relational_matmul(_row_lists(run_ptrs, rows), 1, w.transpose(2, 3).contiguous(), grad_out, g_x, True)
         g_wt = th.empty((T, 1, X_out, K_in), dtype=w.dtype, device=w.device)
         _k.rows_matmul_backward_dw(run_ptrs, rows, grad_out, x_c, g_wt, accumulate=False)  # SUM grad_out[rows[i]]^T (x) x_c[i]
         return None, None, None, g_x.view_as(x_c), g_wt.transpose(2, 3)
@@ -434,67 +433,39 @@ def typed_layer_norm(y, offs, gamma, beta, eps=1e-5):
     return (th.cat(parts, dim=0) if parts else y.float()).to(y.dtype)
 
 
-def hgt_bf16_native_ok(G, K_in, num_heads, d_k, proj_in, out_dim):
-    """Whether a bf16 layer input runs on the bf16 kernels: a full graph (one run per node type), input width and row width
-    X = H * d_pad (heads zero-padded to a power of two >= 8) both 32 or 64, one head group, and an output projection of
-    ``proj_in`` = H * d_k -> ``out_dim`` columns with both in {32, 64}.  Everything else runs fp32 on an upcast copy."""
-    d_pad = _padded_head(d_k)
-    X = num_heads * d_pad
-    if G.graph_data["original"].get("node_segment_types") is not None:
-        return False
-    if not (X in (32, 64) and K_in in (32, 64) and _head_groups(num_heads, d_pad) == 1):
-        return False
-    if not (_k.rows_matmul_bf16_ok(K_in, 2 * X) and _k.rows_matmul_bf16_ok(proj_in, out_dim) and _k.rows_matmul_bf16_ok(out_dim, proj_in)):
-        return False
-    return _k.rows_matmul_backward_split_ok(1, K_in, 2 * X) and _k.rows_matmul_backward_split_ok(1, K_in, X)
-
-
-def hgt_layer_fused(G, h, offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pri, num_heads, fused_attn):
-    """The HGT layer [N, out]: attention + aggregation as one node, then the typed output projection ``a_w`` [T,1,X,out] (one
-    weight per run of offs; the caller folds sigmoid(skip) in) -- on the destinations with in-edges only when those are a
-    minority of the nodes (the other rows of the output are zero by construction)."""
-    bf16 = h.dtype == th.bfloat16
-    if bf16 and not hgt_bf16_native_ok(G, h.shape[1], num_heads, q_w.shape[3] // num_heads, a_w.shape[2], a_w.shape[3]):
-        # graphs and shapes without bf16 kernels: the fp32 path on an upcast copy, one final rounding; autograd casts the gradient back
-        return hgt_layer_fused(G, h.float(), offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pri, num_heads, fused_attn).to(th.bfloat16)
+def hgt_layer_fused(route, G, h, offs, q_w, a_w, k_lin, v_lin, rel_att, rel_msg, rel_pri, num_heads, fused_attn):
+    """The HGT layer [N, out] on path ``fused`` of ``route`` (hgt_route.decide's answer for the call): attention + aggregation as
+    one node, then the typed output projection ``a_w`` [T,1,X,out] (one weight per run of offs; the caller folds sigmoid(skip) in)
+    -- with ``route.compact_dst`` on the destinations with in-edges only (the other rows of the output are zero by construction).
+    A bf16 ``h`` (``route.native_bf16``): h, kv_c, q, new_h, the output and their gradients are bf16 rows, each rounded once where its
+    kernel stores it; the parameters, the folded w_kv, lsum, grad_kv_c / grad_q and every parameter gradient stay fp32 (padded head
+    columns are dropped with torch ops: dtype-agnostic)."""
     if not _has_single_sided_lists(G):
         G.generate_separate_unique_node_indices_single_sided_for_each_etype()
     st, _ = G.get_rel_node_types()
     w_kv = fold_source_weights(k_lin, v_lin, rel_att, rel_msg, rel_pri, st, num_heads, fused_attn)
     N = h.shape[0]
-    d_k = q_w.shape[3] // num_heads
-    d_pad = _padded_head(d_k)
+    d_k, d_pad, groups, Xg = q_w.shape[3] // num_heads, route.d_pad, route.groups, route.Xg
     w_kv, q_w = _pad_heads(w_kv, num_heads, d_k, d_pad, parts=2), _pad_heads(q_w, num_heads, d_k, d_pad)
-    unpad = (lambda t: t) if d_pad == d_k else (lambda t: t.view(t.shape[0], num_heads, d_pad)[..., :d_k].reshape(t.shape[0], -1))
-    col = G.get_separate_coo_original()["col_indices"]
-    dst = _k.destination_lists(col, offs)
-    groups = _head_groups(num_heads, d_pad)
-    compact = dst[0].numel() < COMPACT_DST_BELOW * N
-    if bf16:
-        # bf16 activations: h, kv_c, q, new_h, the output and their gradients are bf16 rows, each rounded once where its kernel stores it;
-        # the parameters, the folded w_kv, lsum, grad_kv_c / grad_q and every parameter gradient stay fp32 (padded head columns are
-        # dropped with torch ops: dtype-agnostic)
-        new_h = unpad(HgtAttentionFunction.apply(G, num_heads, offs, h, w_kv, q_w, dst if compact else None))
-        if compact:
-            return RowsLinearBf16.apply(dst[2], dst[0], N, new_h, a_w)
-        return RowsLinearBf16.apply(offs, None, N, new_h, a_w)
-
-    def attention(dst_lists):
-        if groups == 1:
-            return HgtAttentionFunction.apply(G, num_heads, offs, h, w_kv, q_w, dst_lists)
+    dst = _k.destination_lists(G.get_separate_coo_original()["col_indices"], offs)
+    dst_lists = dst if route.compact_dst else None
+    if groups == 1:
+        new_h = HgtAttentionFunction.apply(G, route, num_heads, offs, h, w_kv, q_w, dst_lists)
+    else:
         # rows wider than the row kernels take: the heads in `groups` passes (columns of a head group in [k' | m] and in q)
-        X, Xg, Hg = num_heads * d_pad, num_heads * d_pad // groups, num_heads // groups
-        parts = []
+        X, parts = num_heads * d_pad, []
         for i in range(groups):
             w_g = th.cat([w_kv[..., i * Xg:(i + 1) * Xg], w_kv[..., X + i * Xg:X + (i + 1) * Xg]], dim=-1).contiguous()
-            parts.append(HgtAttentionFunction.apply(G, Hg, offs, h, w_g, q_w[..., i * Xg:(i + 1) * Xg].contiguous(), dst_lists))
-        return th.cat(parts, dim=1)
-
-    if not compact:
-        new_h = unpad(attention(None))
+            parts.append(HgtAttentionFunction.apply(G, route, num_heads // groups, offs, h, w_g, q_w[..., i * Xg:(i + 1) * Xg].contiguous(),
+                                                    dst_lists))
+        new_h = th.cat(parts, dim=1)
+    if d_pad != d_k:
+        new_h = new_h.view(new_h.shape[0], num_heads, d_pad)[..., :d_k].reshape(new_h.shape[0], -1)
+    if route.out_proj == "bf16_rows":
+        return RowsLinearBf16.apply(*((dst[2], dst[0]) if route.compact_dst else (offs, None)), N, new_h, a_w)
+    if route.out_proj == "typed_gemm":
         return B_matmul_no_scatter_gather(offs, a_w, new_h)
-    new_h_c = unpad(attention(dst))
-    if _k.rows_matmul_backward_split_ok(1, a_w.shape[3], a_w.shape[2]):
-        return RowsLinearScatter.apply(dst[2], dst[0], N, new_h_c, a_w)
-    out_c = B_matmul_no_scatter_gather(dst[2], a_w, new_h_c)  # rows of a type are a contiguous piece of the sorted list
+    if route.out_proj == "rows_scatter":
+        return RowsLinearScatter.apply(dst[2], dst[0], N, new_h, a_w)
+    out_c = B_matmul_no_scatter_gather(dst[2], a_w, new_h)  # rows of a type are a contiguous piece of the sorted list
     return th.zeros((N, out_c.shape[1]), dtype=out_c.dtype, device=out_c.device).index_copy(0, dst[0], out_c)

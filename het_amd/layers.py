@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import backend as B
 from .backend import rgat_fused_layer as FL
 from .backend import hgt_fused_layer as _hgt_fused
+from .backend import hgt_route
 
 
 PAD_HEADS = os.environ.get("HET_RGAT_PAD_HEADS", "1") != "0"  # zero-pad narrow / odd RGAT heads to the row kernels' widths
@@ -397,18 +398,12 @@ class HET_HGTLayerHetero(nn.Module):
     of ``new_h`` once by the typed output projection; ``h.grad`` once, after all of a node's terms are summed in the node-major
     pass.  The log-sum-exp, the gradients of ``kv_c`` and ``q`` (sums over edges that feed the fp32 parameter gradients) and
     every sum, exponential, maximum and dot product are fp32 on widened values; rounding is to nearest even.
-    The bf16 kernels serve a full graph with canonical relations whose padded input width and row width H * d_k are both 32 or 64,
-    heads narrower than 8 or of odd width zero-padded as in fp32 (row width H * d_pad) -- with and without compact destinations.  Everything else is correct,
-    not faster: it runs fp32 on an upcast copy of ``h`` and the result is cast back to bf16 (the gradient likewise, through
-    autograd) --
-      * the fused path is off or not applicable (HET_HGT_FUSED=0, groupings off, relations that mix node types, CPU tensors): the
-        op-by-op composition, ``multiply_among_weights_first_flag`` included;
-      * sampled blocks whose nodes are runs of equal type (``node_segment_types``);
-      * rows wider than 64 (H * d_pad = 128, or two head groups), padded input widths other than 32 / 64, output widths other
-        than 32 / 64.
-    One branch inside the bf16 path keeps an fp32 buffer: a graph with more relations per node type than the node-major input
-    gradient keeps in LDS (4 and more) adds a node's gradient terms relation by relation in an fp32 [N, in] buffer and rounds
-    it once; ``h``, ``kv_c``, ``q`` and ``new_h`` are bf16 there too.
+    Which calls the bf16 kernels serve (NATIVE), and which code serves every other call, fp32 or bf16, is decided in one place: the
+    table in het_amd/backend/hgt_route.py.  A bf16 call outside NATIVE (path ``upcast``) is correct, not faster: it runs fp32 on an
+    upcast copy of ``h`` and the result is cast back to bf16 (the gradient likewise, through autograd).
+    One form of the backward inside the bf16 path keeps an fp32 buffer (``dx`` = fp32_buffer of that table): it adds a node's
+    gradient terms relation by relation in an fp32 [N, in] buffer and rounds it once; ``h``, ``kv_c``, ``q`` and ``new_h`` are bf16
+    there too.
 
     ``use_norm`` (the HGT paper's x = norm_t(W[t] . Agg(x)); HGT/models_dgl.py:131-138 applies the per-type ``LayerNorm(out_dim)`` the
     HET class only builds, HGT/models.py:92-97): the layer's output y, on the full [N, out] result and before the ``num_dst`` slice,
@@ -457,68 +452,79 @@ class HET_HGTLayerHetero(nn.Module):
     def forward(self, G, h, num_dst=None):
         """``num_dst``: ``G`` is a sampled block whose first ``num_dst`` nodes are its destinations (only their rows are
         returned); its nodes are runs of equal type (``node_segment_types``, het_amd/sampling.py) instead of one run per type."""
-        if h.dtype == th.bfloat16 and not (_hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k) and (
-                not self.use_norm or _hgt_fused.hgt_bf16_native_ok(G, _padded_in_width(self.in_dim), self.num_heads, self.d_k,
-                                                                   self.out_dim, self.out_dim))):
-            # no bf16 kernels behind the op-by-op composition: fp32 on an upcast copy, one final rounding (class docstring).  With
-            # use_norm the fused path's own upcast (graphs and shapes without bf16 kernels) is taken here as well, so that the norm
-            # runs in fp32 inside the recursion and its result is the one value that is rounded.
-            return self.forward(G, h.float(), num_dst).to(th.bfloat16)
         offs = G.get_original_node_type_offsets()
+        route = self._route(G, h, offs)
+        if route.path == "upcast":
+            # correct, not faster: the fp32 layer on an upcast copy -- the norm of use_norm runs in fp32 with the rest -- and one
+            # final rounding (class docstring); autograd casts the gradient of the input back
+            return self.forward(G, h.float(), num_dst).to(th.bfloat16)
         seg_types = G.graph_data["original"].get("node_segment_types") if hasattr(G, "graph_data") else None
         per_run = (lambda w: w) if seg_types is None else (lambda w: w.index_select(0, seg_types))
+        out = getattr(self, "_forward_" + route.path)(route, G, h, offs, per_run)  # _forward_fused, _weights_first, _composition
+        # use_norm on the full [N, out] result (one affine pair per run of ``offs``), then the destinations' rows
+        if self.use_norm:
+            out = _hgt_fused.typed_layer_norm(out, offs, per_run(self.norm_weight), per_run(self.norm_bias), self.norm_eps)
+        return out if num_dst is None else out[:num_dst]
 
-        def finish(out):
-            """use_norm on the full [N, out] result (one affine pair per run of ``offs``), then the destinations' rows."""
-            if self.use_norm:
-                out = _hgt_fused.typed_layer_norm(out, offs, per_run(self.norm_weight), per_run(self.norm_bias), self.norm_eps)
-            return out if num_dst is None else out[:num_dst]
-        if _hgt_fused.hgt_fused_ok(G, h, self.num_heads, self.d_k):
-            # attention + aggregation as one node on the distinct (relation, source) rows (backend/hgt_fused_layer.py): the
-            # same function of the parameters for every flag combination below, without the per-edge tensors
-            k_w, q_w, v_w = self.k_linears, self.q_linears, self.v_linears
-            Kp = _padded_in_width(self.in_dim)
-            if Kp != self.in_dim:  # (the layer input meets the three typed projections only: zero columns / zero weight rows)
-                rows = (0, 0, 0, Kp - self.in_dim)
-                h = nn.functional.pad(h, (0, Kp - self.in_dim))
-                k_w, q_w, v_w = nn.functional.pad(k_w, rows), nn.functional.pad(q_w, rows), nn.functional.pad(v_w, rows)
-            out = _hgt_fused.hgt_layer_fused(G, h, offs, per_run(q_w), per_run(th.sigmoid(self.skip) * self.a_linears),
-                                             k_w, v_w, self.relation_att, self.relation_msg,
-                                             self.relation_pri, self.num_heads, self.hgt_fused_attn_score_flag)
-            return finish(out)
-        if self.multiply_among_weights_first_flag:
-            return finish(self._forward_weights_first(G, h, offs, per_run))
-        k = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.k_linears), h).view(-1, self.num_heads, self.d_k)
-        q = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.q_linears), h).view(-1, self.num_heads, self.d_k)
-        v = B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(self.v_linears), h).view(-1, self.num_heads, self.d_k)
+    def _route(self, G, h, offs):
+        """Which code serves the call: the facts hgt_route.decide reads (its Facts) and its answer."""
+        graph, canonical, num_dst_rows, rels_per_type = _hgt_fused.graph_facts(G, offs)
+        d_pad = _hgt_fused._padded_head(self.d_k)
+        facts = hgt_route.Facts(
+            cuda=h.is_cuda, bf16=h.dtype == th.bfloat16, dim=h.dim(), N=h.shape[0], K_padded=_padded_in_width(self.in_dim),
+            H=self.num_heads, d_pad=d_pad, groups=_hgt_fused._head_groups(self.num_heads, d_pad), out_dim=self.out_dim,
+            plan=B.plan_enabled(), fused=_hgt_fused.FUSED, weights_first_flag=self.multiply_among_weights_first_flag,
+            fused_attn_score_flag=self.hgt_fused_attn_score_flag, compact_flag=self.compact_as_of_node_flag,
+            direct_flag=self.compact_direct_indexing_flag, compact_dst_below=_hgt_fused.COMPACT_DST_BELOW, **graph)
+        return hgt_route.decide(facts, canonical, num_dst_rows, rels_per_type)
+
+    def _forward_fused(self, route, G, h, offs, per_run):
+        """Attention + aggregation as one node on the distinct (relation, source) rows (backend/hgt_fused_layer.py): the same
+        function of the parameters for every flag combination of the composition, without the per-edge tensors."""
+        k_w, q_w, v_w = self.k_linears, self.q_linears, self.v_linears
+        if route.Kp != self.in_dim:  # (the layer input meets the three typed projections only: zero columns / zero weight rows)
+            rows = (0, 0, 0, route.Kp - self.in_dim)
+            h = nn.functional.pad(h, (0, route.Kp - self.in_dim))
+            k_w, q_w, v_w = nn.functional.pad(k_w, rows), nn.functional.pad(q_w, rows), nn.functional.pad(v_w, rows)
+        return _hgt_fused.hgt_layer_fused(route, G, h, offs, per_run(q_w), per_run(th.sigmoid(self.skip) * self.a_linears), k_w, v_w,
+                                          self.relation_att, self.relation_msg, self.relation_pri, self.num_heads,
+                                          self.hgt_fused_attn_score_flag)
+
+    def _forward_composition(self, route, G, h, offs, per_run):
+        """The reference's model code op by op (HGT/models.py:120-262); ``route.score`` / ``route.direct``: the form of the score."""
+        k, q, v = (B.rgnn_relational_matmul_no_scatter_gather_list(offs, per_run(w), h).view(-1, self.num_heads, self.d_k)
+                   for w in (self.k_linears, self.q_linears, self.v_linears))
+        return self._edge_ops(route, G, offs, per_run, self.relation_att, self.relation_msg, k, q, v, q)
+
+    def _edge_ops(self, route, G, offs, per_run, att, msg, k, q, v, q_rows):
+        """The attention score in the form of ``route.score``, the edge softmax fused with the message aggregation, and the typed
+        output projection.  ``q_rows``: what the relation weights ``att`` multiply on the destination side -- q, or [N, in] rows
+        with one head (--multiply_among_weights_first_flag)."""
+        one_head = q_rows.dim() == 2
         # The per-edge tensor q[dst] . relation_att[r] of the default flags (models.py:215-241) is read by the inner
         # product only and its rows repeat for every edge of a (relation, destination) pair: when the graph carries the
         # unique (relation, node) lists it is formed on those rows and indexed directly -- the reference's compact
         # dataflow, same values -- instead of being written and re-read as an [E,H,dk] tensor.
-        has_lists = "unique_node_indices_single_sided" in getattr(G, "graph_data", {}).get("separate", {})
-        as_compact = self.compact_as_of_node_flag or (has_lists and h.is_cuda and B.plan_enabled())
-        direct = self.compact_direct_indexing_flag or not self.compact_as_of_node_flag
-        if self.hgt_fused_attn_score_flag:  # models.py:172-175
-            attn_score = B.hgt_full_graph_hetero_attention_ops_coo(G, self.relation_att, k, q)
-        elif as_compact:  # models.py:177-214
+        if route.score == "fused_score":  # models.py:172-175
+            attn_score = B.hgt_full_graph_hetero_attention_ops_coo(G, att, k, q)
+        elif route.score == "compact":  # models.py:177-214
             ss = G.get_separate_unique_node_indices_single_sided()
             compact = B.rgnn_relational_matmul(
                 {"unique_srcs_and_dests_rel_ptrs": ss["rel_ptrs_col"],
-                 "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}, self.relation_att, q, False, 1)
-            attn_score = B.rgnn_inner_product_right_node(G, compact, k, 2 if direct else 1, "_col")
+                 "unique_srcs_and_dests_node_indices": ss["node_indices_col"]}, att, q_rows, one_head, 1)
+            attn_score = B.rgnn_inner_product_right_node(G, compact, k, 2 if route.direct else 1, "_col")
         else:  # models.py:215-241
             s = G.get_separate_coo_original()
             per_edge = B.rgnn_relational_matmul(
                 {"separate_coo_rel_ptrs": s["rel_ptrs"], "separate_coo_node_indices": s["col_indices"],
-                 "separate_coo_eids": s["eids"]}, self.relation_att, q, False, 0)
+                 "separate_coo_eids": s["eids"]}, att, q_rows, one_head, 0)
             attn_score = B.rgnn_inner_product_right_node(G, per_edge, k, 0, "_col")
         new_h = B.hgt_full_graph_message_calc_edge_softmax_and_message_mean_aggregation_coo(
-            self.relation_msg, v, G, (self.relation_pri / self.sqrt_dk), attn_score)
-        out = B.rgnn_relational_matmul_no_scatter_gather_list(
+            msg, v, G, (self.relation_pri / self.sqrt_dk), attn_score)
+        return B.rgnn_relational_matmul_no_scatter_gather_list(
             offs, per_run(th.sigmoid(self.skip) * self.a_linears), new_h.view(-1, self.out_dim))
-        return finish(out)
 
-    def _forward_weights_first(self, G, h, offs, per_run):
+    def _forward_weights_first(self, route, G, h, offs, per_run):
         """--multiply_among_weights_first_flag (see the class docstring): two small batched products per step replace the three
         typed projections of the nodes; the per-relation [in,in] / [in,dk] weights then meet the layer input directly."""
         H, dk = self.num_heads, self.d_k
@@ -533,15 +539,5 @@ class HET_HGTLayerHetero(nn.Module):
         w_msg = th.matmul(Vr, self.relation_msg)  # [R,H,in,dk]
         hh = h.unsqueeze(1) if H == 1 else h.unsqueeze(1).expand(-1, H, -1)
         hh = hh.contiguous()  # k = q = v: the layer input once per head (the reference: h.unsqueeze(1).repeat(1, H, 1))
-        if self.hgt_fused_attn_score_flag:
-            attn_score = B.hgt_full_graph_hetero_attention_ops_coo(G, w_att.contiguous(), hh, hh)
-        else:
-            s = G.get_separate_coo_original()
-            per_edge = B.rgnn_relational_matmul(
-                {"separate_coo_rel_ptrs": s["rel_ptrs"], "separate_coo_node_indices": s["col_indices"],
-                 "separate_coo_eids": s["eids"]}, w_att.contiguous(), h, True, 0)  # [E,H,in] = h[dst] . W_att[r,h]
-            attn_score = B.rgnn_inner_product_right_node(G, per_edge, hh, 0, "_col")
-        new_h = B.hgt_full_graph_message_calc_edge_softmax_and_message_mean_aggregation_coo(
-            w_msg.contiguous(), hh, G, (self.relation_pri / self.sqrt_dk), attn_score)
-        return B.rgnn_relational_matmul_no_scatter_gather_list(
-            offs, per_run(th.sigmoid(self.skip) * self.a_linears), new_h.view(-1, self.out_dim))
+        # (per edge: [E,H,in] = h[dst] . W_att[r,h], from the one-head rows of h)
+        return self._edge_ops(route, G, offs, per_run, w_att.contiguous(), w_msg.contiguous(), hh, hh, hh, h)
