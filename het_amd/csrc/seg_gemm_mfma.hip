@@ -9,6 +9,8 @@
 // (half h owns k in [h*K/2, (h+1)*K/2)) -- A and B use the same permutation, so
 // the sum is unchanged while every lane's fragment is one contiguous half row.
 
+#include <stdlib.h>
+
 #include <type_traits>
 
 #include "seg_gemm_mfma.hip.h"
@@ -479,6 +481,172 @@ __global__ __launch_bounds__(256) void HET_seg_dw_mfma(MfmaDwArgsT<TG, TA> a, in
   }
 }
 
+// ---- weight gradient, wide rows: K = X = 64, fp32 rows on 16-byte boundaries -----------------------
+// The kernel above is bound by the number of its vector-memory instructions: the 32x32x2 operand layout (lane = feature, lane half =
+// row) lets a wave-wide load carry two rows.  Here v_mfma_f32_16x16x4_f32 takes the operands as 16-byte row loads deliver them:
+// lane l = (c = l % 16, g = l / 16) loads the floats 4c .. 4c+3 of row base + g of A and of G -- one instruction per operand and FOUR
+// rows -- and element jA of the A piece with element jG of the G piece are the operands A[m = c][k = g], B[k = g][n = c] of the tile
+// (jA, jG), which holds dW[4m + jA][4n + jG].  Sixteen 4-register accumulators = the whole 64 x 64 product in 64 registers, as above;
+// per four rows 2 loads instead of 4 and 16 MFMAs of 32 cycles instead of 8 of 64.  Row quarters, the two-deep pipeline (ids two
+// batches ahead, rows one), the clamped tail and the four-wave flush are those of the kernel above; a batch is SB steps of 4 rows.
+// The flush additionally transposes every wave's summed quarter through its (by then consumed) LDS region, so that an atomic
+// instruction adds 64 consecutive columns of one row of the product instead of 16 lanes x 4 rows at a stride of 4 floats.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// GA / GG: the launch has a row list for A / for G.  A list that is missing is not read at all here (the kernel above reads
+// seg_ptrs[0] in its place and discards it: a quarter or half of its vector-memory instructions) -- the choice is made at
+// compile time, so the loop stays branch-free.
+template <bool CS, bool GA, bool GG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void HET_seg_dw_mfma_wide(MfmaDwArgs a, int chunk) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // [4][3][16][64] partials handed to wave q by the three others
+  int r;
+  idx_t rb, re;
+  if (!tile_to_relation(a.seg_ptrs, a.num_segs, chunk, blockIdx.x, r, rb, re)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+  const idx_t n = re - rb, q = ((n + 3) / 4 + 3) & ~(idx_t)3;  // rows per wave, a multiple of 4
+  const idx_t wb = rb + wave * q, we = (wb + q < re) ? wb + q : re;
+  f32x4 acc[4][4];  // [jA][jG]
+#pragma unroll
+  for (int ja = 0; ja < 4; ++ja)
+#pragma unroll
+    for (int jg = 0; jg < 4; ++jg)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[ja][jg][e] = 0.f;
+  float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);  // columns 4c .. 4c+3 of the rows this lane loaded
+  if (wb < we) {
+    constexpr int SB = 2;  // 8 rows per batch and wave: the bytes in flight of the kernel above (its SB = 4 two-row steps)
+    const idx_t* __restrict__ gp = a.gather;
+    const idx_t* __restrict__ ggp = a.g_gather;
+    int ar[2][SB], gr[2][SB];
+    float4 av[2][SB], gv[2][SB];
+    auto load_ids = [&](idx_t base, int (&A)[SB], int (&G)[SB]) {  // raw words, chosen against the row's own index in load_rows
+#pragma unroll
+      for (int st = 0; st < SB; ++st) {
+        const idx_t i = base + 4 * st + g, ic = i < we ? i : we - 1;
+        A[st] = GA ? reinterpret_cast<const int*>(gp + ic)[0] : 0;
+        G[st] = GG ? reinterpret_cast<const int*>(ggp + ic)[0] : 0;
+      }
+    };
+    auto load_rows = [&](idx_t base, const int (&Ai)[SB], const int (&Gi)[SB], float4 (&AV)[SB], float4 (&GV)[SB]) {
+      int A[SB], G[SB];
+#pragma unroll
+      for (int st = 0; st < SB; ++st) {
+        const idx_t i = base + 4 * st + g, ic = i < we ? i : we - 1;
+        A[st] = GA ? Ai[st] : (int)ic;
+        G[st] = GG ? Gi[st] : (int)ic;
+      }
+#pragma unroll
+      for (int st = 0; st < SB; ++st) {
+        AV[st] = ld4(a.A + (int64_t)A[st] * a.a_ld + 4 * c);
+        GV[st] = ld4(a.G + (int64_t)G[st] * a.g_ld + 4 * c);
+      }
+    };
+    auto mma = [&](idx_t base, const float4 (&AV)[SB], const float4 (&GV)[SB]) {
+#pragma unroll
+      for (int st = 0; st < SB; ++st) {
+        const bool in = base + 4 * st + g < we;
+        const float gj[4] = {GV[st].x, GV[st].y, GV[st].z, GV[st].w};
+        const float xj[4] = {in ? AV[st].x : 0.f, in ? AV[st].y : 0.f, in ? AV[st].z : 0.f, in ? AV[st].w : 0.f};
+        if (CS) {
+          cs.x += in ? gj[0] : 0.f; cs.y += in ? gj[1] : 0.f; cs.z += in ? gj[2] : 0.f; cs.w += in ? gj[3] : 0.f;
+        }
+#pragma unroll
+        for (int ja = 0; ja < 4; ++ja)
+#pragma unroll
+          for (int jg = 0; jg < 4; ++jg)
+            acc[ja][jg] = __builtin_amdgcn_mfma_f32_16x16x4f32(xj[ja], gj[jg], acc[ja][jg], 0, 0, 0);
+      }
+    };
+    constexpr int B = 4 * SB;
+    int ar2[SB], gr2[SB];
+    load_ids(wb, ar[0], gr[0]);
+    load_ids(wb + B, ar[1], gr[1]);
+    load_ids(wb + 2 * B, ar2, gr2);
+    load_rows(wb, ar[0], gr[0], av[0], gv[0]);
+    auto shift_ids = [&](int (&Anew)[SB], int (&Gnew)[SB]) {
+#pragma unroll
+      for (int st = 0; st < SB; ++st) { ar[1][st] = ar2[st]; gr[1][st] = gr2[st]; ar2[st] = Anew[st]; gr2[st] = Gnew[st]; }
+    };
+    for (idx_t b = wb; b < we; b += 2 * B) {
+      int an[SB], gn[SB];
+      load_rows(b + B, ar[1], gr[1], av[1], gv[1]);
+      load_ids(b + 3 * B, an, gn);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(b, av[0], gv[0]);
+      __builtin_amdgcn_sched_barrier(0);  // (keeps the address arithmetic of the next loads behind the MFMAs)
+      shift_ids(an, gn);
+      load_rows(b + 2 * B, ar[1], gr[1], av[0], gv[0]);
+      load_ids(b + 4 * B, an, gn);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(b + B, av[1], gv[1]);
+      __builtin_amdgcn_sched_barrier(0);
+      shift_ids(an, gn);
+    }
+  }
+  // Flush.  C/D layout of the 16x16 MFMA: register i of lane (c, g) holds D[m = 4g + i][n = c], i.e. accumulator (jA, jG) holds
+  // dW[16g + 4i + jA][4c + jG].  Wave q owns the accumulators jA = q (16 registers), the three others hand it theirs.
+  constexpr int Q = 16;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    if (wave != q4) {
+      const int sr = wave < q4 ? wave : wave - 1;
+#pragma unroll
+      for (int j = 0; j < Q; ++j) smem[((q4 * 3 + sr) * Q + j) * 64 + lane] = acc[q4][j >> 2][j & 3];
+    }
+  }
+  float* csm = smem + 3 * 64 * 64;  // [4][64] column sums of the four waves (CS only)
+  if (CS) {
+    cs.x += __shfl_xor(cs.x, 16); cs.y += __shfl_xor(cs.y, 16); cs.z += __shfl_xor(cs.z, 16); cs.w += __shfl_xor(cs.w, 16);
+    cs.x += __shfl_xor(cs.x, 32); cs.y += __shfl_xor(cs.y, 32); cs.z += __shfl_xor(cs.z, 32); cs.w += __shfl_xor(cs.w, 32);
+    if (g == 0) st4(csm + wave * 64 + 4 * c, cs);
+  }
+  __syncthreads();
+  if (CS && wave == 0) atomicAdd(a.colsum + lane, csm[lane] + csm[64 + lane] + csm[128 + lane] + csm[192 + lane]);
+  float* __restrict__ out = a.dW + (int64_t)r * a.dw_rel_stride;
+  const int Dh = a.headcat_d;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    if (wave == q4) {
+      float v[Q];
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        const int o = (q4 * 3 * Q + j) * 64 + lane;
+        v[j] = acc[q4][j >> 2][j & 3] + smem[o] + smem[Q * 64 + o] + smem[2 * Q * 64 + o];
+      }
+      // v[4 jG + i] = dW[16g + 4i + q][4c + jG]: row t of the wave's [16][64] tile T is the product's row 4t + q.  T lies in the
+      // region only this wave reads, and every read of it has been issued (LDS instructions of a wave execute in order).
+      float* T = smem + q4 * 3 * Q * 64;
+      wave_lds_fence();
+#pragma unroll
+      for (int i = 0; i < 4; ++i) st4(T + (4 * g + i) * 64 + 4 * c, make_float4(v[i], v[4 + i], v[8 + i], v[12 + i]));
+      wave_lds_fence();
+#pragma unroll
+      for (int t = 0; t < Q; ++t) {
+        const int k = 4 * t + q4, nn = lane;
+        int64_t off;
+        if (a.headcat == 1) {
+          const int h = nn / Dh, d = nn - h * Dh;
+          off = (int64_t)h * 64 * Dh + (int64_t)k * Dh + d;
+        } else if (a.headcat == 2) {  // keep the per-head diagonal blocks of the full product only
+          const int Kh = a.blockdiag_k, hk = k / Kh, hn = nn / Dh;
+          if (hk != hn) continue;
+          off = ((int64_t)hk * Kh + (k - hk * Kh)) * Dh + (nn - hn * Dh);
+        } else {
+          off = (int64_t)k * 64 + nn;
+        }
+        atomicAdd(out + off, T[t * 64 + lane]);
+      }
+    }
+  }
+}
+
+// HET_DW_WIDE_ROWS=0: the 64 x 64 fp32 weight gradients on HET_seg_dw_mfma<2, 2> whatever their alignment (A/B switch, read once
+// per process like the others)
+inline bool dw_wide_rows_enabled() {
+  static const bool on = [] { const char* v = getenv("HET_DW_WIDE_ROWS"); return !(v && v[0] == '0'); }();
+  return on;
+}
+
 template <int KT, int NT, typename TG, typename TA>
 int launch_dw_kx(const MfmaDwArgsT<TG, TA>& a, hipStream_t s) {
   const size_t lds = sizeof(float) * (3 * KT * NT * 16 * 64 + (a.colsum ? 3 * NT * 32 : 0));
@@ -494,6 +662,30 @@ int launch_dw_kx(const MfmaDwArgsT<TG, TA>& a, hipStream_t s) {
   chunk = (chunk + 7) & ~7ll;
   const int64_t gx = ceil_div64(a.num_rows, chunk) + a.num_segs;
   const unsigned gy = (unsigned)((a.K / (KT * 32)) * (a.X / (NT * 32)));
+  if constexpr (kAllF32 && KT == 2 && NT == 2) {
+    // one 64 x 64 block of fp32 rows that 16-byte loads can fetch: the wide-row instance (its own timer label: what a test or a
+    // profile reads to see which instance ran)
+    if (a.K == 64 && a.X == 64 && a.a_ld % 4 == 0 && a.g_ld % 4 == 0 && aligned16(a.A, a.G) && dw_wide_rows_enabled()) {
+      const size_t wlds = sizeof(float) * (3 * 64 * 64 + (a.colsum ? 4 * 64 : 0));
+      void (*kern)(MfmaDwArgs, int);
+      const int which = (a.colsum ? 4 : 0) | (a.gather ? 2 : 0) | (a.g_gather ? 1 : 0);
+      switch (which) {
+        case 0: kern = HET_seg_dw_mfma_wide<false, false, false>; break;
+        case 1: kern = HET_seg_dw_mfma_wide<false, false, true>; break;
+        case 2: kern = HET_seg_dw_mfma_wide<false, true, false>; break;
+        case 3: kern = HET_seg_dw_mfma_wide<false, true, true>; break;
+        case 4: kern = HET_seg_dw_mfma_wide<true, false, false>; break;
+        case 5: kern = HET_seg_dw_mfma_wide<true, false, true>; break;
+        case 6: kern = HET_seg_dw_mfma_wide<true, true, false>; break;
+        default: kern = HET_seg_dw_mfma_wide<true, true, true>; break;
+      }
+      HET_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
+      HET_KTIME("HET_seg_dw_mfma<wide>", s);
+      hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), wlds, s, a, (int)chunk);
+      HET_LAUNCH_CHECK("HET_seg_dw_mfma<wide>");
+      return HET_OK;
+    }
+  }
   if (a.colsum) {
     if constexpr (kAllF32) {
       HET_HIP(hipFuncSetAttribute((const void*)HET_seg_dw_mfma<KT, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

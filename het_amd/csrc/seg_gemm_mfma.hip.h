@@ -86,6 +86,8 @@ struct MfmaDwArgsT {
 };
 typedef MfmaDwArgsT<float> MfmaDwArgs;
 bool mfma_dw_supported(int K, int X);
+// K = X = 64 with both row pointers on 16-byte boundaries and a_ld, g_ld multiples of 4 runs the wide-row instance (16-byte row loads,
+// v_mfma_f32_16x16x4_f32; timer label "HET_seg_dw_mfma<wide>") unless HET_DW_WIDE_ROWS=0; everything else the float-pair one
 int launch_seg_dw_mfma(const MfmaDwArgs& a, hipStream_t s);
 // bf16 G rows: K, X in {32, 64}, plain layout, no column sums (the RGCN layer's bf16 weight gradient)
 int launch_seg_dw_mfma(const MfmaDwArgsT<het_bf16>& a, hipStream_t s);
