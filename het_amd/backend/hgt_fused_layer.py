@@ -44,8 +44,13 @@ def _node_dx_plan(G, rp_row, rows_node, offs, K_in, X, dst):
     (Whether the pass serves the graph and the shapes: ``dx`` of hgt_route.decide.)"""
     key = ("hgt_node_dx", K_in, X, dst is not None)
     plan = G._plans.get(key)
-    if plan is not None:
-        return plan
+    if plan is None:
+        with _k._plan.building():  # (kept on the graph: normal tensors whatever the caller's mode)
+            plan = G._plans[key] = _build_node_dx_plan(G, rp_row, rows_node, offs, dst)
+    return plan
+
+
+def _build_node_dx_plan(G, rp_row, rows_node, offs, dst):
     st_l, offs_l = G.get_rel_node_types()[0].tolist(), offs.tolist()
     T, R, N = len(offs_l) - 1, len(st_l), offs_l[-1]
     row_map = _k.node_row_map(rp_row, rows_node, N)
@@ -62,9 +67,8 @@ def _node_dx_plan(G, rp_row, rows_node, offs, K_in, X, dst):
         mask = mask | ((dst_rank >= 0).to(th.int64) << R)
     typ = th.searchsorted(offs[1:].contiguous().to(dev), th.arange(N, device=dev), right=True)
     order = th.argsort(mask | (typ << (R + 1)), stable=True).to(th.int32).contiguous()
-    plan = G._plans[key] = dict(row_map=row_map, dst_rank=dst_rank, order=order, offs=offs_l, has_dst=has_dst,
-                                rels_of=[[r for r in range(R) if st_l[r] == t] for t in range(T)])
-    return plan
+    return dict(row_map=row_map, dst_rank=dst_rank, order=order, offs=offs_l, has_dst=has_dst,
+                rels_of=[[r for r in range(R) if st_l[r] == t] for t in range(T)])
 
 
 def graph_facts(G, offs):

@@ -179,21 +179,26 @@ def _halo_pieces(g, ss, plan):
     key = ("halo_pieces", plan.chunks, plan.n_own, plan.n_halo)
     hit = g._plans.get(key)
     if hit is None:
-        rp_row, nodes = ss["rel_ptrs_row"], ss["node_indices_row"]
-        R = rp_row.numel() - 1
-        rel = th.repeat_interleave(th.arange(R, device=nodes.device), rp_row[1:] - rp_row[:-1])
-        # (the owned sources -- 5 % of a rank's rows on ogbn-mag at 8 ranks -- go with the first piece: a launch less per step, and
-        #  a rank's step at 8 ranks is short enough for every launch to count, profiles/r04/dist_rank_share_halo.txt)
-        cuts = [(0, plan.n_own + plan.halo_chunk_ptr[1])] + [(plan.n_own + plan.halo_chunk_ptr[c], plan.n_own + plan.halo_chunk_ptr[c + 1])
-                                                             for c in range(1, plan.chunks)]
-        hit = []
-        for a, b in cuts:
-            sel = th.nonzero((nodes >= a) & (nodes < b)).flatten()  # ascending: still relation-major
-            rp_c = th.zeros(R + 1, dtype=th.int64, device=nodes.device)
-            rp_c[1:] = th.cumsum(th.bincount(rel[sel], minlength=R), 0)
-            hit.append((rp_c, nodes[sel].contiguous(), sel.contiguous()))
-        assert sum(int(h[2].numel()) for h in hit) == nodes.numel()
-        g._plans[key] = hit
+        with _k._plan.building():  # (kept on the graph: normal tensors whatever the caller's mode)
+            hit = g._plans[key] = _build_halo_pieces(ss, plan)
+    return hit
+
+
+def _build_halo_pieces(ss, plan):
+    rp_row, nodes = ss["rel_ptrs_row"], ss["node_indices_row"]
+    R = rp_row.numel() - 1
+    rel = th.repeat_interleave(th.arange(R, device=nodes.device), rp_row[1:] - rp_row[:-1])
+    # (the owned sources -- 5 % of a rank's rows on ogbn-mag at 8 ranks -- go with the first piece: a launch less per step, and
+    #  a rank's step at 8 ranks is short enough for every launch to count, profiles/r04/dist_rank_share_halo.txt)
+    cuts = [(0, plan.n_own + plan.halo_chunk_ptr[1])] + [(plan.n_own + plan.halo_chunk_ptr[c], plan.n_own + plan.halo_chunk_ptr[c + 1])
+                                                         for c in range(1, plan.chunks)]
+    hit = []
+    for a, b in cuts:
+        sel = th.nonzero((nodes >= a) & (nodes < b)).flatten()  # ascending: still relation-major
+        rp_c = th.zeros(R + 1, dtype=th.int64, device=nodes.device)
+        rp_c[1:] = th.cumsum(th.bincount(rel[sel], minlength=R), 0)
+        hit.append((rp_c, nodes[sel].contiguous(), sel.contiguous()))
+    assert sum(int(h[2].numel()) for h in hit) == nodes.numel()
     return hit
 
 
@@ -204,7 +209,8 @@ def _loop_offsets(nd, device):
     if offs is None:
         if len(_OFFS) > 64:
             _OFFS.clear()
-        offs = _OFFS[(nd, device)] = th.tensor([0, nd], dtype=th.int64, device=device)
+        with _k._plan.building():  # (kept for later calls, whose autograd nodes save it: a normal tensor whatever the caller's mode)
+            offs = _OFFS[(nd, device)] = th.tensor([0, nd], dtype=th.int64, device=device)
     return offs
 
 

@@ -24,6 +24,7 @@ loops).  Both produce the reference builders' results exactly (tests/golden).
 """
 from __future__ import annotations
 
+import functools
 from typing import Dict, Optional
 
 import torch
@@ -31,6 +32,7 @@ import torch
 import ctypes as _C
 
 from . import _lib
+from .plan import building
 from .synth import IntegratedCOO
 
 _I64 = torch.int64
@@ -38,6 +40,17 @@ _I64 = torch.int64
 
 def _p(t):
     return None if t is None else _C.c_void_p(t.data_ptr())
+
+
+def _builder(fn):
+    """Decorator of everything that builds a layout the graph keeps: the function runs under plan.building() (no autograd graph,
+    inference mode off) -- a list that is first needed inside ``torch.inference_mode()`` (the lazily generated unique lists and CSRs,
+    the relations' node types) is then a normal tensor all the same, which a later training step may save for its backward."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        with building():
+            return fn(*args, **kwargs)
+    return wrapped
 
 
 def _native(name, ref, *args):
@@ -240,7 +253,7 @@ class HetGraph:
         return self
 
     # ---- builders -----------------------------------------------------------
-    @torch.no_grad()
+    @_builder
     def generate_separate_coo_adj_for_each_etype(self, transposed_flag: bool = False, rel_eid_sorted_flag: bool = True):
         if transposed_flag:
             raise NotImplementedError("only the original orientation is used by the hot path")
@@ -252,7 +265,7 @@ class HetGraph:
             "rel_ptrs": rp, "row_indices": r, "col_indices": c, "eids": e,
         }
 
-    @torch.no_grad()
+    @_builder
     def canonicalize_eids(self, target_sequential_eids_format: str = "separate_coo"):
         """Renumber eids so that the separate COO's are arange(E): edge data is
         then stored in separate-COO order (hrt/python/utils/mydgl_graph.py:765-823)."""
@@ -275,7 +288,7 @@ class HetGraph:
         self.sequential_eids_format = target_sequential_eids_format
         self._plans.clear()
 
-    @torch.no_grad()
+    @_builder
     def generate_separate_unique_node_indices_for_each_etype(self, produce_inverse_idx: bool = True):
         if produce_inverse_idx:
             self.canonicalize_eids("separate_coo")
@@ -305,7 +318,7 @@ class HetGraph:
             d["inverse_indices"] = torch.cat(parts) if parts else inv
         self.graph_data["separate"]["unique_node_indices"] = d
 
-    @torch.no_grad()
+    @_builder
     def generate_separate_unique_node_indices_single_sided_for_each_etype(self, produce_inverse_idx: bool = True):
         if produce_inverse_idx:
             self.canonicalize_eids("separate_coo")
@@ -317,7 +330,7 @@ class HetGraph:
             d["inverse_indices_row"], d["inverse_indices_col"] = ir, ic
         self.graph_data["separate"]["unique_node_indices_single_sided"] = d
 
-    @torch.no_grad()
+    @_builder
     def generate_csrs(self):
         """Integrated out-CSR (rows = src) under "original" and a true in-CSR
         (rows = dst, col_indices = src) under "transposed"."""
@@ -352,26 +365,39 @@ class HetGraph:
         edge of each relation (an empty relation gets type 0); raises when a relation mixes node types."""
         hit = self._plans.get("rel_node_types")
         if hit is None:
-            s = self.graph_data["separate"]["coo"]["original"]
-            offs = self.graph_data["original"]["node_type_offsets"]
-            rp = s["rel_ptrs"]
-            first = rp[:-1].clamp(max=max(0, s["row_indices"].numel() - 1))
-            empty = rp[1:] == rp[:-1]
-            run = lambda nodes: torch.searchsorted(offs[1:].contiguous(), nodes, right=True).clamp(max=offs.numel() - 2)
-            seg_types = self.graph_data["original"].get("node_segment_types")  # sampled block: runs of equal type (sampling.py)
-            typ = run if seg_types is None else (lambda nodes: seg_types[run(nodes)])
-            E = s["row_indices"].numel()
-            if E == 0:
-                z = torch.zeros(rp.numel() - 1, dtype=_I64, device=rp.device)
-                hit = (z, z.clone())
-            else:
-                st, dt = typ(s["row_indices"][first]), typ(s["col_indices"][first])
-                st, dt = torch.where(empty, torch.zeros_like(st), st), torch.where(empty, torch.zeros_like(dt), dt)
-                rel = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1], output_size=E)
-                if not (bool((typ(s["row_indices"]) == st[rel]).all()) and bool((typ(s["col_indices"]) == dt[rel]).all())):
-                    raise ValueError("get_rel_node_types: a relation mixes node types (not a canonical edge type)")
-                hit = (st.contiguous(), dt.contiguous())
-            self._plans["rel_node_types"] = hit
+            hit = self._plans["rel_node_types"] = self._build_rel_node_types()
+        return hit
+
+    @_builder
+    def _build_rel_node_types(self):
+        s = self.graph_data["separate"]["coo"]["original"]
+        offs = self.graph_data["original"]["node_type_offsets"]
+        rp = s["rel_ptrs"]
+        first = rp[:-1].clamp(max=max(0, s["row_indices"].numel() - 1))
+        empty = rp[1:] == rp[:-1]
+        run = lambda nodes: torch.searchsorted(offs[1:].contiguous(), nodes, right=True).clamp(max=offs.numel() - 2)
+        seg_types = self.graph_data["original"].get("node_segment_types")  # sampled block: runs of equal type (sampling.py)
+        typ = run if seg_types is None else (lambda nodes: seg_types[run(nodes)])
+        E = s["row_indices"].numel()
+        if E == 0:
+            z = torch.zeros(rp.numel() - 1, dtype=_I64, device=rp.device)
+            return (z, z.clone())
+        st, dt = typ(s["row_indices"][first]), typ(s["col_indices"][first])
+        st, dt = torch.where(empty, torch.zeros_like(st), st), torch.where(empty, torch.zeros_like(dt), dt)
+        rel = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1], output_size=E)
+        if not (bool((typ(s["row_indices"]) == st[rel]).all()) and bool((typ(s["col_indices"]) == dt[rel]).all())):
+            raise ValueError("get_rel_node_types: a relation mixes node types (not a canonical edge type)")
+        return (st.contiguous(), dt.contiguous())
+
+    def holds_inference_tensors(self) -> bool:
+        """Whether one of the graph's tensors was created under ``torch.inference_mode()``.  Such a graph serves evaluation only:
+        the autograd nodes save index tensors for their backward, and torch refuses to save an inference tensor (the layers say so
+        at their entry, het_amd/layers.py).  Looked at once per graph; moving the graph (``to_``) or renumbering its edges asks again."""
+        hit = self._plans.get("inference_tensors")
+        if hit is None:
+            def rec(d):
+                return any(rec(v) if isinstance(v, dict) else isinstance(v, torch.Tensor) and v.is_inference() for v in d.values())
+            hit = self._plans["inference_tensors"] = rec(self.graph_data)
         return hit
 
     def get_separate_coo_original(self):

@@ -449,12 +449,18 @@ def _derived_get(tag, tensors, build):
     identity of ALL the tensors they were derived from: (data_ptr, numel, _version) each, as het_amd/plan.py keys its
     groupings -- an in-place edit of any of them (a renumbering of the eids, a reordered block) misses the cache instead of
     returning stale rows.  The entry keeps the source tensors alive, which pins their storage (a data_ptr cannot be
-    recycled for other contents while the entry lives).  Least recently used entries go first."""
+    recycled for other contents while the entry lives).  Least recently used entries go first.
+    A source that is an inference tensor has no version to miss on: such a lookup never hits and is never kept (plan.cacheable);
+    and what ``build`` makes is a normal tensor in whatever mode the caller runs (plan.building): it is handed to later calls,
+    training steps that save it for their backward among them."""
     key = (tag,) + tuple(_plan._ident(t) for t in tensors)
     with _derived_lock:  # (model threads and autograd workers share the cache: lookup, build and eviction under one lock)
         hit = _derived.get(key)
         if hit is None:
-            hit = (build(), tensors)
+            with _plan.building():
+                hit = (build(), tensors)
+            if not _plan.cacheable(*key[1:]):
+                return hit[0]
             _derived[key] = hit
             while len(_derived) > _DERIVED_MAX:
                 _derived.popitem(last=False)
@@ -628,11 +634,18 @@ sorted_stream_hits = 0   # (tests / bench: how often the backward op found its s
 
 
 def _sorted_stream_key(exp, el, er, eids, col, slope):
-    return (_plan._ident(exp)[:2], _plan._ident(el), _plan._ident(er), _plan._ident(eids), _plan._ident(col), slope, exp.device.index)
+    """The key, or None where one of the tensors is an inference tensor (no version counter: an edit in place could not be seen;
+    there is no backward under torch.inference_mode() to stream the copy to either)."""
+    idents = tuple(_plan._ident(t) for t in (exp, el, er, eids, col))
+    if not _plan.cacheable(*idents):
+        return None
+    return (idents[0][:2],) + idents[1:] + (slope, exp.device.index)
 
 
 def _sorted_stream_put(exp, el, er, eids, col, slope, exs):
     key = _sorted_stream_key(exp, el, er, eids, col, slope)
+    if key is None:
+        return
     with _derived_lock:
         _sorted_streams.pop(key, None)
         if exs is not None:
@@ -713,7 +726,8 @@ def grouping_rank_of_position(g):
     r = getattr(g, "rank_of_position", None)
     if r is None:
         keys = g._keep[1]
-        r = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
+        with _plan.building():  # (kept with the grouping: a normal tensor whatever the caller's mode)
+            r = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
         _call(r, "het_grouping_rank_of_position", g.handle, _p(r), _stream(r))
         g.rank_of_position = r  # lives (and is evicted) with the grouping
     return r
@@ -1352,7 +1366,8 @@ def gat_rank_of_position(rel_ptrs, row, col, eids, num_nodes):
         return None
     r = getattr(g, "rank_of_position", None)
     if r is None:
-        r = torch.empty(eids.numel(), dtype=torch.int64, device=eids.device)
+        with _plan.building():  # (kept with the grouping: a normal tensor whatever the caller's mode)
+            r = torch.empty(eids.numel(), dtype=torch.int64, device=eids.device)
         _call(r, "het_grouping_rank_of_position", g.handle, _p(r), _stream(r))
         g.rank_of_position = r  # lives (and is evicted) with the grouping
     return r
@@ -1505,6 +1520,8 @@ def scale_in_rank_order(g, values):
     if g is None or values is None:
         return None
     ident = _plan._ident(values)
+    if ident[2] == _plan.NO_VERSION:  # (an inference tensor: an edit in place could not be seen -- the by-edge-id gather every time)
+        return None
     with _derived_lock:
         hit = getattr(g, "_scale_sorted", None)
         if hit is not None and hit[0] == ident:
@@ -1512,7 +1529,8 @@ def scale_in_rank_order(g, values):
         if getattr(g, "_scale_seen", None) != ident:
             g._scale_seen, g._scale_sorted = ident, None
             return None
-        out = torch.empty_like(values, memory_format=torch.contiguous_format)
+        with _plan.building():  # (kept with the grouping: a normal tensor whatever the caller's mode)
+            out = torch.empty_like(values, memory_format=torch.contiguous_format)
         H = values.numel() // max(1, values.shape[0])
         _call(values, "het_grouping_gather_payload1", g.handle, _p(values), H, _p(out), _stream(values))
         g._scale_sorted = (ident, values, out)

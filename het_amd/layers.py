@@ -17,6 +17,7 @@ import torch as th
 import torch.nn as nn
 
 from . import backend as B
+from ._lib import HetError
 from .backend import rgat_fused_layer as FL
 from .backend import hgt_fused_layer as _hgt_fused
 from .backend import hgt_route
@@ -24,6 +25,22 @@ from .backend import hgt_route
 
 PAD_HEADS = os.environ.get("HET_RGAT_PAD_HEADS", "1") != "0"  # zero-pad narrow / odd RGAT heads to the row kernels' widths
 PAD_WIDTHS = os.environ.get("HET_PAD_WIDTHS", "1") != "0"     # zero-pad RGCN output widths to 32 / 64 / 128
+
+
+def _needs_grad(x, module, *others) -> bool:
+    """The ``grad`` fact of a call: autograd is on and the input, a parameter of the layer or one of ``others`` requires a gradient."""
+    return th.is_grad_enabled() and any(t.requires_grad for t in (x, *others, *module.parameters()))
+
+
+def _refuse_inference_graph(g, module, grad):
+    """A graph whose tensors were created under ``torch.inference_mode()`` serves evaluation only: the autograd nodes save index
+    tensors of the graph for their backward, and torch refuses to save an inference tensor.  A call that needs a gradient
+    (``grad``: a bool, or a callable asked only for such a graph) is refused here, at the layer's entry, before any launch."""
+    holds = getattr(g, "holds_inference_tensors", None)  # (a graph-like object without the method: nothing to ask, not refused)
+    if holds is not None and holds() and (grad() if callable(grad) else grad):
+        raise HetError(f"{type(module).__name__}: the graph's tensors were created in inference mode (torch.inference_mode()), so it "
+                       "serves evaluation only: torch cannot save inference tensors for a backward.  Build the graph (and a "
+                       "sampler and its blocks) outside inference mode to train on it; evaluation may run inside it")
 
 
 def _padded_in_width(K: int) -> int:
@@ -132,12 +149,13 @@ class HET_RGATLayer(nn.Module):
         facts = FL.rgat_route.Facts(
             cuda=x.is_cuda, bf16=x.dtype == th.bfloat16, dim=x.dim(), N=g.get_num_nodes() if halo else x.shape[0], K=self.in_feat, H=self.num_heads,
             D=self.out_feat // self.num_heads, R=self.num_rels, K_padded=_padded_in_width(self.in_feat), edges=g.get_num_edges() > 0,
-            slope=self.leaky_relu_slope, grad=th.is_grad_enabled() and any(t.requires_grad for t in (x, *self.parameters())),
+            slope=self.leaky_relu_slope, grad=_needs_grad(x, self),
             halo=halo, num_dst=num_dst, plan=FL.rgat_layer_fused_ok(), lists=lists, compact_flag=self.compact_as_of_node_flag,
             direct_flag=self.compact_direct_indexing_flag, mulfirst_flag=self.multiply_among_weights_first_flag,
             gat_edge_parallel=self.gat_edge_parallel_flag, reference_op_sequence=self.reference_op_sequence, op_by_op=self.op_by_op,
             self_loop=self.self_loop, bf16_training=self.bf16_training, per_edge=FL.PER_EDGE, literal_er=FL.LITERAL_ER,
             forward_only=FL.FORWARD_ONLY, pad_heads=PAD_HEADS)
+        _refuse_inference_graph(g, self, facts.grad)
         return FL.rgat_route.decide(facts, dst_below, attn_dot_only)
 
     def _fused(self, route, g, inputs, num_dst, halo, attn_out):
@@ -306,6 +324,7 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, g, x, norm, num_dst=None):
+        _refuse_inference_graph(g, self, lambda: _needs_grad(x, self, norm))
         if x.dtype == th.bfloat16:
             return self._forward_bf16(g, x, norm, num_dst)
         weight, x = self._weight_and_input(x)
@@ -452,6 +471,7 @@ class HET_HGTLayerHetero(nn.Module):
     def forward(self, G, h, num_dst=None):
         """``num_dst``: ``G`` is a sampled block whose first ``num_dst`` nodes are its destinations (only their rows are
         returned); its nodes are runs of equal type (``node_segment_types``, het_amd/sampling.py) instead of one run per type."""
+        _refuse_inference_graph(G, self, lambda: _needs_grad(h, self))
         offs = G.get_original_node_type_offsets()
         route = self._route(G, h, offs)
         if route.path == "upcast":

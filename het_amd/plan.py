@@ -9,6 +9,13 @@ function of the index tensors, so it is built once (on the device, by
 holds strong references to its source tensors, which pins their storage: a
 ``data_ptr`` can therefore never be recycled for different contents while the
 entry is alive, and ``_version`` catches in-place edits.
+
+Inference tensors (made under ``torch.inference_mode()``) have no version
+counter, so an in-place edit of one cannot be seen: a lookup whose sources
+include one never hits and never stores (``cacheable``) -- it builds afresh on
+every call.  Whatever a cache builds is made a normal tensor, whatever the
+caller's mode (``building``): it outlives the call, and a later training step
+hands it to ``save_for_backward``, which refuses inference tensors.
 """
 from __future__ import annotations
 
@@ -105,8 +112,32 @@ class Grouping:
             lib.het_grouping_destroy(handle)
 
 
+NO_VERSION = -1  # the version slot of an inference tensor's identity (a real counter starts at 0)
+
+
 def _ident(t: Optional[torch.Tensor]):
-    return None if t is None else (t.data_ptr(), t.numel(), t._version)
+    """(data_ptr, numel, _version) of a source tensor; an inference tensor has no version counter (reading it raises):
+    NO_VERSION stands in its place, and ``cacheable`` keeps such an identity out of every cache."""
+    if t is None:
+        return None
+    try:  # (nothing added to the lookup of a normal tensor: every step makes a few dozen of them)
+        return (t.data_ptr(), t.numel(), t._version)
+    except RuntimeError:  # "Inference tensors do not track version counter"
+        return (t.data_ptr(), t.numel(), NO_VERSION)
+
+
+def cacheable(*idents) -> bool:
+    """Whether a result may be cached under these identities (``_ident``): not when a source is an inference tensor, whose
+    in-place edits nothing can detect."""
+    return not any(i is not None and i[2] == NO_VERSION for i in idents)
+
+
+@contextlib.contextmanager
+def building():
+    """Around everything that builds a tensor a cache keeps: inference mode off (inside ``torch.inference_mode()`` the result
+    would be an inference tensor, which no later training step can save for its backward) and no autograd graph."""
+    with torch.inference_mode(False), torch.no_grad():
+        yield
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -124,7 +155,7 @@ def get_grouping(rel_ptrs: Optional[torch.Tensor], keys: torch.Tensor, key_bound
     # never evicted between its lookup and its return.  (The caller keeps the returned Grouping alive while it uses it: an
     # eviction by another thread only drops the cache's reference.)
     with _cache_lock:
-        g = _cache.get(k)
+        g = _cache.get(k)  # (a key with an inference tensor's identity is never stored: such a lookup cannot hit)
         if g is not None:
             _cache.move_to_end(k)
             # (the stream this op will read the grouping on: het_grouping_destroy orders the release after it, include/het_amd.h)
@@ -149,6 +180,8 @@ def get_grouping(rel_ptrs: Optional[torch.Tensor], keys: torch.Tensor, key_bound
                 torch.cuda.empty_cache()
                 _lib.call("het_grouping_create", *args)
         g = Grouping(out, (rel_ptrs, keys, payload0, payload1))
+        if not cacheable(k[0], k[1], k[3], k[4]):  # (an inference tensor among the sources: built for this call alone)
+            return g
         _cache[k] = g
         while len(_cache) > _MAX_ENTRIES:
             _cache.popitem(last=False)

@@ -48,7 +48,10 @@ class NeighborSampler:
         self.dev = self.ptr.device
         self.gen = torch.Generator(device=self.dev)
         self.gen.manual_seed(seed)
-        self._map = torch.full((self.num_nodes,), -1, dtype=torch.int64, device=self.dev)
+        from .plan import building
+        with building():  # (scratch that every sample_block writes in place: a normal tensor, so that a sampler made inside
+            #               torch.inference_mode() can still sample outside it)
+            self._map = torch.full((self.num_nodes,), -1, dtype=torch.int64, device=self.dev)
         self.by_type = by_type
         self.type_offsets = g.get_original_node_type_offsets().to(self.dev)  # node ids are type-contiguous in the full graph
         self.num_types = int(self.type_offsets.numel() - 1)
