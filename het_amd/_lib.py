@@ -123,6 +123,10 @@ _ENTRIES = {
     "het_rows_gather": [P, P, I64, I64, P, P],
     "het_rows_scatter_add": [P, P, I64, I64, P, P],
     "het_rows_scatter_add_grouped": [P, P, I64, P, I64, P],
+    "het_rows_embed_ok": [I64],
+    "het_rows_embed_gather": [P, P, I64, I64, I64, P, P],
+    "het_rows_embed_gather_bf16": [P, P, I64, I64, I64, P, P],
+    "het_rows_adam": [P, P, P, P, P, P, I64, I64, I64, DBL, DBL, DBL, DBL, DBL, DBL, P],
     "het_layout_separate_coo": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
     "het_layout_coo_to_csr": [P, P, P, P, I64, I64, P, P, P, P, P],
     "het_layout_transpose_csr": [P, P, P, P, I64, I64, I64, P, P, P, P, P],

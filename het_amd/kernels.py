@@ -1197,6 +1197,47 @@ def rows_layer_norm_backward_bf16(offsets, y, gamma, mean, rstd, grad_out, want_
     return _rows_layer_norm_backward("het_rows_layer_norm_backward_bf16", offsets, y, gamma, mean, rstd, grad_out, want_y)
 
 
+# ---- row-sparse embedding table (HET_RelGraphEmbed(sparse=True) + het_amd/optim.py RowSparseAdam; csrc/rows_embed.hip) ----
+def rows_embed_ok(K: int) -> bool:
+    """Row widths het_rows_embed_gather / _bf16 and het_rows_adam cover (a multiple of 4 in 4 .. 1024)."""
+    return bool(_lib.lib().het_rows_embed_ok(int(K)))
+
+
+def rows_embed_gather(table, rows, dtype=None, out=None):
+    """out[i, :] = table[rows[i], :] of the fp32 table [N, K] as float32 (``dtype`` None / torch.float32) or, rounded once at the
+    store, bfloat16 (het_rows_embed_gather / _bf16).  ``out``: a [B, K] tensor of the caller in that dtype with contiguous rows,
+    16-byte (bf16: 8-byte) aligned -- refused before the launch otherwise."""
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.HetError(f"rows_embed_gather: float32 or bfloat16 output rows, not {dtype}")
+    _chk("rows_embed_gather", (table,), (rows,))
+    if table.dim() != 2 or rows.dim() != 1:
+        raise _lib.HetError(f"rows_embed_gather: a [N, K] table and a [B] id list, got {tuple(table.shape)} and {tuple(rows.shape)}")
+    B, (N, K) = rows.numel(), table.shape
+    if out is None:
+        out = torch.empty((B, K), dtype=dtype, device=table.device)
+    elif not (out.is_cuda and out.device == table.device and out.dtype == dtype and out.shape == (B, K) and out.is_contiguous()):
+        raise _lib.HetError(f"rows_embed_gather: out must be a contiguous {dtype} [{B}, {K}] tensor on {table.device}")
+    _call(table, "het_rows_embed_gather_bf16" if dtype == torch.bfloat16 else "het_rows_embed_gather", _p(table), _p(rows), B, N, K,
+          _p(out), _stream(table))
+    return out
+
+
+def rows_adam_(p, exp_avg, exp_avg_sq, rows_sorted, perm, grad, lr, beta1, beta2, eps, step):
+    """One lazy Adam step (torch.optim.SparseAdam's rule) in place on the rows of p, exp_avg, exp_avg_sq [N, K] that ``rows_sorted``
+    [B] (ascending, repeats allowed) names; the gradient row of sorted position j is grad[perm[j]] (``perm`` None: grad[j]); ``step``:
+    the 1-based count of this step (include/het_amd.h: het_rows_adam).  One launch, no atomics, no host synchronisation; the caller
+    bumps p's version counter."""
+    _chk("rows_adam", (p, exp_avg, exp_avg_sq, grad), tuple(t for t in (rows_sorted, perm) if t is not None))
+    B = rows_sorted.numel()
+    if (p.dim() != 2 or exp_avg.shape != p.shape or exp_avg_sq.shape != p.shape or grad.shape != (B, p.shape[1]) or rows_sorted.dim() != 1
+            or (perm is not None and perm.shape != rows_sorted.shape)):
+        raise _lib.HetError(f"rows_adam: p / exp_avg / exp_avg_sq [N, K], grad [B, K], rows_sorted / perm [B] expected, got "
+                            f"{[tuple(t.shape) for t in (p, exp_avg, exp_avg_sq, grad, rows_sorted)]}")
+    _call(p, "het_rows_adam", _p(p), _p(exp_avg), _p(exp_avg_sq), _p(rows_sorted), _p(perm), _p(grad), B, *p.shape, float(lr), float(beta1),
+          float(beta2), float(eps), 1.0 - float(beta1) ** int(step), 1.0 - float(beta2) ** int(step), _stream(p))
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -17,6 +17,7 @@ import torch as th
 import torch.nn as nn
 
 from . import backend as B
+from . import kernels as _k
 from ._lib import HetError
 from .backend import rgat_fused_layer as FL
 from .backend import hgt_fused_layer as _hgt_fused
@@ -53,16 +54,72 @@ def _padded_in_width(K: int) -> int:
     return next((w for w in (32, 64, 128) if w >= K), K)
 
 
-class HET_RelGraphEmbed(nn.Module):
-    """Learnable node embeddings used as input features (RGNNUtils.py:78-119)."""
+def _embed_rows_kernel_ok(embeds, nodes, dtype) -> bool:
+    """Whether csrc/rows_embed.hip serves the gather: a contiguous, 16-byte aligned fp32 table on the GPU of a covered width, ids on
+    the same device, float32 or bfloat16 rows out."""
+    return (embeds.is_cuda and embeds.dtype == th.float32 and embeds.dim() == 2 and embeds.is_contiguous()
+            and embeds.data_ptr() % 16 == 0 and nodes.device == embeds.device and dtype in (th.float32, th.bfloat16)
+            and _k.rows_embed_ok(embeds.shape[1]))
 
-    def __init__(self, num_nodes: int, embed_size: int):
+
+def _embed_rows(embeds, nodes, dtype):
+    """embeds[nodes] as [B, K] in ``dtype``: the gather kernel where it applies (bf16 rounded once at its store), else index_select and
+    a cast -- correct, not fast."""
+    if _embed_rows_kernel_ok(embeds, nodes, dtype):
+        return _k.rows_embed_gather(embeds, nodes.contiguous(), dtype)
+    return embeds.index_select(0, nodes).to(dtype)
+
+
+class _EmbedRowsFunction(th.autograd.Function):
+    """rows = embeds[nodes] as one autograd node that saves ``nodes`` only.  The gradient of the table is dense [N, K] (the values
+    autograd's own index backward gives: zeros + index_put_(accumulate=True)) or, ``sparse``, the uncoalesced
+    torch.sparse_coo_tensor(nodes, grad_out) that nn.Embedding(sparse=True) returns -- B rows instead of N."""
+
+    @staticmethod
+    def forward(ctx, embeds, nodes, dtype, sparse):
+        ctx.save_for_backward(nodes)
+        ctx.table_shape, ctx.sparse = embeds.shape, sparse
+        return _embed_rows(embeds.detach(), nodes, dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        nodes, = ctx.saved_tensors
+        vals = grad_out.detach().to(th.float32).contiguous()  # (a strided or expanded grad_out: read, never written)
+        if ctx.sparse:
+            if vals.data_ptr() == grad_out.data_ptr():
+                vals = vals.clone()  # (grad_out may be shared with another branch: the gradient returned owns its values)
+            return th.sparse_coo_tensor(nodes.reshape(1, -1), vals, ctx.table_shape), None, None, None
+        grad = th.zeros(ctx.table_shape, dtype=th.float32, device=vals.device)
+        grad.index_put_((nodes,), vals, accumulate=True)
+        return grad, None, None, None
+
+
+class HET_RelGraphEmbed(nn.Module):
+    """Learnable node embeddings used as input features (RGNNUtils.py:78-119).
+
+    ``forward()`` returns the whole table, as the reference does.  ``forward(nodes, dtype=None)`` returns ``embeds[nodes]`` as
+    [B, K] rows in ``dtype`` (None: float32; torch.bfloat16: rounded once where the rows are stored) through one autograd node that
+    saves ``nodes`` only -- what a sampled mini-batch needs of the table.  On a GPU table of a width that is a multiple of 4 up to
+    1024 it is a HIP gather (csrc/rows_embed.hip); elsewhere (CPU, other widths, a non-contiguous table) index_select and a cast.
+
+    ``sparse=True`` (opt-in): the gradient of ``forward(nodes)`` is a torch.sparse_coo_tensor of the B rows, uncoalesced, as
+    nn.Embedding(sparse=True) gives -- no [N, K] zero-fill and scatter per step.  It takes an optimizer for sparse gradients:
+    het_amd.optim.RowSparseAdam (one HIP launch per step) or torch.optim.SparseAdam.  ``forward()`` without nodes stays dense."""
+
+    def __init__(self, num_nodes: int, embed_size: int, sparse: bool = False):
         super().__init__()
+        self.sparse = bool(sparse)
         self.embeds = nn.Parameter(th.Tensor(num_nodes, embed_size))
         nn.init.xavier_uniform_(self.embeds)
 
-    def forward(self):
-        return self.embeds
+    def forward(self, nodes=None, dtype=None):
+        if nodes is None:
+            return self.embeds if dtype is None or dtype == self.embeds.dtype else self.embeds.to(dtype)
+        if nodes.dim() != 1 or nodes.dtype != th.int64:
+            raise HetError(f"HET_RelGraphEmbed: nodes is a 1-d int64 tensor of row ids, got {tuple(nodes.shape)} {nodes.dtype}")
+        return _EmbedRowsFunction.apply(self.embeds, nodes, self.embeds.dtype if dtype is None else dtype, self.sparse)
 
 
 class HET_RGATLayer(nn.Module):

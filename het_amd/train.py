@@ -130,6 +130,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                         "parameters and sums); the loss is taken on the logits cast to fp32")
     p.add_argument("--use_norm", action="store_true",
                    help="HGT only: the per-node-type LayerNorm after every layer's output projection (het_amd/layers.py)")
+    p.add_argument("--sparse_embed", action="store_true",
+                   help="sampled mini-batches only: the embedding table gives a row-sparse gradient (HET_RelGraphEmbed(sparse=True)) and is "
+                        "stepped by het_amd.optim.RowSparseAdam -- a lazy Adam: the moments of rows a batch does not touch do not decay; "
+                        "the model's parameters keep the fused Adam")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -153,6 +157,22 @@ def aggregate_times(ms):
     return float(sum(kept) / len(kept)) if kept else float("nan")
 
 
+class OptimizerPair:
+    """The optimizers of one training step behind the two calls HET_RGNN_train makes (--sparse_embed: the fused Adam of the model's
+    parameters and the RowSparseAdam of the embedding table)."""
+
+    def __init__(self, *optimizers):
+        self.optimizers = optimizers
+
+    def zero_grad(self):
+        for o in self.optimizers:
+            o.zero_grad()
+
+    def step(self):
+        for o in self.optimizers:
+            o.step()
+
+
 def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=(), batches=None):
     """``batches``: None for full-graph training, else a callable returning (blocks, seeds) per step -- the sampled
     mini-batch path (het_amd/sampling.py); sampling + per-batch layout building is timed separately."""
@@ -161,6 +181,8 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
 
     inference = getattr(args, "inference", False)
     bf16 = getattr(args, "bf16_training", False)  # (the features enter the model as bf16 rows, the logits leave it as fp32)
+    # --sparse_embed (sampled blocks only): the layer hands out the block's rows, in the model's dtype, through one autograd node
+    sparse_embed = getattr(args, "sparse_embed", False) and batches is not None
 
     def one_eval(timed):
         # the evaluation pass of the reference's scripts (model.eval() + torch.no_grad()): same inputs, same event pair around
@@ -195,7 +217,7 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
         if inference:
             return one_eval(timed)
         optimizer.zero_grad()
-        node_embed = node_embed_layer()
+        node_embed = None if sparse_embed else node_embed_layer()
         cur_labels = labels
         if batches is not None:
             th.cuda.synchronize()
@@ -203,8 +225,12 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
             blocks, seeds = batches()
             th.cuda.synchronize()
             prep_ms.append((time.perf_counter() - t0) * 1e3)
-            node_embed, cur_labels = node_embed[blocks[0].nodes], labels[seeds]
-        if bf16:
+            if sparse_embed:
+                node_embed = node_embed_layer(blocks[0].nodes, dtype=th.bfloat16 if bf16 else None)
+            else:
+                node_embed = node_embed[blocks[0].nodes]
+            cur_labels = labels[seeds]
+        if bf16 and not sparse_embed:
             node_embed = node_embed.to(th.bfloat16)
         th.cuda.synchronize()
         ev = [th.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -250,6 +276,10 @@ def main(argv=None):
         raise SystemExit("--bf16_training is an option of the RGAT layer (RGCN and HGT train in bf16 on a bf16 input as they are)")
     if args.use_norm and args.model != "hgt":
         raise SystemExit("--use_norm is an option of the HGT layer")
+    if args.sparse_embed and args.full_graph_training:
+        raise SystemExit("--sparse_embed is an option of the sampled mini-batch path: --full_graph_training reads every row of the table")
+    if args.sparse_embed and args.inference:
+        raise SystemExit("--sparse_embed is an option of training: --inference takes no optimizer step")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -260,7 +290,7 @@ def main(argv=None):
     layout_ms = (time.perf_counter() - t0) * 1e3
     N, E, R = g.get_num_nodes(), g.get_num_edges(), g.get_num_rels()
     print("Graph stats: ", E, N, R)
-    embed = HET_RelGraphEmbed(N, args.n_infeat).to(dev)
+    embed = HET_RelGraphEmbed(N, args.n_infeat, sparse=args.sparse_embed).to(dev)
     extra = ()
     if args.model == "rgat":
         model = HET_RGATModel(R, args.n_infeat, args.num_classes, args.num_heads, num_hidden_layers=args.num_layers - 1,
@@ -281,11 +311,14 @@ def main(argv=None):
                              hgt_fused_attn_score_flag=getattr(args, "hgt_fused_attn_score_flag", False), use_norm=args.use_norm)
     model = model.to(dev)
     labels = th.randint(0, args.num_classes, (N,), device=dev)  # random labels as train_dgl.py:132-148
-    params = list(model.parameters()) + list(embed.parameters())
+    params = list(model.parameters()) + ([] if args.sparse_embed else list(embed.parameters()))
     try:  # one kernel per step over all parameters (the [N, in] embedding table dominates); same update rule
         optimizer = th.optim.Adam(params, lr=args.lr, fused=True)
     except (RuntimeError, TypeError):
         optimizer = th.optim.Adam(params, lr=args.lr)
+    if args.sparse_embed:
+        from .optim import RowSparseAdam
+        optimizer = OptimizerPair(optimizer, RowSparseAdam(embed.parameters(), lr=args.lr))
     batches = None
     if not args.full_graph_training:  # sampled blocks, one batch of --batch_size seeds per step ("epoch" = one step here)
         from .sampling import NeighborSampler
@@ -317,6 +350,10 @@ def main(argv=None):
         del res["args"]["bf16_training"]
     if not args.use_norm:
         del res["args"]["use_norm"]
+    if args.sparse_embed:
+        res["sparse_embed"] = True
+    else:
+        del res["args"]["sparse_embed"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

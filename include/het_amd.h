@@ -1005,6 +1005,31 @@ int het_rows_scatter_add(const float* src, const int64_t* idx, int64_t num_rows,
 int het_rows_scatter_add_grouped(const het_grouping* by_idx, const float* src, int64_t X, float* out, int64_t out_rows,
                                  het_stream stream);
 
+/* Row-sparse access to a learnable table for sampled mini-batches (no reference counterpart: RGNNUtils.py:78-119 keeps the dense
+ * [N, K] table and dense Adam; het_amd/layers.py HET_RelGraphEmbed(sparse=True) + het_amd/optim.py RowSparseAdam).  table / p / m / v
+ * are fp32 [num_table_rows, K]; row offsets are 64-bit (num_table_rows * K may pass 2^31).
+ * Shapes: K % 4 == 0, 4 <= K <= 1024 (het_rows_embed_ok answers for the width): HET_ERR_UNSUPPORTED otherwise, before any launch.
+ * num_rows == 0 is HET_OK without a launch.  Null or misaligned pointers (fp32 tensors 16 bytes, bf16 rows and id lists 8 bytes) are
+ * HET_ERR_INVALID_ARG, nothing enqueued.  An id outside [0, num_table_rows) is never dereferenced: the gather writes a row of
+ * zeros for it, the Adam step skips it.
+ *   het_rows_embed_gather:       out[i, :] = table[rows[i], :]   i in [0, num_rows); rows may repeat
+ *   het_rows_embed_gather_bf16:  the same with out het_bf16, rounded to nearest even once, at the store */
+int het_rows_embed_ok(int64_t K);
+int het_rows_embed_gather(const float* table, const int64_t* rows, int64_t num_rows, int64_t num_table_rows, int64_t K, float* out,
+                          het_stream stream);
+int het_rows_embed_gather_bf16(const float* table, const int64_t* rows, int64_t num_rows, int64_t num_table_rows, int64_t K,
+                               het_bf16* out, het_stream stream);
+/* One launch of a lazy Adam step on the rows a sparse gradient names.  rows_sorted [num_rows]: ascending ids, repeats allowed; the
+ * gradient row of sorted position j is grad[perm[j], :] (perm [num_rows], a permutation of 0 .. num_rows-1; NULL = the identity);
+ * grad fp32 [num_rows, K].  For every run of equal ids, with g the sum of the run's gradient rows in position order:
+ *   m = beta1 m + (1 - beta1) g     v = beta2 v + (1 - beta2) g g     p -= lr sqrt(bias_correction2) / bias_correction1 * m / (sqrt(v) + eps)
+ * in place -- the rule of torch.optim.SparseAdam (eps is added to sqrt(v) before the bias correction of v, unlike dense Adam; rows the
+ * gradient does not name keep p, m and v bit for bit).  bias_correction{1,2} = 1 - beta{1,2}^step, formed by the caller.
+ * No atomics: one lane group sums a run in a fixed order, the same bits every launch; correctly rounded sqrt and division. */
+int het_rows_adam(float* p, float* m, float* v, const int64_t* rows_sorted, const int64_t* perm, const float* grad, int64_t num_rows,
+                  int64_t num_table_rows, int64_t K, double lr, double beta1, double beta2, double eps, double bias_correction1,
+                  double bias_correction2, het_stream stream);
+
 /* ------------------------------------------------------------------------
  * Layout builders (the step before the path).  Device-side replacements of the reference's CPU
  * converters: torch.ops.torch_hrt.convert_integrated_{coo,csr}_to_separate_{coo,csr} / transpose_csr
