@@ -131,6 +131,12 @@ _ENTRIES = {
     "het_layout_coo_to_csr": [P, P, P, P, I64, I64, P, P, P, P, P],
     "het_layout_transpose_csr": [P, P, P, P, I64, I64, I64, P, P, P, P, P],
     "het_layout_unique_rel_nodes": [P, I64, P, P, I64, I64, P, P, P, P, P],
+    "het_sample_workgroup_degree": [],
+    "het_sample_chunk": [],
+    "het_sample_count": [P, P, I64, I64, I64, P, P, P],
+    "het_sample_select": [P, P, I64, I64, I64, I64, I64, P, I64, P, P, P],
+    "het_block_renumber": [P, I64, P, I64, P, I64, P, I64, P, P, P, P],
+    "het_block_relation_major": [P, P, I64, P, P, P, I64, I64, P, P, P, P, P, P],
 }
 _ENTRIES = {name: decl if isinstance(decl, tuple) else (INT, decl) for name, decl in _ENTRIES.items()}  # name -> (restype, argtypes)
 _SIGNATURES = {name: args for name, (_, args) in _ENTRIES.items()}  # name -> argtypes

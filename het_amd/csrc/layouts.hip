@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hip.h"
+#include "device_scratch.hip.h"
 
 namespace {
 
@@ -15,25 +16,6 @@ inline unsigned blocks_for(int64_t n) {
   int64_t b = ceil_div64(n, kBlock);
   return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
 }
-inline int bits_for(int64_t n) {  // bits to represent values in [0, n)
-  int b = 1;
-  while (b < 62 && (1ll << b) < n) ++b;
-  return b;
-}
-
-struct Scratch {  // frees device temporaries on every exit path
-  void* p[12] = {};
-  int n = 0;
-  hipStream_t s = nullptr;  // the stream the temporaries are used on (a caller's allocator orders their reuse on it)
-  explicit Scratch(hipStream_t st) : s(st) {}
-  ~Scratch() { for (int i = 0; i < n; ++i) (void)het_free_e(p[i]); }
-  hipError_t alloc(void** out, size_t bytes) {
-    hipError_t e = het_malloc_e(out, bytes ? bytes : 8, s);
-    if (e == hipSuccess) p[n++] = *out;
-    return e;
-  }
-};
-
 // key = (hi << lo_bits) | lo for position i of part q (parts are concatenated: position n_per_part * q + i)
 __global__ void HET_layout_make_keys(const idx_t* __restrict__ hi, const idx_t* __restrict__ hi_ptrs, int n_hi,
                                      const idx_t* __restrict__ lo_a, const idx_t* __restrict__ lo_b, int64_t n,

@@ -190,6 +190,33 @@ class HetGraph:
             g.generate_csrs()
         return g
 
+    @classmethod
+    @_builder
+    def from_block_separate_coo(cls, num_nodes: int, num_rels: int, node_type_offsets, rel_ptrs, row, col, rel,
+                                full: bool = True) -> "HetGraph":
+        """The graph of edges that are relation-major already (``rel_ptrs`` [R + 1] over ``row`` / ``col`` / ``rel``) and whose eids
+        are their positions, arange(E) -- what a sampled block is when it leaves the sampler (het_amd/sampling.py).  The integrated
+        and the separate COO then hold the same arrays, so both share the tensors given here, and the eids are canonical from the
+        start: no sort and no host round trip.  Equal, key by key and tensor by tensor, to ``from_integrated_coo`` on the same
+        edges; ``full`` as there."""
+        g = cls()
+        g._num_nodes, g._num_rels = int(num_nodes), int(num_rels)
+        eids = torch.arange(row.numel(), dtype=_I64, device=row.device)
+        g.graph_data["original"] = {
+            "row_indices": row,
+            "col_indices": col,
+            "rel_types": rel,
+            "eids": eids,
+            "node_type_offsets": node_type_offsets,
+        }
+        g.graph_data["separate"] = {"coo": {"original": {"rel_ptrs": rel_ptrs, "row_indices": row, "col_indices": col, "eids": eids}}}
+        g.sequential_eids_format = "separate_coo"
+        if full:
+            g.generate_separate_unique_node_indices_for_each_etype()
+            g.generate_separate_unique_node_indices_single_sided_for_each_etype()
+            g.generate_csrs()
+        return g
+
     # ---- sizes ----------------------------------------------------------
     def get_num_nodes(self) -> int:
         return self._num_nodes

@@ -1238,6 +1238,74 @@ def rows_adam_(p, exp_avg, exp_avg_sq, rows_sorted, perm, grad, lr, beta1, beta2
           float(beta2), float(eps), 1.0 - float(beta1) ** int(step), 1.0 - float(beta2) ** int(step), _stream(p))
 
 
+# ---- keyed neighbour sampling and block construction (het_amd/sampling.py method="keyed"; csrc/block_sample.hip) ----
+def sample_thresholds() -> Dict[str, int]:
+    """The in-degrees at which het_sample_select changes its code path: ``workgroup_degree`` (a workgroup instead of a wave from
+    here on) and ``chunk`` (positions per emission chunk of that workgroup)."""
+    L = _lib.lib()
+    return {"workgroup_degree": int(L.het_sample_workgroup_degree()), "chunk": int(L.het_sample_chunk())}
+
+
+def sample_count(row_ptrs, dst, fanout: int):
+    """(offsets [B + 1], total): the exclusive sum of min(deg, fanout) (deg when fanout <= 0) over the destinations ``dst`` of the
+    in-CSR ``row_ptrs``, and its last entry on the host -- one read-back (het_sample_count)."""
+    _chk("sample_count", (), (row_ptrs, dst))
+    B = dst.numel()
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=dst.device)
+    if B == 0:
+        return offsets.zero_(), 0
+    total = C.c_int64(0)
+    _call(dst, "het_sample_count", _p(row_ptrs), _p(dst), B, row_ptrs.numel() - 1, int(fanout), _p(offsets), C.byref(total), _stream(dst))
+    return offsets, int(total.value)
+
+
+def sample_select(row_ptrs, dst, fanout: int, seed: int, draw: int, offsets, total: int):
+    """(pos [total], owner [total]) of the edges the keyed rule keeps (het_sample_select); ``offsets`` / ``total`` from sample_count
+    with the same arguments.  ``seed`` / ``draw``: any Python ints, taken modulo 2^64."""
+    _chk("sample_select", (), (row_ptrs, dst, offsets))
+    pos = torch.empty(total, dtype=torch.int64, device=dst.device)
+    owner = torch.empty(total, dtype=torch.int64, device=dst.device)
+    as_i64 = lambda v: ((int(v) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63)  # noqa: E731  (the same 64 bits as a signed value)
+    _call(dst, "het_sample_select", _p(row_ptrs), _p(dst), dst.numel(), row_ptrs.numel() - 1, int(fanout), as_i64(seed), as_i64(draw),
+          _p(offsets), int(total), _p(pos), _p(owner), _stream(dst))
+    return pos, owner
+
+
+def block_renumber(src, pos, dst, node_map):
+    """(nodes [B + num_extra], local_src [total]) of a block (het_block_renumber): ``dst`` (distinct ids) followed by the sampled
+    sources ``src[pos]`` that are no destination, ascending; ``node_map`` [N] holds -1 everywhere before and after.  One read-back
+    (the number of new nodes).  ``nodes`` is a view of a buffer of B + total ids."""
+    _chk("block_renumber", (), (src, pos, dst, node_map))
+    B, total = dst.numel(), pos.numel()
+    if B == 0 or total == 0:
+        return dst.clone(), torch.empty(0, dtype=torch.int64, device=dst.device)
+    nodes = torch.empty(B + total, dtype=torch.int64, device=dst.device)
+    local_src = torch.empty(total, dtype=torch.int64, device=dst.device)
+    extra = C.c_int64(0)
+    try:
+        _call(dst, "het_block_renumber", _p(src), src.numel(), _p(pos), total, _p(dst), B, _p(node_map), node_map.numel(), _p(nodes),
+              _p(local_src), C.byref(extra), _stream(dst))
+    except _lib.HetError:
+        node_map.fill_(-1)  # (a call that failed half way may have left marks behind)
+        raise
+    return nodes[: B + int(extra.value)], local_src
+
+
+def block_relation_major(rel, eids, pos, owner, local_src, num_rels: int):
+    """(rel_ptrs [R + 1], row, col, rel_types, edge_ids) of the kept edges in relation-major order, stable
+    (het_block_relation_major): row = local source, col = owner, edge_ids = eids[pos]."""
+    _chk("block_relation_major", (), (rel, eids, pos, owner, local_src))
+    total, dev = pos.numel(), pos.device
+    if total == 0:
+        e = lambda: torch.empty(0, dtype=torch.int64, device=dev)  # noqa: E731
+        return torch.zeros(int(num_rels) + 1, dtype=torch.int64, device=dev), e(), e(), e(), e()
+    rel_ptrs = torch.empty(int(num_rels) + 1, dtype=torch.int64, device=dev)
+    row, col, rel_out, eids_out = (torch.empty(total, dtype=torch.int64, device=dev) for _ in range(4))
+    _call(pos, "het_block_relation_major", _p(rel), _p(eids), rel.numel(), _p(pos), _p(owner), _p(local_src), total, int(num_rels),
+          _p(rel_ptrs), _p(row), _p(col), _p(rel_out), _p(eids_out), _stream(pos))
+    return rel_ptrs, row, col, rel_out, eids_out
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -134,6 +134,9 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                    help="sampled mini-batches only: the embedding table gives a row-sparse gradient (HET_RelGraphEmbed(sparse=True)) and is "
                         "stepped by het_amd.optim.RowSparseAdam -- a lazy Adam: the moments of rows a batch does not touch do not decay; "
                         "the model's parameters keep the fused Adam")
+    p.add_argument("--keyed_sampler", action="store_true",
+                   help="sampled mini-batches only: NeighborSampler(method='keyed') -- the kept in-edges are a pure function of (seed, "
+                        "draw, edge position) and the blocks are built by the library's kernels (het_amd/sampling.py)")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -280,6 +283,8 @@ def main(argv=None):
         raise SystemExit("--sparse_embed is an option of the sampled mini-batch path: --full_graph_training reads every row of the table")
     if args.sparse_embed and args.inference:
         raise SystemExit("--sparse_embed is an option of training: --inference takes no optimizer step")
+    if args.keyed_sampler and args.full_graph_training:
+        raise SystemExit("--keyed_sampler is an option of the sampled mini-batch path: --full_graph_training samples nothing")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -325,7 +330,8 @@ def main(argv=None):
         fan = list(args.fanout)[: args.num_layers] + [args.fanout[-1]] * max(0, args.num_layers - len(args.fanout))
         sampler = NeighborSampler(g, fan, seed=args.seed,
                                   full_layouts=bool(args.compact_as_of_node_flag) or not args.gat_edge_parallel_flag
-                                  or args.model == "hgt", by_type=args.model == "hgt")
+                                  or args.model == "hgt", by_type=args.model == "hgt",
+                                  method="keyed" if args.keyed_sampler else "sort")
         gen = th.Generator(device=dev)
         gen.manual_seed(args.seed)
 
@@ -354,6 +360,10 @@ def main(argv=None):
         res["sparse_embed"] = True
     else:
         del res["args"]["sparse_embed"]
+    if args.keyed_sampler:
+        res["sampler"] = "keyed"
+    else:
+        del res["args"]["keyed_sampler"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

@@ -1056,6 +1056,44 @@ int het_layout_unique_rel_nodes(const int64_t* rel_ptrs, int64_t num_rels, const
                                 int64_t num_edges, int64_t num_nodes, int64_t* out_nodes, int64_t* out_rel_ptrs,
                                 int64_t* out_inverse, int64_t* out_count, het_stream stream);
 
+/* ------------------------------------------------------------------------
+ * Keyed neighbour sampling and block construction for sampled mini-batches (csrc/block_sample.hip; het_amd/sampling.py
+ * NeighborSampler(method="keyed"); no reference counterpart: RGNNUtils.py:164-196 samples with DGL on the CPU).
+ * The rule, in wrapping uint64 arithmetic, with pos an edge's position in the in-CSR (row_ptrs over destinations):
+ *   sm(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *   stream = sm(seed ^ sm(draw));  key(pos) = sm(stream + pos)
+ *   a destination keeps all its in-edges when deg <= fanout or fanout <= 0, else the fanout edges with the smallest (key, pos);
+ *   the kept edges are listed destination by destination (the order of dst), in ascending pos inside one.
+ * int64 device arrays, caller-allocated outputs.  Before anything is enqueued: negative counts and num_rels < 1 are
+ * HET_ERR_INVALID_ARG; num_dst == 0 or total == 0 is HET_OK (the host results are 0); null pointers are HET_ERR_INVALID_ARG.
+ * Ids and positions outside their ranges are never turned into addresses.  The device temporaries come from het_set_allocator's
+ * allocator and are released in stream order; only the two entries that return a count to the host wait for the stream.
+ * ------------------------------------------------------------------------ */
+/* in-degree from which het_sample_select gives a destination to a workgroup instead of a wave, and the positions per emission
+ * chunk (= threads) of that workgroup */
+int het_sample_workgroup_degree(void);
+int het_sample_chunk(void);
+/* out_offsets [num_dst + 1] = exclusive sum of the kept counts min(deg, fanout) (deg when fanout <= 0); *out_total (host) = the sum */
+int het_sample_count(const int64_t* row_ptrs, const int64_t* dst, int64_t num_dst, int64_t num_nodes, int64_t fanout,
+                     int64_t* out_offsets, int64_t* out_total, het_stream stream);
+/* out_pos / out_owner [total]: in-CSR position and index into dst of every kept edge; offsets / total as het_sample_count gave
+ * them for the same row_ptrs, dst and fanout (an offset that would write past total writes nothing).  Reads row_ptrs only. */
+int het_sample_select(const int64_t* row_ptrs, const int64_t* dst, int64_t num_dst, int64_t num_nodes, int64_t fanout, int64_t seed,
+                      int64_t draw, const int64_t* offsets, int64_t total, int64_t* out_pos, int64_t* out_owner, het_stream stream);
+/* Local node ids of a block.  src [num_edges]: the in-CSR's column (source) of every position; dst [num_dst]: DISTINCT node ids;
+ * map [num_nodes]: scratch that holds -1 everywhere on entry and again when the enqueued work has run.  out_nodes (capacity
+ * num_dst + total) = dst followed by the sampled sources that are no destination, ascending by global id; out_local_src [total] =
+ * index into out_nodes of every kept edge's source; *out_num_extra (host) = number of appended nodes.  New nodes are claimed with
+ * compare-and-swap in whatever order the hardware runs them and then sorted, so the result does not depend on that order. */
+int het_block_renumber(const int64_t* src, int64_t num_edges, const int64_t* pos, int64_t total, const int64_t* dst, int64_t num_dst,
+                       int64_t* map, int64_t num_nodes, int64_t* out_nodes, int64_t* out_local_src, int64_t* out_num_extra,
+                       het_stream stream);
+/* The kept edges relation-major, stable (the order of pos / owner inside a relation): out_rel_ptrs [num_rels + 1], and per block
+ * edge out_row = local source, out_col = owner, out_rel = relation, out_eids = eids[pos] (rel / eids [num_edges]: the in-CSR's) */
+int het_block_relation_major(const int64_t* rel, const int64_t* eids, int64_t num_edges, const int64_t* pos, const int64_t* owner,
+                             const int64_t* local_src, int64_t total, int64_t num_rels, int64_t* out_rel_ptrs, int64_t* out_row,
+                             int64_t* out_col, int64_t* out_rel, int64_t* out_eids, het_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
