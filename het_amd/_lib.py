@@ -137,6 +137,11 @@ _ENTRIES = {
     "het_sample_select": [P, P, I64, I64, I64, I64, I64, P, I64, P, P, P],
     "het_block_renumber": [P, I64, P, I64, P, I64, P, I64, P, P, P, P],
     "het_block_relation_major": [P, P, I64, P, P, P, I64, I64, P, P, P, P, P, P],
+    "het_keyed_dropout": [P, P, I64, I64, INT, DBL, I64, I64, P],
+    "het_keyed_dropout_backward": [P, P, P, I64, I64, INT, DBL, I64, I64, P],
+    "het_keyed_dropout_bf16": [P, P, I64, I64, INT, DBL, I64, I64, P],
+    "het_keyed_dropout_backward_bf16": [P, P, P, I64, I64, INT, DBL, I64, I64, P],
+    "het_keyed_dropout_params": [DBL, C.POINTER(C.c_uint32), C.POINTER(C.c_float)],
 }
 _ENTRIES = {name: decl if isinstance(decl, tuple) else (INT, decl) for name, decl in _ENTRIES.items()}  # name -> (restype, argtypes)
 _SIGNATURES = {name: args for name, (_, args) in _ENTRIES.items()}  # name -> argtypes

@@ -23,7 +23,7 @@
 // All stores are ordinary vector stores; the atomics are LDS adds (histogram) and global compare-and-swap / add (renumbering).
 #include <hipcub/hipcub.hpp>
 
-#include "common.hip.h"
+#include "common.hip.h"  // (sm64)
 #include "device_scratch.hip.h"
 
 namespace {
@@ -32,13 +32,6 @@ constexpr int kSampleWorkgroupDegree = 512;                        // in-degree 
 constexpr int kSampleWaveItems = kSampleWorkgroupDegree / HET_WAVE;  // keys per lane on the wave path
 constexpr int kSampleChunk = 1024;                                 // threads of the long-row workgroup = positions per emission chunk
 constexpr int kSampleChunkWaves = kSampleChunk / HET_WAVE;
-
-__host__ __device__ __forceinline__ uint64_t sm64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
 

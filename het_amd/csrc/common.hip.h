@@ -290,6 +290,16 @@ __device__ __forceinline__ void strow4_at(T* base, O byte_off, float4 v) {
   strow4(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off), v);
 }
 
+// ---- the keyed streams (block_sample.hip: neighbour sampling; keyed_dropout.hip: dropout masks) ----------------------------
+// sm of include/het_amd.h: an addition and two xor-shift / odd-multiply rounds, a bijection of the 64-bit integers.
+// stream = sm64(seed ^ sm64(draw)), key(position) = sm64(stream + position): the same bits on the host and on the device.
+__host__ __device__ __forceinline__ uint64_t sm64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 constexpr int het_log2_ce(int v) { return v <= 1 ? 0 : 1 + het_log2_ce(v >> 1); }
 // rows * row_bytes fits an unsigned 32-bit byte offset (with room for the lane's piece of the row)
 static inline bool het_fits_u32(int64_t rows, int64_t row_bytes) { return rows >= 0 && rows * row_bytes <= 0xffffffffll - 4096; }

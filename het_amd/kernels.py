@@ -1306,6 +1306,63 @@ def block_relation_major(rel, eids, pos, owner, local_src, num_rels: int):
     return rel_ptrs, row, col, rel_out, eids_out
 
 
+# ---- keyed dropout fused with the activation (het_amd/layers.py KeyedDropout; csrc/keyed_dropout.hip) ----
+def keyed_dropout_params(p: float):
+    """(T, scale) of the keyed dropout rule for a rate ``p`` in [0, 1): an element is dropped when its 16-bit field is below T, a kept
+    one is multiplied by the float32 ``scale`` = 65536 / (65536 - T) (het_keyed_dropout_params; runs on the host)."""
+    L = _lib.lib()
+    T, scale = C.c_uint32(0), C.c_float(0.0)
+    rc = L.het_keyed_dropout_params(float(p), C.byref(T), C.byref(scale))
+    if rc != 0:
+        raise _lib.HetError(f"het_keyed_dropout_params failed (code {rc}): {L.het_last_error().decode()}")
+    return int(T.value), float(scale.value)
+
+
+def _as_i64(v) -> int:
+    return ((int(v) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63)  # (the same 64 bits as a signed value)
+
+
+def keyed_dropout_ok(*tensors) -> bool:
+    """Whether the keyed dropout kernels take these tensors: contiguous float32 / bfloat16 on one GPU, 16-byte (bf16: 8-byte) aligned."""
+    t0 = tensors[0]
+    return all(t.is_cuda and t.device == t0.device and t.dtype == t0.dtype and t.dtype in (torch.float32, torch.bfloat16)
+               and t.is_contiguous() and t.data_ptr() % (4 * t.element_size()) == 0 for t in tensors)
+
+
+def _keyed_dropout_chk(name, tensors):
+    if not keyed_dropout_ok(*tensors):
+        raise _lib.HetError(f"{name}: expected contiguous float32 or bfloat16 GPU tensors of one dtype, 16-byte (bf16: 8-byte) aligned, got "
+                            f"{[(t.dtype, str(t.device), t.is_contiguous(), t.data_ptr() % 16) for t in tensors]}")
+    if any(t.shape != tensors[0].shape for t in tensors):
+        raise _lib.HetError(f"{name}: tensors of one shape expected, got {[tuple(t.shape) for t in tensors]}")
+
+
+def keyed_dropout(y, p, seed, draw, relu=False, base=0):
+    """out = drop(a(y)) in one launch (het_keyed_dropout / _bf16): a = relu or the identity, the mask a pure function of
+    (``seed``, ``draw``, ``base`` + the element's index in the contiguous tensor) -- the rule in include/het_amd.h.  ``seed`` / ``draw``:
+    any Python ints, taken modulo 2^64; ``base``: a multiple of 4, at least 0."""
+    _keyed_dropout_chk("keyed_dropout", (y,))
+    out = torch.empty_like(y)
+    _call(y, "het_keyed_dropout_bf16" if y.dtype == torch.bfloat16 else "het_keyed_dropout", _p(y), _p(out), y.numel(), int(base),
+          int(bool(relu)), float(p), _as_i64(seed), _as_i64(draw), _stream(y))
+    return out
+
+
+def keyed_dropout_backward(grad_out, out, p, seed, draw, relu=False, base=0, grad_y=None):
+    """The gradient of keyed_dropout's input (het_keyed_dropout_backward / _bf16) for the same (p, seed, draw, relu, base): ``out`` is
+    the forward's result, read for relu only (None otherwise).  ``grad_y``: the tensor to write, which may be ``grad_out`` itself."""
+    saved = (out,) if relu else ()
+    if relu and out is None:
+        raise _lib.HetError("keyed_dropout_backward: relu needs the forward's out")
+    if grad_y is None:
+        grad_y = torch.empty_like(grad_out)
+    _keyed_dropout_chk("keyed_dropout_backward", (grad_out, grad_y) + saved)
+    _call(grad_out, "het_keyed_dropout_backward_bf16" if grad_out.dtype == torch.bfloat16 else "het_keyed_dropout_backward", _p(grad_out),
+          _p(out) if relu else None, _p(grad_y), grad_out.numel(), int(base), int(bool(relu)), float(p), _as_i64(seed), _as_i64(draw),
+          _stream(grad_out))
+    return grad_y
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -122,6 +122,171 @@ class HET_RelGraphEmbed(nn.Module):
         return _EmbedRowsFunction.apply(self.embeds, nodes, self.embeds.dtype if dtype is None else dtype, self.sparse)
 
 
+_M64 = (1 << 64) - 1
+
+
+def _i64(v: int) -> int:
+    """The 64 bits of ``v`` as a signed value (what an int64 tensor holds)."""
+    return ((int(v) & _M64) ^ (1 << 63)) - (1 << 63)
+
+
+def keyed_dropout_params(p: float):
+    """(T, scale) of the keyed dropout rule (KeyedDropout) in plain Python: T = min(round-half-away(p * 65536), 65535), scale =
+    65536 / (65536 - T) rounded once to float32 -- the values het_keyed_dropout_params gives."""
+    import struct
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"keyed dropout: a rate in [0, 1), not {p}")
+    x = p * 65536.0
+    T = int(math.floor(x))
+    if x - T >= 0.5:
+        T += 1
+    T = min(T, 65535)
+    return T, struct.unpack("f", struct.pack("f", 65536.0 / (65536 - T)))[0]
+
+
+def _lsr(z, k: int):
+    """Logical right shift of an int64 tensor: the arithmetic shift with the copied sign bits masked off."""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _sm_tensor(z):
+    """sm of het_amd/sampling.py on an int64 tensor: the same 64 bits as the uint64 arithmetic (int64 add and multiply wrap)."""
+    z = z + _i64(0x9E3779B97F4A7C15)
+    z = (z ^ _lsr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr(z, 27)) * _i64(0x94D049BB133111EB)
+    return z ^ _lsr(z, 31)
+
+
+def keyed_dropout_mask(seed: int, draw: int, base: int, n: int, p: float, device=None):
+    """kept [n] (bool) of the keyed dropout rule in torch int64 arithmetic, on any device: the bits the kernels recompute."""
+    from .sampling import _sm_int
+    T, _ = keyed_dropout_params(p)
+    if base < 0 or base % 4:
+        raise ValueError(f"keyed dropout: base is a multiple of 4, at least 0, not {base}")
+    stream = _sm_int((int(seed) & _M64) ^ _sm_int(int(draw) & _M64))
+    groups = th.arange((n + 3) // 4, dtype=th.int64, device=device)
+    key = _sm_tensor(groups + _i64(stream + base // 4))
+    field = th.stack([(key >> (16 * j)) & 0xFFFF for j in range(4)], dim=1).reshape(-1)[:n]
+    return field >= T
+
+
+def _keyed_dropout_torch(y, p, seed, draw, base, relu):
+    """The rule as a torch composition in fp32, cast back: correct, not fast (CPU tensors, other dtypes, strided or misaligned ones)."""
+    _, scale = keyed_dropout_params(p)
+    kept = keyed_dropout_mask(seed, draw, base, y.numel(), p, y.device).view(y.shape)
+    v = y.to(th.float32)
+    if relu:
+        v = th.where(v < 0, th.zeros_like(v), v)  # (not th.relu: a NaN stays a NaN and -0 stays -0, as the kernel's select does)
+    return th.where(kept, v * scale, th.zeros_like(v)).to(y.dtype)
+
+
+def _keyed_dropout_backward_torch(grad_out, out, p, seed, draw, base, relu):
+    _, scale = keyed_dropout_params(p)
+    kept = keyed_dropout_mask(seed, draw, base, grad_out.numel(), p, grad_out.device).view(grad_out.shape)
+    if relu:
+        kept = kept & (out > 0)
+    g = grad_out.to(th.float32)
+    return th.where(kept, g * scale, th.zeros_like(g)).to(grad_out.dtype)
+
+
+class _KeyedDropoutFunction(th.autograd.Function):
+    """out = drop(a(y)) as one autograd node that keeps (p, seed, draw, base) of its own call and saves ``out`` for relu, nothing
+    for the identity: the mask is recomputed from the key in the backward.  One HIP launch each way where the kernels take the
+    tensors (csrc/keyed_dropout.hip), the torch composition with the same mask bits elsewhere."""
+
+    @staticmethod
+    def forward(ctx, y, p, seed, draw, base, relu):
+        ctx.key = (float(p), int(seed), int(draw), int(base), bool(relu))
+        yd = y.detach()
+        out = _k.keyed_dropout(yd, p, seed, draw, relu, base) if _k.keyed_dropout_ok(yd) else _keyed_dropout_torch(yd, p, seed, draw, base, relu)
+        if relu:
+            ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0] or grad_out is None:
+            return None, None, None, None, None, None
+        p, seed, draw, base, relu = ctx.key
+        out = ctx.saved_tensors[0] if relu else None
+        go = grad_out.detach().contiguous()  # (an expanded or strided grad_out: read, never written)
+        if _k.keyed_dropout_ok(*((go, out) if relu else (go,))):
+            grad_y = _k.keyed_dropout_backward(go, out, p, seed, draw, relu, base)
+        else:
+            grad_y = _keyed_dropout_backward_torch(go, out, p, seed, draw, base, relu)
+        return grad_y, None, None, None, None, None
+
+
+class KeyedDropout(nn.Module):
+    """Dropout whose mask is a pure function of (seed, draw, position), fused with the activation that precedes it: ``out =
+    drop(a(y))`` in one pass, its backward in one pass, no mask stored (opt-in).
+
+    **A different sample than nn.Dropout's for the same torch seed**, with the same distribution.  All arithmetic is uint64 and wraps;
+    ``sm`` is the keyed sampler's (het_amd/sampling.py); ``i`` is the element's index in the contiguous tensor::
+
+        T      = min(round(p * 65536), 65535)       the effective rate is T / 65536 (0.5 is exact)
+        scale  = float32(65536 / (65536 - T))
+        stream = sm(seed ^ sm(draw))
+        key(g) = sm(stream + g)                     g = i // 4: one key per 4 consecutive elements
+        field  = (key(g) >> (16 * (i % 4))) & 0xFFFF
+        kept   = field >= T
+        out[i]    = a(y[i]) * scale if kept else +0             a = identity, or y < 0 ? 0 : y ("relu")
+        grad_y[i] = grad_out[i] * scale if kept and (a is the identity or out[i] > 0) else +0
+
+    bf16 tensors are widened, multiplied in fp32 and rounded once; every output is determined to the bit, on every device.
+
+    ``seed=None`` draws the seed once, at construction, from torch's default CPU generator (deterministic under
+    ``torch.manual_seed``).  ``draw`` is a counter of the module: 0 at first, one more per training call that drops something, so
+    that successive steps use different streams; ``forward(y, draw=)`` sets it for one call and leaves the counter alone (the
+    sampler's convention).  The autograd node of a call keeps that call's own (seed, draw).
+
+    In training with p > 0, a contiguous, aligned float32 / bfloat16 GPU tensor takes the HIP kernels; everything else (CPU tensors,
+    other dtypes, non-contiguous or misaligned inputs) takes a torch composition that produces the same mask bits in fp32, cast
+    back: correct, not fast.  In ``eval()``, or when nothing would be dropped (T = 0), the module is the activation alone in torch
+    and the counter does not move."""
+
+    def __init__(self, p: float = 0.5, activation=None, seed=None):
+        super().__init__()
+        if activation not in (None, "relu"):
+            raise ValueError(f"KeyedDropout: activation None or 'relu', not {activation!r}")
+        self.T, self.scale = keyed_dropout_params(p)
+        self.p, self.activation = float(p), activation
+        self.seed = int(th.randint(0, 2 ** 63 - 1, (1,))) if seed is None else int(seed) & _M64
+        self.draw = 0
+
+    def extra_repr(self):
+        return f"p={self.p}, activation={self.activation!r}"
+
+    def forward(self, y, draw=None):
+        if not self.training or self.T == 0:
+            return th.relu(y) if self.activation == "relu" else y
+        if draw is None:
+            draw, self.draw = self.draw, self.draw + 1
+        return _KeyedDropoutFunction.apply(y, self.p, self.seed, int(draw), 0, self.activation == "relu")
+
+
+def _activation_dropout(layer, h):
+    """The end of an RGAT / RGCN layer: ``dropout(activation(h))`` -- two torch ops, or with ``keyed_dropout=True`` one KeyedDropout
+    call (relu inside it; any other activation applied in torch first)."""
+    if not layer.keyed_dropout:
+        if layer.activation:
+            h = layer.activation(h)
+        return layer.dropout(h)
+    if layer.activation and layer.dropout.activation is None:
+        h = layer.activation(h)
+    return layer.dropout(h if h.is_contiguous() else h.contiguous())  # (a sliced padded width: one copy instead of the composition)
+
+
+def _make_dropout(layer, dropout, keyed_dropout):
+    """nn.Dropout, or (``keyed_dropout=True``, opt-in) KeyedDropout with relu fused where the layer's activation is relu."""
+    layer.keyed_dropout = bool(keyed_dropout)
+    if not layer.keyed_dropout:
+        return nn.Dropout(dropout)
+    return KeyedDropout(dropout, "relu" if layer.activation in (th.relu, nn.functional.relu) else None)
+
+
 class HET_RGATLayer(nn.Module):
     """Relational graph attention layer (RGAT/models.py:16-385).
 
@@ -149,7 +314,7 @@ class HET_RGATLayer(nn.Module):
     def __init__(self, in_feat, out_feat, num_rels, num_heads, *, bias=True, activation=None, self_loop=False,
                  compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
                  multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True, dropout=0.5,
-                 leaky_relu_slope=0.2, reference_op_sequence=False, bf16_training=False):
+                 leaky_relu_slope=0.2, reference_op_sequence=False, bf16_training=False, keyed_dropout=False):
         super().__init__()
         assert out_feat % num_heads == 0, "out_feat must be a multiple of num_heads"
         self.in_feat, self.out_feat, self.num_rels, self.num_heads = in_feat, out_feat, num_rels, num_heads
@@ -175,7 +340,7 @@ class HET_RGATLayer(nn.Module):
             self.h_bias = nn.Parameter(th.Tensor(out_feat))
         if self_loop:
             self.loop_weight = nn.Parameter(th.Tensor(in_feat, out_feat))
-        self.dropout = nn.Dropout(dropout)
+        self.dropout = _make_dropout(self, dropout, keyed_dropout)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -269,9 +434,7 @@ class HET_RGATLayer(nn.Module):
             h = self._composition(g, inputs, num_dst)
         else:
             h = self._fused(route, g, inputs, num_dst, halo, attn_out)
-        if self.activation:
-            h = self.activation(h)
-        return self.dropout(h)
+        return _activation_dropout(self, h)
 
     def _composition(self, g, inputs, num_dst):
         """The reference's model code op by op on this package's backend wrappers, up to and including the bias."""
@@ -363,7 +526,7 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
     of the input and rounds its output to bf16: correct, not faster, and it needs the fp32 copy."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_bases=-1, *, bias=True, activation=None,
-                 compact_as_of_node_flag=False, compact_direct_indexing_flag=False, dropout=0.0):
+                 compact_as_of_node_flag=False, compact_direct_indexing_flag=False, dropout=0.0, keyed_dropout=False):
         super().__init__()
         self.in_feat, self.out_feat, self.num_rels = in_feat, out_feat, num_rels
         self.num_bases = num_rels if num_bases <= 0 or num_bases > num_rels else num_bases
@@ -378,7 +541,7 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
             nn.init.xavier_uniform_(self.w_comp, gain=gain)
         if bias:
             self.h_bias = nn.Parameter(th.zeros(out_feat))
-        self.dropout = nn.Dropout(dropout)
+        self.dropout = _make_dropout(self, dropout, keyed_dropout)
 
     def forward(self, g, x, norm, num_dst=None):
         _refuse_inference_graph(g, self, lambda: _needs_grad(x, self, norm))
@@ -397,18 +560,14 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
             bias_in_op = self.bias and (num_dst is None or num_dst >= g.get_num_nodes()) and weight.shape[2] == self.out_feat
             node_repr = B.rgcn_layer1_separate_coo(g, x, weight, norm, self.h_bias if bias_in_op else None)
             if bias_in_op:
-                if self.activation:
-                    node_repr = self.activation(node_repr)
-                return self.dropout(node_repr)
+                return _activation_dropout(self, node_repr)
         if num_dst is not None and num_dst < node_repr.shape[0]:
             node_repr = node_repr[:num_dst]
         if node_repr.shape[1] != self.out_feat:  # (padded widths: see above)
             node_repr = node_repr[:, :self.out_feat]
         if self.bias:
             node_repr = node_repr + self.h_bias
-        if self.activation:
-            node_repr = self.activation(node_repr)
-        return self.dropout(node_repr)
+        return _activation_dropout(self, node_repr)
 
     def _weight_and_input(self, x):
         """The layer's [R, K, D] weight (basis-composed, zero-padded to the kernels' widths) and the input, padded to match."""
@@ -440,9 +599,7 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
                     node_repr = node_repr[:num_dst]
                 if node_repr.shape[1] != self.out_feat:
                     node_repr = node_repr[:, :self.out_feat]
-                if self.activation:
-                    node_repr = self.activation(node_repr)
-                return self.dropout(node_repr)
+                return _activation_dropout(self, node_repr)
         return self.forward(g, x.float(), norm, num_dst).to(th.bfloat16)
 
 

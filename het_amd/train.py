@@ -32,9 +32,9 @@ class HET_RGATModel(nn.Module):
 
     def __init__(self, num_etypes, h_dim, out_dim, num_heads, num_hidden_layers=1, dropout=0.5, use_self_loop=True,
                  last_layer_act=False, compact_as_of_node_flag=False, compact_direct_indexing_flag=False,
-                 multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True, bf16_training=False):
+                 multiply_among_weights_first_flag=False, gat_edge_parallel_flag=True, bf16_training=False, keyed_dropout=False):
         super().__init__()
-        flags = dict(compact_as_of_node_flag=compact_as_of_node_flag, compact_direct_indexing_flag=compact_direct_indexing_flag,
+        flags = dict(keyed_dropout=keyed_dropout, compact_as_of_node_flag=compact_as_of_node_flag, compact_direct_indexing_flag=compact_direct_indexing_flag,
                      multiply_among_weights_first_flag=multiply_among_weights_first_flag,
                      gat_edge_parallel_flag=gat_edge_parallel_flag, self_loop=use_self_loop, bf16_training=bf16_training)
         self.layers = nn.ModuleList(
@@ -54,14 +54,14 @@ class HET_RGCNModel(nn.Module):
     """hrt/python/RGCN/RGCN.py:353-405 (full-graph, edge-parallel separate-COO layers)."""
 
     def __init__(self, num_rels, h_dim, out_dim, num_layers=1, num_bases=-1, dropout=0.0, compact_as_of_node_flag=False,
-                 compact_direct_indexing_flag=False):
+                 compact_direct_indexing_flag=False, keyed_dropout=False):
         super().__init__()
         dims = [h_dim] * num_layers + [out_dim]
         self.layers = nn.ModuleList(
             [HET_EglRelGraphConv_EdgeParallel(dims[i], dims[i + 1], num_rels, num_bases,
                                               activation=F.relu if i + 1 < num_layers else None, dropout=dropout,
                                               compact_as_of_node_flag=compact_as_of_node_flag,
-                                              compact_direct_indexing_flag=compact_direct_indexing_flag)
+                                              compact_direct_indexing_flag=compact_direct_indexing_flag, keyed_dropout=keyed_dropout)
              for i in range(num_layers)])
 
     def forward(self, g, h, norm):
@@ -137,6 +137,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
     p.add_argument("--keyed_sampler", action="store_true",
                    help="sampled mini-batches only: NeighborSampler(method='keyed') -- the kept in-edges are a pure function of (seed, "
                         "draw, edge position) and the blocks are built by the library's kernels (het_amd/sampling.py)")
+    p.add_argument("--keyed_dropout", action="store_true",
+                   help="RGAT / RGCN only: every layer ends with one KeyedDropout pass (activation and dropout fused, the mask a pure "
+                        "function of (seed, draw, position), nothing stored for the backward; het_amd/layers.py) -- a different sample "
+                        "than nn.Dropout's for the same --seed, the same distribution")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -279,6 +283,8 @@ def main(argv=None):
         raise SystemExit("--bf16_training is an option of the RGAT layer (RGCN and HGT train in bf16 on a bf16 input as they are)")
     if args.use_norm and args.model != "hgt":
         raise SystemExit("--use_norm is an option of the HGT layer")
+    if args.keyed_dropout and args.model == "hgt":
+        raise SystemExit("--keyed_dropout is an option of the RGAT and RGCN layers (the HGT layer applies no dropout)")
     if args.sparse_embed and args.full_graph_training:
         raise SystemExit("--sparse_embed is an option of the sampled mini-batch path: --full_graph_training reads every row of the table")
     if args.sparse_embed and args.inference:
@@ -303,11 +309,12 @@ def main(argv=None):
                               compact_as_of_node_flag=args.compact_as_of_node_flag,
                               compact_direct_indexing_flag=args.compact_direct_indexing_flag,
                               multiply_among_weights_first_flag=args.multiply_among_weights_first_flag,
-                              gat_edge_parallel_flag=args.gat_edge_parallel_flag, bf16_training=args.bf16_training)
+                              gat_edge_parallel_flag=args.gat_edge_parallel_flag, bf16_training=args.bf16_training,
+                              keyed_dropout=args.keyed_dropout)
     elif args.model == "rgcn":
         model = HET_RGCNModel(R, args.n_infeat, args.num_classes, num_layers=args.num_layers, num_bases=args.n_bases,
                               dropout=args.dropout, compact_as_of_node_flag=args.compact_as_of_node_flag,
-                              compact_direct_indexing_flag=args.compact_direct_indexing_flag)
+                              compact_direct_indexing_flag=args.compact_direct_indexing_flag, keyed_dropout=args.keyed_dropout)
         extra = (th.rand(E, 1, device=dev),)  # edge norm as RGCN.py:527-530
     else:
         model = HET_HGTModel(g.get_num_ntypes(), R, args.n_infeat, args.num_classes, args.num_heads,
@@ -364,6 +371,10 @@ def main(argv=None):
         res["sampler"] = "keyed"
     else:
         del res["args"]["keyed_sampler"]
+    if args.keyed_dropout:
+        res["dropout"] = "keyed"
+    else:
+        del res["args"]["keyed_dropout"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

@@ -1094,6 +1094,38 @@ int het_block_relation_major(const int64_t* rel, const int64_t* eids, int64_t nu
                              const int64_t* local_src, int64_t total, int64_t num_rels, int64_t* out_rel_ptrs, int64_t* out_row,
                              int64_t* out_col, int64_t* out_rel, int64_t* out_eids, het_stream stream);
 
+/* ------------------------------------------------------------------------
+ * Keyed dropout fused with the activation (csrc/keyed_dropout.hip; het_amd/layers.py KeyedDropout; no reference counterpart: the
+ * reference's layers end with activation(h) and nn.Dropout).  The mask is a pure function of (seed, draw, position) on the
+ * sampler's stream above, recomputed by the backward and never stored.  With i the index in the contiguous tensor of n elements:
+ *   T      = min(llround(p * 65536), 65535)              the effective rate is T / 65536 (0.5 is exact)
+ *   scale  = (float)(65536.0 / (65536 - T))              computed in double, rounded once to float
+ *   stream = sm(seed ^ sm(draw));  key(g) = sm(stream + g),  g = (base + i) / 4: one key per 4 consecutive elements
+ *   field  = (key(g) >> (16 * ((base + i) % 4))) & 0xFFFF;   kept(i) = field >= T
+ *   a(y)   = y (activation 0: none)  |  y < 0 ? 0 : y (activation 1: relu; a NaN stays a NaN)
+ *   out[i]    = kept(i) ? a(y[i]) * scale : +0           (a select, not a multiply: a dropped NaN or inf is +0)
+ *   grad_y[i] = kept(i) && (activation == 0 || out[i] > 0) ? grad_out[i] * scale : +0
+ * base: the index of the tensor's first element in the stream, a multiple of 4, at least 0 (a mask cut into parts; 0 for a whole
+ * tensor).  A tail of n % 4 elements uses the low fields of its group.  bf16 rows are widened (exact), multiplied in fp32 and
+ * rounded once, to nearest even, at the store; the fp32 product is one correctly rounded multiply: every output is determined to
+ * the bit.  seed and draw are the 64 bits of the rule's unsigned values, passed as int64_t like het_sample_select's.
+ * Before anything is enqueued: n < 0, a null pointer, a pointer off a 16-byte (bf16: 8-byte) boundary, base < 0 or base % 4 != 0,
+ * p outside [0, 1) or a NaN, and relu's backward without out are HET_ERR_INVALID_ARG; an activation other than 0 / 1 is
+ * HET_ERR_UNSUPPORTED; n == 0 is HET_OK with nothing looked at.  out may not overlap y (refused).  grad_y MAY be grad_out itself:
+ * every element is read before its own store and no other lane touches it; any other overlap of grad_y is refused.  out is read
+ * by the backward for relu only (NULL otherwise).  One launch each, no workspace, no atomics, no host synchronisation.
+ * ------------------------------------------------------------------------ */
+int het_keyed_dropout(const float* y, float* out, int64_t n, int64_t base, int activation, double p, int64_t seed, int64_t draw,
+                      het_stream stream);
+int het_keyed_dropout_backward(const float* grad_out, const float* out, float* grad_y, int64_t n, int64_t base, int activation,
+                               double p, int64_t seed, int64_t draw, het_stream stream);
+int het_keyed_dropout_bf16(const het_bf16* y, het_bf16* out, int64_t n, int64_t base, int activation, double p, int64_t seed,
+                           int64_t draw, het_stream stream);
+int het_keyed_dropout_backward_bf16(const het_bf16* grad_out, const het_bf16* out, het_bf16* grad_y, int64_t n, int64_t base,
+                                    int activation, double p, int64_t seed, int64_t draw, het_stream stream);
+/* the rule's T and scale for a rate p in [0, 1) (HET_ERR_INVALID_ARG otherwise, and for a null pointer) */
+int het_keyed_dropout_params(double p, uint32_t* T, float* scale);
+
 #ifdef __cplusplus
 }
 #endif
