@@ -142,6 +142,12 @@ _ENTRIES = {
     "het_keyed_dropout_bf16": [P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_backward_bf16": [P, P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_params": [DBL, C.POINTER(C.c_uint32), C.POINTER(C.c_float)],
+    "het_softmax_xent_workspace": (I64, [I64, I64]),
+    "het_softmax_xent": [P, P, I64, I64, I64, INT, P, P, P, P, I64, P],
+    "het_softmax_xent_bf16": [P, P, I64, I64, I64, INT, P, P, P, P, I64, P],
+    "het_softmax_xent_backward": [P, P, P, P, P, I64, I64, I64, INT, P, P],
+    "het_softmax_xent_backward_bf16": [P, P, P, P, P, I64, I64, I64, INT, P, P],
+    "het_softmax_xent_params": [C.POINTER(I64)],
 }
 _ENTRIES = {name: decl if isinstance(decl, tuple) else (INT, decl) for name, decl in _ENTRIES.items()}  # name -> (restype, argtypes)
 _SIGNATURES = {name: args for name, (_, args) in _ENTRIES.items()}  # name -> argtypes

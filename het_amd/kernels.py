@@ -1363,6 +1363,109 @@ def keyed_dropout_backward(grad_out, out, p, seed, draw, relu=False, base=0, gra
     return grad_y
 
 
+# ---- softmax cross-entropy over rows of logits (het_amd/layers.py SoftmaxCrossEntropy; csrc/softmax_xent.hip) ----
+XENT_REDUCTIONS = {"mean": 0, "sum": 1}  # HET_XENT_MEAN / HET_XENT_SUM of include/het_amd.h
+
+
+def softmax_xent_params() -> Dict[str, int]:
+    """The launch constants of csrc/softmax_xent.hip (het_softmax_xent_params; runs on the host): ``lane_elems`` columns per lane
+    before a row gets another lane, at most ``max_lanes`` lanes per row, at most ``max_blocks`` workgroups of ``block`` threads."""
+    L = _lib.lib()
+    out = (C.c_int64 * 4)()
+    rc = L.het_softmax_xent_params(out)
+    if rc != 0:
+        raise _lib.HetError(f"het_softmax_xent_params failed (code {rc}): {L.het_last_error().decode()}")
+    return dict(zip(("lane_elems", "max_lanes", "max_blocks", "block"), (int(v) for v in out)))
+
+
+def softmax_xent_lanes(C_: int) -> int:
+    """Lanes a row of ``C_`` logits gets: the power of two G with C_ <= G * lane_elems, at most max_lanes."""
+    p = softmax_xent_params()
+    g = 1
+    while g < p["max_lanes"] and g * p["lane_elems"] < C_:
+        g *= 2
+    return g
+
+
+def softmax_xent_thresholds():
+    """The class counts up to which a row gets 1, 2, 4 ... lanes (one more column gives it twice as many)."""
+    p = softmax_xent_params()
+    out, g = [], 1
+    while g < p["max_lanes"]:
+        out.append(g * p["lane_elems"])
+        g *= 2
+    return tuple(out)
+
+
+def softmax_xent_rows_per_pass(C_: int) -> int:
+    """Rows a full grid takes before a wave takes a second one."""
+    p = softmax_xent_params()
+    return p["max_blocks"] * p["block"] // softmax_xent_lanes(C_)
+
+
+def softmax_xent_ok(logits, labels=None) -> bool:
+    """Whether the softmax cross-entropy kernels take these tensors: [N, C] contiguous float32 / bfloat16 logits on a GPU with C >= 1,
+    16-byte (bf16: 8-byte) aligned, and [N] contiguous int64 labels on the same device."""
+    return (logits.is_cuda and logits.dim() == 2 and logits.shape[1] >= 1 and logits.dtype in (torch.float32, torch.bfloat16)
+            and logits.is_contiguous() and logits.data_ptr() % (4 * logits.element_size()) == 0
+            and (labels is None or (labels.device == logits.device and labels.dtype == torch.int64 and labels.dim() == 1
+                                    and labels.shape[0] == logits.shape[0] and labels.is_contiguous() and labels.data_ptr() % 8 == 0)))
+
+
+def _softmax_xent_chk(name, logits, labels, reduction):
+    if not softmax_xent_ok(logits, labels):
+        raise _lib.HetError(f"{name}: expected contiguous float32 or bfloat16 GPU logits [N, C], 16-byte (bf16: 8-byte) aligned, and int64 "
+                            f"labels [N] on the same device, got {logits.dtype} {tuple(logits.shape)} on {logits.device}"
+                            f"{'' if logits.is_contiguous() else ' (non-contiguous)'} at offset {logits.data_ptr() % 16} and "
+                            f"{labels.dtype} {tuple(labels.shape)} on {labels.device}")
+    if reduction not in XENT_REDUCTIONS:
+        raise _lib.HetError(f"{name}: reduction 'mean' or 'sum', not {reduction!r}")
+
+
+def softmax_xent(logits, labels, ignore_index=-100, reduction="mean", want_lse=True):
+    """(loss, lse, stats) of het_softmax_xent / _bf16: the fp32 scalar loss of the rule in include/het_amd.h, lse [N] fp32 for the
+    backward (None with ``want_lse=False``) and stats int64 [3] = (valid, correct, bad rows), all on the device; nothing is read back."""
+    _softmax_xent_chk("softmax_xent", logits, labels, reduction)
+    return _softmax_xent(logits, labels, ignore_index, reduction, want_lse)
+
+
+def _softmax_xent(logits, labels, ignore_index, reduction, want_lse):
+    """softmax_xent behind its tensor checks (the autograd node has asked softmax_xent_ok once)."""
+    N, C_ = logits.shape
+    dev = logits.device
+    lse = torch.empty(N, dtype=torch.float32, device=dev) if want_lse else None
+    if N == 0:  # (no launch: the entry writes nothing)
+        return (torch.full((), float("nan") if reduction == "mean" else 0.0, dtype=torch.float32, device=dev), lse,
+                torch.zeros(3, dtype=torch.int64, device=dev))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    ws, nbytes = _workspace(logits, "het_softmax_xent_workspace", N, C_)
+    _call(logits, "het_softmax_xent_bf16" if logits.dtype == torch.bfloat16 else "het_softmax_xent", _p(logits), _p(labels), N, C_,
+          int(ignore_index), XENT_REDUCTIONS[reduction], _p(loss), _p(lse), _p(stats), _p(ws), nbytes, _stream(logits))
+    return loss, lse, stats
+
+
+def softmax_xent_backward(logits, labels, lse, stats, grad_loss, ignore_index=-100, reduction="mean"):
+    """grad_logits [N, C] in the logits' dtype (het_softmax_xent_backward / _bf16) for the forward's ``lse`` and ``stats``;
+    ``grad_loss``: the fp32 scalar gradient of the loss, on the device (it is read there, like stats[0])."""
+    _softmax_xent_chk("softmax_xent_backward", logits, labels, reduction)
+    N, C_ = logits.shape
+    _chk("softmax_xent_backward", (lse, grad_loss), (stats,))
+    if lse.shape != (N,) or stats.shape != (3,) or grad_loss.numel() != 1 or any(t.device != logits.device for t in (lse, stats, grad_loss)):
+        raise _lib.HetError(f"softmax_xent_backward: lse [{N}], stats [3] and a scalar grad_loss on {logits.device} expected, got "
+                            f"{tuple(lse.shape)}, {tuple(stats.shape)}, {tuple(grad_loss.shape)}")
+    return _softmax_xent_backward(logits, labels, lse, stats, grad_loss, ignore_index, reduction)
+
+
+def _softmax_xent_backward(logits, labels, lse, stats, grad_loss, ignore_index, reduction):
+    """softmax_xent_backward behind its tensor checks (the autograd node passes what its own forward made)."""
+    N, C_ = logits.shape
+    grad = torch.empty_like(logits)
+    _call(logits, "het_softmax_xent_backward_bf16" if logits.dtype == torch.bfloat16 else "het_softmax_xent_backward", _p(logits),
+          _p(labels), _p(lse), _p(stats), _p(grad_loss), N, C_, int(ignore_index), XENT_REDUCTIONS[reduction], _p(grad), _stream(logits))
+    return grad
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -287,6 +287,133 @@ def _make_dropout(layer, dropout, keyed_dropout):
     return KeyedDropout(dropout, "relu" if layer.activation in (th.relu, nn.functional.relu) else None)
 
 
+def _xent_rows(z, labels, ignore_index):
+    """(valid [N] bool, bad [N] bool, label-or-0 [N]) of the cross-entropy rule: a label is used as an index only where it is valid."""
+    valid = (labels != ignore_index) & (labels >= 0) & (labels < z.shape[1])
+    return valid, (labels != ignore_index) & ~valid, th.where(valid, labels, th.zeros_like(labels))
+
+
+def _softmax_xent_torch(z, labels, ignore_index, reduction, want_lse):
+    """The rule of SoftmaxCrossEntropy as a torch composition (fp32; fp64 logits in fp64): (loss, lse or None, stats).  Correct, not
+    fast: CPU tensors, other dtypes, non-contiguous or misaligned logits."""
+    acc = th.float64 if z.dtype == th.float64 else th.float32
+    zf = z.to(acc)
+    valid, bad, lab = _xent_rows(zf, labels, ignore_index)
+    m = zf.max(dim=1).values
+    lsum = th.log(th.exp(zf - m[:, None]).sum(dim=1))  # (a row of -inf, a NaN, +inf: NaN, as the kernels give)
+    zl = zf.gather(1, lab[:, None]).squeeze(1)
+    zero = th.zeros((), dtype=acc, device=z.device)
+    row_loss = th.where(valid, lsum + (m - zl), zero)
+    total = row_loss.double().sum()
+    n_valid = valid.sum()
+    loss = (total / n_valid if reduction == "mean" else total).to(th.float32 if acc == th.float32 else acc)
+    # correct: the label's logit is the first of the row's maxima, a NaN above everything (torch.argmax on the CPU, on any device)
+    lower = th.arange(zf.shape[1], device=z.device)[None, :] < lab[:, None]
+    nan, zlc = zf.isnan(), zl[:, None]
+    beaten = th.where(zl.isnan()[:, None], nan & lower, nan | (zf > zlc) | ((zf == zlc) & lower)).any(dim=1)
+    stats = th.stack([n_valid, (valid & ~beaten).sum(), bad.sum()]).to(th.int64)
+    return loss, (th.where(valid, m + lsum, zero) if want_lse else None), stats
+
+
+def _softmax_xent_backward_torch(z, labels, lse, stats, grad_loss, ignore_index, reduction):
+    acc = lse.dtype
+    valid, _, lab = _xent_rows(z, labels, ignore_index)
+    gs = grad_loss.to(acc) / stats[0].to(acc) if reduction == "mean" else grad_loss.to(acc)
+    p = th.exp(z.to(acc) - lse[:, None])
+    p = p - th.nn.functional.one_hot(lab, z.shape[1]).to(acc)
+    return th.where(valid[:, None], p * gs, th.zeros((), dtype=acc, device=z.device)).to(z.dtype)
+
+
+class SoftmaxCrossEntropyFunction(th.autograd.Function):
+    """(loss, stats) = softmax cross-entropy of ``logits`` [N, C] against ``labels`` [N] as one autograd node: one HIP launch and a
+    one-wave finish forward, one launch backward where the kernels take the tensors (csrc/softmax_xent.hip), the torch composition
+    of the same rule elsewhere.  Saved for the backward: the logits, the labels, lse [N] and stats -- nothing else of size [N, C];
+    nothing when ``logits`` needs no gradient.  ``stats`` (int64 [3]: valid, correct, bad rows) is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, reduction):
+        z, lab = logits.detach(), labels.detach()
+        if lab.dtype != th.int64:
+            lab = lab.to(th.int64)
+        want = ctx.needs_input_grad[0]
+        ctx.rule = (int(ignore_index), reduction)
+        ctx.native = _k.softmax_xent_ok(z, lab)
+        if ctx.native:
+            if reduction not in _k.XENT_REDUCTIONS:
+                raise HetError(f"SoftmaxCrossEntropyFunction: reduction 'mean' or 'sum', not {reduction!r}")
+            loss, lse, stats = _k._softmax_xent(z, lab, int(ignore_index), reduction, want)
+        else:
+            loss, lse, stats = _softmax_xent_torch(z, lab, int(ignore_index), reduction, want)
+        if want:
+            ctx.save_for_backward(z, lab, lse, stats)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)  # (no zero-filled int64 [3] made and launched per backward for the gradient stats never has)
+        return loss, stats
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        if not ctx.needs_input_grad[0] or grad_loss is None:
+            return None, None, None, None
+        z, lab, lse, stats = ctx.saved_tensors
+        ignore_index, reduction = ctx.rule
+        g = grad_loss.detach().to(device=z.device, dtype=lse.dtype).contiguous()  # (read on the device, never written)
+        if ctx.native:
+            return _k._softmax_xent_backward(z, lab, lse, stats, g, ignore_index, reduction), None, None, None
+        return _softmax_xent_backward_torch(z, lab, lse, stats, g, ignore_index, reduction), None, None, None
+
+
+class SoftmaxCrossEntropy(nn.Module):
+    """Softmax cross-entropy of ``logits`` [N, C] against integer ``labels`` [N] as one pass each way (opt-in): what
+    ``F.cross_entropy(logits, labels, ignore_index=, reduction=)`` computes, with two deliberate differences.
+
+    * A label that is neither ``ignore_index`` nor in [0, C) does not assert on the device: its row is skipped like an ignored one
+      and counted (``last_stats[2]``).  ``check_labels=True`` reads that count back after every call -- the module's only host
+      synchronisation -- and raises ValueError naming it.
+    * The loss is summed in fp64 in a fixed order, without float atomics: the same inputs give the same bits on every call.
+
+    Per valid row, in fp32 (bf16 logits widened first): ``m = max z``, ``lse = m + log(sum(exp(z - m)))``, ``loss_i = lse - z[label]``;
+    ``reduction="mean"`` divides the sum by the number of valid rows, counted on the device (none: NaN, and a gradient of zeros);
+    ``grad[i, c] = (exp(z_c - lse_i) - [c == label_i]) * g * (1 or 1 / valid)`` in the logits' dtype, +0 in skipped rows.
+
+    ``forward`` returns the fp32 scalar loss.  ``last_stats`` is the int64 device tensor (valid rows, rows whose argmax is the label,
+    bad rows) of the last call; ``accuracy()`` is correct / valid as a device tensor.  Ignored labels take the place of indexing the
+    logits with a training / validation subset: no gather, and no index-put into a zero-filled [N, C] in the backward.
+
+    Contiguous, aligned float32 / bfloat16 GPU logits take the HIP kernels; everything else (CPU tensors, fp16 / fp64, non-contiguous
+    or misaligned logits) takes a torch composition of the same rule: correct, not fast.  Labels of another integer type are cast."""
+
+    def __init__(self, ignore_index: int = -100, reduction: str = "mean", check_labels: bool = False):
+        super().__init__()
+        if reduction not in _k.XENT_REDUCTIONS:
+            raise ValueError(f"SoftmaxCrossEntropy: reduction 'mean' or 'sum', not {reduction!r}")
+        self.ignore_index, self.reduction, self.check_labels = int(ignore_index), reduction, bool(check_labels)
+        self.last_stats = None
+
+    def extra_repr(self):
+        return f"ignore_index={self.ignore_index}, reduction={self.reduction!r}, check_labels={self.check_labels}"
+
+    def forward(self, logits, labels):
+        if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or logits.shape[1] < 1:
+            raise ValueError(f"SoftmaxCrossEntropy: logits [N, C] with C >= 1 and labels [N], got {tuple(logits.shape)} and {tuple(labels.shape)}")
+        if labels.is_floating_point() or labels.dtype == th.bool:
+            raise ValueError(f"SoftmaxCrossEntropy: integer class labels, not {labels.dtype}")
+        loss, stats = SoftmaxCrossEntropyFunction.apply(logits, labels, self.ignore_index, self.reduction)
+        self.last_stats = stats
+        if self.check_labels:
+            bad = int(stats[2])
+            if bad:
+                raise ValueError(f"SoftmaxCrossEntropy: {bad} label(s) are neither ignore_index ({self.ignore_index}) nor in "
+                                 f"[0, {logits.shape[1]})")
+        return loss
+
+    def accuracy(self):
+        """correct / valid of the last call, as a device tensor (NaN when no row was valid)."""
+        if self.last_stats is None:
+            raise HetError("SoftmaxCrossEntropy.accuracy(): no call yet")
+        return self.last_stats[1].to(th.float32) / self.last_stats[0].to(th.float32)
+
+
 class HET_RGATLayer(nn.Module):
     """Relational graph attention layer (RGAT/models.py:16-385).
 

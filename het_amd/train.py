@@ -141,6 +141,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                    help="RGAT / RGCN only: every layer ends with one KeyedDropout pass (activation and dropout fused, the mask a pure "
                         "function of (seed, draw, position), nothing stored for the backward; het_amd/layers.py) -- a different sample "
                         "than nn.Dropout's for the same --seed, the same distribution")
+    p.add_argument("--fused_loss", action="store_true",
+                   help="the loss (and the evaluation's) from het_amd.layers.SoftmaxCrossEntropy on the logits as the model returns them: "
+                        "one HIP pass forward, one backward, no log-softmax tensor kept, summed in a fixed order -- instead of the torch "
+                        "expression on logits.float()")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -190,6 +194,10 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
     bf16 = getattr(args, "bf16_training", False)  # (the features enter the model as bf16 rows, the logits leave it as fp32)
     # --sparse_embed (sampled blocks only): the layer hands out the block's rows, in the model's dtype, through one autograd node
     sparse_embed = getattr(args, "sparse_embed", False) and batches is not None
+    loss_fn = None  # --fused_loss: one pass each way over the logits in their own dtype
+    if getattr(args, "fused_loss", False):
+        from .layers import SoftmaxCrossEntropy
+        loss_fn = SoftmaxCrossEntropy()
 
     def one_eval(timed):
         # the evaluation pass of the reference's scripts (model.eval() + torch.no_grad()): same inputs, same event pair around
@@ -215,8 +223,11 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
                 else:
                     logits = run_blocks(model.layers, blocks, node_embed, extra[0] if extra else None)
                 ev[1].record()
-                logits = logits.float()
-                loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
+                if loss_fn is not None:
+                    loss = loss_fn(logits, cur_labels)
+                else:
+                    logits = logits.float()
+                    loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
             th.cuda.synchronize()
         return (ev[0].elapsed_time(ev[1]), 0.0, float(loss)) if timed else None
 
@@ -248,11 +259,14 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
             else:
                 logits = run_blocks(model.layers, blocks, node_embed, extra[0] if extra else None)
             ev[1].record()
-            logits = logits.float()
+            logits = logits if loss_fn is not None else logits.float()
             # = F.nll_loss(logits.log_softmax(dim=-1), labels) (RGNNUtils.py:301-302), written as gather + mean: torch's 2-d
             # nll_loss kernels reduce 1.9 M rows in ONE workgroup on ROCm (4.6 ms forward, 3.0 ms backward on ogbn-mag --
             # more than the layer's own backward inside the protocol's "backward" figure)
-            loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
+            if loss_fn is not None:
+                loss = loss_fn(logits, cur_labels)
+            else:
+                loss = -logits.log_softmax(dim=-1).gather(1, cur_labels.view(-1, 1)).mean()
             ev[2].record()
             loss.backward()
         optimizer.step()  # the reference times the optimizer inside "backward" (RGNNUtils.py:304-311)
@@ -375,6 +389,10 @@ def main(argv=None):
         res["dropout"] = "keyed"
     else:
         del res["args"]["keyed_dropout"]
+    if args.fused_loss:
+        res["loss"] = "fused"
+    else:
+        del res["args"]["fused_loss"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

@@ -1126,6 +1126,47 @@ int het_keyed_dropout_backward_bf16(const het_bf16* grad_out, const het_bf16* ou
 /* the rule's T and scale for a rate p in [0, 1) (HET_ERR_INVALID_ARG otherwise, and for a null pointer) */
 int het_keyed_dropout_params(double p, uint32_t* T, float* scale);
 
+/* ------------------------------------------------------------------------
+ * Softmax cross-entropy over the rows of [n, c] logits with integer labels (csrc/softmax_xent.hip; het_amd/layers.py
+ * SoftmaxCrossEntropy; the reference's scripts call F.cross_entropy / F.nll_loss of torch).  The forward is one launch plus a
+ * one-wave finish, the backward one launch; neither reads anything back to the host.
+ *   logits [n, c] float (or het_bf16, widened first: exact), contiguous; labels [n] int64.
+ *   Row i is VALID when labels[i] != ignore_index and 0 <= labels[i] < c.  Any other row is skipped: it adds nothing to the loss,
+ *   its lse is +0 and its gradient row is +0; a skipped row whose label is not ignore_index is counted as BAD.  No address is formed
+ *   from a label that has not passed this test (torch asserts on the device instead).
+ *   Per valid row, in fp32:  m = max_c z_c;  lse = m + logf(sum_c exp(z_c - m));  loss_i = logf(sum) + (m - z[label]).
+ *     A -inf logit adds 0 to the sum; -inf at the label gives +inf; a row of -inf, or one holding a NaN or +inf, has a NaN lse and loss.
+ *     exp in the two streaming passes is the hardware's exp2 of x * log2(e): relative error about (|x| + 1) * 2^-23, exact at 0.
+ *   correct_i: z[label] is the first of the row's maxima, a NaN ordered above everything (torch.argmax on the CPU).
+ *   loss (fp32 scalar) = sum_i loss_i (HET_XENT_SUM) or that / valid (HET_XENT_MEAN; no valid row: NaN).  Every wave adds its rows
+ *     in fp64 in a fixed order and stores one partial in the workspace, one wave adds the partials in a fixed order: no float
+ *     atomics, the same bits on every call.  stats [3] int64 = (valid, correct, bad), summed the same way (nothing is zero-filled).
+ *   lse [n] float, written for the backward; NULL = not wanted (evaluation).
+ *   grad_logits[i, j] = (exp(z_j - lse_i) - [j == labels[i]]) * g * (1 | 1 / valid), in the logits' type (het_bf16: rounded once,
+ *     to nearest even, at the store); g = *grad_loss and valid = stats[0] are read from DEVICE memory.  Every element of grad_logits
+ *     is written: nothing has to be zero-filled.  Nothing of size [n, c] passes from the forward to the backward but the logits.
+ * Any c >= 1 is served, rows that are not 16-byte aligned (c = 3 floats) included; het_softmax_xent_params gives the launch constants
+ * (out [4] on the host: columns per lane before a row gets another lane, the most lanes a row gets, the most workgroups, threads
+ * per workgroup): a row gets the power-of-two number of lanes G with c <= G * out[0], at most out[1].
+ * Before anything is enqueued: n < 0, c < 1, a null pointer where n > 0, logits / grad_logits off a 16-byte (bf16: 8-byte) boundary,
+ * labels / stats / workspace off an 8-byte one, a workspace smaller than het_softmax_xent_workspace(n, c) bytes and grad_logits
+ * overlapping logits are HET_ERR_INVALID_ARG; a reduction other than the two is HET_ERR_UNSUPPORTED.  n == 0 is HET_OK with no
+ * launch and nothing written: the caller's loss is +0 (sum) / NaN (mean) and its stats are zeros.
+ * ------------------------------------------------------------------------ */
+#define HET_XENT_MEAN 0
+#define HET_XENT_SUM 1
+int64_t het_softmax_xent_workspace(int64_t n, int64_t c); /* bytes; -1 (and het_last_error) for n < 0 or c < 1 */
+int het_softmax_xent(const float* logits, const int64_t* labels, int64_t n, int64_t c, int64_t ignore_index, int reduction, float* loss,
+                     float* lse, int64_t* stats, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_softmax_xent_bf16(const het_bf16* logits, const int64_t* labels, int64_t n, int64_t c, int64_t ignore_index, int reduction,
+                          float* loss, float* lse, int64_t* stats, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_softmax_xent_backward(const float* logits, const int64_t* labels, const float* lse, const int64_t* stats, const float* grad_loss,
+                              int64_t n, int64_t c, int64_t ignore_index, int reduction, float* grad_logits, het_stream stream);
+int het_softmax_xent_backward_bf16(const het_bf16* logits, const int64_t* labels, const float* lse, const int64_t* stats,
+                                   const float* grad_loss, int64_t n, int64_t c, int64_t ignore_index, int reduction,
+                                   het_bf16* grad_logits, het_stream stream);
+int het_softmax_xent_params(int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
