@@ -142,6 +142,15 @@ _ENTRIES = {
     "het_keyed_dropout_bf16": [P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_backward_bf16": [P, P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_params": [DBL, C.POINTER(C.c_uint32), C.POINTER(C.c_float)],
+    "het_triple_corrupt": [P, P, P, I64, I64, I64, I64, P, I64, I64, P, P, P, P],
+    "het_triple_plan_workspace": (I64, [I64, I64, I64]),
+    "het_triple_plan": [P, P, P, I64, I64, I64, P, P, P, P, P, P, P, I64, P],
+    "het_distmult_score": [P, P, P, P, P, I64, I64, I64, I64, P, P],
+    "het_distmult_score_bf16": [P, P, P, P, P, I64, I64, I64, I64, P, P],
+    "het_distmult_score_backward_workspace": (I64, [I64, I64, I64]),
+    "het_distmult_score_backward": [P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, I64, P],
+    "het_distmult_score_backward_bf16": [P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, I64, P],
+    "het_triple_params": [C.POINTER(I64)],
     "het_softmax_xent_workspace": (I64, [I64, I64]),
     "het_softmax_xent": [P, P, I64, I64, I64, INT, P, P, P, P, I64, P],
     "het_softmax_xent_bf16": [P, P, I64, I64, I64, INT, P, P, P, P, I64, P],

@@ -13,6 +13,7 @@ device-side builders (csrc/layouts.hip) on GPU tensors and torch index ops on CP
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from collections import OrderedDict
 from typing import Dict, List, Optional
@@ -1464,6 +1465,180 @@ def _softmax_xent_backward(logits, labels, lse, stats, grad_loss, ignore_index, 
     _call(logits, "het_softmax_xent_backward_bf16" if logits.dtype == torch.bfloat16 else "het_softmax_xent_backward", _p(logits),
           _p(labels), _p(lse), _p(stats), _p(grad_loss), N, C_, int(ignore_index), XENT_REDUCTIONS[reduction], _p(grad), _stream(logits))
     return grad
+
+
+# ---- link prediction on triples: keyed corruption, the plan of a batch, the DistMult score (het_amd/linkpred.py; csrc/triple_score.hip) ----
+_TRIPLE_PARAMS = ("min_width", "max_width", "max_lanes", "list_chunk", "rel_chunk", "max_blocks", "block")
+TriplePlan = collections.namedtuple("TriplePlan", "node_ptr node_slots rel_ptr rel_order chunk_ptr bad num_nodes num_rels")
+
+
+def triple_params() -> Dict[str, int]:
+    """The launch constants of csrc/triple_score.hip (het_triple_params; runs on the host): the widths D served natively are the
+    multiples of 4 from ``min_width`` to ``max_width``; a triple gets the power-of-two number of lanes G with D <= 4 G, at most
+    ``max_lanes``; a node's slot list longer than ``list_chunk`` (L) is summed in chunks of L; grad_w in chunks of ``rel_chunk``."""
+    L = _lib.lib()
+    out = (C.c_int64 * len(_TRIPLE_PARAMS))()
+    rc = L.het_triple_params(out)
+    if rc != 0:
+        raise _lib.HetError(f"het_triple_params failed (code {rc}): {L.het_last_error().decode()}")
+    return dict(zip(_TRIPLE_PARAMS, (int(v) for v in out)))
+
+
+def triple_lanes(D: int) -> int:
+    """Lanes a triple (a node, a chunk) of width ``D`` gets."""
+    p = triple_params()
+    g = 1
+    while g < p["max_lanes"] and 4 * g < D:
+        g *= 2
+    return g
+
+
+def triple_lane_thresholds():
+    """The widths up to which a triple gets 1, 2, 4 ... lanes (4 more columns give it twice as many)."""
+    p = triple_params()
+    out, g = [], 1
+    while g < p["max_lanes"]:
+        out.append(4 * g)
+        g *= 2
+    return tuple(out)
+
+
+def triple_long_list() -> int:
+    """L: a node with more slots than this has its gradient row summed in chunks of L."""
+    return triple_params()["list_chunk"]
+
+
+def triple_width_ok(D: int) -> bool:
+    p = triple_params()
+    return p["min_width"] <= D <= p["max_width"] and D % 4 == 0
+
+
+def distmult_ok(h, w) -> bool:
+    """Whether the DistMult kernels take these tables: h [N, D] contiguous float32 / bfloat16 on a GPU, 16-byte (bf16: 8-byte) aligned,
+    w [R, D] contiguous float32 on the same device, D a width of triple_params(), N and R below 2^31 - 1."""
+    return (h.is_cuda and h.dim() == 2 and w.dim() == 2 and h.dtype in (torch.float32, torch.bfloat16) and w.dtype == torch.float32
+            and w.device == h.device and h.shape[1] == w.shape[1] and h.is_contiguous() and w.is_contiguous()
+            and h.data_ptr() % (4 * h.element_size()) == 0 and w.data_ptr() % 16 == 0 and triple_width_ok(h.shape[1])
+            and h.shape[0] < 2 ** 31 - 1 and w.shape[0] < 2 ** 31 - 1)
+
+
+def _triple_ids_chk(name, like, *ids):
+    n = ids[0].shape[0] if ids[0].dim() == 1 else -1
+    for t in ids:
+        if not (t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == n and t.is_contiguous() and t.data_ptr() % 8 == 0
+                and (like is None or t.device == like.device)):
+            raise _lib.HetError(f"{name}: expected contiguous int64 GPU id tensors of one length on one device, got {t.dtype} {tuple(t.shape)} "
+                                f"on {t.device}")
+    if n >= 2 ** 30:
+        raise _lib.HetError(f"{name}: {n} triples (fewer than 2^30 expected)")
+
+
+def _distmult_chk(name, h, w, s, r, o):
+    if not distmult_ok(h, w):
+        raise _lib.HetError(f"{name}: expected contiguous float32 or bfloat16 GPU rows h [N, D], 16-byte (bf16: 8-byte) aligned, and float32 "
+                            f"w [R, D] on the same device with D a multiple of 4 in the widths of triple_params(), got {h.dtype} "
+                            f"{tuple(h.shape)} on {h.device}{'' if h.is_contiguous() else ' (non-contiguous)'} and {w.dtype} {tuple(w.shape)} "
+                            f"on {w.device}")
+    _triple_ids_chk(name, h, s, r, o)
+
+
+def _key_i64(v: int) -> int:
+    """The 64 bits of a seed or draw number as the signed value the C entries take."""
+    v = int(v) & ((1 << 64) - 1)
+    return v - (1 << 64) if v >> 63 else v
+
+
+def triple_corrupt(src, rel, dst, num_neg: int, seed: int, draw: int, node_type_offsets=None, num_nodes: int = 0):
+    """(s, r, o), each [P * (1 + num_neg)] int64: the positives followed by their keyed corruptions (het_triple_corrupt; the rule in
+    het_amd/linkpred.py).  One launch; ``node_type_offsets``: an int64 tensor on the positives' device, or None."""
+    _triple_ids_chk("triple_corrupt", None, src, rel, dst)
+    num_neg, num_nodes = int(num_neg), int(num_nodes)
+    if num_neg < 0 or not 0 <= num_nodes < 2 ** 31:
+        raise _lib.HetError(f"triple_corrupt: num_neg={num_neg} (at least 0), num_nodes={num_nodes} (below 2^31)")
+    offs, ntypes = None, 0
+    if node_type_offsets is not None:
+        offs = node_type_offsets
+        if not (offs.is_cuda and offs.device == src.device and offs.dtype == torch.int64 and offs.dim() == 1 and offs.numel() >= 2
+                and offs.is_contiguous()):
+            raise _lib.HetError(f"triple_corrupt: node_type_offsets is a contiguous int64 tensor [num_types + 1] on {src.device}, got "
+                                f"{offs.dtype} {tuple(offs.shape)} on {offs.device}")
+        ntypes = offs.numel() - 1
+    P = src.shape[0]
+    T = P * (1 + num_neg)
+    if T >= 2 ** 30:
+        raise _lib.HetError(f"triple_corrupt: {T} triples (fewer than 2^30 expected)")
+    s, r, o = (torch.empty(T, dtype=torch.int64, device=src.device) for _ in range(3))
+    if P:
+        _call(src, "het_triple_corrupt", _p(src), _p(rel), _p(dst), P, num_neg, _key_i64(seed), _key_i64(draw), _p(offs), ntypes, num_nodes,
+              _p(s), _p(r), _p(o), _stream(src))
+    return s, r, o
+
+
+def triple_plan(s, r, o, num_nodes: int, num_rels: int) -> TriplePlan:
+    """The inverted index of a batch of triples (het_triple_plan): per node the ascending slots 2 j + side it owns, per relation its
+    triples in ascending j, the chunk offsets of both and the device count of bad triples.  Nothing is read back."""
+    _triple_ids_chk("triple_plan", None, s, r, o)
+    return _triple_plan(s, r, o, int(num_nodes), int(num_rels))
+
+
+def _triple_plan(s, r, o, N, R):
+    T, dev = s.shape[0], s.device
+    if not (0 <= N < 2 ** 31 - 1 and 0 <= R < 2 ** 31 - 1):
+        raise _lib.HetError(f"triple_plan: num_nodes={N}, num_rels={R} (both below 2^31 - 1)")
+    i64 = dict(dtype=torch.int64, device=dev)
+    if T == 0:  # (no launch: the backward reads no plan)
+        return TriplePlan(torch.zeros(N + 1, **i64), torch.zeros(0, **i64), torch.zeros(R + 1, **i64), torch.zeros(0, **i64),
+                          torch.zeros(N + R + 2, **i64), torch.zeros(1, **i64), N, R)
+    plan = TriplePlan(torch.empty(N + 1, **i64), torch.empty(2 * T, **i64), torch.empty(R + 1, **i64), torch.empty(T, **i64),
+                      torch.empty(N + R + 2, **i64), torch.empty(1, **i64), N, R)
+    ws, nbytes = _workspace(s, "het_triple_plan_workspace", T, N, R)
+    _call(s, "het_triple_plan", _p(s), _p(r), _p(o), T, N, R, _p(plan.node_ptr), _p(plan.node_slots), _p(plan.rel_ptr), _p(plan.rel_order),
+          _p(plan.chunk_ptr), _p(plan.bad), _p(ws), nbytes, _stream(s))
+    return plan
+
+
+def distmult_score(h, w, s, r, o):
+    """score [T] fp32 = sum_d h[s, d] * w[r, d] * h[o, d] (het_distmult_score / _bf16; one launch); +0 for a triple with an id outside
+    its table."""
+    _distmult_chk("distmult_score", h, w, s, r, o)
+    return _distmult_score(h, w, s, r, o)
+
+
+def _distmult_score(h, w, s, r, o):
+    T = s.shape[0]
+    score = torch.empty(T, dtype=torch.float32, device=h.device)
+    if T:
+        _call(h, "het_distmult_score_bf16" if h.dtype == torch.bfloat16 else "het_distmult_score", _p(h), _p(w), _p(s), _p(r), _p(o), T,
+              h.shape[0], w.shape[0], h.shape[1], _p(score), _stream(h))
+    return score
+
+
+def distmult_score_backward(h, w, s, r, o, grad_score, plan: TriplePlan, want_h: bool = True, want_w: bool = True):
+    """(grad_h [N, D] in h's dtype or None, grad_w [R, D] fp32 or None) of het_distmult_score_backward / _bf16 for ``grad_score`` [T] fp32
+    and the batch's ``plan`` (triple_plan): node-major and relation-major sums in a fixed order, every row written once."""
+    _distmult_chk("distmult_score_backward", h, w, s, r, o)
+    _chk("distmult_score_backward", (grad_score,), tuple(plan[:6]))
+    T, N, R = s.shape[0], h.shape[0], w.shape[0]
+    if (grad_score.shape != (T,) or grad_score.device != h.device or (plan.num_nodes, plan.num_rels) != (N, R)
+            or plan.node_ptr.shape != (N + 1,) or plan.node_slots.shape != (2 * T,) or plan.rel_ptr.shape != (R + 1,)
+            or plan.rel_order.shape != (T,) or plan.chunk_ptr.shape != (N + R + 2,) or any(t.device != h.device for t in plan[:6])):
+        raise _lib.HetError(f"distmult_score_backward: grad_score [{T}] and the plan of these {T} triples over {N} nodes and {R} relations on "
+                            f"{h.device} expected, got {tuple(grad_score.shape)} and a plan for {plan.num_nodes} nodes, {plan.num_rels} "
+                            f"relations, {plan.rel_order.shape[0]} triples")
+    return _distmult_score_backward(h, w, s, r, o, grad_score, plan, want_h, want_w)
+
+
+def _distmult_score_backward(h, w, s, r, o, grad_score, plan, want_h, want_w):
+    T, (N, D), R = s.shape[0], h.shape, w.shape[0]
+    grad_h = torch.empty_like(h) if want_h else None
+    grad_w = torch.empty_like(w) if want_w else None
+    if not (want_h or want_w):
+        return None, None
+    ws, nbytes = _workspace(h, "het_distmult_score_backward_workspace", T, R, D)
+    _call(h, "het_distmult_score_backward_bf16" if h.dtype == torch.bfloat16 else "het_distmult_score_backward", _p(h), _p(w), _p(s), _p(r),
+          _p(o), _p(grad_score), _p(plan.node_ptr), _p(plan.node_slots), _p(plan.rel_ptr), _p(plan.rel_order), _p(plan.chunk_ptr), T, N, R, D,
+          _p(grad_h), _p(grad_w), _p(ws), nbytes, _stream(h))
+    return grad_h, grad_w
 
 
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,

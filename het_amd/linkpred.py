@@ -1,0 +1,253 @@
+"""Link prediction with a DistMult head and keyed negatives (opt-in; csrc/triple_score.hip).
+
+The rule.  All key arithmetic is uint64, wrapping; ``sm`` and the stream are those of the keyed sampler and keyed dropout
+(DESIGN.md 4.10): ``stream = sm(seed ^ sm(draw))``.
+
+Triples.  A batch has P positives ``(src_i, rel_i, dst_i)`` and K >= 0 negatives per positive: T = P (1 + K) triples
+``(s_j, r_j, o_j)``.  ``j < P`` is positive j; ``j = P + m`` with ``m = i K + k`` is the k-th corruption of positive i.  The label is 1
+for ``j < P`` and 0 otherwise: it is the position, there is no label tensor.
+
+Keyed corruption (unfiltered)::
+
+    key   = sm(stream + m)
+    side  = key >> 63                     0: replace the tail o, 1: replace the head s
+    u     = (key >> 31) & 0xFFFFFFFF
+    v_old = dst_i if side == 0 else src_i
+    [lo, hi) = the run of node_type_offsets that contains v_old   ([0, N) when no offsets are given)
+    v_new = lo + ((u * (hi - lo)) >> 32)
+    r_j   = rel_i
+
+The replaced end keeps its node type.  N < 2^31, so the product stays below 2^63.  **Unfiltered: v_new == v_old and collisions with
+true edges are allowed** -- a different sample than any filtered or torch.randint sampler's for the same seed.  A node of a run of
+``hi - lo`` nodes is drawn with a probability that differs from uniform by less than ``(hi - lo) / 2^32``.  An end that lies in no
+run (outside [0, N)) is copied as it is.
+
+Score.  ``score_j = sum_d h[s_j, d] * w[r_j, d] * h[o_j, d]`` in fp32; h is [N, D] fp32, or bf16 widened exactly on load; w is [R, D]
+fp32; score is [T] fp32.
+
+Gradients for ``g = grad_score`` ([T] fp32), all sums fp32 on widened values:
+
+* ``grad_h[v] = sum_{j: s_j = v} g_j w[r_j] (.) h[o_j] + sum_{j: o_j = v} g_j w[r_j] (.) h[s_j]``; a triple with ``s_j == o_j == v``
+  contributes both terms.  Each node's list is summed in ascending slot ``2 j + side`` (side 0: v is the head s_j, side 1: the tail
+  o_j); a list longer than L slots (``kernels.triple_long_list()``) is cut into chunks of L from its start, the chunks are summed
+  separately and their sums are added in chunk order.  A row without triples is +0.  Every row is written exactly once.  A bf16 h
+  gives a bf16 grad_h, rounded once to nearest even after the whole sum.
+* ``grad_w[r] = sum_{j: r_j = r} g_j h[s_j] (.) h[o_j]``, in ascending j within chunks of ``triple_params()["rel_chunk"]`` triples
+  of the relation's list, then the chunk sums in chunk order.  A relation without triples is +0.  Always fp32.
+
+Ids outside the tables.  A triple with s or o outside [0, N) or r outside [0, R) is **counted, not asserted** (the rule of
+SoftmaxCrossEntropy): its score is +0, it contributes to no gradient, the count lands in an int64 on the device
+(``DistMultDecoder.last_bad``) and no kernel reads a table through such an id.
+
+Loss.  The head returns scores; the loss over [T] floats stays a torch expression (``link_prediction_loss``: BCE-with-logits
+against the implicit labels).  T floats are nothing beside the 2 T D gathered ones, and a score op serves any loss -- a margin, a
+softmax over each positive's negatives.
+
+No float atomics anywhere: the same inputs give the same bits on every call, and the autograd node keeps nothing of T D elements.
+"""
+from __future__ import annotations
+
+import torch as th
+import torch.nn as nn
+
+from . import kernels as _k
+from ._lib import HetError
+from .layers import _M64, _i64, _lsr, _sm_tensor
+
+
+def _stream(seed: int, draw: int) -> int:
+    from .sampling import _sm_int
+    return _sm_int((int(seed) & _M64) ^ _sm_int(int(draw) & _M64))
+
+
+def _keyed_corruptions_torch(src, rel, dst, K, seed, draw, offs, N):
+    """The rule in torch int64 arithmetic on any device: the bits het_triple_corrupt gives."""
+    P = src.shape[0]
+    m = th.arange(P * K, dtype=th.int64, device=src.device)
+    key = _sm_tensor(m + _i64(_stream(seed, draw)))
+    head = _lsr(key, 63) == 1
+    u = _lsr(key, 31) & 0xFFFFFFFF
+    i = th.div(m, max(K, 1), rounding_mode="floor")
+    si, ri, oi = src[i], rel[i], dst[i]
+    v_old = th.where(head, si, oi)
+    if offs is None:
+        inside = (v_old >= 0) & (v_old < N)
+        lo, span = th.zeros_like(v_old), th.full_like(v_old, N)
+    else:
+        inside = (v_old >= offs[0]) & (v_old < offs[-1])
+        ty = (th.searchsorted(offs[:-1].contiguous(), v_old, right=True) - 1).clamp_(0, offs.numel() - 2)
+        lo = offs[ty]
+        span = offs[ty + 1] - lo
+    v_new = th.where(inside, lo + ((u * span) >> 32), v_old)
+    return (th.cat([src, th.where(head, v_new, si)]), th.cat([rel, ri]), th.cat([dst, th.where(head, oi, v_new)]))
+
+
+def keyed_corruptions(src, rel, dst, num_neg: int, *, seed: int, draw: int, node_type_offsets=None, num_nodes: int):
+    """(s, r, o), each [P (1 + num_neg)] int64: the P positives followed by ``num_neg`` keyed corruptions of each (the module's rule;
+    **unfiltered: a corruption may equal its positive or another true edge**).  One HIP launch on CUDA tensors; on the CPU, or
+    where the library is absent, a torch implementation gives the same bits."""
+    num_neg, num_nodes = int(num_neg), int(num_nodes)
+    if num_neg < 0:
+        raise ValueError(f"keyed_corruptions: num_neg={num_neg} (at least 0)")
+    if not 0 <= num_nodes < 2 ** 31:
+        raise ValueError(f"keyed_corruptions: num_nodes={num_nodes} (0 <= num_nodes < 2^31)")
+    if not (src.dim() == rel.dim() == dst.dim() == 1 and src.shape == rel.shape == dst.shape):
+        raise ValueError(f"keyed_corruptions: src, rel and dst are 1-d tensors of one length, got {tuple(src.shape)}, {tuple(rel.shape)}, "
+                         f"{tuple(dst.shape)}")
+    src, rel, dst = (t.detach().to(th.int64).contiguous() for t in (src, rel, dst))
+    offs = None
+    if node_type_offsets is not None:
+        offs = th.as_tensor(node_type_offsets).detach().to(device=src.device, dtype=th.int64).contiguous()
+        if offs.dim() != 1 or offs.numel() < 2:
+            raise ValueError(f"keyed_corruptions: node_type_offsets [num_types + 1], got {tuple(offs.shape)}")
+    if src.shape[0] * (1 + num_neg) >= 2 ** 30:
+        raise ValueError(f"keyed_corruptions: {src.shape[0]} positives with {num_neg} negatives each are 2^30 triples or more")
+    if src.is_cuda and _native_available():
+        return _k.triple_corrupt(src, rel, dst, num_neg, seed, draw, offs, num_nodes)
+    return _keyed_corruptions_torch(src, rel, dst, num_neg, seed, draw, offs, num_nodes)
+
+
+def _native_available() -> bool:
+    try:
+        from . import _lib
+        _lib.lib()
+        return True
+    except HetError:
+        return False
+
+
+def keyed_positive_edges(g, batch_size: int, *, seed: int, draw: int):
+    """(src, rel, dst), each [batch_size] int64: edges of ``g`` drawn with replacement from its separate COO (relation-major), position
+    ``e_i = (((sm(stream + i) >> 31) & 0xFFFFFFFF) * E) >> 32`` with the stream of (seed, draw); E < 2^31.  Torch only: P elements."""
+    coo = g.get_separate_coo_original()
+    rel_ptrs, row, col = coo["rel_ptrs"], coo["row_indices"], coo["col_indices"]
+    E = int(row.shape[0])
+    if not 0 < E < 2 ** 31:
+        raise ValueError(f"keyed_positive_edges: a graph of {E} edges (0 < E < 2^31)")
+    i = th.arange(int(batch_size), dtype=th.int64, device=row.device)
+    key = _sm_tensor(i + _i64(_stream(seed, draw)))
+    e = ((_lsr(key, 31) & 0xFFFFFFFF) * E) >> 32
+    rel = th.searchsorted(rel_ptrs.to(row.device).contiguous(), e, right=True) - 1
+    return row[e], rel, col[e]
+
+
+def _count_bad(s, r, o, N, R):
+    return (((s < 0) | (s >= N) | (o < 0) | (o >= N) | (r < 0) | (r >= R)).sum()).reshape(1)
+
+
+def distmult_score_torch(h, w, s, r, o):
+    """(score [T] fp32 (fp64 for fp64 tables), bad [1] int64) of the module's rule as a differentiable torch composition: correct, not
+    fast -- three [T, D] gathers, two [T, D] products kept for the backward, an index_add_ in it."""
+    N, R = h.shape[0], w.shape[0]
+    ok = (s >= 0) & (s < N) & (o >= 0) & (o < N) & (r >= 0) & (r < R)
+    zero = th.zeros_like(s)
+    acc = th.float64 if h.dtype == th.float64 else th.float32
+    hf = h.to(acc)  # (widened before the gathers: the backward's index_add_ then sums in fp32 and a bf16 grad_h is rounded once)
+    hs, ho, wr = hf[th.where(ok, s, zero)], hf[th.where(ok, o, zero)], w[th.where(ok, r, zero)].to(acc)
+    score = (hs * wr * ho).sum(-1)
+    return th.where(ok, score, th.zeros((), dtype=acc, device=h.device)), (~ok).sum().reshape(1)
+
+
+def _aligned_rows(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=th.contiguous_format)
+
+
+class DistMultScoreFunction(th.autograd.Function):
+    """(score, bad) = the DistMult scores of the triples (s, r, o) over the rows ``h`` and the relation vectors ``w`` as one autograd
+    node on the HIP kernels: one launch forward; the plan of the batch (sorts and searches on the device, no read-back) is built in the
+    forward only when a gradient is needed; the backward is node-major and relation-major, without float atomics.  Saved for the
+    backward: h, w, the ids and the plan -- nothing of T D elements.  ``bad`` (int64 [1]) is not differentiable.  Tensors the kernels
+    do not take raise HetError (DistMultDecoder routes those to the torch composition).  A double backward is refused:
+    the backward is once_differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, w, s, r, o):
+        hd, wd = _aligned_rows(h.detach()), _aligned_rows(w.detach())  # (a strided or misaligned table: the kernels run on a copy)
+        ids = tuple(t.detach().to(th.int64).contiguous() for t in (s, r, o))
+        _k._distmult_chk("DistMultScoreFunction", hd, wd, *ids)
+        want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        score = _k._distmult_score(hd, wd, *ids)
+        if want_h or want_w:
+            plan = _k._triple_plan(*ids, hd.shape[0], wd.shape[0])
+            bad = plan.bad
+            ctx.ids, ctx.plan = ids, plan  # (index tensors: nothing autograd tracks, and nothing an inference-mode id would break)
+            ctx.save_for_backward(hd, wd)
+        else:
+            bad = _count_bad(*ids, hd.shape[0], wd.shape[0])
+        ctx.mark_non_differentiable(bad)
+        ctx.set_materialize_grads(False)
+        return score, bad
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad_score, _grad_bad):
+        want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_score is None or not (want_h or want_w):
+            return None, None, None, None, None
+        hd, wd = ctx.saved_tensors
+        g = grad_score.detach().to(device=hd.device, dtype=th.float32).contiguous()
+        grad_h, grad_w = _k._distmult_score_backward(hd, wd, *ctx.ids, g, ctx.plan, want_h, want_w)
+        return grad_h, grad_w, None, None, None
+
+
+class DistMultDecoder(nn.Module):
+    """The DistMult head: ``forward(h, s, r, o)`` returns the [T] fp32 scores of the triples over the node rows ``h`` [N, dim] and the
+    module's ``w_relation`` [num_rels, dim] (fp32, xavier-uniform).  Labels are implicit in the position (the module docstring);
+    ``link_prediction_loss`` is the usual loss, any other expression of the scores works as well.
+
+    A triple with an id outside its table is **counted, not asserted**: its score is +0 and it gets no gradient.  ``last_bad`` holds
+    the count of the last call as an int64 [1] device tensor; ``check_ids=True`` reads it back after every call -- the module's only
+    host synchronisation -- and raises ValueError on a non-zero count.
+
+    Contiguous or strided float32 / bfloat16 GPU rows of a native width (``kernels.distmult_ok``) take the HIP kernels
+    (DistMultScoreFunction); everything else -- CPU tensors, fp16 / fp64, a ``dim`` that is no multiple of 4 -- and every call of a
+    module built with ``native=False`` (an ``h`` that needs a double backward) takes the torch composition of the same rule: correct, not
+    faster."""
+
+    def __init__(self, num_rels: int, dim: int, check_ids: bool = False, native: bool = True):
+        super().__init__()
+        self.num_rels, self.dim, self.check_ids, self.native = int(num_rels), int(dim), bool(check_ids), bool(native)
+        self.w_relation = nn.Parameter(th.empty(self.num_rels, self.dim, dtype=th.float32))
+        nn.init.xavier_uniform_(self.w_relation)
+        self.last_bad = None
+
+    def extra_repr(self):
+        return f"num_rels={self.num_rels}, dim={self.dim}, check_ids={self.check_ids}, native={self.native}"
+
+    def takes_native(self, h) -> bool:
+        """Whether a call with these rows runs the HIP kernels."""
+        w = self.w_relation
+        return (self.native and h.is_cuda and w.device == h.device and h.dim() == 2 and h.dtype in (th.float32, th.bfloat16)
+                and w.dtype == th.float32 and _k.triple_width_ok(h.shape[1]) and h.shape[0] < 2 ** 31 - 1 and _native_available())
+
+    def forward(self, h, s, r, o):
+        if h.dim() != 2 or h.shape[1] != self.dim:
+            raise ValueError(f"DistMultDecoder: h [N, {self.dim}], got {tuple(h.shape)}")
+        if not (s.dim() == r.dim() == o.dim() == 1 and s.shape == r.shape == o.shape):
+            raise ValueError(f"DistMultDecoder: s, r and o are 1-d id tensors of one length, got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(o.shape)}")
+        if any(t.is_floating_point() or t.dtype == th.bool for t in (s, r, o)):
+            raise ValueError("DistMultDecoder: integer ids expected")
+        if s.shape[0] >= 2 ** 30:
+            raise ValueError(f"DistMultDecoder: {s.shape[0]} triples (fewer than 2^30)")
+        if self.takes_native(h):
+            score, bad = DistMultScoreFunction.apply(h, self.w_relation, s, r, o)
+        else:
+            score, bad = distmult_score_torch(h, self.w_relation, *(t.to(th.int64) for t in (s, r, o)))
+            score = score.to(th.float32)
+        self.last_bad = bad.detach()
+        if self.check_ids:
+            n_bad = int(bad)
+            if n_bad:
+                raise ValueError(f"DistMultDecoder: {n_bad} triple(s) have an id outside [0, {h.shape[0]}) nodes or [0, {self.num_rels}) relations")
+        return score
+
+
+def link_prediction_loss(scores, num_pos: int):
+    """Mean binary cross-entropy with logits of ``scores`` [T] against the implicit labels: 1 for the first ``num_pos``, 0 after."""
+    num_pos = int(num_pos)
+    if scores.dim() != 1 or not 0 <= num_pos <= scores.shape[0]:
+        raise ValueError(f"link_prediction_loss: scores [T] and 0 <= num_pos <= T, got {tuple(scores.shape)} and {num_pos}")
+    labels = th.zeros_like(scores)
+    labels[:num_pos] = 1.0
+    return nn.functional.binary_cross_entropy_with_logits(scores, labels)

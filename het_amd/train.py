@@ -145,6 +145,11 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                    help="the loss (and the evaluation's) from het_amd.layers.SoftmaxCrossEntropy on the logits as the model returns them: "
                         "one HIP pass forward, one backward, no log-softmax tensor kept, summed in a fixed order -- instead of the torch "
                         "expression on logits.float()")
+    p.add_argument("--link_prediction", action="store_true",
+                   help="full-graph encoder only: train for link prediction instead of node classification -- a DistMult head on the "
+                        "encoder's output, --batch_size positive edges per step drawn by key from the graph, --num_negatives keyed "
+                        "corruptions of each, BCE-with-logits (het_amd/linkpred.py); unfiltered negatives: a corruption may be a true edge")
+    p.add_argument("--num_negatives", type=int, default=1, help="--link_prediction: keyed corruptions per positive edge")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -288,6 +293,52 @@ def HET_RGNN_train(g, model, node_embed_layer, optimizer, labels, args, extra=()
     return fwd, bwd, losses
 
 
+def HET_linkpred_train(g, model, node_embed_layer, decoder, optimizer, args, extra=()):
+    """--link_prediction: the full-graph encoder followed by a DistMult head (het_amd/linkpred.py).  Per step: h = model(g, embed()),
+    --batch_size positive edges and --num_negatives corruptions of each, keyed by (--seed, draw = 2 step and 2 step + 1), scores,
+    BCE-with-logits, backward, optimizer.  The event pairs are those of HET_RGNN_train: "forward" is the encoder; the batch, the
+    decoder and the loss count inside "backward", with the optimizer."""
+    from .linkpred import keyed_corruptions, keyed_positive_edges, link_prediction_loss
+    N = g.get_num_nodes()
+    offsets = g.get_original_node_type_offsets()
+    offsets = None if offsets is None or offsets.numel() <= 2 else offsets
+    steps = [0]
+
+    def one_step(timed):
+        step = steps[0]
+        steps[0] += 1
+        optimizer.zero_grad()
+        node_embed = node_embed_layer()
+        th.cuda.synchronize()
+        ev = [th.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        h = model(g, node_embed, *extra)
+        ev[1].record()
+        ev[2].record()
+        src, rel, dst = keyed_positive_edges(g, args.batch_size, seed=args.seed, draw=2 * step)
+        s, r, o = keyed_corruptions(src, rel, dst, args.num_negatives, seed=args.seed, draw=2 * step + 1, node_type_offsets=offsets,
+                                    num_nodes=N)
+        loss = link_prediction_loss(decoder(h, s, r, o), args.batch_size)
+        loss.backward()
+        optimizer.step()
+        ev[3].record()
+        th.cuda.synchronize()
+        return (ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3]), float(loss.detach())) if timed else None
+
+    model.train(True)
+    node_embed_layer.train(True)
+    decoder.train(True)
+    if not args.no_warm_up:
+        for _ in range(5):
+            one_step(False)
+    fwd, bwd, losses = [], [], []
+    for epoch in range(args.n_epochs):
+        f, b, l = one_step(True)
+        fwd.append(f); bwd.append(b); losses.append(l)
+        print(f"Epoch {epoch:02d} | forward {f:.3f} ms | backward {b:.3f} ms | loss {l:.4f}")
+    return fwd, bwd, losses
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="HET RGAT / RGCN / HGT benchmark driver on het_amd (MI355X)")
     add_generic_RGNN_args(p, "het_amd_train.json")
@@ -305,6 +356,12 @@ def main(argv=None):
         raise SystemExit("--sparse_embed is an option of training: --inference takes no optimizer step")
     if args.keyed_sampler and args.full_graph_training:
         raise SystemExit("--keyed_sampler is an option of the sampled mini-batch path: --full_graph_training samples nothing")
+    if args.link_prediction and not args.full_graph_training:
+        raise SystemExit("--link_prediction runs the full-graph encoder: add --full_graph_training (edge-seeded sampled blocks are not built)")
+    if args.link_prediction and args.inference:
+        raise SystemExit("--link_prediction is an option of training: --inference scores no triples")
+    if args.link_prediction and args.num_negatives < 0:
+        raise SystemExit("--num_negatives is at least 0")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -338,6 +395,11 @@ def main(argv=None):
     model = model.to(dev)
     labels = th.randint(0, args.num_classes, (N,), device=dev)  # random labels as train_dgl.py:132-148
     params = list(model.parameters()) + ([] if args.sparse_embed else list(embed.parameters()))
+    decoder = None
+    if args.link_prediction:  # the head scores the encoder's output rows: their width is --num_classes
+        from .linkpred import DistMultDecoder
+        decoder = DistMultDecoder(R, args.num_classes).to(dev)
+        params += list(decoder.parameters())
     try:  # one kernel per step over all parameters (the [N, in] embedding table dominates); same update rule
         optimizer = th.optim.Adam(params, lr=args.lr, fused=True)
     except (RuntimeError, TypeError):
@@ -360,7 +422,11 @@ def main(argv=None):
             seeds = th.randperm(N, device=dev, generator=gen)[: args.batch_size]
             blocks = sampler.sample_blocks(seeds)
             return blocks, blocks[-1].nodes[: blocks[-1].num_dst]  # the seeds in block order (by node type for HGT)
-    fwd, bwd, losses = HET_RGNN_train(g, model, embed, optimizer, labels, args, extra, batches)
+    if args.link_prediction:
+        HET_RGNN_train.last_prep_ms = []
+        fwd, bwd, losses = HET_linkpred_train(g, model, embed, decoder, optimizer, args, extra)
+    else:
+        fwd, bwd, losses = HET_RGNN_train(g, model, embed, optimizer, labels, args, extra, batches)
     res = {"model": args.model, "dataset": args.edges_npy or args.dataset, "num_nodes": N, "num_edges": E, "num_rels": R,
            "mean_forward_ms": round(aggregate_times(fwd), 4), "mean_backward_ms": round(aggregate_times(bwd), 4),
            "layout_build_ms": round(layout_ms, 1), "final_loss": losses[-1] if losses else None,
@@ -393,6 +459,11 @@ def main(argv=None):
         res["loss"] = "fused"
     else:
         del res["args"]["fused_loss"]
+    if args.link_prediction:
+        res["task"] = "link_prediction"
+    else:
+        del res["args"]["link_prediction"]
+        del res["args"]["num_negatives"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

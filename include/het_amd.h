@@ -1127,6 +1127,62 @@ int het_keyed_dropout_backward_bf16(const het_bf16* grad_out, const het_bf16* ou
 int het_keyed_dropout_params(double p, uint32_t* T, float* scale);
 
 /* ------------------------------------------------------------------------
+ * Link prediction on triples (csrc/triple_score.hip; het_amd/linkpred.py): keyed corruption of positive edges, the
+ * inverted index ("plan") of a batch of triples, the DistMult score and its backward.  No entry reads anything back to the host or
+ * waits for the stream; no float is added by more than one writer: the same bits on every call.
+ *   Triples: p positives (src_i, rel_i, dst_i) and k >= 0 corruptions of each: t = p * (1 + k) triples (s_j, r_j, o_j); j < p is
+ *   positive j, j = p + m with m = i * k + c is corruption c of positive i.  The label (1 for j < p, else 0) is the position.
+ *   het_triple_corrupt (one launch, reads no table), all key arithmetic in wrapping uint64, sm as for the keyed sampler:
+ *     stream = sm(seed ^ sm(draw));  key = sm(stream + m);  side = key >> 63 (0: the tail o is replaced, 1: the head s);
+ *     u = (key >> 31) & 0xFFFFFFFF;  v_old = side ? src_i : dst_i;  [lo, hi) = the run of node_type_offsets [num_types + 1] (DEVICE
+ *     memory; NULL: [0, num_nodes)) that holds v_old;  v_new = lo + ((u * (hi - lo)) >> 32);  r_j = rel_i.
+ *     Unfiltered: v_new == v_old and true edges may be drawn.  An end that lies in no run is copied as it is.
+ *   A triple with s or o outside [0, num_nodes) or r outside [0, num_rels) is BAD: counted, its score is +0, it is in no list of the
+ *   plan and in no gradient, and no address is formed from its ids.
+ *   het_triple_plan: node_ptr [num_nodes + 1], node_slots [2 t] (slot 2 j + side: side 0 is the head s_j, side 1 the tail o_j; ascending
+ *     inside a node), rel_ptr [num_rels + 1], rel_order [t] (ascending j inside a relation), chunk_ptr [num_nodes + num_rels + 2] (the
+ *     exclusive sums of the chunk counts of the nodes' and then the relations' lists) and bad [1], all int64 on the device; the
+ *     workspace holds het_triple_plan_workspace bytes.  num_nodes and num_rels below 2^31 - 1, t below 2^30.
+ *   score_j = sum_d h[s_j, d] * w[r_j, d] * h[o_j, d] in fp32: h [num_nodes, dim] float (or het_bf16, widened first: exact), w
+ *     [num_rels, dim] float, score [t] float.  One launch.
+ *   het_distmult_score_backward, for grad_score [t]:
+ *     grad_h[v] = sum over v's slots, ascending, of grad_score_j * w[r_j] (.) h[the other end of j] (a triple with s_j == o_j == v has
+ *       two slots); a list longer than L = params[3] slots is summed in chunks of L from its start and the chunk sums are added in
+ *       chunk order.  In h's type (het_bf16: rounded once, to nearest even, after the whole sum).
+ *     grad_w[r] = sum over r's triples, ascending j in chunks of params[4], of grad_score_j * (h[s_j] (.) h[o_j]); chunk sums in chunk order.
+ *     Every row of both is written exactly once, +0 where a list is empty: nothing has to be zero-filled.  grad_h or grad_w NULL: that
+ *     gradient is not wanted and its launches are left out.  With t == 0 both are still written (+0) and no plan is read.
+ * het_triple_params (out [7] on the host): the least and the greatest dim served (a multiple of 4 between them), the most lanes a
+ * triple gets (the power of two G with dim <= 4 * G, at most out[2]), L, the grad_w chunk, the most workgroups, threads per workgroup.
+ * Before anything is enqueued: negative counts, dim < 1, a null pointer where the count is positive, a misaligned pointer (h / grad_h
+ * on 16-byte (bf16: 8-byte), w / grad_w / workspace on 16-byte, int64 arrays on 8-byte, score / grad_score on 4-byte boundaries), a
+ * workspace smaller than its query says and grad_h overlapping h are HET_ERR_INVALID_ARG; a dim the kernels do not take is
+ * HET_ERR_UNSUPPORTED.  t == 0 (p == 0) is HET_OK with no launch, but for the backward (above).
+ * ------------------------------------------------------------------------ */
+int het_triple_corrupt(const int64_t* src, const int64_t* rel, const int64_t* dst, int64_t num_pos, int64_t num_neg, int64_t seed,
+                       int64_t draw, const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t* s, int64_t* r,
+                       int64_t* o, het_stream stream);
+int64_t het_triple_plan_workspace(int64_t num_triples, int64_t num_nodes, int64_t num_rels); /* bytes; -1 (and het_last_error) on bad sizes */
+int het_triple_plan(const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples, int64_t num_nodes, int64_t num_rels,
+                    int64_t* node_ptr, int64_t* node_slots, int64_t* rel_ptr, int64_t* rel_order, int64_t* chunk_ptr, int64_t* bad,
+                    void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_distmult_score(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                       int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream);
+int het_distmult_score_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                            int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream);
+int64_t het_distmult_score_backward_workspace(int64_t num_triples, int64_t num_rels, int64_t dim); /* bytes; -1 on bad sizes */
+int het_distmult_score_backward(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                                const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
+                                const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes, int64_t num_rels,
+                                int64_t dim, float* grad_h, float* grad_w, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_distmult_score_backward_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                                     const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
+                                     const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes,
+                                     int64_t num_rels, int64_t dim, het_bf16* grad_h, float* grad_w, void* workspace,
+                                     int64_t workspace_bytes, het_stream stream);
+int het_triple_params(int64_t* out);
+
+/* ------------------------------------------------------------------------
  * Softmax cross-entropy over the rows of [n, c] logits with integer labels (csrc/softmax_xent.hip; het_amd/layers.py
  * SoftmaxCrossEntropy; the reference's scripts call F.cross_entropy / F.nll_loss of torch).  The forward is one launch plus a
  * one-wave finish, the backward one launch; neither reads anything back to the host.
