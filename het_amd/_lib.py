@@ -137,6 +137,10 @@ _ENTRIES = {
     "het_sample_select": [P, P, I64, I64, I64, I64, I64, P, I64, P, P, P],
     "het_block_renumber": [P, I64, P, I64, P, I64, P, I64, P, P, P, P],
     "het_block_relation_major": [P, P, I64, P, P, P, I64, I64, P, P, P, P, P, P],
+    "het_triple_rank_workspace": (I64, [I64, I64, I64, I64]),
+    "het_triple_rank": [P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],
+    "het_triple_rank_bf16": [P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],
+    "het_triple_rank_params": [C.POINTER(I64)],
     "het_keyed_dropout": [P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_backward": [P, P, P, I64, I64, INT, DBL, I64, I64, P],
     "het_keyed_dropout_bf16": [P, P, I64, I64, INT, DBL, I64, I64, P],

@@ -1641,6 +1641,70 @@ def _distmult_score_backward(h, w, s, r, o, grad_score, plan, want_h, want_w):
     return grad_h, grad_w
 
 
+# ---- filtered ranking of link-prediction queries (het_amd/linkpred.py distmult_rank; csrc/triple_rank.hip) ----
+_TRIPLE_RANK_PARAMS = ("query_tile", "cand_tile", "min_width", "max_width", "block", "max_blocks", "chunk_tiles", "max_span")
+
+
+def triple_rank_params() -> Dict[str, int]:
+    """The launch constants of csrc/triple_rank.hip (het_triple_rank_params; runs on the host): a workgroup multiplies tiles of
+    ``query_tile`` queries by ``cand_tile`` candidates; the widths D served are the multiples of 4 from ``min_width`` to ``max_width``;
+    ``block`` threads per workgroup, at most ``max_blocks`` workgroups; a workgroup keeps the counters of ``chunk_tiles`` query tiles
+    and takes at most ``max_span`` candidate tiles per work item."""
+    L = _lib.lib()
+    out = (C.c_int64 * len(_TRIPLE_RANK_PARAMS))()
+    rc = L.het_triple_rank_params(out)
+    if rc != 0:
+        raise _lib.HetError(f"het_triple_rank_params failed (code {rc}): {L.het_last_error().decode()}")
+    return dict(zip(_TRIPLE_RANK_PARAMS, (int(v) for v in out)))
+
+
+def triple_rank_ok(h, w) -> bool:
+    """Whether het_triple_rank takes these tables: h [N, D] contiguous float32 / bfloat16 on a GPU, 16-byte (bf16: 8-byte) aligned, w
+    [R, D] contiguous float32 on the same device, D a width of triple_rank_params(), N and R below 2^31 - 1."""
+    p = triple_rank_params()
+    return (h.is_cuda and h.dim() == 2 and w.dim() == 2 and h.dtype in (torch.float32, torch.bfloat16) and w.dtype == torch.float32
+            and w.device == h.device and h.shape[1] == w.shape[1] and h.is_contiguous() and w.is_contiguous()
+            and h.data_ptr() % (4 * h.element_size()) == 0 and w.data_ptr() % 16 == 0
+            and p["min_width"] <= h.shape[1] <= p["max_width"] and h.shape[1] % 4 == 0
+            and h.shape[0] < 2 ** 31 - 1 and w.shape[0] < 2 ** 31 - 1)
+
+
+def triple_rank(h, w, anchor, rel, truth, pair_query=None, pair_cand=None, node_type_offsets=None):
+    """(greater, equal, cands) int32 [Q] and bad int64 [1] of het_triple_rank / _bf16: every query (anchor, rel, truth) ranked against
+    the nodes of its true node's run with the DistMult score (the rule in include/het_amd.h), the listed (pair_query, pair_cand) pairs
+    and the true node excluded.  ``node_type_offsets``: an int64 tensor on h's device, or None.  Nothing is read back."""
+    if not triple_rank_ok(h, w):
+        raise _lib.HetError(f"triple_rank: expected contiguous float32 or bfloat16 GPU rows h [N, D], 16-byte (bf16: 8-byte) aligned, and "
+                            f"float32 w [R, D] on the same device with D a multiple of 4 in the widths of triple_rank_params(), got {h.dtype} "
+                            f"{tuple(h.shape)} on {h.device}{'' if h.is_contiguous() else ' (non-contiguous)'} and {w.dtype} "
+                            f"{tuple(w.shape)} on {w.device}")
+    _triple_ids_chk("triple_rank", h, anchor, rel, truth)
+    if (pair_query is None) != (pair_cand is None):
+        raise _lib.HetError("triple_rank: pair_query and pair_cand come together")
+    NP = 0
+    if pair_query is not None:
+        _triple_ids_chk("triple_rank", h, pair_query, pair_cand)
+        NP = pair_query.shape[0]
+    offs, ntypes = None, 0
+    if node_type_offsets is not None:
+        offs = node_type_offsets
+        if not (offs.is_cuda and offs.device == h.device and offs.dtype == torch.int64 and offs.dim() == 1 and offs.numel() >= 2
+                and offs.is_contiguous()):
+            raise _lib.HetError(f"triple_rank: node_type_offsets is a contiguous int64 tensor [num_types + 1] on {h.device}, got "
+                                f"{offs.dtype} {tuple(offs.shape)} on {offs.device}")
+        ntypes = offs.numel() - 1
+    Q, (N, D), R = anchor.shape[0], h.shape, w.shape[0]
+    out = torch.empty(3, Q, dtype=torch.int32, device=h.device)
+    bad = torch.empty(1, dtype=torch.int64, device=h.device)
+    if Q == 0:
+        return out[0], out[1], out[2], bad.zero_()
+    ws, nbytes = _workspace(h, "het_triple_rank_workspace", Q, NP, N, D)
+    _call(h, "het_triple_rank_bf16" if h.dtype == torch.bfloat16 else "het_triple_rank", _p(h), _p(w), _p(anchor), _p(rel), _p(truth), Q,
+          _p(pair_query) if NP else None, _p(pair_cand) if NP else None, NP, _p(offs), ntypes, N, R, D, _p(out[0]), _p(out[1]), _p(out[2]),
+          _p(bad), _p(ws), nbytes, _stream(h))
+    return out[0], out[1], out[2], bad
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -44,8 +44,36 @@ against the implicit labels).  T floats are nothing beside the 2 T D gathered on
 softmax over each positive's negatives.
 
 No float atomics anywhere: the same inputs give the same bits on every call, and the autograd node keeps nothing of T D elements.
+
+Filtered ranking (evaluation; DESIGN.md 4.14; csrc/triple_rank.hip; ``distmult_rank``, ``ranking_metrics``).  The rule::
+
+    query j    (a_j, r_j, t_j): anchor node, relation, true node.  Tail ranking of (s, r, o): a = s, t = o.
+               Head ranking: a = o, t = s.  DistMult is symmetric, so one kernel serves both.
+               sides="both" gives Q = 2 P queries: the P tail queries first, then the P head queries.
+    run        [lo_j, hi_j) = the run of node_type_offsets that holds t_j  ([0, N) without offsets)
+    q_j[d]     = fl32(h[a_j, d] * w[r_j, d])        h fp32, or bf16 widened on load (exact); w fp32
+    score_j(c) = the fp32 fma chain over ascending d, from +0:  acc = fmaf(q_j[d], h[c, d], acc)
+    p_j        = score_j(t_j), by the same chain
+    excluded   c == t_j; for a tail query every c with (a_j, r_j, c) in the filter set, for a head query every c with
+               (c, r_j, a_j) in it; a c listed twice is excluded once; a listed c outside the run changes nothing
+    greater_j  = #{ c in run, not excluded : score_j(c) >  p_j }
+    equal_j    = #{ c in run, not excluded : score_j(c) == p_j }
+    cands_j    = #{ c in run, not excluded }
+    bad        a or t outside [0, N), r outside [0, R), or t in no run: **counted, not asserted**.
+               greater = equal = cands = 0; no table is read through such an id.
+               A filter triple with an id outside its range is ignored.
+    rank_j     = 1 + greater_j + equal_j / 2   (fp64, in torch).
+               MRR, mean rank and Hits@k (rank_j <= k) are taken over the queries that are not bad.
+
+The chain is the arithmetic of gfx950's fp32 MFMA, which scores the candidates; p_j is a sequential fmaf chain: a candidate whose row
+has the bits of the true node's row ties with it exactly.  The three counts are integers added with integer atomics: the same bits on
+every call.  The ``[Q, N]`` score matrix never exists.  **The filter serves evaluation only: training negatives stay unfiltered.**
+The pairs (query, excluded candidate) of a batch come from two ``searchsorted`` and one expansion in torch over a ``FilterIndex``
+built once; the expansion needs the pair count on the host -- **the one read-back of a ranking call** (none without a filter).
 """
 from __future__ import annotations
+
+import collections
 
 import torch as th
 import torch.nn as nn
@@ -242,6 +270,14 @@ class DistMultDecoder(nn.Module):
                 raise ValueError(f"DistMultDecoder: {n_bad} triple(s) have an id outside [0, {h.shape[0]}) nodes or [0, {self.num_rels}) relations")
         return score
 
+    def rank(self, h, s, r, o, **kw):
+        """``distmult_rank(h, self.w_relation, s, r, o, **kw)``: the filtered ranks of the triples under this head (no gradient; a module
+        built with ``native=False`` takes the torch composition)."""
+        if h.dim() != 2 or h.shape[1] != self.dim:
+            raise ValueError(f"DistMultDecoder: h [N, {self.dim}], got {tuple(h.shape)}")
+        kw.setdefault("native", self.native)
+        return distmult_rank(h, self.w_relation, s, r, o, **kw)
+
 
 def link_prediction_loss(scores, num_pos: int):
     """Mean binary cross-entropy with logits of ``scores`` [T] against the implicit labels: 1 for the first ``num_pos``, 0 after."""
@@ -251,3 +287,207 @@ def link_prediction_loss(scores, num_pos: int):
     labels = th.zeros_like(scores)
     labels[:num_pos] = 1.0
     return nn.functional.binary_cross_entropy_with_logits(scores, labels)
+
+
+# ---- filtered ranking (evaluation): the rule in the module docstring -------------------------------------------------------------
+RankResult = collections.namedtuple("RankResult", "greater equal candidates bad")
+RankResult.__doc__ = """What ``distmult_rank`` returns, one entry per query: ``greater``, ``equal`` and ``candidates`` int32 [Q] (the rule's three
+counts) and ``bad`` bool [Q] (the queries with an id outside its table or a true node in no run: their counts are 0 and
+``ranking_metrics`` leaves them out; ``bad.sum()`` is the count the kernel keeps on the device)."""
+
+
+class FilterIndex:
+    """The known triples of a graph as two sorted key arrays, built once in torch: ``tail_keys`` = ``r * N + s`` with ``tail_vals`` = o
+    (the known tails of (s, r)), ``head_keys`` = ``r * N + o`` with ``head_vals`` = s (the known heads of (r, o)); both stable-sorted by
+    key.  A triple with an id outside [0, num_nodes) or [0, num_rels) is ignored; duplicates are kept (they exclude once)."""
+
+    def __init__(self, s, r, o, num_nodes: int, num_rels: int):
+        N, R = int(num_nodes), int(num_rels)
+        if not (0 <= N < 2 ** 31 - 1 and 0 <= R < 2 ** 31 - 1):
+            raise ValueError(f"FilterIndex: num_nodes={N}, num_rels={R} (both below 2^31 - 1)")
+        if not (s.dim() == r.dim() == o.dim() == 1 and s.shape == r.shape == o.shape):
+            raise ValueError(f"FilterIndex: s, r and o are 1-d id tensors of one length, got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(o.shape)}")
+        with th.no_grad():
+            s, r, o = (t.detach().to(th.int64) for t in (s, r, o))
+            ok = (s >= 0) & (s < N) & (o >= 0) & (o < N) & (r >= 0) & (r < R)
+            s, r, o = s[ok], r[ok], o[ok]
+            tk, ti = th.sort(r * N + s, stable=True)
+            hk, hi = th.sort(r * N + o, stable=True)
+            self._set(tk, o[ti], hk, s[hi], N, R)
+
+    def _set(self, tk, tv, hk, hv, N, R):
+        self.num_nodes, self.num_rels = N, R
+        self._keys = th.cat([tk, hk + R * N]).contiguous()  # one array for one searchsorted: the head keys lie behind every tail key
+        self._vals = th.cat([tv, hv]).contiguous()
+        E = tk.shape[0]
+        self.tail_keys, self.tail_vals, self.head_keys, self.head_vals = self._keys[:E], self._vals[:E], hk, self._vals[E:]
+
+    @classmethod
+    def from_graph(cls, g):
+        """The index of the graph's own edges (its separate COO, relation-major: row = s, col = o)."""
+        coo = g.get_separate_coo_original()
+        rel_ptrs, row, col = coo["rel_ptrs"].to(coo["row_indices"].device), coo["row_indices"], coo["col_indices"]
+        R = int(rel_ptrs.numel()) - 1
+        rel = th.repeat_interleave(th.arange(R, dtype=th.int64, device=row.device), rel_ptrs[1:] - rel_ptrs[:-1], output_size=int(row.shape[0]))
+        return cls(row, rel, col, g.get_num_nodes(), R)
+
+    @property
+    def device(self):
+        return self._keys.device
+
+    def to(self, device):
+        device = th.device(device)
+        if self._keys.device == device:
+            return self
+        new = object.__new__(FilterIndex)
+        new._set(self.tail_keys.to(device), self.tail_vals.to(device), self.head_keys.to(device), self.head_vals.to(device), self.num_nodes,
+                 self.num_rels)
+        return new
+
+    def pairs(self, anchor, rel, head):
+        """(pair_query, pair_cand), int64 [n] each: for query j every known c -- the tails of (anchor_j, rel_j) where ``head[j]`` is
+        False, the heads of (rel_j, anchor_j) where it is True -- in query order.  Two searchsorted and one expansion; the expansion's
+        length is **read back to the host**: the one synchronisation of a filtered ranking call."""
+        N, R = self.num_nodes, self.num_rels
+        Q, dev = anchor.shape[0], anchor.device
+        ok = (anchor >= 0) & (anchor < N) & (rel >= 0) & (rel < R)
+        key = th.where(ok, rel * N + anchor + head.to(th.int64) * (R * N), th.full_like(anchor, -1))
+        lo = th.searchsorted(self._keys, key)
+        cnt = th.searchsorted(self._keys, key, right=True) - lo
+        total = int(cnt.sum())  # (the read-back)
+        if total == 0:
+            e = th.zeros(0, dtype=th.int64, device=dev)
+            return e, e.clone()
+        qi = th.repeat_interleave(th.arange(Q, dtype=th.int64, device=dev), cnt, output_size=total)
+        first = th.cumsum(cnt, 0) - cnt
+        pos = th.arange(total, dtype=th.int64, device=dev) - first[qi] + lo[qi]
+        return qi, self._vals[pos]
+
+
+def _rank_queries(s, r, o, sides):
+    """(anchor, rel, truth, head) of the rule: the tail queries, the head queries, or the tail queries followed by the head queries."""
+    f = th.zeros(s.shape[0], dtype=th.bool, device=s.device)
+    if sides == "tail":
+        return s, r, o, f
+    if sides == "head":
+        return o, r, s, ~f
+    if sides == "both":
+        return th.cat([s, o]), th.cat([r, r]), th.cat([o, s]), th.cat([f, ~f])
+    raise ValueError(f"distmult_rank: sides is 'both', 'tail' or 'head', got {sides!r}")
+
+
+def _rank_prepare(name, h, w, s, r, o, sides, filter, node_type_offsets):
+    """Checks, then (anchor, rel, truth, lo, hi, bad, offsets, pair_query, pair_cand) on h's device."""
+    if h.dim() != 2 or w.dim() != 2 or h.shape[1] != w.shape[1] or not (h.is_floating_point() and w.is_floating_point()):
+        raise ValueError(f"{name}: floating-point h [N, D] and w [R, D], got {h.dtype} {tuple(h.shape)} and {w.dtype} {tuple(w.shape)}")
+    if not (s.dim() == r.dim() == o.dim() == 1 and s.shape == r.shape == o.shape):
+        raise ValueError(f"{name}: s, r and o are 1-d id tensors of one length, got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(o.shape)}")
+    if any(t.is_floating_point() or t.dtype == th.bool for t in (s, r, o)):
+        raise ValueError(f"{name}: integer ids expected")
+    N, R, dev = h.shape[0], w.shape[0], h.device
+    if w.device != dev:
+        raise ValueError(f"{name}: h on {dev} and w on {w.device}")
+    if not (N < 2 ** 31 - 1 and R < 2 ** 31 - 1 and 2 * s.shape[0] < 2 ** 30):
+        raise ValueError(f"{name}: {N} nodes, {R} relations (both below 2^31 - 1), {s.shape[0]} triples (fewer than 2^29)")
+    a, rr, t, head = _rank_queries(*(x.detach().to(device=dev, dtype=th.int64) for x in (s, r, o)), sides)
+    a, rr, t = a.contiguous(), rr.contiguous(), t.contiguous()
+    offs = None
+    if node_type_offsets is not None:
+        offs = th.as_tensor(node_type_offsets).detach().to(device=dev, dtype=th.int64).contiguous()
+        if offs.dim() != 1 or offs.numel() < 2:
+            raise ValueError(f"{name}: node_type_offsets [num_types + 1], got {tuple(offs.shape)}")
+    inrun = (t >= 0) & (t < N)
+    lo, hi = th.zeros_like(t), th.full_like(t, N)
+    if offs is not None:
+        inrun &= (t >= offs[0]) & (t < offs[-1])
+        ty = (th.searchsorted(offs[:-1].contiguous(), t, right=True) - 1).clamp_(0, offs.numel() - 2)
+        lo, hi = offs[ty].clamp(min=0), offs[ty + 1].clamp(max=N)
+    bad = ~(inrun & (a >= 0) & (a < N) & (rr >= 0) & (rr < R))
+    pq = pc = None
+    if filter is not None:
+        if not isinstance(filter, FilterIndex) or (filter.num_nodes, filter.num_rels) != (N, R):
+            raise ValueError(f"{name}: filter is a FilterIndex over {N} nodes and {R} relations")
+        pq, pc = filter.to(dev).pairs(a, rr, head)
+    return a, rr, t, lo, hi, bad, offs, pq, pc
+
+
+def _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, chunk):
+    acc = th.float64 if h.dtype == th.float64 else th.float32
+    N, Q, dev = h.shape[0], a.shape[0], h.device
+    zero = th.zeros_like(a)
+    lo, hi = th.where(bad, zero, lo), th.where(bad, zero, hi)
+    q = h[th.where(bad, zero, a)].to(acc) * w[th.where(bad, zero, rr)].to(acc)  # (the rounded product)
+    p = (q * h[th.where(bad, zero, t)].to(acc)).sum(-1) if N else th.zeros(Q, dtype=acc, device=dev)
+    out = th.zeros(3, Q, dtype=th.int64, device=dev)
+    for c0 in range(0, N, chunk):
+        c1 = min(N, c0 + chunk)
+        sc = q @ h[c0:c1].to(acc).t()
+        c = th.arange(c0, c1, dtype=th.int64, device=dev)[None]
+        valid = (c >= lo[:, None]) & (c < hi[:, None]) & (c != t[:, None])
+        if pq is not None and pq.numel():
+            sel = (pc >= c0) & (pc < c1)
+            valid[pq[sel], pc[sel] - c0] = False
+        out[0] += (valid & (sc > p[:, None])).sum(1)
+        out[1] += (valid & (sc == p[:, None])).sum(1)
+        out[2] += valid.sum(1)
+    out = out.to(th.int32)
+    return RankResult(out[0], out[1], out[2], bad)
+
+
+def distmult_rank_torch(h, w, s, r, o, *, sides: str = "both", filter=None, node_type_offsets=None, chunk: int = 65536):
+    """``distmult_rank`` as a torch composition of the same rule, chunked over ``chunk`` candidates: q as the rounded product, one
+    [Q, chunk] matmul per chunk, the same masks (the filter as an index_put_ into the chunk's mask).  Correct, not fast; the order of
+    the sums is the matmul's, so on inputs that are not exactly representable a near-tie may fall on the other side than in the
+    kernels.  It serves CPU tensors, fp16 / fp64 tables, widths the kernels do not take and ``native=False``."""
+    with th.no_grad():
+        h, w = h.detach(), w.detach()
+        a, rr, t, lo, hi, bad, _, pq, pc = _rank_prepare("distmult_rank_torch", h, w, s, r, o, sides, filter, node_type_offsets)
+        return _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, max(1, int(chunk)))
+
+
+def distmult_rank(h, w, s, r, o, *, sides: str = "both", filter=None, node_type_offsets=None, native: bool = True):
+    """The filtered ranks of the triples (s, r, o) under the DistMult score of the rows ``h`` [N, D] and the relation vectors ``w`` [R, D]
+    (the module's rule): ``RankResult(greater, equal, candidates, bad)``, one entry per query -- ``sides="both"``: the P tail queries
+    (rank o among the tails of (s, r)), then the P head queries; ``"tail"`` / ``"head"``: one of them.  ``filter``: a ``FilterIndex`` of
+    the known triples (None: only the true node is excluded -- the raw setting); ``node_type_offsets``: candidates are the nodes of the
+    true node's type.
+
+    Runs under ``no_grad`` and keeps nothing: inputs that require grad are detached, the counts carry no graph.  Contiguous or strided
+    float32 / bfloat16 GPU rows of a width of ``kernels.triple_rank_params()`` take the HIP kernels (a strided or misaligned table
+    runs on a copy): a prelude, with a filter a sort of the pairs, one MFMA pass that reads ``h`` once and stores no score.  Everything
+    else, and ``native=False``, takes ``distmult_rank_torch``.  With a filter the pair count is read back once (``FilterIndex.pairs``)."""
+    with th.no_grad():
+        h, w = h.detach(), w.detach()
+        a, rr, t, lo, hi, bad, offs, pq, pc = _rank_prepare("distmult_rank", h, w, s, r, o, sides, filter, node_type_offsets)
+        if (native and h.is_cuda and h.dtype in (th.float32, th.bfloat16) and w.dtype == th.float32 and _native_available()):
+            hd, wd = _aligned_rows(h), _aligned_rows(w)
+            if _k.triple_rank_ok(hd, wd):
+                if pq is not None and pq.numel() == 0:
+                    pq = pc = None
+                inv = None
+                if offs is not None and a.shape[0] > 1:  # queries of one type side by side: a query tile then skips the other types' tiles
+                    order = th.sort(lo, stable=True).indices
+                    inv = th.empty_like(order)
+                    inv[order] = th.arange(order.shape[0], dtype=th.int64, device=order.device)
+                    a, rr, t = a[order], rr[order], t[order]
+                    pq = None if pq is None else inv[pq]
+                g, e, c, _ = _k.triple_rank(hd, wd, a, rr, t, pq, pc, offs)
+                if inv is not None:
+                    g, e, c = g[inv], e[inv], c[inv]
+                return RankResult(g, e, c, bad)
+        return _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, 65536)
+
+
+def ranking_metrics(result, ks=(1, 3, 10)):
+    """{"mrr", "mean_rank", "hits@k" for k in ks, "queries"} of a ``RankResult``: ``rank = 1 + greater + equal / 2`` in fp64 (a tie
+    counts half), the means over the queries that are not bad; NaN means with no such query.  Reads the result back."""
+    with th.no_grad():
+        good = ~result.bad
+        rank = (1.0 + result.greater.to(th.float64) + result.equal.to(th.float64) / 2)[good]
+        n = int(rank.numel())
+        nan = float("nan")
+        out = {"mrr": float((1.0 / rank).mean()) if n else nan, "mean_rank": float(rank.mean()) if n else nan}
+        for k in ks:
+            out[f"hits@{int(k)}"] = float((rank <= int(k)).to(th.float64).mean()) if n else nan
+        out["queries"] = n
+        return out

@@ -150,6 +150,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                         "encoder's output, --batch_size positive edges per step drawn by key from the graph, --num_negatives keyed "
                         "corruptions of each, BCE-with-logits (het_amd/linkpred.py); unfiltered negatives: a corruption may be a true edge")
     p.add_argument("--num_negatives", type=int, default=1, help="--link_prediction: keyed corruptions per positive edge")
+    p.add_argument("--eval_ranking", type=int, default=0, metavar="P",
+                   help="--link_prediction: after the last epoch rank P keyed positive edges on both sides against every node of the "
+                        "true node's type, filtered on the graph's own edges, and log MRR, mean rank and Hits@1/3/10 "
+                        "(het_amd/linkpred.py distmult_rank; the filter serves evaluation only, training negatives stay unfiltered)")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -339,6 +343,39 @@ def HET_linkpred_train(g, model, node_embed_layer, decoder, optimizer, args, ext
     return fwd, bwd, losses
 
 
+RANKING_DRAW = -1  # the draw of the evaluation's positives: training uses the draws 2 step and 2 step + 1, all >= 0
+
+
+def HET_linkpred_evaluate(g, model, node_embed_layer, decoder, args, extra=()):
+    """--eval_ranking P: the encoder once under no_grad in evaluation mode, P positive edges keyed by (--seed, RANKING_DRAW) -- a draw
+    no training step uses --, both sides ranked against the nodes of the true node's type, filtered on the graph's own edges
+    (het_amd/linkpred.py).  Returns {mrr, mean_rank, hits@1, hits@3, hits@10, queries, ms}; ms is the ranking call alone (the pair
+    plan included), between two events."""
+    from .linkpred import FilterIndex, keyed_positive_edges, ranking_metrics
+    offsets = g.get_original_node_type_offsets()
+    offsets = None if offsets is None or offsets.numel() <= 2 else offsets
+    was = model.training, node_embed_layer.training, decoder.training
+    model.train(False)
+    node_embed_layer.train(False)
+    decoder.train(False)
+    with th.no_grad():
+        h = model(g, node_embed_layer(), *extra)
+        src, rel, dst = keyed_positive_edges(g, args.eval_ranking, seed=args.seed, draw=RANKING_DRAW)
+        filt = FilterIndex.from_graph(g)
+        ev = [th.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        res = decoder.rank(h, src, rel, dst, sides="both", filter=filt, node_type_offsets=offsets)
+        ev[1].record()
+        th.cuda.synchronize()
+        out = ranking_metrics(res, ks=(1, 3, 10))
+    out["ms"] = round(ev[0].elapsed_time(ev[1]), 4)
+    model.train(was[0])
+    node_embed_layer.train(was[1])
+    decoder.train(was[2])
+    print("Ranking | " + " | ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in out.items()))
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="HET RGAT / RGCN / HGT benchmark driver on het_amd (MI355X)")
     add_generic_RGNN_args(p, "het_amd_train.json")
@@ -362,6 +399,10 @@ def main(argv=None):
         raise SystemExit("--link_prediction is an option of training: --inference scores no triples")
     if args.link_prediction and args.num_negatives < 0:
         raise SystemExit("--num_negatives is at least 0")
+    if args.eval_ranking and not args.link_prediction:
+        raise SystemExit("--eval_ranking ranks the triples of a link-prediction run: add --link_prediction")
+    if args.eval_ranking < 0 or args.eval_ranking >= 2 ** 29:
+        raise SystemExit("--eval_ranking is a number of positive edges, at least 0 and fewer than 2^29")
     th.manual_seed(args.seed)
     coo = load_graph(args)
     for f in ("row", "col", "rel", "eids", "node_type_offsets"):
@@ -425,6 +466,7 @@ def main(argv=None):
     if args.link_prediction:
         HET_RGNN_train.last_prep_ms = []
         fwd, bwd, losses = HET_linkpred_train(g, model, embed, decoder, optimizer, args, extra)
+        ranking = HET_linkpred_evaluate(g, model, embed, decoder, args, extra) if args.eval_ranking else None
     else:
         fwd, bwd, losses = HET_RGNN_train(g, model, embed, optimizer, labels, args, extra, batches)
     res = {"model": args.model, "dataset": args.edges_npy or args.dataset, "num_nodes": N, "num_edges": E, "num_rels": R,
@@ -464,6 +506,10 @@ def main(argv=None):
     else:
         del res["args"]["link_prediction"]
         del res["args"]["num_negatives"]
+    if args.eval_ranking:
+        res["ranking"] = ranking
+    else:
+        del res["args"]["eval_ranking"]
     res["million_edges_per_s"] = round(E / ((res["mean_forward_ms"] + res["mean_backward_ms"]) * 1e-3) / 1e6, 2)
     print(json.dumps(res))
     if args.logfile_enabled:

@@ -1095,6 +1095,54 @@ int het_block_relation_major(const int64_t* rel, const int64_t* eids, int64_t nu
                              int64_t* out_col, int64_t* out_rel, int64_t* out_eids, het_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Filtered ranking of link-prediction queries with the DistMult score (csrc/triple_rank.hip; het_amd/linkpred.py distmult_rank;
+ * DESIGN.md 4.14).  Every query is ranked against every node of its true node's type; no score is stored, three int32 per query
+ * come out.  (The section stands here, before keyed dropout, because the sections after it are pinned to their neighbours.)
+ *   query j    (a_j, r_j, t_j) = (anchor [j], rel [j], truth [j]): anchor node, relation, true node.  Tail ranking of (s, r, o): a = s,
+ *              t = o.  Head ranking: a = o, t = s.  DistMult is symmetric, so one kernel serves both.
+ *   run        [lo_j, hi_j) = the run of node_type_offsets [num_types + 1] (DEVICE memory) that holds t_j; NULL: [0, num_nodes)
+ *   q_j[d]     = fl32(h[a_j, d] * w[r_j, d])       h [num_nodes, dim] float, or het_bf16 widened on load (exact); w [num_rels, dim] float
+ *   score_j(c) = the fp32 fma chain over ascending d, from +0:  acc = fmaf(q_j[d], h[c, d], acc)
+ *   p_j        = score_j(t_j), by the same chain
+ *   excluded   c == t_j, and every c with a listed pair (pair_query [i], pair_cand [i]) = (j, c), i < num_pairs; a pair listed twice
+ *              excludes once; a listed c outside the run changes nothing; a pair with an id outside [0, num_queries) x [0, num_nodes)
+ *              is ignored
+ *   greater[j] = #{ c in run, not excluded : score_j(c) >  p_j }
+ *   equal[j]   = #{ c in run, not excluded : score_j(c) == p_j }
+ *   cands[j]   = #{ c in run, not excluded }
+ *   bad        a_j or t_j outside [0, num_nodes), r_j outside [0, num_rels), or t_j in no run: counted in bad [1] (int64, device),
+ *              not asserted; greater = equal = cands = 0 and no table is read through such an id.
+ * The chain is the arithmetic of v_mfma_f32_16x16x4_f32 (one rounding per product, k ascending), which scores the candidates; p_j is
+ * a sequential fmaf chain in plain C++: a candidate whose row has the bits of t_j's row ties with it exactly.
+ * The counters start at zero by the library's own doing: the prelude launch stores 0 into greater / equal / cands of every query
+ * before the rank pass (the next launch on the stream) adds to them with integer atomics, and bad is cleared by an 8-byte
+ * hipMemsetAsync before the prelude counts into it.  No float atomic: the same inputs give the same bits on every call.
+ * Launches: the memset, the prelude, with pairs a key launch, one stable radix sort of the pairs by tile cell and a launch that
+ * finds every candidate tile's run of them, the rank pass.  Nothing is read back and nothing waits for the stream.  The workspace
+ * holds het_triple_rank_workspace(num_queries, num_pairs, num_nodes, dim) bytes: q [num_queries, dim] float, p / lo / hi / t
+ * [num_queries] 4 bytes each, and with pairs the sort's keys (8 bytes) and values (4 bytes) in and out, 4 bytes per candidate tile
+ * plus 4, each part rounded up to 256 bytes, and the sort's own scratch.
+ * het_triple_rank_params (out [8] on the host): queries of a tile, candidates of a tile, the least and the greatest dim served (a
+ * multiple of 4 between them), threads per workgroup, the most workgroups, the query tiles whose counters a workgroup keeps, the most
+ * candidate tiles of one work item.
+ * Before anything is enqueued: negative counts, num_queries or num_pairs >= 2^30, num_nodes or num_rels >= 2^31 - 1, dim < 1,
+ * node_type_offsets with num_types < 1, a null pointer where the count is positive, a misaligned pointer (h on 16-byte (bf16: 8-byte),
+ * w / workspace on 16-byte, int64 arrays on 8-byte, the counts on 4-byte boundaries) and a workspace smaller than its query says are
+ * HET_ERR_INVALID_ARG; a dim the kernels do not take is HET_ERR_UNSUPPORTED.  num_queries == 0 is HET_OK with no launch.
+ * ------------------------------------------------------------------------ */
+int64_t het_triple_rank_workspace(int64_t num_queries, int64_t num_pairs, int64_t num_nodes, int64_t dim); /* bytes; -1 on bad sizes */
+int het_triple_rank(const float* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth, int64_t num_queries,
+                    const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs, const int64_t* node_type_offsets,
+                    int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim, int32_t* greater, int32_t* equal, int32_t* cands,
+                    int64_t* bad, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_triple_rank_bf16(const het_bf16* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth,
+                         int64_t num_queries, const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs,
+                         const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim,
+                         int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes,
+                         het_stream stream);
+int het_triple_rank_params(int64_t* out);
+
+/* ------------------------------------------------------------------------
  * Keyed dropout fused with the activation (csrc/keyed_dropout.hip; het_amd/layers.py KeyedDropout; no reference counterpart: the
  * reference's layers end with activation(h) and nn.Dropout).  The mask is a pure function of (seed, draw, position) on the
  * sampler's stream above, recomputed by the backward and never stored.  With i the index in the contiguous tensor of n elements:
