@@ -111,6 +111,12 @@ _ENTRIES = {
     "het_rgcn_layer_backward": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
     "het_rgcn_layer_forward_bf16": [P, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64, P],
     "het_rgcn_layer_backward_bf16": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P],
+    "het_grouping_node_rows": [P, I64, P, P, P, P],
+    "het_rgcn_bdd_layer_ok": [I64, I64, I64, I64],
+    "het_rgcn_bdd_layer_backward_workspace": (I64, [I64, I64, I64, I64, I64, I64]),
+    "het_rgcn_bdd_layer_forward": [P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, P],
+    "het_rgcn_bdd_layer_backward": [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, P, I64, P],
+    "het_rgcn_bdd_params": [C.POINTER(I64)],
     "het_rows_linear_bias": [P, P, P, P, P, I64, I64, I64, P],
     "het_rows_linear_bias_bf16": [P, P, P, P, P, I64, I64, I64, P],
     "het_rows_add_bias": [P, P, P, P, I64, I64, P],

@@ -14,6 +14,7 @@ FUSED = os.environ.get("HET_RGCN_FUSED", "1") != "0"
 
 __all__ = [
     "RgcnLayer1SeparateCoo", "RgcnLayerFused", "rgcn_layer1_separate_coo", "rgcn_layer_fused_applies", "RGCNNodeMeanAggregationCompactAsOfNodeSeparateCOO",
+    "RgcnLayerBdd", "rgcn_layer_bdd", "rgcn_bdd_route", "rgcn_bdd_route_of", "bdd_dense_weight",
     "RGCNNodeMeanAggregationCompactAsOfNodeDirectIndexingSeparateCOO",
     "rgcn_node_mean_aggregation_compact_as_of_node_separate_coo_single_sided",
 ]
@@ -135,6 +136,92 @@ def rgcn_layer1_separate_coo(graph, x, weight, norm, bias=None):
     return RgcnLayer1SeparateCoo.apply(s["rel_ptrs"], s["eids"], s["row_indices"], s["col_indices"], o["row_ptrs"],
                                        o["col_indices"], o["eids"], o["rel_types"], x.contiguous(), weight.contiguous(),
                                        norm.contiguous(), ret)
+
+
+# ---- block-diagonal relation weights (regularizer="bdd"): weight [R, B, K/B, D/B] ------------------------------------------
+def bdd_dense_weight(weight):
+    """The [R, K, D] relation weights of block-diagonal ``weight`` [R, B, si, so]: block b of relation r on the diagonal at rows
+    b*si .., columns b*so .., zeros elsewhere (torch.block_diag per relation, as one differentiable expression)."""
+    R, nb, si, so = weight.shape
+    eye = th.eye(nb, dtype=weight.dtype, device=weight.device)
+    return (weight.unsqueeze(3) * eye.view(1, nb, 1, nb, 1)).reshape(R, nb * si, nb * so)
+
+
+BDD_DENSE_UP_TO_RELS = 4  # rgcn_bdd_route: relation counts measured faster on the dense two-call layer (where it applies)
+
+
+def rgcn_bdd_route(*, cuda, fp32, groupings, shape_ok, compact_flag=False, env_on=True, few_rels_dense=False) -> str:
+    """Which code serves a bdd layer call, from plain facts: ``"native"`` (csrc/rgcn_bdd.hip through RgcnLayerBdd) or ``"dense"``
+    (the blocks expanded to [R, K, D] by bdd_dense_weight, then the layer's existing code, whatever it runs for these arguments).
+
+    native needs ALL of: ``cuda`` and ``fp32`` -- x a float32 GPU tensor (a bf16 x keeps the dense layer's upcast behaviour) --;
+    ``groupings`` -- het_amd.plan on for this thread (off inside sampling.one_shot_graphs, so sampled blocks go dense) --;
+    ``shape_ok`` -- kernels.rgcn_bdd_ok(R, K, D, B) on the UNPADDED widths (padded widths go dense) --; not ``compact_flag``
+    (compact_as_of_node_flag); ``env_on`` -- HET_RGCN_BDD is not 0; not ``few_rels_dense`` -- R <= BDD_DENSE_UP_TO_RELS = 4 AND the
+    dense two-call layer applies to the expansion (kernels.rgcn_layer_ok(R, K, D): all R dense weights in LDS).
+
+    The last rule is measured (exp/rgcn_bdd_ab.py, profiles/r18/rgcn_bdd_ab.txt; MI355X, one layer 64 -> 64, B = 8, forward +
+    backward medians of 200 interleaved steps): at the ogbn-mag shape, R = 4, native 1.11 + 1.46 ms against dense 0.84 + 1.15 ms --
+    the dense layer's MFMA node pass with its four weights in LDS is 1.29x faster than the block products on the vector units, so
+    such calls go dense.  At the AIFB size, R = 104, native 0.045 + 0.114 ms against 0.085 + 0.124 ms (0.76x); at the wikikg2
+    size, R = 535, 5.03 + 6.90 ms against 5.25 + 6.87 ms (0.98x: a tie).  Nothing between R = 4 and R = 104 was timed: 5 <= R stays
+    native, where the dense layer stops applying at R = 9 anyway (64 x 64)."""
+    if cuda and fp32 and groupings and shape_ok and not compact_flag and env_on and not few_rels_dense:
+        return "native"
+    return "dense"
+
+
+def rgcn_bdd_env_on() -> bool:
+    return os.environ.get("HET_RGCN_BDD", "1") != "0"
+
+
+def rgcn_bdd_route_of(graph, x, weight, norm, bias=None, compact_as_of_node_flag=False) -> str:
+    """rgcn_bdd_route for these arguments."""
+    R, nb, si, so = weight.shape
+    fp32 = x.dtype == weight.dtype == norm.dtype == th.float32 and (bias is None or bias.dtype == th.float32)
+    shape_ok = (x.dim() == 2 and x.shape[1] == nb * si and x.is_cuda and _k.rgcn_bdd_ok(R, nb * si, nb * so, nb) and
+                x.shape[0] == graph.get_num_nodes() and (bias is None or bias.numel() == nb * so))
+    # (HET_RGCN_BDD=native: the few-relations rule off -- what exp/rgcn_bdd_ab.py times at R = 4)
+    few = bool(shape_ok and R <= BDD_DENSE_UP_TO_RELS and _k.rgcn_layer_ok(R, nb * si, nb * so) and
+               os.environ.get("HET_RGCN_BDD") != "native")
+    return rgcn_bdd_route(cuda=x.is_cuda, fp32=fp32, groupings=_k._plan.is_enabled(), shape_ok=shape_ok,
+                          compact_flag=compact_as_of_node_flag, env_on=rgcn_bdd_env_on(), few_rels_dense=few)
+
+
+@_consistent_plan
+class RgcnLayerBdd(th.autograd.Function):
+    """The RGCN layer with block-diagonal relation weights [R, B, si, so] as two library calls (include/het_amd.h:
+    het_rgcn_bdd_layer_forward / _backward): RgcnLayerFused's dataflow with node passes and a weight gradient that multiply blocks.
+    No gradient for norm (zeros when asked, as its neighbours)."""
+
+    @staticmethod
+    def forward(ctx, plan, x, weight, norm, bias):
+        ret, ssum = _k.rgcn_bdd_layer_forward(plan, x, weight, norm, bias)
+        ctx.plan, ctx.has_bias = plan, bias is not None
+        ctx.save_for_backward(weight, norm, ssum)
+        return ret
+
+    @staticmethod
+    def backward(ctx, gradout):
+        weight, norm, ssum = ctx.saved_tensors
+        grad_x, grad_w, grad_bias = _k.rgcn_bdd_layer_backward(
+            ctx.plan, ssum, weight.transpose(2, 3).contiguous(), norm, gradout.float().contiguous(),
+            ctx.has_bias and ctx.needs_input_grad[4], want_x=ctx.needs_input_grad[1])
+        grad_norm = th.zeros_like(norm) if ctx.needs_input_grad[3] else None
+        return None, grad_x, grad_w if ctx.needs_input_grad[2] else None, grad_norm, grad_bias
+
+
+def rgcn_layer_bdd(graph, x, weight, norm, bias=None, compact_as_of_node_flag=False):
+    """out [N, D] = bias + SUM_r SUM_{e: rel r, dst v} norm_e * x[src_e] . blockdiag(weight[r]);  weight [R, B, K/B, D/B].
+    Routed by rgcn_bdd_route (rgcn_bdd_route_of tells which route these arguments take)."""
+    if rgcn_bdd_route_of(graph, x, weight, norm, bias, compact_as_of_node_flag) == "native":
+        s = graph.get_separate_coo_original()
+        plan = _k.rgcn_bdd_layer_plan(s["rel_ptrs"], s["eids"], s["row_indices"], s["col_indices"], graph.get_num_nodes())
+        if plan is None:
+            raise _k._lib.HetError("rgcn_layer_bdd: the native route was chosen without groupings")
+        return RgcnLayerBdd.apply(plan, x.contiguous(), weight.contiguous(), norm.contiguous(),
+                                  None if bias is None else bias.contiguous())
+    return rgcn_layer1_separate_coo(graph, x, bdd_dense_weight(weight), norm, bias)
 
 
 @_consistent_plan

@@ -4,6 +4,7 @@
 #include "seg_gemm_any.hip.h"
 #include "seg_rowdot.hip.h"
 #include "seg_reduce.hip.h"
+#include "rgcn_rows.hip.h"
 
 namespace {
 
@@ -784,61 +785,6 @@ extern "C" int het_backward_rgcn_layer1_separate_coo(const int64_t* rel_ptrs, co
 
 // ---- the RGCN layer as two calls (layer-level fusion of a7 / a8 with the layer's bias; include/het_amd.h) -------------------
 namespace {
-// column sums of a [rows, 4 * LPR] matrix: per-workgroup partial rows (grid-stride, 16 bytes per lane), finished by HET_colsum_finish
-// (T: the element type of `in`, float or het_bf16; the sums are fp32)
-template <int LPR, typename T = float>
-__global__ __launch_bounds__(256) void HET_colsum_partial(const T* __restrict__ in, int64_t rows, float* __restrict__ part) {
-  constexpr int RPI = 256 / LPR;
-  __shared__ float4 red[256];
-  const int c = threadIdx.x % LPR, r = threadIdx.x / LPR;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int64_t i = (int64_t)blockIdx.x * RPI + r; i < rows; i += (int64_t)gridDim.x * RPI) {
-    const float4 v = ldrow4(in + i * (4 * LPR) + 4 * c);
-    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  if (r == 0) {
-    for (int k = 1; k < RPI; ++k) {
-      const float4 v = red[k * LPR + c];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    *reinterpret_cast<float4*>(part + (int64_t)blockIdx.x * (4 * LPR) + 4 * c) = acc;
-  }
-}
-__global__ __launch_bounds__(256) void HET_colsum_finish(const float* __restrict__ part, int P, int X, float* __restrict__ out) {
-  __shared__ float red[256];
-  const int x = blockIdx.x, t = threadIdx.x;
-  float a = 0.f;
-  for (int p = t; p < P; p += 256) a += part[(int64_t)p * X + x];
-  red[t] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  if (t == 0) out[x] = red[0];
-}
-constexpr int kColsumBlocks = 1024;
-
-template <typename T>
-int launch_colsum(const T* in, int64_t rows, int X, float* part, float* out, hipStream_t s) {
-  HET_KTIME("HET_colsum", s);
-  const int lpr = X / 4;
-  const int64_t rpi = 256 / lpr;
-  int blocks = (int)(ceil_div64(rows, rpi) < kColsumBlocks ? ceil_div64(rows, rpi) : kColsumBlocks);
-  if (blocks < 1) blocks = 1;
-  switch (lpr) {
-    case 8: hipLaunchKernelGGL((HET_colsum_partial<8, T>), dim3(blocks), dim3(256), 0, s, in, rows, part); break;
-    case 16: hipLaunchKernelGGL((HET_colsum_partial<16, T>), dim3(blocks), dim3(256), 0, s, in, rows, part); break;
-    default: het_set_error("colsum: %d columns unsupported", X); return HET_ERR_UNSUPPORTED;
-  }
-  HET_LAUNCH_CHECK("HET_colsum_partial");
-  hipLaunchKernelGGL(HET_colsum_finish, dim3(X), dim3(256), 0, s, part, blocks, X, out);
-  HET_LAUNCH_CHECK("HET_colsum_finish");
-  return HET_OK;
-}
-
 bool rgcn_layer_shape_ok(int64_t R, int64_t K, int64_t D) {
   return (K == 32 || K == 64) && (D == 32 || D == 64) && R >= 1 && het_node_rows_matmul_sum_ok(R, K, D) &&
          het_node_rows_matmul_sum_ok(R, D, K) && segment_sum_supported((int)K) && segment_sum_supported((int)D) &&
@@ -866,14 +812,6 @@ int node_rows_matmul_sum_bias_bf16(int64_t n_begin, int64_t n_end, int64_t num_n
 namespace {
 // The launches of the layer for activation rows of type T (float, or het_bf16: x, ret, gradout and grad_x; every sum, ssum / gsum,
 // the weights, the norm and the bias stay fp32)
-int rgcn_gather_sum(const het_grouping* g, const float* in, float* out, int X, const float* norm, const float* norm_sorted,
-                    hipStream_t s) {
-  return launch_segment_sum(g, in, out, X, norm_sorted ? norm_sorted : norm, s, 0, -1, 0, 0, 0, norm_sorted ? 1 : 0);
-}
-int rgcn_gather_sum(const het_grouping* g, const het_bf16* in, float* out, int X, const float* norm, const float* norm_sorted,
-                    hipStream_t s) {
-  return launch_segment_sum_bf16(g, in, out, X, norm_sorted ? norm_sorted : norm, s, norm_sorted ? 1 : 0);
-}
 int rgcn_node_pass(int64_t num_nodes, int64_t S, const float* const* rows, const int64_t* strides, const int32_t* const* maps,
                    const int64_t* ident, const float* const* wts, const float* bias, float* out, int64_t KS, int64_t XO,
                    const int32_t* node_order, het_stream stream) {

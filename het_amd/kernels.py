@@ -2108,6 +2108,84 @@ def rgcn_layer_backward_bf16(plan, ssum, weights_t, norm, gradout, want_bias: bo
     return _rgcn_layer_backward("het_rgcn_layer_backward_bf16", plan, ssum, weights_t, norm, gradout, want_bias, want_x)
 
 
+# ---- the RGCN layer with block-diagonal relation weights (include/het_amd.h: het_rgcn_bdd_layer_forward; csrc/rgcn_bdd.hip) ----
+def rgcn_bdd_ok(R: int, K: int, D: int, B: int) -> bool:
+    """Shapes of the native bdd layer (het_rgcn_bdd_layer_ok): K, D in {32, 64, 128}, K / B and D / B in {4, 8, 16, 32}, R >= 1."""
+    return bool(_lib.lib().het_rgcn_bdd_layer_ok(int(R), int(K), int(D), int(B)))
+
+
+def rgcn_bdd_params() -> Dict[str, int]:
+    """The launch constants of csrc/rgcn_bdd.hip (het_rgcn_bdd_params; runs on the host): ``chunk_rows`` (relation, node) rows per
+    weight-gradient work item, ``lds_weight_bytes`` up to which the blocks of all relations are held in LDS, ``block`` threads per
+    workgroup, block sides from ``min_side`` to ``max_side``, ``colsum_blocks`` partial rows of the bias gradient."""
+    L = _lib.lib()
+    out = (C.c_int64 * 6)()
+    rc = L.het_rgcn_bdd_params(out)
+    if rc != 0:
+        raise _lib.HetError(f"het_rgcn_bdd_params failed (code {rc}): {L.het_last_error().decode()}")
+    return dict(zip(("chunk_rows", "lds_weight_bytes", "block", "min_side", "max_side", "colsum_blocks"), (int(v) for v in out)))
+
+
+def rgcn_bdd_lds_relations(K: int, D: int, B: int) -> int:
+    """The largest relation count whose blocks the node pass holds in LDS at this shape (one more reads them through the caches)."""
+    return rgcn_bdd_params()["lds_weight_bytes"] // (4 * K * D // B)
+
+
+def grouping_node_rows(g, rel_ptrs, keys, num_keys: int):
+    """(node_ptr [num_keys + 1], ent_row [S], ent_rel [S]) int32 of het_grouping_node_rows: per node the segments of the grouping
+    ``g`` of ``keys`` by (relation, key) that belong to it, in ascending relation order, and their relations.  Built once per graph
+    on the device and cached by the identity of the lists the grouping was built from, like the segment maps."""
+    def build():
+        S = g.num_segments
+        node_ptr = torch.empty(num_keys + 1, dtype=torch.int32, device=keys.device)
+        ent_row = torch.empty(max(1, S), dtype=torch.int32, device=keys.device)
+        ent_rel = torch.empty(max(1, S), dtype=torch.int32, device=keys.device)
+        _call(keys, "het_grouping_node_rows", g.handle, num_keys, _p(node_ptr), _p(ent_row), _p(ent_rel), _stream(keys))
+        return node_ptr, ent_row[:S], ent_rel[:S]
+    return _derived_get(("noderows", num_keys), (rel_ptrs, keys), build)
+
+
+def rgcn_bdd_layer_plan(rel_ptrs, eids, row, col, num_nodes: int):
+    """What the native bdd layer needs per graph: (by_rel_dst, by_rel_src, dst_rows, src_rows) -- the groupings of the two-call layer
+    and their per-node row lists (grouping_node_rows) --, or None without groupings."""
+    gd = _plan.get_grouping(rel_ptrs, col, num_nodes, row, eids)
+    gs = _plan.get_grouping(rel_ptrs, row, num_nodes, col, eids)
+    if gd is None or gs is None:
+        return None
+    return gd, gs, grouping_node_rows(gd, rel_ptrs, col, num_nodes), grouping_node_rows(gs, rel_ptrs, row, num_nodes)
+
+
+def rgcn_bdd_layer_forward(plan, x, weights, norm, bias):
+    """(ret [N,D], ssum [S_col,K]) of het_rgcn_bdd_layer_forward; weights [R,B,K/B,D/B]."""
+    _chk("rgcn_bdd_layer_forward", tuple(t for t in (x, weights, norm, bias) if t is not None))
+    gd, _, (node_ptr, ent_row, ent_rel), _ = plan
+    R, B, si, so = weights.shape
+    K, D, N = B * si, B * so, node_ptr.numel() - 1
+    ssum = torch.empty((max(1, gd.num_segments), K), dtype=torch.float32, device=x.device)
+    ret = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    _call(ret, "het_rgcn_bdd_layer_forward", gd.handle, R, N, _p(x), _p(weights), _p(norm), _p(scale_in_rank_order(gd, norm)), _p(bias),
+          _p(node_ptr), _p(ent_row), _p(ent_rel), _p(ssum), _p(ret), K, D, B, _stream(ret))
+    return ret, ssum
+
+
+def rgcn_bdd_layer_backward(plan, ssum, weights_t, norm, gradout, want_bias: bool, want_x: bool = True):
+    """(grad_x [N,K] or None, grad_w [R,B,K/B,D/B], grad_bias [D] or None) of het_rgcn_bdd_layer_backward; weights_t [R,B,D/B,K/B]:
+    every block transposed."""
+    _chk("rgcn_bdd_layer_backward", (ssum, weights_t, norm, gradout))
+    gd, gs, _, (node_ptr, ent_row, ent_rel) = plan
+    R, B, so, si = weights_t.shape
+    K, D, N = B * si, B * so, node_ptr.numel() - 1
+    dev = gradout.device
+    grad_x = torch.empty((N, K), dtype=torch.float32, device=dev) if want_x else None
+    grad_w = torch.empty((R, B, si, so), dtype=torch.float32, device=dev)
+    grad_bias = torch.empty((D,), dtype=torch.float32, device=dev) if want_bias else None
+    ws, nbytes = _workspace(gradout, "het_rgcn_bdd_layer_backward_workspace", gs.num_segments, gd.num_segments, R, K, D, B)
+    _call(gradout, "het_rgcn_bdd_layer_backward", gs.handle, gd.handle, R, N, gradout.shape[0], _p(ssum), _p(weights_t), _p(norm),
+          _p(scale_in_rank_order(gs, norm) if want_x else None), _p(gradout), _p(node_ptr), _p(ent_row), _p(ent_rel), _p(grad_x),
+          _p(grad_w), _p(grad_bias), K, D, B, _p(ws), nbytes, _stream(gradout))
+    return grad_x, grad_w, grad_bias
+
+
 # ---- the HGT layer with bf16 activations (backend/hgt_fused_layer.py): activation rows bf16, everything else fp32 ----
 def rows_matmul_bf16_ok(K: int, X: int) -> bool:
     """Shapes het_rows_matmul_bf16 / het_rows_matmul_backward_dw_bf16 cover."""

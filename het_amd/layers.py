@@ -650,17 +650,38 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
     bf16 entries run and the bias, zero-padded to a padded width, is added inside them, so the output is rounded once.  Every
     other path -- compact_as_of_node_flag, groupings off (plan.forced(False): one-shot block graphs), shapes outside
     rgcn_layer_ok such as 8 relations at 64 x 64, HET_RGCN_FUSED=0, widths padded to 128 -- runs the fp32 layer on an upcast copy
-    of the input and rounds its output to bf16: correct, not faster, and it needs the fp32 copy."""
+    of the input and rounds its output to bf16: correct, not faster, and it needs the fp32 copy.
+
+    ``regularizer="bdd"`` (DGL's RelGraphConv; RGCN/RGCN.py names it): ``num_bases`` = B diagonal blocks per relation, ``weight``
+    [num_rels, B, in_feat / B, out_feat / B], no ``w_comp``; B must divide both widths (ValueError).  A call is served by the
+    block kernels (csrc/rgcn_bdd.hip) or by this layer's existing code on the dense expansion of the blocks, as
+    backend.rgcn_bdd_route decides; ``last_route`` is "native" or "dense" after every call."""
 
     def __init__(self, in_feat, out_feat, num_rels, num_bases=-1, *, bias=True, activation=None,
-                 compact_as_of_node_flag=False, compact_direct_indexing_flag=False, dropout=0.0, keyed_dropout=False):
+                 compact_as_of_node_flag=False, compact_direct_indexing_flag=False, dropout=0.0, keyed_dropout=False,
+                 regularizer="basis"):
         super().__init__()
-        self.in_feat, self.out_feat, self.num_rels = in_feat, out_feat, num_rels
-        self.num_bases = num_rels if num_bases <= 0 or num_bases > num_rels else num_bases
+        if regularizer not in ("basis", "bdd"):
+            raise ValueError("Regularizer must be either 'basis' or 'bdd'")  # (RGCN/RGCN.py)
+        self.in_feat, self.out_feat, self.num_rels, self.regularizer = in_feat, out_feat, num_rels, regularizer
         self.bias, self.activation = bias, activation
         self.compact_as_of_node_flag = compact_as_of_node_flag
         self.compact_direct_indexing_flag = compact_direct_indexing_flag
+        self._upcast_of_bf16 = False
+        self.last_route = None  # "native" / "dense" of the last bdd call (backend: rgcn_bdd_route); None for the basis regularizer
         gain = nn.init.calculate_gain("relu")
+        if regularizer == "bdd":
+            # DGL's RelGraphConv(regularizer="bdd"): num_bases diagonal blocks of [in_feat / B, out_feat / B] per relation, no w_comp
+            if num_bases < 1 or in_feat % num_bases != 0 or out_feat % num_bases != 0:
+                raise ValueError(f"Feature size must be a multiplier of num_bases ({num_bases}): got {in_feat} -> {out_feat}")
+            self.num_bases = num_bases
+            self.weight = nn.Parameter(th.Tensor(num_rels, num_bases, in_feat // num_bases, out_feat // num_bases))
+            nn.init.xavier_uniform_(self.weight, gain=gain)
+            if bias:
+                self.h_bias = nn.Parameter(th.zeros(out_feat))
+            self.dropout = _make_dropout(self, dropout, keyed_dropout)
+            return
+        self.num_bases = num_rels if num_bases <= 0 or num_bases > num_rels else num_bases
         self.weight = nn.Parameter(th.Tensor(self.num_bases, in_feat, out_feat))
         nn.init.xavier_uniform_(self.weight, gain=gain)
         if self.num_bases < num_rels:
@@ -672,6 +693,14 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
 
     def forward(self, g, x, norm, num_dst=None):
         _refuse_inference_graph(g, self, lambda: _needs_grad(x, self, norm))
+        if self.regularizer == "bdd" and not self._upcast_of_bf16:
+            bias = self.h_bias if self.bias else None
+            self.last_route = B.rgcn_bdd_route_of(g, x, self.weight, norm, bias, self.compact_as_of_node_flag)
+            if self.last_route == "native":  # (the bias inside the op; the destinations' rows are sliced afterwards)
+                node_repr = B.rgcn_layer_bdd(g, x, self.weight, norm, bias)
+                if num_dst is not None and num_dst < node_repr.shape[0]:
+                    node_repr = node_repr[:num_dst]
+                return _activation_dropout(self, node_repr)
         if x.dtype == th.bfloat16:
             return self._forward_bf16(g, x, norm, num_dst)
         weight, x = self._weight_and_input(x)
@@ -698,7 +727,9 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
 
     def _weight_and_input(self, x):
         """The layer's [R, K, D] weight (basis-composed, zero-padded to the kernels' widths) and the input, padded to match."""
-        if self.num_bases < self.num_rels:  # basis decomposition, RGCN.py:286-301
+        if self.regularizer == "bdd":  # (the dense route: the blocks expanded to [R, K, D], the code below unchanged)
+            weight = B.bdd_dense_weight(self.weight)
+        elif self.num_bases < self.num_rels:  # basis decomposition, RGCN.py:286-301
             weight = th.matmul(self.w_comp, self.weight.view(self.num_bases, -1)).view(
                 self.num_rels, self.in_feat, self.out_feat)
         else:
@@ -727,7 +758,11 @@ class HET_EglRelGraphConv_EdgeParallel(nn.Module):
                 if node_repr.shape[1] != self.out_feat:
                     node_repr = node_repr[:, :self.out_feat]
                 return _activation_dropout(self, node_repr)
-        return self.forward(g, x.float(), norm, num_dst).to(th.bfloat16)
+        self._upcast_of_bf16 = True  # (a bdd layer: the fp32 pass below is part of this call's dense route, not a call of its own)
+        try:
+            return self.forward(g, x.float(), norm, num_dst).to(th.bfloat16)
+        finally:
+            self._upcast_of_bf16 = False
 
 
 def _heads_first(w, H):

@@ -54,11 +54,11 @@ class HET_RGCNModel(nn.Module):
     """hrt/python/RGCN/RGCN.py:353-405 (full-graph, edge-parallel separate-COO layers)."""
 
     def __init__(self, num_rels, h_dim, out_dim, num_layers=1, num_bases=-1, dropout=0.0, compact_as_of_node_flag=False,
-                 compact_direct_indexing_flag=False, keyed_dropout=False):
+                 compact_direct_indexing_flag=False, keyed_dropout=False, regularizer="basis"):
         super().__init__()
         dims = [h_dim] * num_layers + [out_dim]
         self.layers = nn.ModuleList(
-            [HET_EglRelGraphConv_EdgeParallel(dims[i], dims[i + 1], num_rels, num_bases,
+            [HET_EglRelGraphConv_EdgeParallel(dims[i], dims[i + 1], num_rels, num_bases, regularizer=regularizer,
                                               activation=F.relu if i + 1 < num_layers else None, dropout=dropout,
                                               compact_as_of_node_flag=compact_as_of_node_flag,
                                               compact_direct_indexing_flag=compact_direct_indexing_flag, keyed_dropout=keyed_dropout)
@@ -145,6 +145,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                    help="the loss (and the evaluation's) from het_amd.layers.SoftmaxCrossEntropy on the logits as the model returns them: "
                         "one HIP pass forward, one backward, no log-softmax tensor kept, summed in a fixed order -- instead of the torch "
                         "expression on logits.float()")
+    p.add_argument("--regularizer", choices=("basis", "bdd"), default="basis",
+                   help="RGCN only: 'bdd' gives every relation --n_bases diagonal blocks of [in / n_bases, out / n_bases] instead of a "
+                        "dense (or basis-composed) weight, as DGL's RelGraphConv(regularizer='bdd'); --n_bases must divide --n_infeat "
+                        "and --num_classes (het_amd/layers.py; the native kernels serve block sides 4 .. 32 of widths 32 / 64 / 128)")
     p.add_argument("--link_prediction", action="store_true",
                    help="full-graph encoder only: train for link prediction instead of node classification -- a DistMult head on the "
                         "encoder's output, --batch_size positive edges per step drawn by key from the graph, --num_negatives keyed "
@@ -387,6 +391,10 @@ def main(argv=None):
         raise SystemExit("--use_norm is an option of the HGT layer")
     if args.keyed_dropout and args.model == "hgt":
         raise SystemExit("--keyed_dropout is an option of the RGAT and RGCN layers (the HGT layer applies no dropout)")
+    if args.regularizer != "basis" and args.model != "rgcn":
+        raise SystemExit("--regularizer is an option of the RGCN layer: add --model rgcn")
+    if args.regularizer == "bdd" and (args.n_bases < 1 or args.n_infeat % args.n_bases or args.num_classes % args.n_bases):
+        raise SystemExit("--regularizer bdd needs --n_bases >= 1 that divides --n_infeat and --num_classes")
     if args.sparse_embed and args.full_graph_training:
         raise SystemExit("--sparse_embed is an option of the sampled mini-batch path: --full_graph_training reads every row of the table")
     if args.sparse_embed and args.inference:
@@ -426,7 +434,8 @@ def main(argv=None):
     elif args.model == "rgcn":
         model = HET_RGCNModel(R, args.n_infeat, args.num_classes, num_layers=args.num_layers, num_bases=args.n_bases,
                               dropout=args.dropout, compact_as_of_node_flag=args.compact_as_of_node_flag,
-                              compact_direct_indexing_flag=args.compact_direct_indexing_flag, keyed_dropout=args.keyed_dropout)
+                              compact_direct_indexing_flag=args.compact_direct_indexing_flag, keyed_dropout=args.keyed_dropout,
+                              regularizer=args.regularizer)
         extra = (th.rand(E, 1, device=dev),)  # edge norm as RGCN.py:527-530
     else:
         model = HET_HGTModel(g.get_num_ntypes(), R, args.n_infeat, args.num_classes, args.num_heads,
@@ -501,6 +510,8 @@ def main(argv=None):
         res["loss"] = "fused"
     else:
         del res["args"]["fused_loss"]
+    if args.regularizer == "basis":
+        del res["args"]["regularizer"]
     if args.link_prediction:
         res["task"] = "link_prediction"
     else:

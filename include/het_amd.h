@@ -947,6 +947,51 @@ int het_rgcn_layer_backward_bf16(const het_grouping* by_rel_src, const het_group
                                  const int32_t* node_order, het_bf16* grad_x, float* grad_w, float* grad_bias, int64_t K, int64_t D,
                                  void* workspace, int64_t workspace_bytes, het_stream stream);
 
+/* ------------------------------------------------------------------------
+ * The RGCN layer with block-diagonal relation weights (DGL's RelGraphConv(regularizer="bdd"); RGCN/RGCN.py names the regularizer,
+ * the reference does not implement it).  B blocks, si = K / B, so = D / B, weights [R, B, si, so]:
+ *   out[v, b*so + j] = bias[b*so + j] + SUM_r SUM_{e: rel r, dst v} norm[eid_e] * SUM_i x[src_e, b*si + i] * weights[r, b, i, j]
+ * as the two-call layer above with its node passes and its weight gradient replaced:
+ *   forward   ssum[(r,v), :]   = SUM over the in-edges e of v in relation r of norm[eid_e] * x[src_e, :]     (kept for the backward)
+ *             ret[v, :]        = bias + SUM over the entries (r, row) of v of ssum[row, :] . blockdiag(weights[r])
+ *   backward  gsum[(r,u), :]   = SUM over the out-edges e of u in relation r of norm[eid_e] * gradout[dst_e, :]
+ *             grad_x[u, :]     = SUM over the entries (r, row) of u of gsum[row, :] . blockdiag(weights[r])^T
+ *             grad_w[r, b]     = SUM over the rows (r,v) of ssum[row, block b]^T (x) gradout[v, block b];  grad_bias = column sums of gradout
+ * Summation order: the entries of a node in ascending relation order, one fused multiply-add per term, the bias last; the rows of
+ * a relation in chunks of het_rgcn_bdd_params()[0] rows (inside a chunk: 256 / D interleaved row groups, then the groups in order),
+ * the chunk partials in chunk order.  No float atomics and no buffer the caller has to fill: a node without entries gets the bias
+ * (or zeros), a relation without rows gets a zero gradient; the same inputs give the same bits (the gather-sum adds the parts of a
+ * split segment atomically -- only segments of more than 256 edges are split).
+ *
+ * het_grouping_node_rows: the per-node list of a grouping by (relation, key) -- node_ptr [num_keys + 1], and per entry the segment
+ * (ent_row [S]: the row of ssum / gsum) and its relation (ent_rel [S]); S = het_grouping_num_segments.  Built on the device from the
+ * grouping's segment list by a stable sort by key, so a node's entries are in ascending relation order; nothing is read back.  It
+ * replaces the [R, N] map of het_grouping_segment_map: ent_row[node_ptr[n] ..] are the non-negative values of map[:, n], in order.
+ * The forward takes the list of by_rel_dst, the backward that of by_rel_src.
+ *
+ * Shapes (het_rgcn_bdd_layer_ok): fp32, K and D in {32, 64, 128}, si and so in {4, 8, 16, 32}, any R >= 1, fewer than 2^31 nodes;
+ * HET_ERR_UNSUPPORTED otherwise.  Bad counts, null or misaligned pointers (16 bytes: x, weights, bias, ssum, ret, gradout, grad_x,
+ * grad_w, workspace), a missing grouping or a short workspace: HET_ERR_INVALID_ARG.  Either answer names the entry and comes before
+ * anything is enqueued.  weights_t [R, B, so, si]: every block transposed.  workspace: het_rgcn_bdd_layer_backward_workspace(segments
+ * of by_rel_src, segments of by_rel_dst, R, K, D, B) bytes (-1: bad arguments).  grad_x NULL: no source-side gather and no node pass.
+ * The blocks of all relations are held in LDS while R * K * D / B * 4 <= het_rgcn_bdd_params()[1] bytes and read through the caches
+ * beyond.  het_rgcn_bdd_params(out[6]): chunk rows, LDS weight bytes, threads per workgroup, smallest and largest block side, column
+ * sum workgroups. */
+int het_grouping_node_rows(const het_grouping* g, int64_t num_keys, int32_t* node_ptr, int32_t* ent_row, int32_t* ent_rel,
+                           het_stream stream);
+int het_rgcn_bdd_layer_ok(int64_t num_rels, int64_t K, int64_t D, int64_t B);
+int64_t het_rgcn_bdd_layer_backward_workspace(int64_t n_src_rows, int64_t n_dst_rows, int64_t num_rels, int64_t K, int64_t D, int64_t B);
+int het_rgcn_bdd_layer_forward(const het_grouping* by_rel_dst, int64_t num_rels, int64_t num_nodes, const float* x,
+                               const float* weights, const float* norm, const float* norm_sorted, const float* bias,
+                               const int32_t* node_ptr, const int32_t* ent_row, const int32_t* ent_rel, float* ssum, float* ret,
+                               int64_t K, int64_t D, int64_t B, het_stream stream);
+int het_rgcn_bdd_layer_backward(const het_grouping* by_rel_src, const het_grouping* by_rel_dst, int64_t num_rels,
+                                int64_t num_src_nodes, int64_t num_dst_nodes, const float* ssum, const float* weights_t,
+                                const float* norm, const float* norm_sorted, const float* gradout, const int32_t* node_ptr,
+                                const int32_t* ent_row, const int32_t* ent_rel, float* grad_x, float* grad_w, float* grad_bias,
+                                int64_t K, int64_t D, int64_t B, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_rgcn_bdd_params(int64_t* out);
+
 /* self-loop + bias of a layer as one pass (RGAT/models.py:378-381: h + th.matmul(inputs_dst, loop_weight) + h_bias):
  * out[i,:] = x[i,:] . w + bias for rows [offsets[0], offsets[1]) (offsets: device array), w [K,X], bias [X] or NULL.
  * Matrix-core shapes only (HET_ERR_UNSUPPORTED otherwise). */
