@@ -143,6 +143,12 @@ _ENTRIES = {
     "het_sample_select": [P, P, I64, I64, I64, I64, I64, P, I64, P, P, P],
     "het_block_renumber": [P, I64, P, I64, P, I64, P, I64, P, P, P, P],
     "het_block_relation_major": [P, P, I64, P, P, P, I64, I64, P, P, P, P, P, P],
+    "het_complex_score": [P, P, P, P, P, I64, I64, I64, I64, P, P],
+    "het_complex_score_bf16": [P, P, P, P, P, I64, I64, I64, I64, P, P],
+    "het_complex_score_backward": [P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, I64, P],
+    "het_complex_score_backward_bf16": [P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, I64, P],
+    "het_complex_rank": [P, P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],
+    "het_complex_rank_bf16": [P, P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],
     "het_triple_rank_workspace": (I64, [I64, I64, I64, I64]),
     "het_triple_rank": [P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],
     "het_triple_rank_bf16": [P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P, P, I64, P],

@@ -10,6 +10,9 @@
 //   A query with a or t outside [0, N), r outside [0, R) or t in no run is BAD: counted, its three counts are 0 and no table is read
 //   through its ids.
 //
+// ComplEx (het_complex_rank): the same pass behind HET_complex_rank_prelude, whose q_j follows the side of the query
+// (the rule above rank_q_complex below); the pass never looks at w.
+//
 // Launches: HET_rank_prelude (one lane per query: the ids, the run, q_j, p_j as a sequential fmaf chain in plain C++, the three
 // counters of the query set to zero, the bad queries counted with one integer atomic per wave into a counter an 8-byte memset
 // cleared), HET_rank_pair_keys + one stable hipCUB radix sort of the listed pairs by the tile cell they fall in + HET_rank_tile_ptr
@@ -60,25 +63,42 @@ size_t rank_lds_bytes(int64_t d) {
 }
 
 // ---- prelude: one lane per query ----------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kBlock) void HET_rank_prelude(const T* __restrict__ h, const float* __restrict__ w, const idx_t* __restrict__ a,
-                                                           const idx_t* __restrict__ r, const idx_t* __restrict__ t, idx_t nq,
-                                                           const idx_t* __restrict__ offs, int num_types, idx_t n, idx_t nr, idx_t d,
-                                                           float* __restrict__ q, float* __restrict__ p, int* __restrict__ lo,
-                                                           int* __restrict__ hi, int* __restrict__ tt, int* __restrict__ greater,
-                                                           int* __restrict__ equal, int* __restrict__ cands,
-                                                           unsigned long long* __restrict__ bad) {
+// q of a piece.  DistMult: the rounded product.  ComplEx (column 2k the real, 2k + 1 the imaginary part; x = h[a_j], b = w[r_j]):
+//   side 0 (tails are ranked, x stands for the head):  q[2k] = fl(fl(x_r b_r) - fl(x_i b_i))   q[2k+1] = fl(fl(x_r b_i) + fl(x_i b_r))
+//   side 1 (heads are ranked, x stands for the tail):  q[2k] = fl(fl(b_r x_r) + fl(b_i x_i))   q[2k+1] = fl(fl(b_r x_i) - fl(b_i x_r))
+// three separately rounded fp32 operations per element: nothing here may be contracted into a fused multiply-add
+__device__ __forceinline__ float4 rank_q_distmult(const float4& x, const float4& y) {
+  return make_float4(x.x * y.x, x.y * y.y, x.z * y.z, x.w * y.w);
+}
+__device__ __forceinline__ float4 rank_q_complex(const float4& x, const float4& b, bool head) {
+#pragma clang fp contract(off)  // (plain operators under the pragma: the products and the sums below carry no licence to fuse)
+  const float rr0 = x.x * b.x, ii0 = x.y * b.y, ri0 = x.x * b.y, ir0 = x.y * b.x;
+  const float rr1 = x.z * b.z, ii1 = x.w * b.w, ri1 = x.z * b.w, ir1 = x.w * b.z;
+  if (head) return make_float4(rr0 + ii0, ir0 - ri0, rr1 + ii1, ir1 - ri1);
+  return make_float4(rr0 - ii0, ri0 + ir0, rr1 - ii1, ri1 + ir1);
+}
+
+// the per-query work of both preludes: the ids, the run, the bad count, q_j and p_j, the zeroed counters.  CPX: side [nq] picks the
+// ComplEx rule's q (a side outside {0, 1} makes the query bad); else side is not read.
+template <typename T, bool CPX>
+__device__ __forceinline__ void rank_prelude_body(const T* __restrict__ h, const float* __restrict__ w, const idx_t* __restrict__ a,
+                                                  const idx_t* __restrict__ r, const idx_t* __restrict__ t, const idx_t* __restrict__ side,
+                                                  idx_t nq, const idx_t* __restrict__ offs, int num_types, idx_t n, idx_t nr, idx_t d,
+                                                  float* __restrict__ q, float* __restrict__ p, int* __restrict__ lo, int* __restrict__ hi,
+                                                  int* __restrict__ tt, int* __restrict__ greater, int* __restrict__ equal,
+                                                  int* __restrict__ cands, unsigned long long* __restrict__ bad) {
   const idx_t step = (idx_t)gridDim.x * kBlock, np = d >> 2;
   for (idx_t j0 = (idx_t)blockIdx.x * kBlock; j0 < nq; j0 += step) {  // (the same trip count in every lane of a wave: the ballot below)
     const idx_t j = j0 + threadIdx.x;
     const bool in = j < nq;
-    idx_t aj = -1, rj = -1, tj = -1;
+    idx_t aj = -1, rj = -1, tj = -1, sd = 0;
     if (in) {
       aj = a[j];
       rj = r[j];
       tj = t[j];
+      if (CPX) sd = side[j];
     }
-    bool ok = (uint64_t)aj < (uint64_t)n && (uint64_t)tj < (uint64_t)n && (uint64_t)rj < (uint64_t)nr;
+    bool ok = (uint64_t)aj < (uint64_t)n && (uint64_t)tj < (uint64_t)n && (uint64_t)rj < (uint64_t)nr && (uint64_t)sd < 2ull;
     idx_t l = 0, u = n;
     if (ok && offs) {
       ok = tj >= offs[0] && tj < offs[num_types];
@@ -99,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void HET_rank_prelude(const T* __restrict__
       const float* wr = w + rj * d;
       for (idx_t pc = 0; pc < np; ++pc) {
         const float4 x = ldrow4(ha + 4 * pc), y = ld4(wr + 4 * pc), z = ldrow4(ht + 4 * pc);
-        const float4 m = make_float4(x.x * y.x, x.y * y.y, x.z * y.z, x.w * y.w);
+        const float4 m = CPX ? rank_q_complex(x, y, sd != 0) : rank_q_distmult(x, y);
         st4(qj + 4 * pc, m);
         acc = fmaf(m.x, z.x, acc);
         acc = fmaf(m.y, z.y, acc);
@@ -117,6 +137,30 @@ __global__ __launch_bounds__(kBlock) void HET_rank_prelude(const T* __restrict__
     equal[j] = 0;
     cands[j] = 0;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void HET_rank_prelude(const T* __restrict__ h, const float* __restrict__ w, const idx_t* __restrict__ a,
+                                                           const idx_t* __restrict__ r, const idx_t* __restrict__ t, idx_t nq,
+                                                           const idx_t* __restrict__ offs, int num_types, idx_t n, idx_t nr, idx_t d,
+                                                           float* __restrict__ q, float* __restrict__ p, int* __restrict__ lo,
+                                                           int* __restrict__ hi, int* __restrict__ tt, int* __restrict__ greater,
+                                                           int* __restrict__ equal, int* __restrict__ cands,
+                                                           unsigned long long* __restrict__ bad) {
+  rank_prelude_body<T, false>(h, w, a, r, t, nullptr, nq, offs, num_types, n, nr, d, q, p, lo, hi, tt, greater, equal, cands, bad);
+}
+
+// the ComplEx prelude: the same work, q by the two-sided rule
+template <typename T>
+__global__ __launch_bounds__(kBlock) void HET_complex_rank_prelude(const T* __restrict__ h, const float* __restrict__ w,
+                                                                   const idx_t* __restrict__ a, const idx_t* __restrict__ r,
+                                                                   const idx_t* __restrict__ t, const idx_t* __restrict__ side, idx_t nq,
+                                                                   const idx_t* __restrict__ offs, int num_types, idx_t n, idx_t nr, idx_t d,
+                                                                   float* __restrict__ q, float* __restrict__ p, int* __restrict__ lo,
+                                                                   int* __restrict__ hi, int* __restrict__ tt, int* __restrict__ greater,
+                                                                   int* __restrict__ equal, int* __restrict__ cands,
+                                                                   unsigned long long* __restrict__ bad) {
+  rank_prelude_body<T, true>(h, w, a, r, t, side, nq, offs, num_types, n, nr, d, q, p, lo, hi, tt, greater, equal, cands, bad);
 }
 
 // ---- the listed pairs: the sort key is the tile cell, candidate tile major; a pair with an id outside its range sorts behind every cell
@@ -367,9 +411,11 @@ int rank_check_sizes(const char* op, int64_t nq, int64_t npairs, int64_t d) {
   return HET_OK;
 }
 
+// complex_prelude: the ComplEx rule's q (side [nq]: 0 ranks tails, 1 ranks heads); everything behind the prelude is the same
 template <typename T>
-int triple_rank(const char* op, const T* h, const float* w, const int64_t* a, const int64_t* r, const int64_t* t, int64_t nq,
-                const int64_t* pq, const int64_t* pc, int64_t npairs, const int64_t* offs, int64_t num_types, int64_t n, int64_t nr, int64_t d,
+int triple_rank(const char* op, bool complex_prelude, const T* h, const float* w, const int64_t* a, const int64_t* r, const int64_t* t,
+                const int64_t* side, int64_t nq, const int64_t* pq, const int64_t* pc, int64_t npairs, const int64_t* offs,
+                int64_t num_types, int64_t n, int64_t nr, int64_t d,
                 int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes, het_stream stream) {
   int rc = rank_check_sizes(op, nq, npairs, d);
   if (rc != HET_OK) return rc;
@@ -378,9 +424,10 @@ int triple_rank(const char* op, const T* h, const float* w, const int64_t* a, co
   HET_REQUIRE(num_types >= 0 && num_types < kRankMaxNodes && (!offs || num_types >= 1), "%s: num_types=%lld%s", op, (long long)num_types,
               offs ? " with node_type_offsets (at least one run)" : "");
   if (nq == 0) return HET_OK;
-  HET_REQUIRE(a && r && t && greater && equal && cands && bad && (h || n == 0) && (w || nr == 0) && (npairs == 0 || (pq && pc)),
+  HET_REQUIRE(a && r && t && (side || !complex_prelude) && greater && equal && cands && bad && (h || n == 0) && (w || nr == 0) &&
+                  (npairs == 0 || (pq && pc)),
               "%s: null pointer", op);
-  HET_REQUIRE((sizeof(T) == 4 ? aligned16(h) : aligned8(h)) && aligned16(w, workspace) && aligned8(a, r, t, pq, pc, offs, bad) &&
+  HET_REQUIRE((sizeof(T) == 4 ? aligned16(h) : aligned8(h)) && aligned16(w, workspace) && aligned8(a, r, t, side, pq, pc, offs, bad) &&
                   (((uintptr_t)greater | (uintptr_t)equal | (uintptr_t)cands) & 3) == 0,
               "%s: misaligned pointer (h on %d-byte, w and workspace on 16-byte, int64 arrays on 8-byte, the counts on 4-byte boundaries)", op,
               (int)(4 * sizeof(T)));
@@ -408,7 +455,13 @@ int triple_rank(const char* op, const T* h, const float* w, const int64_t* a, co
   int* tile_ptr = (int*)(base + L.tile_ptr);
   hipStream_t st = (hipStream_t)stream;
   HET_HIP(hipMemsetAsync(bad, 0, sizeof(int64_t), st));
-  {
+  if (complex_prelude) {
+    HET_KTIME("HET_complex_rank_prelude", st);
+    hipLaunchKernelGGL((HET_complex_rank_prelude<T>), dim3(grid_for(nq)), dim3(kBlock), 0, st, h, w, (const idx_t*)a, (const idx_t*)r,
+                       (const idx_t*)t, (const idx_t*)side, (idx_t)nq, (const idx_t*)offs, (int)num_types, (idx_t)n, (idx_t)nr, (idx_t)d, q, p, lo,
+                       hi, tt, greater, equal, cands, (unsigned long long*)bad);
+    HET_LAUNCH_CHECK("HET_complex_rank_prelude");
+  } else {
     HET_KTIME("HET_rank_prelude", st);
     hipLaunchKernelGGL((HET_rank_prelude<T>), dim3(grid_for(nq)), dim3(kBlock), 0, st, h, w, (const idx_t*)a, (const idx_t*)r, (const idx_t*)t,
                        (idx_t)nq, (const idx_t*)offs, (int)num_types, (idx_t)n, (idx_t)nr, (idx_t)d, q, p, lo, hi, tt, greater, equal, cands,
@@ -495,8 +548,8 @@ extern "C" int het_triple_rank(const float* h, const float* w, const int64_t* an
                                const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs, const int64_t* node_type_offsets,
                                int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim, int32_t* greater, int32_t* equal,
                                int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes, het_stream stream) {
-  return triple_rank("het_triple_rank", h, w, anchor, rel, truth, num_queries, pair_query, pair_cand, num_pairs, node_type_offsets, num_types,
-                     num_nodes, num_rels, dim, greater, equal, cands, bad, workspace, workspace_bytes, stream);
+  return triple_rank("het_triple_rank", false, h, w, anchor, rel, truth, nullptr, num_queries, pair_query, pair_cand, num_pairs,
+                     node_type_offsets, num_types, num_nodes, num_rels, dim, greater, equal, cands, bad, workspace, workspace_bytes, stream);
 }
 
 extern "C" int het_triple_rank_bf16(const het_bf16* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth,
@@ -504,6 +557,25 @@ extern "C" int het_triple_rank_bf16(const het_bf16* h, const float* w, const int
                                     const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim,
                                     int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes,
                                     het_stream stream) {
-  return triple_rank("het_triple_rank_bf16", h, w, anchor, rel, truth, num_queries, pair_query, pair_cand, num_pairs, node_type_offsets,
+  return triple_rank("het_triple_rank_bf16", false, h, w, anchor, rel, truth, nullptr, num_queries, pair_query, pair_cand, num_pairs,
+                     node_type_offsets, num_types, num_nodes, num_rels, dim, greater, equal, cands, bad, workspace, workspace_bytes, stream);
+}
+
+// ---- ComplEx: the same launches behind its own prelude (side [num_queries]: 0 ranks tails, 1 ranks heads) -----------------------------
+extern "C" int het_complex_rank(const float* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth,
+                                const int64_t* side, int64_t num_queries, const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs,
+                                const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim,
+                                int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes,
+                                het_stream stream) {
+  return triple_rank("het_complex_rank", true, h, w, anchor, rel, truth, side, num_queries, pair_query, pair_cand, num_pairs, node_type_offsets,
                      num_types, num_nodes, num_rels, dim, greater, equal, cands, bad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int het_complex_rank_bf16(const het_bf16* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth,
+                                     const int64_t* side, int64_t num_queries, const int64_t* pair_query, const int64_t* pair_cand,
+                                     int64_t num_pairs, const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels,
+                                     int64_t dim, int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace,
+                                     int64_t workspace_bytes, het_stream stream) {
+  return triple_rank("het_complex_rank_bf16", true, h, w, anchor, rel, truth, side, num_queries, pair_query, pair_cand, num_pairs,
+                     node_type_offsets, num_types, num_nodes, num_rels, dim, greater, equal, cands, bad, workspace, workspace_bytes, stream);
 }

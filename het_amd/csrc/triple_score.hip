@@ -1,5 +1,6 @@
-// Link prediction on triples (s, r, o): keyed corruption of positives, the inverted index of a batch, the DistMult score and its
-// backward (het_amd/linkpred.py; the rule in include/het_amd.h).
+// Link prediction on triples (s, r, o): keyed corruption of positives, the inverted index of a batch, the DistMult and the ComplEx
+// score and their backward (het_amd/linkpred.py; the rules in include/het_amd.h).  One body per kernel: the
+// decoder is a type that gives the three per-piece terms (DistMultTerms, ComplExTerms below); the lists, chunks and owners are shared.
 //
 // The rule (fp32 unless said otherwise; bf16 rows of h are widened first, which is exact):
 //   score_j = sum_d h[s_j, d] * w[r_j, d] * h[o_j, d]; a triple with s or o outside [0, N) or r outside [0, R) is BAD: its score is +0,
@@ -15,6 +16,14 @@
 // lanes there.  No LDS.  Every index and row offset is 64-bit.
 // The plan is built on the device alone: two stable radix sorts (hipCUB) of 32-bit (id, position) pairs, boundaries by binary search,
 // two exclusive scans of the chunk counts.  Nothing is read back and nothing waits for the stream.
+//
+// ComplEx (the same lists, orders and conventions; D even, column 2k the real and 2k + 1 the imaginary part of component k, so a piece
+// is two whole complex numbers and every product stays inside the lane that owns the piece).  With a = h[s_j], b = w[r_j], c = h[o_j]:
+//   score_j = sum_k Re(a_k b_k conj(c_k)) = sum_k (a_r b_r - a_i b_i) c_r + (a_r b_i + a_i b_r) c_i
+//   slot side 0 (v is the head):  grad a_r += g (b_r c_r + b_i c_i)    grad a_i += g (b_r c_i - b_i c_r)
+//   slot side 1 (v is the tail):  grad c_r += g (a_r b_r - a_i b_i)    grad c_i += g (a_r b_i + a_i b_r)
+//   grad b_r += g (a_r c_r + a_i c_i)    grad b_i += g (a_r c_i - a_i c_r)
+// written as explicit fmaf chains (ComplExTerms), so the roundings are the source's and not the compiler's choice.
 #include <algorithm>
 
 #include <hipcub/hipcub.hpp>
@@ -159,11 +168,81 @@ __global__ __launch_bounds__(kBlock) void HET_triple_bounds(const uint32_t* __re
   }
 }
 
+// ---- the decoders: the arithmetic of one piece (4 columns) in the score, in a node's walk over its slots and in a relation's walk ----
+struct DistMultTerms {
+  static constexpr const char* kScore = "HET_distmult_score";
+  static constexpr const char* kChunksH = "HET_distmult_grad_chunks_h";
+  static constexpr const char* kChunksW = "HET_distmult_grad_chunks_w";
+  static constexpr const char* kChunks = "HET_distmult_grad_chunks";
+  static constexpr const char* kGradH = "HET_distmult_grad_h";
+  static constexpr const char* kGradW = "HET_distmult_grad_w";
+  // acc + the piece's four products a * b * c
+  static __device__ __forceinline__ float score(float acc, const float4& a, const float4& b, const float4& c) {
+    acc += a.x * b.x * c.x;
+    acc += a.y * b.y * c.y;
+    acc += a.z * b.z * c.z;
+    acc += a.w * b.w * c.w;
+    return acc;
+  }
+  // acc += (g * b) * x: b the relation's piece, x the other end's; the side of the slot does not matter
+  static __device__ __forceinline__ void slot_term(float4& acc, float gj, const float4& b, const float4& x, bool /*tail*/) {
+    acc.x += (gj * b.x) * x.x;
+    acc.y += (gj * b.y) * x.y;
+    acc.z += (gj * b.z) * x.z;
+    acc.w += (gj * b.w) * x.w;
+  }
+  // acc += (a * c) * g: a the head's piece, c the tail's
+  static __device__ __forceinline__ void rel_term(float4& acc, float gj, const float4& a, const float4& c) {
+    acc.x += (a.x * c.x) * gj;
+    acc.y += (a.y * c.y) * gj;
+    acc.z += (a.z * c.z) * gj;
+    acc.w += (a.w * c.w) * gj;
+  }
+};
+
+struct ComplExTerms {
+  static constexpr const char* kScore = "HET_complex_score";
+  static constexpr const char* kChunksH = "HET_complex_grad_chunks_h";
+  static constexpr const char* kChunksW = "HET_complex_grad_chunks_w";
+  static constexpr const char* kChunks = "HET_complex_grad_chunks";
+  static constexpr const char* kGradH = "HET_complex_grad_h";
+  static constexpr const char* kGradW = "HET_complex_grad_w";
+  // one complex number: re = a_r b_r - a_i b_i, im = a_r b_i + a_i b_r, then acc = fmaf(im, c_i, fmaf(re, c_r, acc))
+  static __device__ __forceinline__ float score1(float acc, float ar, float ai, float br, float bi, float cr, float ci) {
+    const float re = fmaf(-ai, bi, ar * br), im = fmaf(ai, br, ar * bi);
+    return fmaf(im, ci, fmaf(re, cr, acc));
+  }
+  static __device__ __forceinline__ float score(float acc, const float4& a, const float4& b, const float4& c) {
+    acc = score1(acc, a.x, a.y, b.x, b.y, c.x, c.y);
+    return score1(acc, a.z, a.w, b.z, b.w, c.z, c.w);
+  }
+  // one complex number with u = g b_r, v = g b_i negated on a tail slot:  re += u x_r + v x_i,  im += u x_i - v x_r
+  // (head slot, x = c: g (b_r c_r + b_i c_i), g (b_r c_i - b_i c_r); tail slot, x = a: g (a_r b_r - a_i b_i), g (a_r b_i + a_i b_r))
+  static __device__ __forceinline__ void slot1(float& re, float& im, float u, float v, float xr, float xi) {
+    re = fmaf(v, xi, fmaf(u, xr, re));
+    im = fmaf(-v, xr, fmaf(u, xi, im));
+  }
+  static __device__ __forceinline__ void slot_term(float4& acc, float gj, const float4& b, const float4& x, bool tail) {
+    const float u0 = gj * b.x, v0 = gj * b.y, u1 = gj * b.z, v1 = gj * b.w;
+    slot1(acc.x, acc.y, u0, tail ? -v0 : v0, x.x, x.y);
+    slot1(acc.z, acc.w, u1, tail ? -v1 : v1, x.z, x.w);
+  }
+  // one complex number: re += (a_r c_r + a_i c_i) g,  im += (a_r c_i - a_i c_r) g
+  static __device__ __forceinline__ void rel1(float& re, float& im, float gj, float ar, float ai, float cr, float ci) {
+    re = fmaf(fmaf(ai, ci, ar * cr), gj, re);
+    im = fmaf(fmaf(-ai, cr, ar * ci), gj, im);
+  }
+  static __device__ __forceinline__ void rel_term(float4& acc, float gj, const float4& a, const float4& c) {
+    rel1(acc.x, acc.y, gj, a.x, a.y, c.x, c.y);
+    rel1(acc.z, acc.w, gj, a.z, a.w, c.z, c.w);
+  }
+};
+
 // ---- the score ---------------------------------------------------------------------------------------------------------------------
-template <typename T, int G>
-__global__ __launch_bounds__(kBlock) void HET_distmult_score(const T* __restrict__ h, const float* __restrict__ w, const idx_t* __restrict__ s,
-                                                             const idx_t* __restrict__ r, const idx_t* __restrict__ o, idx_t t, idx_t n, idx_t nr,
-                                                             idx_t d, float* __restrict__ score) {
+template <typename DEC, typename T, int G>
+__global__ __launch_bounds__(kBlock) void HET_triple_score(const T* __restrict__ h, const float* __restrict__ w, const idx_t* __restrict__ s,
+                                                           const idx_t* __restrict__ r, const idx_t* __restrict__ o, idx_t t, idx_t n, idx_t nr,
+                                                           idx_t d, float* __restrict__ score) {
   constexpr int GPB = kBlock / G;
   const int gi = threadIdx.x / G, l = threadIdx.x % G;
   const idx_t step = (idx_t)gridDim.x * GPB, np = d >> 2;
@@ -184,10 +263,7 @@ __global__ __launch_bounds__(kBlock) void HET_distmult_score(const T* __restrict
       const float* wr = w + rj * d;
       for (idx_t p = l; p < np; p += G) {
         const float4 a = ldrow4(hs + 4 * p), b = ld4(wr + 4 * p), c = ldrow4(ho + 4 * p);
-        acc += a.x * b.x * c.x;
-        acc += a.y * b.y * c.y;
-        acc += a.z * b.z * c.z;
-        acc += a.w * b.w * c.w;
+        acc = DEC::score(acc, a, b, c);
       }
     }
 #pragma unroll
@@ -204,9 +280,10 @@ struct TripleIds {
   idx_t t, n, nr, d;
 };
 
-// piece p of sum over the slots at positions [b, e) of g_j * w[r_j] (.) h[other end], in that order.  An id is used as an index only
-// when it lies inside its table (the plan lists no other; a plan that is not this batch's reads nothing out of bounds either).
-template <typename T>
+// piece p of sum over the slots at positions [b, e) of the decoder's slot term (DistMult: g_j * w[r_j] (.) h[other end]), in that
+// order.  An id is used as an index only when it lies inside its table (the plan lists no other; a plan that is not this batch's
+// reads nothing out of bounds either).
+template <typename DEC, typename T>
 __device__ __forceinline__ float4 triple_sum_slots(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ g,
                                                    const TripleIds& ids, const idx_t* __restrict__ slots, idx_t b, idx_t e, idx_t p) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -217,16 +294,14 @@ __device__ __forceinline__ float4 triple_sum_slots(const T* __restrict__ h, cons
     if ((uint64_t)other >= (uint64_t)ids.n || (uint64_t)rj >= (uint64_t)ids.nr) continue;
     const float gj = g[j];
     const float4 a = ld4(w + rj * ids.d + 4 * p), c = ldrow4(h + other * ids.d + 4 * p);
-    acc.x += (gj * a.x) * c.x;
-    acc.y += (gj * a.y) * c.y;
-    acc.z += (gj * a.z) * c.z;
-    acc.w += (gj * a.w) * c.w;
+    DEC::slot_term(acc, gj, a, c, (slot & 1) != 0);
   }
   return acc;
 }
 
-// piece p of the sum over the triples at positions [b, e) of a relation's order of g_j * (h[s_j] (.) h[o_j]), in that order
-template <typename T>
+// piece p of the sum over the triples at positions [b, e) of a relation's order of the decoder's relation term (DistMult:
+// g_j * (h[s_j] (.) h[o_j])), in that order
+template <typename DEC, typename T>
 __device__ __forceinline__ float4 triple_sum_rel(const T* __restrict__ h, const float* __restrict__ g, const TripleIds& ids,
                                                  const idx_t* __restrict__ order, idx_t b, idx_t e, idx_t p) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -237,10 +312,7 @@ __device__ __forceinline__ float4 triple_sum_rel(const T* __restrict__ h, const 
     if ((uint64_t)sj >= (uint64_t)ids.n || (uint64_t)oj >= (uint64_t)ids.n) continue;
     const float gj = g[j];
     const float4 a = ldrow4(h + sj * ids.d + 4 * p), c = ldrow4(h + oj * ids.d + 4 * p);
-    acc.x += (a.x * c.x) * gj;
-    acc.y += (a.y * c.y) * gj;
-    acc.z += (a.z * c.z) * gj;
-    acc.w += (a.w * c.w) * gj;
+    DEC::rel_term(acc, gj, a, c);
   }
   return acc;
 }
@@ -259,8 +331,8 @@ __device__ __forceinline__ idx_t triple_clamp(idx_t v, idx_t top) { return v < 0
 
 // one lane group per chunk of a list: `lists` lists with boundaries ptr and chunk offsets cptr, chunks of `chunk` positions.
 // REL: the lists are relations (grad_w), else nodes (grad_h).  part [max_chunks, d] floats.
-template <typename T, int G, bool REL>
-__global__ __launch_bounds__(kBlock) void HET_distmult_grad_chunks(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ g,
+template <typename DEC, typename T, int G, bool REL>
+__global__ __launch_bounds__(kBlock) void HET_triple_grad_chunks(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ g,
                                                                   TripleIds ids, const idx_t* __restrict__ ptr, const idx_t* __restrict__ list,
                                                                   const idx_t* __restrict__ cptr, idx_t lists, idx_t chunk, idx_t positions,
                                                                   idx_t max_chunks, float* __restrict__ part) {
@@ -275,15 +347,15 @@ __global__ __launch_bounds__(kBlock) void HET_distmult_grad_chunks(const T* __re
     const idx_t b = triple_clamp(ptr[v] + (c - cptr[v]) * chunk, end);
     const idx_t e = b + chunk < end ? b + chunk : end;
     for (idx_t p = l; p < np; p += G) {
-      const float4 acc = REL ? triple_sum_rel(h, g, ids, list, b, e, p) : triple_sum_slots(h, w, g, ids, list, b, e, p);
+      const float4 acc = REL ? triple_sum_rel<DEC>(h, g, ids, list, b, e, p) : triple_sum_slots<DEC>(h, w, g, ids, list, b, e, p);
       st4(part + c * ids.d + 4 * p, acc);
     }
   }
 }
 
 // one lane group per node: a list of at most L slots summed here, a longer one from its chunk partials in chunk order; every row stored
-template <typename T, int G>
-__global__ __launch_bounds__(kBlock) void HET_distmult_grad_h(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ g,
+template <typename DEC, typename T, int G>
+__global__ __launch_bounds__(kBlock) void HET_triple_grad_h(const T* __restrict__ h, const float* __restrict__ w, const float* __restrict__ g,
                                                              TripleIds ids, const idx_t* __restrict__ node_ptr, const idx_t* __restrict__ slots,
                                                              const idx_t* __restrict__ cptr, idx_t max_chunks, const float* __restrict__ part,
                                                              T* __restrict__ gh) {
@@ -314,16 +386,16 @@ __global__ __launch_bounds__(kBlock) void HET_distmult_grad_h(const T* __restric
           acc.w += q.w;
         }
       } else {
-        acc = triple_sum_slots(h, w, g, ids, slots, b, e, p);
+        acc = triple_sum_slots<DEC>(h, w, g, ids, slots, b, e, p);
       }
       strow4(gh + v * ids.d + 4 * p, acc);
     }
   }
 }
 
-// one lane group per relation: its chunk partials in chunk order
+// one lane group per relation: its chunk partials in chunk order (the same for every decoder)
 template <int G>
-__global__ __launch_bounds__(kBlock) void HET_distmult_grad_w(const idx_t* __restrict__ cptr, idx_t t, idx_t nr, idx_t d, idx_t max_chunks,
+__global__ __launch_bounds__(kBlock) void HET_triple_grad_w(const idx_t* __restrict__ cptr, idx_t t, idx_t nr, idx_t d, idx_t max_chunks,
                                                              const float* __restrict__ part, float* __restrict__ gw) {
   constexpr int GPB = kBlock / G;
   const int gi = threadIdx.x / G, l = threadIdx.x % G;
@@ -403,8 +475,8 @@ int64_t plan_temp_bytes(int64_t t, int64_t n, int64_t nr) {
   return align256((int64_t)m);
 }
 
-template <typename T>
-int distmult_score(const char* op, const T* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t t, int64_t n,
+template <typename DEC, typename T>
+int triple_score(const char* op, const T* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t t, int64_t n,
                    int64_t nr, int64_t d, float* score, het_stream stream) {
   int rc = triple_check_sizes(op, t, n, nr);
   if (rc != HET_OK) return rc;
@@ -416,10 +488,10 @@ int distmult_score(const char* op, const T* h, const float* w, const int64_t* s,
               "%s: misaligned pointer (h on %d-byte, w on 16-byte, ids on 8-byte, score on 4-byte boundaries)", op, (int)(4 * sizeof(T)));
   const int g = triple_lanes(d);
   hipStream_t st = (hipStream_t)stream;
-  HET_KTIME("HET_distmult_score", st);
-  HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_distmult_score<T, G>), dim3(triple_blocks(t, g)), dim3(kBlock), 0, st, h, w, (const idx_t*)s,
+  HET_KTIME(DEC::kScore, st);
+  HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_triple_score<DEC, T, G>), dim3(triple_blocks(t, g)), dim3(kBlock), 0, st, h, w, (const idx_t*)s,
                                                   (const idx_t*)r, (const idx_t*)o, (idx_t)t, (idx_t)n, (idx_t)nr, (idx_t)d, score));
-  HET_LAUNCH_CHECK("HET_distmult_score");
+  HET_LAUNCH_CHECK(DEC::kScore);
   return HET_OK;
 }
 
@@ -427,8 +499,8 @@ int64_t backward_workspace_bytes(int64_t t, int64_t nr, int64_t d) {
   return t == 0 ? 0 : (triple_max_node_chunks(t) + triple_max_rel_chunks(t, nr)) * d * 4;
 }
 
-template <typename T>
-int distmult_score_backward(const char* op, const T* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+template <typename DEC, typename T>
+int triple_score_backward(const char* op, const T* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
                             const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
                             const int64_t* rel_order, const int64_t* chunk_ptr, int64_t t, int64_t n, int64_t nr, int64_t d, T* grad_h,
                             float* grad_w, void* workspace, int64_t workspace_bytes, het_stream stream) {
@@ -461,30 +533,30 @@ int distmult_score_backward(const char* op, const T* h, const float* w, const in
   const idx_t* rcp = ncp ? ncp + n + 1 : nullptr;
   if (grad_h && n > 0) {
     if (t > 0) {
-      HET_KTIME("HET_distmult_grad_chunks_h", st);
-      HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_distmult_grad_chunks<T, G, false>), dim3(triple_blocks(node_chunks, g)), dim3(kBlock), 0, st,
+      HET_KTIME(DEC::kChunksH, st);
+      HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_triple_grad_chunks<DEC, T, G, false>), dim3(triple_blocks(node_chunks, g)), dim3(kBlock), 0, st,
                                                       h, w, grad_score, ids, (const idx_t*)node_ptr, (const idx_t*)node_slots, ncp, (idx_t)n,
                                                       (idx_t)kTripleListChunk, (idx_t)(2 * t), (idx_t)node_chunks, part_h));
-      HET_LAUNCH_CHECK("HET_distmult_grad_chunks");
+      HET_LAUNCH_CHECK(DEC::kChunks);
     }
-    HET_KTIME("HET_distmult_grad_h", st);
-    HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_distmult_grad_h<T, G>), dim3(triple_blocks(n, g)), dim3(kBlock), 0, st, h, w, grad_score, ids,
+    HET_KTIME(DEC::kGradH, st);
+    HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_triple_grad_h<DEC, T, G>), dim3(triple_blocks(n, g)), dim3(kBlock), 0, st, h, w, grad_score, ids,
                                                     (const idx_t*)node_ptr, (const idx_t*)node_slots, ncp, (idx_t)node_chunks,
                                                     (const float*)part_h, grad_h));
-    HET_LAUNCH_CHECK("HET_distmult_grad_h");
+    HET_LAUNCH_CHECK(DEC::kGradH);
   }
   if (grad_w && nr > 0) {
     if (t > 0) {
-      HET_KTIME("HET_distmult_grad_chunks_w", st);
-      HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_distmult_grad_chunks<T, G, true>), dim3(triple_blocks(rel_chunks, g)), dim3(kBlock), 0, st,
+      HET_KTIME(DEC::kChunksW, st);
+      HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_triple_grad_chunks<DEC, T, G, true>), dim3(triple_blocks(rel_chunks, g)), dim3(kBlock), 0, st,
                                                       h, w, grad_score, ids, (const idx_t*)rel_ptr, (const idx_t*)rel_order, rcp, (idx_t)nr,
                                                       (idx_t)kTripleRelChunk, (idx_t)t, (idx_t)rel_chunks, part_w));
-      HET_LAUNCH_CHECK("HET_distmult_grad_chunks");
+      HET_LAUNCH_CHECK(DEC::kChunks);
     }
-    HET_KTIME("HET_distmult_grad_w", st);
-    HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_distmult_grad_w<G>), dim3(triple_blocks(nr, g)), dim3(kBlock), 0, st, rcp, (idx_t)t, (idx_t)nr,
+    HET_KTIME(DEC::kGradW, st);
+    HET_DISPATCH_TRIPLE_LANES(g, hipLaunchKernelGGL((HET_triple_grad_w<G>), dim3(triple_blocks(nr, g)), dim3(kBlock), 0, st, rcp, (idx_t)t, (idx_t)nr,
                                                     (idx_t)d, (idx_t)rel_chunks, (const float*)part_w, grad_w));
-    HET_LAUNCH_CHECK("HET_distmult_grad_w");
+    HET_LAUNCH_CHECK(DEC::kGradW);
   }
   return HET_OK;
 }
@@ -593,12 +665,12 @@ extern "C" int het_triple_plan(const int64_t* s, const int64_t* r, const int64_t
 
 extern "C" int het_distmult_score(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
                                   int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream) {
-  return distmult_score("het_distmult_score", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
+  return triple_score<DistMultTerms>("het_distmult_score", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
 }
 
 extern "C" int het_distmult_score_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
                                        int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream) {
-  return distmult_score("het_distmult_score_bf16", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
+  return triple_score<DistMultTerms>("het_distmult_score_bf16", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
 }
 
 extern "C" int64_t het_distmult_score_backward_workspace(int64_t num_triples, int64_t num_rels, int64_t dim) {
@@ -615,7 +687,7 @@ extern "C" int het_distmult_score_backward(const float* h, const float* w, const
                                            const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes,
                                            int64_t num_rels, int64_t dim, float* grad_h, float* grad_w, void* workspace, int64_t workspace_bytes,
                                            het_stream stream) {
-  return distmult_score_backward("het_distmult_score_backward", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order, chunk_ptr,
+  return triple_score_backward<DistMultTerms>("het_distmult_score_backward", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order, chunk_ptr,
                                  num_triples, num_nodes, num_rels, dim, grad_h, grad_w, workspace, workspace_bytes, stream);
 }
 
@@ -624,6 +696,35 @@ extern "C" int het_distmult_score_backward_bf16(const het_bf16* h, const float* 
                                                 const int64_t* rel_ptr, const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples,
                                                 int64_t num_nodes, int64_t num_rels, int64_t dim, het_bf16* grad_h, float* grad_w, void* workspace,
                                                 int64_t workspace_bytes, het_stream stream) {
-  return distmult_score_backward("het_distmult_score_backward_bf16", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order, chunk_ptr,
+  return triple_score_backward<DistMultTerms>("het_distmult_score_backward_bf16", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order, chunk_ptr,
                                  num_triples, num_nodes, num_rels, dim, grad_h, grad_w, workspace, workspace_bytes, stream);
+}
+
+// ---- ComplEx: the same entries over the same plan and workspace (dim a multiple of 4: whole complex numbers in every piece) ----------
+extern "C" int het_complex_score(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                                 int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream) {
+  return triple_score<ComplExTerms>("het_complex_score", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
+}
+
+extern "C" int het_complex_score_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                                      int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream) {
+  return triple_score<ComplExTerms>("het_complex_score_bf16", h, w, s, r, o, num_triples, num_nodes, num_rels, dim, score, stream);
+}
+
+extern "C" int het_complex_score_backward(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                                          const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
+                                          const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes,
+                                          int64_t num_rels, int64_t dim, float* grad_h, float* grad_w, void* workspace, int64_t workspace_bytes,
+                                          het_stream stream) {
+  return triple_score_backward<ComplExTerms>("het_complex_score_backward", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order,
+                                             chunk_ptr, num_triples, num_nodes, num_rels, dim, grad_h, grad_w, workspace, workspace_bytes, stream);
+}
+
+extern "C" int het_complex_score_backward_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                                               const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots,
+                                               const int64_t* rel_ptr, const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples,
+                                               int64_t num_nodes, int64_t num_rels, int64_t dim, het_bf16* grad_h, float* grad_w, void* workspace,
+                                               int64_t workspace_bytes, het_stream stream) {
+  return triple_score_backward<ComplExTerms>("het_complex_score_backward_bf16", h, w, s, r, o, grad_score, node_ptr, node_slots, rel_ptr, rel_order,
+                                             chunk_ptr, num_triples, num_nodes, num_rels, dim, grad_h, grad_w, workspace, workspace_bytes, stream);
 }

@@ -1705,6 +1705,102 @@ def triple_rank(h, w, anchor, rel, truth, pair_query=None, pair_cand=None, node_
     return out[0], out[1], out[2], bad
 
 
+# ---- the ComplEx head (het_amd/linkpred.py ComplExDecoder, complex_rank; csrc/triple_score.hip, csrc/triple_rank.hip) ----
+def complex_ok(h, w) -> bool:
+    """Whether the ComplEx score kernels take these tables: what ``distmult_ok`` asks (a width of triple_params() is a multiple of 4,
+    so every 16-byte piece of a row holds two whole complex numbers: column 2k the real, 2k + 1 the imaginary part)."""
+    return distmult_ok(h, w)
+
+
+def _complex_chk(name, h, w, s, r, o):
+    if not complex_ok(h, w):
+        raise _lib.HetError(f"{name}: expected contiguous float32 or bfloat16 GPU rows h [N, D], 16-byte (bf16: 8-byte) aligned, and float32 "
+                            f"w [R, D] on the same device with D a multiple of 4 in the widths of triple_params(), got {h.dtype} "
+                            f"{tuple(h.shape)} on {h.device}{'' if h.is_contiguous() else ' (non-contiguous)'} and {w.dtype} {tuple(w.shape)} "
+                            f"on {w.device}")
+    _triple_ids_chk(name, h, s, r, o)
+
+
+def complex_score(h, w, s, r, o):
+    """score [T] fp32 = sum_k Re(h[s]_k * w[r]_k * conj(h[o]_k)) over the D / 2 complex components of the rows (het_complex_score /
+    _bf16; one launch); +0 for a triple with an id outside its table."""
+    _complex_chk("complex_score", h, w, s, r, o)
+    return _complex_score(h, w, s, r, o)
+
+
+def _complex_score(h, w, s, r, o):
+    T = s.shape[0]
+    score = torch.empty(T, dtype=torch.float32, device=h.device)
+    if T:
+        _call(h, "het_complex_score_bf16" if h.dtype == torch.bfloat16 else "het_complex_score", _p(h), _p(w), _p(s), _p(r), _p(o), T,
+              h.shape[0], w.shape[0], h.shape[1], _p(score), _stream(h))
+    return score
+
+
+def complex_score_backward(h, w, s, r, o, grad_score, plan: TriplePlan, want_h: bool = True, want_w: bool = True):
+    """(grad_h [N, D] in h's dtype or None, grad_w [R, D] fp32 or None) of het_complex_score_backward / _bf16 for ``grad_score`` [T] fp32
+    and the batch's ``plan`` (triple_plan, the one the DistMult head uses): the same lists, chunks and orders."""
+    _complex_chk("complex_score_backward", h, w, s, r, o)
+    _chk("complex_score_backward", (grad_score,), tuple(plan[:6]))
+    T, N, R = s.shape[0], h.shape[0], w.shape[0]
+    if (grad_score.shape != (T,) or grad_score.device != h.device or (plan.num_nodes, plan.num_rels) != (N, R)
+            or plan.node_ptr.shape != (N + 1,) or plan.node_slots.shape != (2 * T,) or plan.rel_ptr.shape != (R + 1,)
+            or plan.rel_order.shape != (T,) or plan.chunk_ptr.shape != (N + R + 2,) or any(t.device != h.device for t in plan[:6])):
+        raise _lib.HetError(f"complex_score_backward: grad_score [{T}] and the plan of these {T} triples over {N} nodes and {R} relations on "
+                            f"{h.device} expected, got {tuple(grad_score.shape)} and a plan for {plan.num_nodes} nodes, {plan.num_rels} "
+                            f"relations, {plan.rel_order.shape[0]} triples")
+    return _complex_score_backward(h, w, s, r, o, grad_score, plan, want_h, want_w)
+
+
+def _complex_score_backward(h, w, s, r, o, grad_score, plan, want_h, want_w):
+    T, (N, D), R = s.shape[0], h.shape, w.shape[0]
+    grad_h = torch.empty_like(h) if want_h else None
+    grad_w = torch.empty_like(w) if want_w else None
+    if not (want_h or want_w):
+        return None, None
+    ws, nbytes = _workspace(h, "het_distmult_score_backward_workspace", T, R, D)
+    _call(h, "het_complex_score_backward_bf16" if h.dtype == torch.bfloat16 else "het_complex_score_backward", _p(h), _p(w), _p(s), _p(r),
+          _p(o), _p(grad_score), _p(plan.node_ptr), _p(plan.node_slots), _p(plan.rel_ptr), _p(plan.rel_order), _p(plan.chunk_ptr), T, N, R, D,
+          _p(grad_h), _p(grad_w), _p(ws), nbytes, _stream(h))
+    return grad_h, grad_w
+
+
+def complex_rank(h, w, anchor, rel, truth, side, pair_query=None, pair_cand=None, node_type_offsets=None):
+    """(greater, equal, cands) int32 [Q] and bad int64 [1] of het_complex_rank / _bf16: ``triple_rank`` with the ComplEx score (the rule
+    in include/het_amd.h).  ``side`` [Q] int64: 0 ranks tails (the anchor is the head), 1 ranks heads (the anchor is the tail); any
+    other value makes the query bad.  Nothing is read back."""
+    if not triple_rank_ok(h, w):
+        raise _lib.HetError(f"complex_rank: expected contiguous float32 or bfloat16 GPU rows h [N, D], 16-byte (bf16: 8-byte) aligned, and "
+                            f"float32 w [R, D] on the same device with D a multiple of 4 in the widths of triple_rank_params(), got {h.dtype} "
+                            f"{tuple(h.shape)} on {h.device}{'' if h.is_contiguous() else ' (non-contiguous)'} and {w.dtype} "
+                            f"{tuple(w.shape)} on {w.device}")
+    _triple_ids_chk("complex_rank", h, anchor, rel, truth, side)
+    if (pair_query is None) != (pair_cand is None):
+        raise _lib.HetError("complex_rank: pair_query and pair_cand come together")
+    NP = 0
+    if pair_query is not None:
+        _triple_ids_chk("complex_rank", h, pair_query, pair_cand)
+        NP = pair_query.shape[0]
+    offs, ntypes = None, 0
+    if node_type_offsets is not None:
+        offs = node_type_offsets
+        if not (offs.is_cuda and offs.device == h.device and offs.dtype == torch.int64 and offs.dim() == 1 and offs.numel() >= 2
+                and offs.is_contiguous()):
+            raise _lib.HetError(f"complex_rank: node_type_offsets is a contiguous int64 tensor [num_types + 1] on {h.device}, got "
+                                f"{offs.dtype} {tuple(offs.shape)} on {offs.device}")
+        ntypes = offs.numel() - 1
+    Q, (N, D), R = anchor.shape[0], h.shape, w.shape[0]
+    out = torch.empty(3, Q, dtype=torch.int32, device=h.device)
+    bad = torch.empty(1, dtype=torch.int64, device=h.device)
+    if Q == 0:
+        return out[0], out[1], out[2], bad.zero_()
+    ws, nbytes = _workspace(h, "het_triple_rank_workspace", Q, NP, N, D)
+    _call(h, "het_complex_rank_bf16" if h.dtype == torch.bfloat16 else "het_complex_rank", _p(h), _p(w), _p(anchor), _p(rel), _p(truth),
+          _p(side), Q, _p(pair_query) if NP else None, _p(pair_cand) if NP else None, NP, _p(offs), ntypes, N, R, D, _p(out[0]), _p(out[1]),
+          _p(out[2]), _p(bad), _p(ws), nbytes, _stream(h))
+    return out[0], out[1], out[2], bad
+
+
 def rgat_backward_compact(groupings, feat_c, el_c, er_c, sum, ret, gradout, grad_feat_c, grad_el_c, grad_er_c, slope,
                           fold_attn_l=None, row_rel_ptrs=None, grad_bias=None, bias_rows=0, runs=None, drow_nodes=None,
                           grad_attn_l=None, finish_attn_grad=True):

@@ -1,4 +1,4 @@
-"""Link prediction with a DistMult head and keyed negatives (opt-in; csrc/triple_score.hip).
+"""Link prediction with a DistMult or a ComplEx head and keyed negatives (opt-in; csrc/triple_score.hip).
 
 The rule.  All key arithmetic is uint64, wrapping; ``sm`` and the stream are those of the keyed sampler and keyed dropout
 (DESIGN.md 4.10): ``stream = sm(seed ^ sm(draw))``.
@@ -70,6 +70,37 @@ has the bits of the true node's row ties with it exactly.  The three counts are 
 every call.  The ``[Q, N]`` score matrix never exists.  **The filter serves evaluation only: training negatives stay unfiltered.**
 The pairs (query, excluded candidate) of a batch come from two ``searchsorted`` and one expansion in torch over a ``FilterIndex``
 built once; the expansion needs the pair count on the host -- **the one read-back of a ranking call** (none without a filter).
+
+The ComplEx head (``ComplExDecoder``, ``complex_rank``).  DistMult's score is symmetric in s and o: it gives a triple
+and its reverse the same score to the bit.  ComplEx is the smallest trilinear decoder without that defect.  Layout: ``h [N, D]`` and
+``w [R, D]`` with D even; column 2k is the real part of component k and column 2k + 1 the imaginary part
+(``torch.view_as_complex(x.view(-1, D // 2, 2))``).  With ``a = h[s_j]``, ``b = w[r_j]``, ``c = h[o_j]``, per component (a_r, a_i) and
+so on, and ``g = grad_score_j``::
+
+    score_j    = sum_k Re(a_k * b_k * conj(c_k))
+               = sum_k (a_r b_r - a_i b_i) c_r + (a_r b_i + a_i b_r) c_i
+    grad a_r  += g (b_r c_r + b_i c_i)      grad a_i += g (b_r c_i - b_i c_r)      (slot side 0: v is the head s_j)
+    grad c_r  += g (a_r b_r - a_i b_i)      grad c_i += g (a_r b_i + a_i b_r)      (slot side 1: v is the tail o_j)
+    grad b_r  += g (a_r c_r + a_i c_i)      grad b_i += g (a_r c_i - a_i c_r)
+
+Everything else is the DistMult head's, to the letter: slots ascending ``2 j + side``, lists longer than L summed in chunks of L with the
+chunk sums added in chunk order, grad_w in chunks of the relation chunk, every grad_h and grad_w row written exactly once (+0 where a
+list is empty), a bf16 grad_h rounded once after the whole sum, a bad id **counted, not asserted** and never an address, a triple with
+``s == o`` in both slots, no float atomics, no zero-fill, no read-back, the same bits on every call.  The plan and the workspaces are the
+DistMult head's own.  The native widths are the multiples of 4 of ``kernels.triple_params()``: a 16-byte piece of a row is two whole
+complex numbers.
+
+ComplEx ranking.  A query is ``(a_j, r_j, t_j, side_j)``: side 0 ranks tails (the anchor is the head s, the candidates stand in o's
+place), side 1 ranks heads (the anchor is the tail o, the candidates stand in s's place); any other side makes the query bad.  Unlike
+DistMult the two sides need different q; with ``x = h[a_j]``, ``b = w[r_j]``::
+
+    side 0:   q_j[2k] = fl32(fl32(x_r b_r) - fl32(x_i b_i))     q_j[2k+1] = fl32(fl32(x_r b_i) + fl32(x_i b_r))
+    side 1:   q_j[2k] = fl32(fl32(b_r x_r) + fl32(b_i x_i))     q_j[2k+1] = fl32(fl32(b_r x_i) - fl32(b_i x_r))
+    score_j(c) = the fp32 fma chain over ascending d, from +0:  acc = fmaf(q_j[d], h[c, d], acc);   p_j = score_j(t_j), the same chain
+
+Each q element is three separately rounded fp32 operations, never a fused multiply-add: float32 arithmetic in numpy or torch gives the
+same bits.  The run, the exclusions, the three counts, the bad queries and the metrics follow the DistMult rule above unchanged; the
+rank pass is the same launch (it reads q, never w).
 """
 from __future__ import annotations
 
@@ -176,6 +207,26 @@ def distmult_score_torch(h, w, s, r, o):
     return th.where(ok, score, th.zeros((), dtype=acc, device=h.device)), (~ok).sum().reshape(1)
 
 
+def _complex_parts(x):
+    return x[..., 0::2], x[..., 1::2]
+
+
+def complex_score_torch(h, w, s, r, o):
+    """(score [T] fp32 (fp64 for fp64 tables), bad [1] int64) of the module's ComplEx rule as a differentiable torch composition:
+    correct, not fast -- three [T, D] gathers and a dozen [T, D / 2] products kept for the backward.  The CPU and odd-dtype fallback."""
+    N, R = h.shape[0], w.shape[0]
+    if h.dim() != 2 or w.dim() != 2 or h.shape[1] != w.shape[1] or h.shape[1] % 2:
+        raise ValueError(f"complex_score_torch: h [N, D] and w [R, D] with D even, got {tuple(h.shape)} and {tuple(w.shape)}")
+    ok = (s >= 0) & (s < N) & (o >= 0) & (o < N) & (r >= 0) & (r < R)
+    zero = th.zeros_like(s)
+    acc = th.float64 if h.dtype == th.float64 else th.float32
+    hf = h.to(acc)  # (widened before the gathers: the backward's index_add_ then sums in fp32 and a bf16 grad_h is rounded once)
+    (ar, ai), (cr, ci) = _complex_parts(hf[th.where(ok, s, zero)]), _complex_parts(hf[th.where(ok, o, zero)])
+    br, bi = _complex_parts(w[th.where(ok, r, zero)].to(acc))
+    score = ((ar * br - ai * bi) * cr + (ar * bi + ai * br) * ci).sum(-1)
+    return th.where(ok, score, th.zeros((), dtype=acc, device=h.device)), (~ok).sum().reshape(1)
+
+
 def _aligned_rows(t):
     t = t.contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=th.contiguous_format)
@@ -191,32 +242,57 @@ class DistMultScoreFunction(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, w, s, r, o):
-        hd, wd = _aligned_rows(h.detach()), _aligned_rows(w.detach())  # (a strided or misaligned table: the kernels run on a copy)
-        ids = tuple(t.detach().to(th.int64).contiguous() for t in (s, r, o))
-        _k._distmult_chk("DistMultScoreFunction", hd, wd, *ids)
-        want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        score = _k._distmult_score(hd, wd, *ids)
-        if want_h or want_w:
-            plan = _k._triple_plan(*ids, hd.shape[0], wd.shape[0])
-            bad = plan.bad
-            ctx.ids, ctx.plan = ids, plan  # (index tensors: nothing autograd tracks, and nothing an inference-mode id would break)
-            ctx.save_for_backward(hd, wd)
-        else:
-            bad = _count_bad(*ids, hd.shape[0], wd.shape[0])
-        ctx.mark_non_differentiable(bad)
-        ctx.set_materialize_grads(False)
-        return score, bad
+        return _score_forward(ctx, "DistMultScoreFunction", _k._distmult_chk, _k._distmult_score, h, w, s, r, o)
 
     @staticmethod
     @th.autograd.function.once_differentiable
     def backward(ctx, grad_score, _grad_bad):
-        want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_score is None or not (want_h or want_w):
-            return None, None, None, None, None
-        hd, wd = ctx.saved_tensors
-        g = grad_score.detach().to(device=hd.device, dtype=th.float32).contiguous()
-        grad_h, grad_w = _k._distmult_score_backward(hd, wd, *ctx.ids, g, ctx.plan, want_h, want_w)
-        return grad_h, grad_w, None, None, None
+        return _score_backward(ctx, _k._distmult_score_backward, grad_score)
+
+
+class ComplExScoreFunction(th.autograd.Function):
+    """(score, bad) = the ComplEx scores of the triples (s, r, o) (the module's rule) as one autograd node on the HIP kernels, with
+    DistMultScoreFunction's contract: one launch forward, the plan built only when a gradient is needed, a node-major and
+    relation-major backward without float atomics; saved: h, w, the ids and the plan -- nothing of T D elements.  ``bad`` is not
+    differentiable; tensors the kernels do not take raise HetError; a double backward is refused (once_differentiable)."""
+
+    @staticmethod
+    def forward(ctx, h, w, s, r, o):
+        return _score_forward(ctx, "ComplExScoreFunction", _k._complex_chk, _k._complex_score, h, w, s, r, o)
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad_score, _grad_bad):
+        return _score_backward(ctx, _k._complex_score_backward, grad_score)
+
+
+def _score_forward(ctx, name, chk, score_fn, h, w, s, r, o):
+    """The forward of both score nodes: ``chk`` and ``score_fn`` are the decoder's check and score launch of het_amd.kernels."""
+    hd, wd = _aligned_rows(h.detach()), _aligned_rows(w.detach())  # (a strided or misaligned table: the kernels run on a copy)
+    ids = tuple(t.detach().to(th.int64).contiguous() for t in (s, r, o))
+    chk(name, hd, wd, *ids)
+    want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    score = score_fn(hd, wd, *ids)
+    if want_h or want_w:
+        plan = _k._triple_plan(*ids, hd.shape[0], wd.shape[0])
+        bad = plan.bad
+        ctx.ids, ctx.plan = ids, plan  # (index tensors: nothing autograd tracks, and nothing an inference-mode id would break)
+        ctx.save_for_backward(hd, wd)
+    else:
+        bad = _count_bad(*ids, hd.shape[0], wd.shape[0])
+    ctx.mark_non_differentiable(bad)
+    ctx.set_materialize_grads(False)
+    return score, bad
+
+
+def _score_backward(ctx, backward_fn, grad_score):
+    want_h, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if grad_score is None or not (want_h or want_w):
+        return None, None, None, None, None
+    hd, wd = ctx.saved_tensors
+    g = grad_score.detach().to(device=hd.device, dtype=th.float32).contiguous()
+    grad_h, grad_w = backward_fn(hd, wd, *ctx.ids, g, ctx.plan, want_h, want_w)
+    return grad_h, grad_w, None, None, None
 
 
 class DistMultDecoder(nn.Module):
@@ -232,6 +308,9 @@ class DistMultDecoder(nn.Module):
     (DistMultScoreFunction); everything else -- CPU tensors, fp16 / fp64, a ``dim`` that is no multiple of 4 -- and every call of a
     module built with ``native=False`` (an ``h`` that needs a double backward) takes the torch composition of the same rule: correct, not
     faster."""
+
+    _function = DistMultScoreFunction  # (what ComplExDecoder replaces: the native node, the torch composition, the ranking call)
+    _score_torch = staticmethod(distmult_score_torch)
 
     def __init__(self, num_rels: int, dim: int, check_ids: bool = False, native: bool = True):
         super().__init__()
@@ -250,33 +329,57 @@ class DistMultDecoder(nn.Module):
                 and w.dtype == th.float32 and _k.triple_width_ok(h.shape[1]) and h.shape[0] < 2 ** 31 - 1 and _native_available())
 
     def forward(self, h, s, r, o):
+        name = type(self).__name__
         if h.dim() != 2 or h.shape[1] != self.dim:
-            raise ValueError(f"DistMultDecoder: h [N, {self.dim}], got {tuple(h.shape)}")
+            raise ValueError(f"{name}: h [N, {self.dim}], got {tuple(h.shape)}")
         if not (s.dim() == r.dim() == o.dim() == 1 and s.shape == r.shape == o.shape):
-            raise ValueError(f"DistMultDecoder: s, r and o are 1-d id tensors of one length, got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(o.shape)}")
+            raise ValueError(f"{name}: s, r and o are 1-d id tensors of one length, got {tuple(s.shape)}, {tuple(r.shape)}, {tuple(o.shape)}")
         if any(t.is_floating_point() or t.dtype == th.bool for t in (s, r, o)):
-            raise ValueError("DistMultDecoder: integer ids expected")
+            raise ValueError(f"{name}: integer ids expected")
         if s.shape[0] >= 2 ** 30:
-            raise ValueError(f"DistMultDecoder: {s.shape[0]} triples (fewer than 2^30)")
+            raise ValueError(f"{name}: {s.shape[0]} triples (fewer than 2^30)")
         if self.takes_native(h):
-            score, bad = DistMultScoreFunction.apply(h, self.w_relation, s, r, o)
+            score, bad = self._function.apply(h, self.w_relation, s, r, o)
         else:
-            score, bad = distmult_score_torch(h, self.w_relation, *(t.to(th.int64) for t in (s, r, o)))
+            score, bad = self._score_torch(h, self.w_relation, *(t.to(th.int64) for t in (s, r, o)))
             score = score.to(th.float32)
         self.last_bad = bad.detach()
         if self.check_ids:
             n_bad = int(bad)
             if n_bad:
-                raise ValueError(f"DistMultDecoder: {n_bad} triple(s) have an id outside [0, {h.shape[0]}) nodes or [0, {self.num_rels}) relations")
+                raise ValueError(f"{name}: {n_bad} triple(s) have an id outside [0, {h.shape[0]}) nodes or [0, {self.num_rels}) relations")
         return score
 
     def rank(self, h, s, r, o, **kw):
         """``distmult_rank(h, self.w_relation, s, r, o, **kw)``: the filtered ranks of the triples under this head (no gradient; a module
         built with ``native=False`` takes the torch composition)."""
         if h.dim() != 2 or h.shape[1] != self.dim:
-            raise ValueError(f"DistMultDecoder: h [N, {self.dim}], got {tuple(h.shape)}")
+            raise ValueError(f"{type(self).__name__}: h [N, {self.dim}], got {tuple(h.shape)}")
         kw.setdefault("native", self.native)
-        return distmult_rank(h, self.w_relation, s, r, o, **kw)
+        return self._rank(h, self.w_relation, s, r, o, **kw)
+
+    @staticmethod
+    def _rank(h, w, s, r, o, **kw):
+        return distmult_rank(h, w, s, r, o, **kw)
+
+
+class ComplExDecoder(DistMultDecoder):
+    """The ComplEx head: DistMultDecoder's surface (``forward(h, s, r, o)``, ``last_bad``, ``check_ids``, ``takes_native``, ``rank``,
+    ``w_relation`` [num_rels, dim] fp32 xavier-uniform) with the module's ComplEx rule: ``dim`` is even, column 2k the real and
+    2k + 1 the imaginary part of component k, and ``score(s, r, o) != score(o, r, s)`` in general.  Rows of a native width (a
+    multiple of 4, ``kernels.complex_ok``) take the HIP kernels (ComplExScoreFunction); everything else, and ``native=False``, takes
+    ``complex_score_torch``."""
+    _function = ComplExScoreFunction
+    _score_torch = staticmethod(complex_score_torch)
+
+    def __init__(self, num_rels: int, dim: int, check_ids: bool = False, native: bool = True):
+        if int(dim) % 2:
+            raise ValueError(f"ComplExDecoder: dim={dim} (even: pairs of a real and an imaginary column)")
+        super().__init__(num_rels, dim, check_ids=check_ids, native=native)
+
+    @staticmethod
+    def _rank(h, w, s, r, o, **kw):
+        return complex_rank(h, w, s, r, o, **kw)
 
 
 def link_prediction_loss(scores, num_pos: int):
@@ -364,7 +467,7 @@ class FilterIndex:
         return qi, self._vals[pos]
 
 
-def _rank_queries(s, r, o, sides):
+def _rank_queries(s, r, o, sides, name="distmult_rank"):
     """(anchor, rel, truth, head) of the rule: the tail queries, the head queries, or the tail queries followed by the head queries."""
     f = th.zeros(s.shape[0], dtype=th.bool, device=s.device)
     if sides == "tail":
@@ -373,11 +476,12 @@ def _rank_queries(s, r, o, sides):
         return o, r, s, ~f
     if sides == "both":
         return th.cat([s, o]), th.cat([r, r]), th.cat([o, s]), th.cat([f, ~f])
-    raise ValueError(f"distmult_rank: sides is 'both', 'tail' or 'head', got {sides!r}")
+    raise ValueError(f"{name}: sides is 'both', 'tail' or 'head', got {sides!r}")
 
 
-def _rank_prepare(name, h, w, s, r, o, sides, filter, node_type_offsets):
-    """Checks, then (anchor, rel, truth, lo, hi, bad, offsets, pair_query, pair_cand) on h's device."""
+def _rank_prepare(name, h, w, s, r, o, sides, filter, node_type_offsets, with_head=False):
+    """Checks, then (anchor, rel, truth, lo, hi, bad, offsets, pair_query, pair_cand) on h's device; ``with_head``: and the side of every
+    query (bool: True ranks heads)."""
     if h.dim() != 2 or w.dim() != 2 or h.shape[1] != w.shape[1] or not (h.is_floating_point() and w.is_floating_point()):
         raise ValueError(f"{name}: floating-point h [N, D] and w [R, D], got {h.dtype} {tuple(h.shape)} and {w.dtype} {tuple(w.shape)}")
     if not (s.dim() == r.dim() == o.dim() == 1 and s.shape == r.shape == o.shape):
@@ -389,7 +493,7 @@ def _rank_prepare(name, h, w, s, r, o, sides, filter, node_type_offsets):
         raise ValueError(f"{name}: h on {dev} and w on {w.device}")
     if not (N < 2 ** 31 - 1 and R < 2 ** 31 - 1 and 2 * s.shape[0] < 2 ** 30):
         raise ValueError(f"{name}: {N} nodes, {R} relations (both below 2^31 - 1), {s.shape[0]} triples (fewer than 2^29)")
-    a, rr, t, head = _rank_queries(*(x.detach().to(device=dev, dtype=th.int64) for x in (s, r, o)), sides)
+    a, rr, t, head = _rank_queries(*(x.detach().to(device=dev, dtype=th.int64) for x in (s, r, o)), sides, name)
     a, rr, t = a.contiguous(), rr.contiguous(), t.contiguous()
     offs = None
     if node_type_offsets is not None:
@@ -408,15 +512,30 @@ def _rank_prepare(name, h, w, s, r, o, sides, filter, node_type_offsets):
         if not isinstance(filter, FilterIndex) or (filter.num_nodes, filter.num_rels) != (N, R):
             raise ValueError(f"{name}: filter is a FilterIndex over {N} nodes and {R} relations")
         pq, pc = filter.to(dev).pairs(a, rr, head)
+    if with_head:
+        return a, rr, t, lo, hi, bad, offs, pq, pc, head
     return a, rr, t, lo, hi, bad, offs, pq, pc
 
 
-def _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, chunk):
+def _complex_q(x, b, head):
+    """q of the ComplEx ranking rule: every product and every sum is its own torch operation, so each is rounded on its own."""
+    (xr, xi), (br, bi) = _complex_parts(x), _complex_parts(b)
+    q = th.empty_like(x)
+    q[:, 0::2] = th.where(head[:, None], br * xr + bi * xi, xr * br - xi * bi)
+    q[:, 1::2] = th.where(head[:, None], br * xi - bi * xr, xr * bi + xi * br)
+    return q
+
+
+def _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, chunk, head=None):
+    """``head`` (bool [Q]): the ComplEx rule's q for these sides; None: DistMult's."""
     acc = th.float64 if h.dtype == th.float64 else th.float32
     N, Q, dev = h.shape[0], a.shape[0], h.device
     zero = th.zeros_like(a)
     lo, hi = th.where(bad, zero, lo), th.where(bad, zero, hi)
-    q = h[th.where(bad, zero, a)].to(acc) * w[th.where(bad, zero, rr)].to(acc)  # (the rounded product)
+    if head is None:
+        q = h[th.where(bad, zero, a)].to(acc) * w[th.where(bad, zero, rr)].to(acc)  # (the rounded product)
+    else:
+        q = _complex_q(h[th.where(bad, zero, a)].to(acc), w[th.where(bad, zero, rr)].to(acc), head)
     p = (q * h[th.where(bad, zero, t)].to(acc)).sum(-1) if N else th.zeros(Q, dtype=acc, device=dev)
     out = th.zeros(3, Q, dtype=th.int64, device=dev)
     for c0 in range(0, N, chunk):
@@ -476,6 +595,47 @@ def distmult_rank(h, w, s, r, o, *, sides: str = "both", filter=None, node_type_
                     g, e, c = g[inv], e[inv], c[inv]
                 return RankResult(g, e, c, bad)
         return _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, 65536)
+
+
+def complex_rank_torch(h, w, s, r, o, *, sides: str = "both", filter=None, node_type_offsets=None, chunk: int = 65536):
+    """``complex_rank`` as a torch composition of the same rule, chunked over ``chunk`` candidates: ``distmult_rank_torch`` with the
+    ComplEx rule's q (three separately rounded operations per element).  Correct, not fast; the order of the sums is the matmul's."""
+    with th.no_grad():
+        h, w = h.detach(), w.detach()
+        if h.dim() == 2 and h.shape[1] % 2:
+            raise ValueError(f"complex_rank_torch: h [N, D] with D even, got {tuple(h.shape)}")
+        a, rr, t, lo, hi, bad, _, pq, pc, head = _rank_prepare("complex_rank_torch", h, w, s, r, o, sides, filter, node_type_offsets, True)
+        return _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, max(1, int(chunk)), head)
+
+
+def complex_rank(h, w, s, r, o, *, sides: str = "both", filter=None, node_type_offsets=None, native: bool = True):
+    """The filtered ranks of the triples (s, r, o) under the ComplEx score (the module's rule): ``distmult_rank``'s arguments, routes and
+    ``RankResult``.  A tail query ranks c by score(s, r, c), a head query by score(c, r, o): the two differ, so the prelude forms q by
+    the side of the query; the sort of the pairs and the MFMA pass are the DistMult head's launches.  ``FilterIndex.pairs`` is already
+    directional.  Everything the kernels do not take, and ``native=False``, takes ``complex_rank_torch``."""
+    with th.no_grad():
+        h, w = h.detach(), w.detach()
+        if h.dim() == 2 and h.shape[1] % 2:
+            raise ValueError(f"complex_rank: h [N, D] with D even, got {tuple(h.shape)}")
+        a, rr, t, lo, hi, bad, offs, pq, pc, head = _rank_prepare("complex_rank", h, w, s, r, o, sides, filter, node_type_offsets, True)
+        if (native and h.is_cuda and h.dtype in (th.float32, th.bfloat16) and w.dtype == th.float32 and _native_available()):
+            hd, wd = _aligned_rows(h), _aligned_rows(w)
+            if _k.triple_rank_ok(hd, wd):
+                if pq is not None and pq.numel() == 0:
+                    pq = pc = None
+                side = head.to(th.int64)
+                inv = None
+                if offs is not None and a.shape[0] > 1:  # queries of one type side by side: a query tile then skips the other types' tiles
+                    order = th.sort(lo, stable=True).indices
+                    inv = th.empty_like(order)
+                    inv[order] = th.arange(order.shape[0], dtype=th.int64, device=order.device)
+                    a, rr, t, side = a[order], rr[order], t[order], side[order]
+                    pq = None if pq is None else inv[pq]
+                g, e, c, _ = _k.complex_rank(hd, wd, a, rr, t, side, pq, pc, offs)
+                if inv is not None:
+                    g, e, c = g[inv], e[inv], c[inv]
+                return RankResult(g, e, c, bad)
+        return _rank_torch(h, w, a, rr, t, lo, hi, bad, pq, pc, 65536, head)
 
 
 def ranking_metrics(result, ks=(1, 3, 10)):

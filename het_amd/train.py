@@ -158,6 +158,10 @@ def add_generic_RGNN_args(p: argparse.ArgumentParser, default_logfilename: str):
                    help="--link_prediction: after the last epoch rank P keyed positive edges on both sides against every node of the "
                         "true node's type, filtered on the graph's own edges, and log MRR, mean rank and Hits@1/3/10 "
                         "(het_amd/linkpred.py distmult_rank; the filter serves evaluation only, training negatives stay unfiltered)")
+    p.add_argument("--decoder", choices=("distmult", "complex"), default="distmult",
+                   help="--link_prediction: the head that scores the triples -- distmult (symmetric in head and tail) or complex "
+                        "(ComplEx: tells a triple from its reverse; --num_classes is the even row width, a multiple of 4 for the HIP "
+                        "kernels; het_amd/linkpred.py ComplExDecoder)")
 
 
 def load_graph(args) -> IntegratedCOO:
@@ -407,6 +411,11 @@ def main(argv=None):
         raise SystemExit("--link_prediction is an option of training: --inference scores no triples")
     if args.link_prediction and args.num_negatives < 0:
         raise SystemExit("--num_negatives is at least 0")
+    if args.decoder != "distmult" and not args.link_prediction:
+        raise SystemExit("--decoder chooses the head of a link-prediction run: add --link_prediction")
+    if args.decoder == "complex" and args.num_classes % 2:
+        raise SystemExit("--decoder complex needs an even --num_classes (pairs of a real and an imaginary column; a multiple of 4 for "
+                         "the HIP kernels)")
     if args.eval_ranking and not args.link_prediction:
         raise SystemExit("--eval_ranking ranks the triples of a link-prediction run: add --link_prediction")
     if args.eval_ranking < 0 or args.eval_ranking >= 2 ** 29:
@@ -447,8 +456,8 @@ def main(argv=None):
     params = list(model.parameters()) + ([] if args.sparse_embed else list(embed.parameters()))
     decoder = None
     if args.link_prediction:  # the head scores the encoder's output rows: their width is --num_classes
-        from .linkpred import DistMultDecoder
-        decoder = DistMultDecoder(R, args.num_classes).to(dev)
+        from .linkpred import ComplExDecoder, DistMultDecoder
+        decoder = (ComplExDecoder if args.decoder == "complex" else DistMultDecoder)(R, args.num_classes).to(dev)
         params += list(decoder.parameters())
     try:  # one kernel per step over all parameters (the [N, in] embedding table dominates); same update rule
         optimizer = th.optim.Adam(params, lr=args.lr, fused=True)
@@ -517,6 +526,8 @@ def main(argv=None):
     else:
         del res["args"]["link_prediction"]
         del res["args"]["num_negatives"]
+    if args.decoder == "distmult":
+        del res["args"]["decoder"]
     if args.eval_ranking:
         res["ranking"] = ranking
     else:

@@ -1140,6 +1140,59 @@ int het_block_relation_major(const int64_t* rel, const int64_t* eids, int64_t nu
                              int64_t* out_col, int64_t* out_rel, int64_t* out_eids, het_stream stream);
 
 /* ------------------------------------------------------------------------
+ * The ComplEx head for link prediction (csrc/triple_score.hip, csrc/triple_rank.hip; het_amd/linkpred.py ComplExDecoder,
+ * complex_rank): the score, its backward and the filtered ranking of the DistMult head (the two sections below, whose
+ * triples, plan, lists, chunks, bad ids, counters, workspaces and checks hold here word for word) with another trilinear form, one
+ * that tells a triple from its reverse.  (The section stands here because the sections after it are pinned to their neighbours.)
+ *   Layout: h [num_nodes, dim] and w [num_rels, dim] with dim even; column 2k is the real and column 2k + 1 the imaginary part of
+ *   component k (torch.view_as_complex(x.view(-1, dim / 2, 2))).  A 16-byte piece of a row is two whole complex numbers: the widths
+ *   served are those of het_triple_params (score, backward) and het_triple_rank_params (ranking), multiples of 4.
+ *   With a = h[s_j], b = w[r_j], c = h[o_j], per component (a_r, a_i), (b_r, b_i), (c_r, c_i), g = grad_score_j:
+ *     score_j    = sum_k Re(a_k * b_k * conj(c_k)) = sum_k (a_r b_r - a_i b_i) c_r + (a_r b_i + a_i b_r) c_i
+ *     grad a_r  += g (b_r c_r + b_i c_i)      grad a_i += g (b_r c_i - b_i c_r)      (slot side 0: v is the head s_j)
+ *     grad c_r  += g (a_r b_r - a_i b_i)      grad c_i += g (a_r b_i + a_i b_r)      (slot side 1: v is the tail o_j)
+ *     grad b_r  += g (a_r c_r + a_i c_i)      grad b_i += g (a_r c_i - a_i c_r)
+ *   The orders are het_distmult_score_backward's: a node's slots ascending 2 j + side, a list longer than L in chunks of L with the
+ *   chunk sums added in chunk order, grad_w in chunks of the relation chunk, every grad_h and grad_w row written exactly once (+0 where
+ *   a list is empty), het_bf16 grad_h rounded once after the whole sum, a triple with s_j == o_j has both slots, a bad id is counted
+ *   and never forms an address.  No float atomics, no zero-fill, no read-back: the same bits on every call.  The plan is
+ *   het_triple_plan's and the backward's workspace holds het_distmult_score_backward_workspace bytes.
+ *   het_complex_rank: query j = (anchor [j], rel [j], truth [j], side [j]).  side 0 ranks tails: the anchor is the head s and the
+ *   candidates stand in o's place.  side 1 ranks heads: the anchor is the tail o and the candidates stand in s's place.  A side
+ *   outside {0, 1} makes the query bad.  With x = h[a_j], b = w[r_j], every operation a separately rounded fp32 one (no fused
+ *   multiply-add):
+ *     side 0:  q_j[2k] = fl32(fl32(x_r b_r) - fl32(x_i b_i))     q_j[2k+1] = fl32(fl32(x_r b_i) + fl32(x_i b_r))
+ *     side 1:  q_j[2k] = fl32(fl32(b_r x_r) + fl32(b_i x_i))     q_j[2k+1] = fl32(fl32(b_r x_i) - fl32(b_i x_r))
+ *     score_j(c) = the fp32 fma chain over ascending d from +0: acc = fmaf(q_j[d], h[c, d], acc);  p_j = score_j(t_j) by the same chain
+ *   so that score_j(c) is the ComplEx score of (a_j, r_j, c) on side 0 and of (c, r_j, a_j) on side 1.  The run, the exclusions, the
+ *   three counters, the bad count, the launches behind the prelude and the workspace (het_triple_rank_workspace) are het_triple_rank's.
+ * The checks, codes and messages are those of the DistMult entries, each naming its own entry; a dim that is odd or no multiple of 4
+ * is HET_ERR_UNSUPPORTED; het_complex_rank refuses a null or misaligned side (HET_ERR_INVALID_ARG).
+ * ------------------------------------------------------------------------ */
+int het_complex_score(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                      int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream);
+int het_complex_score_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o, int64_t num_triples,
+                           int64_t num_nodes, int64_t num_rels, int64_t dim, float* score, het_stream stream);
+int het_complex_score_backward(const float* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                               const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
+                               const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes, int64_t num_rels,
+                               int64_t dim, float* grad_h, float* grad_w, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_complex_score_backward_bf16(const het_bf16* h, const float* w, const int64_t* s, const int64_t* r, const int64_t* o,
+                                    const float* grad_score, const int64_t* node_ptr, const int64_t* node_slots, const int64_t* rel_ptr,
+                                    const int64_t* rel_order, const int64_t* chunk_ptr, int64_t num_triples, int64_t num_nodes,
+                                    int64_t num_rels, int64_t dim, het_bf16* grad_h, float* grad_w, void* workspace,
+                                    int64_t workspace_bytes, het_stream stream);
+int het_complex_rank(const float* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth, const int64_t* side,
+                     int64_t num_queries, const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs,
+                     const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim, int32_t* greater,
+                     int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes, het_stream stream);
+int het_complex_rank_bf16(const het_bf16* h, const float* w, const int64_t* anchor, const int64_t* rel, const int64_t* truth,
+                          const int64_t* side, int64_t num_queries, const int64_t* pair_query, const int64_t* pair_cand, int64_t num_pairs,
+                          const int64_t* node_type_offsets, int64_t num_types, int64_t num_nodes, int64_t num_rels, int64_t dim,
+                          int32_t* greater, int32_t* equal, int32_t* cands, int64_t* bad, void* workspace, int64_t workspace_bytes,
+                          het_stream stream);
+
+/* ------------------------------------------------------------------------
  * Filtered ranking of link-prediction queries with the DistMult score (csrc/triple_rank.hip; het_amd/linkpred.py distmult_rank;
  * DESIGN.md 4.14).  Every query is ranked against every node of its true node's type; no score is stored, three int32 per query
  * come out.  (The section stands here, before keyed dropout, because the sections after it are pinned to their neighbours.)
